@@ -17,12 +17,21 @@ Without a torchrun environment, ``--gpus N`` (N > 1) starts N worker processes i
 anything touches the GPU (desco_amd.distributed.launch: fresh children, never an exec), each
 joins the RCCL group and asserts world_size == N.
 
-Prints ONE JSON line on rank 0 with the driver's contract plus
+Prints ONE JSON line on rank 0 with the driver's contract (metric, value, unit, higher_is_better,
+dtype, ms_per_step = milliseconds of one timed step, ...).  A plain run does only that: set-up,
+warm-up, the timed steps, the line.  ``--full`` adds everything else the benchmark measures:
   "roofline":     dominant kernel, achieved vs peak from HIP events recorded live in the timed
                   region; "gather" = the fused SHMP layer kernel (the north_star's gather) priced
-                  against HBM, with its PMC traffic
+                  against HBM, with its PMC traffic; "kernels" = the per-launch table
+  "secondary", "latency_x1", "train_syn_1827", "train_gossip": the other workload shapes, the
+                  un-replicated latency and the training legs (N=1 only for the last three)
   "cpu_baseline": the CPU oracle (reference-form torch port) on PRE-BUILT batches, timed with
                   1 thread and with all physical cores on a bounded sample (N=1 only)
+  "collective.grad_allreduce_selftest" (N > 1): the bucketed gradient all-reduce check
+
+``--dump-outputs DIR`` writes the arrays the last timed step returned (InferencePipeline.run's dict,
+rank 0) as DIR/<name>.npy, float32; an array above DUMP_BYTES_PER_ARRAY is cut to a fixed, seeded
+sample of its rows, so that two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -46,6 +55,24 @@ PEAK_X6_TFLOPS = PEAK_BF16_MFMA_TFLOPS / 6.0
 # ... and on the fp16 pipe in THREE products ("f16x3", round 4: hi/lo fp16 split with power-of-two scales; the fp16
 # MFMA runs at the bf16 rate): the algorithm's speed of light is the fp16 peak / 3
 PEAK_X3_TFLOPS = PEAK_BF16_MFMA_TFLOPS / 3.0
+# --dump-outputs: the five [rows, 29] arrays of a pass stay under 64 MB in all
+DUMP_BYTES_PER_ARRAY = 12 << 20
+
+
+def dump_outputs(out, path, seed=0):
+    """``--dump-outputs``: every array of ``out`` as ``path/<name>.npy`` (float32).  An array larger than
+    DUMP_BYTES_PER_ARRAY keeps only a sample of its rows: drawn from ``seed`` and the row count alone, in row order,
+    so the same arguments select the same rows in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in sorted(out.items()):
+        t = t.detach()
+        if 4 * t.numel() > DUMP_BYTES_PER_ARRAY:
+            keep = DUMP_BYTES_PER_ARRAY // (4 * t[0].numel())
+            rows = np.sort(np.random.default_rng(seed).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.float().cpu().numpy())
 
 
 def gather_kernel() -> str:
@@ -772,9 +799,19 @@ def main():
                     help="timed passes over the training legs' batches (default 1; the gossip leg runs twice as many)")
     ap.add_argument("--selftest-nccl", action="store_true",
                     help="2-rank RCCL gradient all-reduce check (needs 2 visible GPUs; skips otherwise)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: per-launch HIP events (kernel table, roofline, attainable MFMA "
+                         "rate), the other workload shapes, the x1 latency line, the training legs, the CPU baseline and "
+                         "(N > 1) the gradient all-reduce self-test; the --no-* options switch single parts off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays of the last timed step (rank 0) as DIR/<name>.npy, float32, at most 64 MB")
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--ddp-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps and the result line, nothing else
+        args.no_profile = args.no_attainable = args.no_secondary = args.no_x1 = True
+        args.no_train = args.no_cpu_baseline = True
     if args.cpu_worker:
         sys.exit(cpu_worker_main())
     if args.ddp_child:
@@ -829,9 +866,9 @@ def main():
         collective = {"backend": torch.distributed.get_backend(), "ranks_seen": int(round(float(ones.item()))),
                       "shared_gpu_test_mode": bool(share)}
         assert collective["ranks_seen"] == world, collective
-        # the gradient all-reduce check on the live backend: always for nccl (RCCL, < 2 s); in the shared-GPU test mode
-        # (gloo, host-staged) only when asked, since the test-suite times these runs
-        if collective["backend"] == "nccl" or os.environ.get("DESCO_BENCH_GRAD_CHECK") == "1":
+        # the gradient all-reduce check on the live backend (--full): always for nccl (RCCL, < 2 s); in the shared-GPU
+        # test mode (gloo, host-staged) only when asked, since the test-suite times these runs
+        if args.full and (collective["backend"] == "nccl" or os.environ.get("DESCO_BENCH_GRAD_CHECK") == "1"):
             # (a failing self-test must not cost the measurement: the inference pass below uses no collective but the
             #  barrier and the max over ranks)
             try:
@@ -906,6 +943,8 @@ def main():
         g_all = D.gather_rows(out["graph_gossip_count"])
         if rank == 0:
             assert g_all.shape[0] == graphs.num_graphs * world and torch.isfinite(g_all).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     primary_summary = {}
     if not args.no_profile:

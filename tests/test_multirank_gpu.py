@@ -214,7 +214,7 @@ def test_bench_starts_its_own_ranks(scaling):
     env = dict(os.environ, DESCO_SHARE_GPU="1", DESCO_BENCH_GRAD_CHECK="1" if scaling == "weak" else "0")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--replicas", "2", "--scaling", scaling, "--no-cpu-baseline"],
+                        "--warmup", "1", "--replicas", "2", "--scaling", scaling, "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

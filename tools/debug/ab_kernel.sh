@@ -8,7 +8,7 @@ for round in 1 2; do
   for v in base new; do
     cp tools/debug/_ab/$v.hip desco_amd/csrc/$F
     make -C desco_amd/csrc > /dev/null 2>&1
-    python bench.py --by-shape --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | K="$K" V=$v python -c "
+    python bench.py --full --by-shape --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | K="$K" V=$v python -c "
 import sys, json, os
 for l in sys.stdin:
     if l.startswith('{'):

@@ -12,5 +12,5 @@ PY
 for WL in "$@"; do set -- $WL
 for rep in 1 2; do for LIBV in $LIBS; do
   if [ $LIBV = base ]; then unset DESCO_LIB; else export DESCO_LIB=$PWD/desco_amd/libdesco_$LIBV.so; fi
-  python bench.py --workload $1 --replicas $2 --steps 5 --warmup 2 --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-train 2>/dev/null | tail -1 | python /tmp/_ab_fmt.py "$1 x$2 $LIBV"
+  python bench.py --workload $1 --replicas $2 --steps 5 --warmup 2 --full --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-train 2>/dev/null | tail -1 | python /tmp/_ab_fmt.py "$1 x$2 $LIBV"
 done; done; done

@@ -8,7 +8,7 @@ LIBS=(); EXTRA=()
 while [ $# -gt 0 ]; do if [ "$1" = "--" ]; then shift; EXTRA=("$@"); break; fi; LIBS+=("$1"); shift; done
 for round in 1 2; do
   for v in "${LIBS[@]}"; do
-    DESCO_ALLOW_DEBUG_LIB=1 DESCO_LIB=$PWD/tools/debug/_ab/lib$v.so python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-secondary \
+    DESCO_ALLOW_DEBUG_LIB=1 DESCO_LIB=$PWD/tools/debug/_ab/lib$v.so python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-secondary \
       --no-x1 --no-attainable --no-train "${EXTRA[@]}" 2>/dev/null | V=$v python -c "
 import sys, json, os
 for l in sys.stdin:

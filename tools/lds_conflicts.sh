@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/lds_$W -- python3 $ROOT/bench.py --workload $W --replicas $R --steps 1 --warmup 1 --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-profile > $OUT/lds_$W.log 2>&1
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/lds_$W -- python3 $ROOT/bench.py --workload $W --replicas $R --steps 1 --warmup 1 --full --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-profile > $OUT/lds_$W.log 2>&1
 cd $ROOT
 python3 - "$OUT/lds_$W" <<'PY' | tee $OUT/lds_conflicts_$W.txt
 import csv, glob, collections, sys

@@ -16,7 +16,7 @@ for P in "TA_BUSY_avr GRBM_GUI_ACTIVE" \
          "TD_TD_BUSY_sum TD_TC_STALL_sum TA_FLAT_READ_WAVEFRONTS_sum"; do
   i=$((i+1))
   # (a counter set the hardware cannot collect aborts and then hangs in finalize: bound every pass)
-  timeout 150 rocprofv3 --pmc $P --output-format csv -d $OUT/mem_${W}_p$i -- python3 $ROOT/bench.py --workload $W --replicas $R --steps 1 --warmup 1 --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-profile > $OUT/mem_${W}_p$i.log 2>&1
+  timeout 150 rocprofv3 --pmc $P --output-format csv -d $OUT/mem_${W}_p$i -- python3 $ROOT/bench.py --workload $W --replicas $R --steps 1 --warmup 1 --full --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-profile > $OUT/mem_${W}_p$i.log 2>&1
 done
 cd $ROOT
 python3 - "$OUT" "$W" <<'PY' | tee $OUT/mem_counters_$W.txt

@@ -23,10 +23,10 @@ for WL in $WLS; do
   # their own pass only -- the training legs and the CPU baseline do not depend on the inference workload
   EXTRA=""
   [ "$W" != "cox2" ] && EXTRA="--no-train --no-cpu-baseline --no-secondary --no-x1"
-  python3 bench.py $ARGS --steps 10 --warmup 3 $EXTRA > $OUT/bench_$K.json 2> $OUT/bench_$K.err
+  python3 bench.py $ARGS --steps 10 --warmup 3 --full $EXTRA > $OUT/bench_$K.json 2> $OUT/bench_$K.err
   head -c 300 $OUT/bench_$K.json; echo
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$K -- python3 $ROOT/bench.py $ARGS --steps 5 --warmup 2 --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-train > $OUT/stats_$K.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$K -- python3 $ROOT/bench.py $ARGS --steps 5 --warmup 2 --full --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-train > $OUT/stats_$K.log 2>&1
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$K -- python3 $ROOT/bench.py $ARGS --steps 2 --warmup 1 --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-train --no-profile > $OUT/pmc_fetch_$K.log 2>&1
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_$K -- python3 $ROOT/bench.py $ARGS --steps 2 --warmup 1 --no-cpu-baseline --no-x1 --no-secondary --no-attainable --no-train --no-profile > $OUT/pmc_write_$K.log 2>&1
   i=0
@@ -82,4 +82,4 @@ if [ "${PROFILE_TRAIN:-1}" = "1" ]; then
     find $OUT/pmc_fetch_train_$LEG $OUT/pmc_write_train_$LEG -name "*.csv" -delete 2>/dev/null
   done
 fi
-python3 bench.py --steps 50 --warmup 5 --replicas 1 --no-cpu-baseline --no-train > $OUT/bench_cox2_x1.json 2>> $OUT/bench_cox2_x64.err
+python3 bench.py --steps 50 --warmup 5 --replicas 1 --full --no-cpu-baseline --no-train > $OUT/bench_cox2_x1.json 2>> $OUT/bench_cox2_x64.err

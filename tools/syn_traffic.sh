@@ -12,7 +12,7 @@ ARGS="--workload syn_1827 --replicas $R --steps 2 --warmup 1 --no-cpu-baseline -
 for DS in 1 0; do
   export DESCO_DEGREE_SORT=$DS
   cd $ROOT
-  python3 bench.py $ARGS --steps 5 > $OUT/bench_ds$DS.json 2> $OUT/bench_ds$DS.err
+  python3 bench.py $ARGS --steps 5 --full > $OUT/bench_ds$DS.json 2> $OUT/bench_ds$DS.err
   cd /tmp && export TMPDIR=/tmp
   i=0
   for P in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_EA_RDREQ_sum TCC_EA_RDREQ_32B_sum" \
