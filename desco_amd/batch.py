@@ -109,19 +109,13 @@ class NeighborhoodBatch(_TrainIndexMixin):
             m = self.__dict__["_max_count_rows"] = int(d.max()) if len(d) else 0
         return m
 
-    def pool_index(self, tile_rows: Optional[int] = None):
-        """(pool_bits, pool_slot, num_slots) of the fused pooling (desco_shmp_layer_pool_bf16x6_f32):
-        per wave tile (``tile_rows`` = 16 or 32 count rows; default: what the library's layer kernel
-        uses), the bitmap of rows that END a neighborhood and the first partial slot of the tile (a
-        tile uses one slot per neighborhood that has a row in it)."""
-        if tile_rows is None:
-            from . import ops
-            tile_rows = ops.pool_tile_rows()
-        if tile_rows not in (16, 32):
-            raise ValueError("tile_rows must be 16 or 32")
-        cache = self.__dict__.setdefault("_pool_index", {})
-        if tile_rows not in cache:
-            TR, sh = tile_rows, 4 if tile_rows == 16 else 5
+    def pool_index(self):
+        """(pool_bits, pool_slot, num_slots) of the fused pooling (desco_shmp_layer_pool_f16x3_f32 and its bf16x6 twin):
+        per 16-row wave tile of the layer kernel, the bitmap of count rows that END a neighborhood and the first partial
+        slot of the tile (a tile uses one slot per neighborhood that has a row in it)."""
+        idx = self.__dict__.get("_pool_index")
+        if idx is None:
+            TR = 16
             cp = self.part.count_ptr.astype(np.int64)
             nc = int(cp[-1])
             if (np.diff(cp) <= 0).any():
@@ -129,9 +123,9 @@ class NeighborhoodBatch(_TrainIndexMixin):
             nt = (nc + TR - 1) // TR
             ends = cp[1:] - 1
             bits = np.zeros(nt, dtype=np.uint32)
-            np.bitwise_or.at(bits, ends >> sh, (np.uint32(1) << (ends & (TR - 1)).astype(np.uint32)))
+            np.bitwise_or.at(bits, ends // TR, (np.uint32(1) << (ends & (TR - 1)).astype(np.uint32)))
             pop = np.zeros(nt, dtype=np.int64)
-            np.add.at(pop, ends >> sh, 1)
+            np.add.at(pop, ends // TR, 1)
             last_row = np.minimum(TR * np.arange(nt, dtype=np.int64) + TR - 1, nc - 1)
             carry = ((bits >> (last_row & (TR - 1)).astype(np.uint32)) & 1) == 0    # a segment runs on into the next tile
             nseg = pop + carry
@@ -139,9 +133,9 @@ class NeighborhoodBatch(_TrainIndexMixin):
             if slot[-1] >= 2 ** 31:
                 raise ValueError("too many pooling slots for int32")
             dev = self.device
-            cache[tile_rows] = (torch.from_numpy(bits.view(np.int32)).to(dev),
-                                torch.from_numpy(slot[:-1].astype(np.int32)).to(dev), int(slot[-1]))
-        return cache[tile_rows]
+            idx = self.__dict__["_pool_index"] = (torch.from_numpy(bits.view(np.int32)).to(dev),
+                                                   torch.from_numpy(slot[:-1].astype(np.int32)).to(dev), int(slot[-1]))
+        return idx
 
     def degree_table_index(self, max_rows: int = 1 << 16):
         """The count rows' S slot degrees as an index into their DISTINCT tuples (built once per batch, on the device):

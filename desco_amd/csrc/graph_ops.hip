@@ -765,15 +765,15 @@ extern "C" int desco_pool_reduce_f32(const float* part, const uint32_t* pool_bit
                                      int tile_rows, desco_stream_t stream) {
   if (num_seg == 0) return 0;
   auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
-  if (tile_rows != 16 && tile_rows != 32)
-    return fail(DESCO_EINVAL, "desco_pool_reduce_f32: tile_rows must be desco_shmp_pool_tile_rows()");
+  if (tile_rows != 16)
+    return fail(DESCO_EINVAL, "desco_pool_reduce_f32: tile_rows must be desco_shmp_pool_tile_rows() (16)");
   if (!part || !pool_bits || !pool_slot || !seg_ptr || !out || num_seg < 0 || ldo % 4 || !al16(part) ||
       !al16(out) || (extra && (ld_extra % 4 || !al16(extra))))
     return fail(DESCO_EINVAL, "desco_pool_reduce_f32: bad argument");
   const int64_t blocks = (num_seg + 15) / 16;
   if (!grid_ok(blocks)) return fail(DESCO_EINVAL, "desco_pool_reduce_f32: too many segments");
   hipLaunchKernelGGL(pool_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, part,
-                     pool_bits, pool_slot, seg_ptr, num_seg, extra, ld_extra, out, ldo, tile_rows == 16 ? 4 : 5);
+                     pool_bits, pool_slot, seg_ptr, num_seg, extra, ld_extra, out, ldo, 4);   // tsh = log2(16)
   return launch_status("desco_pool_reduce_f32");
 }
 
@@ -783,7 +783,7 @@ extern "C" int desco_pool_reduce_multi_f32(int num, const float* const* pool_par
                                            int tile_rows, desco_stream_t stream) {
   if (num == 0 || num_seg == 0) return 0;
   auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
-  if (num < 0 || num > 8 || !pool_parts || !outs || (tile_rows != 16 && tile_rows != 32) || !pool_bits || !pool_slot ||
+  if (num < 0 || num > 8 || !pool_parts || !outs || tile_rows != 16 || !pool_bits || !pool_slot ||
       !seg_ptr || num_seg < 0 || ldo % 4 || (extras && ld_extra % 4))
     return fail(DESCO_EINVAL, "desco_pool_reduce_multi_f32: bad argument (1..8 layers)");
   PoolMulti pm;
@@ -798,7 +798,7 @@ extern "C" int desco_pool_reduce_multi_f32(int num, const float* const* pool_par
   const int64_t blocks = (num_seg + 15) / 16;
   if (!grid_ok(blocks)) return fail(DESCO_EINVAL, "desco_pool_reduce_multi_f32: too many segments");
   hipLaunchKernelGGL(pool_reduce_multi_kernel, dim3((unsigned)blocks, (unsigned)num), dim3(256), 0, (hipStream_t)stream,
-                     pm, pool_bits, pool_slot, seg_ptr, num_seg, ld_extra, ldo, tile_rows == 16 ? 4 : 5);
+                     pm, pool_bits, pool_slot, seg_ptr, num_seg, ld_extra, ldo, 4);
   return launch_status("desco_pool_reduce_multi_f32");
 }
 

@@ -1,9 +1,11 @@
-// Arguments of the fused SHMP layer kernels (shmp_layer.hip: 32-row wave tiles; shmp_layer16.hip: 16-row
-// wave tiles, 16 waves per CU).
+// Arguments of the fused SHMP layer kernels (shmp_layer.hip: the f32 form, 32-row wave tiles; shmp_layer16.hip: the
+// bf16x6 and f16x3 split forms, 16-row wave tiles).
 #pragma once
 #include <stdint.h>
 
 namespace desco {
+
+constexpr int MAXS = 4;       // relation slots stored per row
 
 struct ShmpArgs {
   const float* x;
@@ -26,12 +28,11 @@ struct ShmpArgs {
                             // per-row bound desco_gemm_f16x3_f32 wants for the operand these rows are a column block of
   int act;                  // DESCO_ACT_* of the epilogue (relu for the SHMP layer)
   float slope;
-  // fused pooling (global_add_pool of the produced rows, gnn_model.py:107), optional: see
+  // fused pooling (global_add_pool of the produced rows, gnn_model.py:107; 16-row form only), optional: see
   // desco_shmp_layer_pool_bf16x6_f32 in desco_hip.h.  out may then be null (rows not stored).
-  const uint32_t* pool_bits;   // [ceil(rows / TR)] bit r of word t: row TR t + r is the last row of its segment
-  const int32_t* pool_slot;    // [ceil(rows / TR)] first partial slot of TR-row tile t
+  const uint32_t* pool_bits;   // [ceil(rows / 16)] bit r of word t: row 16 t + r is the last row of its segment
+  const int32_t* pool_slot;    // [ceil(rows / 16)] first partial slot of 16-row tile t
   float* pool_part;            // [num slots][64] partial segment sums
-  int pool_rows;               // TR = 32 (shmp_layer.hip) or 16 (shmp_layer16.hip)
   // round 6 (16-row form only): the launch's OWN rows (the self block's operand) read from another tensor than the gather
   // sources: row i of the launch at xself + i * ldxs (i = the same global row index that addresses x).  The canonical
   // launches use it to read their rows from the anchor operand's column block (row stride 576) -- the only place the
@@ -45,7 +46,15 @@ struct ShmpArgs {
   const float* self_coef;
 };
 
-// 16-row-tile form (shmp_layer16.hip); returns false when the shape is not one it is built for
-bool shmp16_launch(const ShmpArgs& g, int cus, void* stream);
+// The argument checks both forms share: operands present and 16-byte aligned (float4 loads and stores), slot counts
+// within S <= MAXS, out / out2 not aliasing x.  Each form adds its own (slots_mfma bound, out, pooling, ...).
+inline bool shmp_args_ok(const ShmpArgs& g, const void* weights) {
+  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  return g.x && (g.vrowptr || g.S == 0) && weights && g.row0 >= 0 && g.num_rows >= 0 && g.sm >= 0 && g.st >= 0 &&
+         g.st <= 2 && g.sm + g.st <= g.S && g.S <= MAXS && !(g.S == 0 && (g.sm || g.st)) && (g.st == 0 || g.ytab) &&
+         g.ldx % 4 == 0 && (g.st == 0 || g.ldy % 4 == 0) && !mis16(g.x) && !mis16(weights) &&
+         (g.st == 0 || !mis16(g.ytab)) && g.x != g.out && g.x != g.out2 && (!g.out || (!mis16(g.out) && g.ldo % 4 == 0)) &&
+         (!g.out2 || (!mis16(g.out2) && g.ldo2 % 4 == 0));
+}
 
 }  // namespace desco

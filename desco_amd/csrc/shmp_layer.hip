@@ -26,27 +26,19 @@
 //   * the first gather step of the next LIVE K block is issued BEFORE the MFMAs of block b, and the
 //     first live block of the next tile before the epilogue stores of the current one, so
 //     feature-row latency hides under the matrix work of the same wave; a relation slot without a
-//     source in the wave's 32 rows is dead: no gather, no split, no MFMAs (exact zeros);
+//     source in the wave's 32 rows is dead: no gather, no MFMAs (exact zeros);
 //   * rows with more than 2 sources in a slot take up to EXTRA_STEPS more batched steps; beyond that
 //     (hub rows, canonical rows of dense neighborhoods, ids past WCAP) they are finished
 //     cooperatively by the whole wave (8 lane groups stride over one row's sources);
 //   * table slots run as one extra pseudo K block: their pre-transformed source rows are gathered
 //     the same way, staged in the A image and ADDED to the accumulators in the C/D layout;
 //   * HBM traffic per row and layer: one 256-B read of x, one 256-B write, ~20 B of indices
-//     (neighbour re-reads hit L2 / MALL: a neighborhood's rows are contiguous);
-//   * optional fused pooling (global_add_pool of the produced rows): after the stores a wave swaps
-//     the two lane halves of its accumulators (v_permlane32_swap: lane = column, all 32 rows of the
-//     tile in registers in row order), runs one running sum down the rows and writes it out at every
-//     segment end -- one 256-B partial per (tile, segment), summed per segment by pool_reduce_kernel.
-//     All control flow of that pass is wave-uniform (the segment-end bitmap of the tile is a scalar).
+//     (neighbour re-reads hit L2 / MALL: a neighborhood's rows are contiguous).
 //
-// Two arithmetic modes share the gather:
-//   f32   v_mfma_f32_32x32x2_f32 on an fp32 A image [32][33] and fp32 weights [K][64];
-//   x6    the fp32-accurate 6-product bf16 split of gemm_split.hip: the gathered sums are split
-//         into three bf16 planes [3][32][40] when they are written to LDS, the weights arrive
-//         pre-split (n-major planes) and v_mfma_f32_32x32x16_bf16 does 24 MFMAs of 32 cycles per
-//         32-deep half block instead of 32 MFMAs of 64 cycles (sm <= 2: the planes of four weight
-//         blocks do not fit beside eight waves).
+// Arithmetic: exact fp32, v_mfma_f32_32x32x2_f32 on an fp32 A image [32][33] and fp32 weights [K][64]
+// (sm <= 3).  The split forms of the same layer (bf16x6, f16x3; fused pooling) run in 16-row wave tiles,
+// shmp_layer16.hip.  This file also holds linear64_kernel, the layer's self block on its own in the bf16x6
+// form (desco_linear64_bf16x6_f32).
 #include "common_device.hpp"
 #include "shmp_args.hpp"
 
@@ -56,13 +48,13 @@ constexpr int WR = 32;        // rows per wave
 constexpr int NW = 8;         // waves per block (2 per SIMD)
 constexpr int AH = 33;        // half-K fp32 A image row stride (floats): conflict-free ds_read_b32
 constexpr int APS = 40;       // half-K bf16 plane row stride (shorts, 80 B): conflict-free ds_read_b128
-constexpr int MAXS = 4;       // relation slots stored per row
 constexpr int RPN = WR * MAXS + 1;
 constexpr int EXTRA_STEPS = 9; // batched 2-source steps after the prefetched one (<= 20 sources per row)
 constexpr int WCAP = 512;     // source ids staged per wave (longer slices fall back to global);
                               // one buffer: the next tile's first 256 ids wait in registers until
                               // the switch, a denser tile fetches the rest then
-constexpr int A_FLOATS = 3 * WR * APS / 2;               // A region per wave: max(32*33, 3*32*40/2) floats
+constexpr int A_FLOATS = 3 * WR * APS / 2;               // A region per wave: max(32*33, 3*32*40/2) floats (the layer
+                                                         // kernel's fp32 image, linear64_kernel's bf16 planes)
 constexpr int WAVE_LDS = A_FLOATS + 2 * RPN + WCAP;      // floats per wave
 static_assert(A_FLOATS >= WR * AH, "the fp32 image must fit in the plane region");
 
@@ -331,38 +323,22 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
         acc_[reg] += Aw[((reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)) * AH + cl];         \
   }
 
-// KB = sm + 1 resident weight blocks (1..4), ST table slots (0..2), X6: bf16 6-product arithmetic,
-// LD64: x rows are 64 floats and ytab rows 64*ST floats apart (the product path's layouts): source-row
-// addresses then need a shift instead of a 64-bit multiply per gathered row
-// POOL: fused pooling epilogue (instantiated for the count-row launches of the x6 form only)
-template <int KB, int ST, bool X6, bool LD64, bool POOL = false>
+// KB = sm + 1 resident weight blocks (1..4), ST table slots (0..2), LD64: x rows are 64 floats and ytab
+// rows 64*ST floats apart (the product path's layouts): source-row addresses then need a shift instead of a
+// 64-bit multiply per gathered row
+template <int KB, int ST, bool LD64>
 __global__ __launch_bounds__(NW * 64) void shmp_layer_f32_kernel(ShmpArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int WST = KB * 64 + 8;                         // weight plane row stride (shorts)
-  constexpr int WPL = 64 * WST;                            // shorts per weight plane
-  constexpr int W_FLOATS = X6 ? 3 * WPL / 2 : KB * 64 * 64;
-  float* Bimg = lds;                                       // f32: [KB*64][64]
-  short* Wp = reinterpret_cast<short*>(lds);               // x6:  [3][64 n][WST]
+  constexpr int W_FLOATS = KB * 64 * 64;
+  float* Bimg = lds;                                       // [KB*64][64]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float* Aw = lds + W_FLOATS + wave * WAVE_LDS;            // fp32 half image [32][33] (f32 mode, table block)
-  short* Ap = reinterpret_cast<short*>(Aw);                // x6: bf16 planes [3][32][40] of a half image
+  float* Aw = lds + W_FLOATS + wave * WAVE_LDS;            // fp32 half image [32][33]
   int* rpb = reinterpret_cast<int*>(Aw + A_FLOATS);        // 2 x [32*S+1] row pointers (absolute)
   int* ec = rpb + 2 * RPN;                                 // [WCAP] source ids of the current tile
-  (void)Bimg; (void)Wp; (void)Ap;
 
   // ---- resident weights -------------------------------------------------------------------
-  if (X6) {
-    // global planes [3][64][KB*64] -> LDS [3][64][WST], 16 bytes at a time
-    constexpr int CH = KB * 8;                             // uint4 chunks per row
-    for (int i = tid; i < 3 * 64 * CH; i += NW * 64) {
-      const int row = i / CH, ch = i - row * CH;           // row = plane*64 + n
-      *reinterpret_cast<uint4*>(Wp + row * WST + 8 * ch) =
-          *reinterpret_cast<const uint4*>(g.wplanes + (int64_t)row * (KB * 64) + 8 * ch);
-    }
-  } else {
-    for (int i = tid; i < KB * 1024; i += NW * 64)
-      *reinterpret_cast<float4*>(Bimg + 4 * i) = *reinterpret_cast<const float4*>(g.wt + 4 * i);
-  }
+  for (int i = tid; i < KB * 1024; i += NW * 64)
+    *reinterpret_cast<float4*>(Bimg + 4 * i) = *reinterpret_cast<const float4*>(g.wt + 4 * i);
   __syncthreads();
 
   const int g8 = lane >> 3, l8 = lane & 7;                 // 8 groups of 8 lanes: one half row each
@@ -442,15 +418,6 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer_f32_kernel(ShmpArgs g) {
     }
     int qn0 = 0, qn1 = 0, qn2 = 0, qn3 = 0;   // source ids of the next tile (registers until the tile ends)
     int ebn = 0, ecntn = 0;
-    // fused pooling: this tile's segment-end bitmap and first partial slot (wave-uniform address:
-    // scalar loads, in flight under the whole tile)
-    uint32_t pool_e = 0;
-    int pool_s = 0;
-    if constexpr (POOL) {
-      const int t32 = __builtin_amdgcn_readfirstlane((int)(grow0 >> 5));
-      pool_e = g.pool_bits[t32];
-      pool_s = g.pool_slot[t32];
-    }
 
     // ---- accumulator init: bias ----------------------------------------------------------------
     f32x16 acc0, acc1;
@@ -504,34 +471,18 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer_f32_kernel(ShmpArgs g) {
       }
       // ---- the two 32-column halves of block b; the first gather step of block b+1 goes out
       //      under this block's MFMAs (after the low halves have left their registers)
-      {
-        if (X6 && b < KB) {
-          DESCO_PUT_X6(lo0, 0) DESCO_PUT_X6(lo1, 1) DESCO_PUT_X6(lo2, 2) DESCO_PUT_X6(lo3, 3)
-        } else {
-          DESCO_PUT_F32(lo0, 0) DESCO_PUT_F32(lo1, 1) DESCO_PUT_F32(lo2, 2) DESCO_PUT_F32(lo3, 3)
-        }
-      }
+      DESCO_PUT_F32(lo0, 0) DESCO_PUT_F32(lo1, 1) DESCO_PUT_F32(lo2, 2) DESCO_PUT_F32(lo3, 3)
       DESCO_ISSUE_AFTER(b)
-      {
-        if (b >= KB) {
-          DESCO_TAB_HALF(acc0)
-        } else if (X6) {
-          DESCO_MFMA_HALF_X6(b, 0)
-        } else {
-          DESCO_MFMA_HALF_F32(b, 0)
-        }
-        if (X6 && b < KB) {
-          DESCO_PUT_X6(hi0, 0) DESCO_PUT_X6(hi1, 1) DESCO_PUT_X6(hi2, 2) DESCO_PUT_X6(hi3, 3)
-        } else {
-          DESCO_PUT_F32(hi0, 0) DESCO_PUT_F32(hi1, 1) DESCO_PUT_F32(hi2, 2) DESCO_PUT_F32(hi3, 3)
-        }
-        if (b >= KB) {
-          DESCO_TAB_HALF(acc1)
-        } else if (X6) {
-          DESCO_MFMA_HALF_X6(b, 1)
-        } else {
-          DESCO_MFMA_HALF_F32(b, 1)
-        }
+      if (b >= KB) {
+        DESCO_TAB_HALF(acc0)
+      } else {
+        DESCO_MFMA_HALF_F32(b, 0)
+      }
+      DESCO_PUT_F32(hi0, 0) DESCO_PUT_F32(hi1, 1) DESCO_PUT_F32(hi2, 2) DESCO_PUT_F32(hi3, 3)
+      if (b >= KB) {
+        DESCO_TAB_HALF(acc1)
+      } else {
+        DESCO_MFMA_HALF_F32(b, 1)
       }
     }
 
@@ -563,51 +514,19 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer_f32_kernel(ShmpArgs g) {
       acc0[reg] = apply_act(acc0[reg], g.act, g.slope);
       acc1[reg] = apply_act(acc1[reg], g.act, g.slope);
     }
-    if (!POOL || g.out) {
 #pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int r = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-        if (r < nr_out) {
-          float* o = g.out + (grow_out + r) * g.ldo + cl;
-          o[0] = acc0[reg];
-          o[32] = acc1[reg];
-          if (g.out2) {        // e.g. the canonical rows' column block of the anchor-MLP operand
-            float* o2 = g.out2 + (grow_out - g.row0 + r) * g.ldo2 + cl;
-            o2[0] = acc0[reg];
-            o2[32] = acc1[reg];
-          }
+    for (int reg = 0; reg < 16; ++reg) {
+      const int r = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+      if (r < nr_out) {
+        float* o = g.out + (grow_out + r) * g.ldo + cl;
+        o[0] = acc0[reg];
+        o[32] = acc1[reg];
+        if (g.out2) {          // e.g. the canonical rows' column block of the anchor-MLP operand
+          float* o2 = g.out2 + (grow_out - g.row0 + r) * g.ldo2 + cl;
+          o2[0] = acc0[reg];
+          o2[32] = acc1[reg];
         }
       }
-    }
-    if constexpr (POOL) {
-      // lane halves swapped: acc0[reg] = row (reg&3)+8*(reg>>2), acc1[reg] = that row + 4, column = lane
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        const u32x2 t_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc0[reg]), __float_as_uint(acc1[reg]),
-                                                          false, false);
-        acc0[reg] = __uint_as_float(t_[0]);
-        acc1[reg] = __uint_as_float(t_[1]);
-      }
-      const uint32_t E = __builtin_amdgcn_readfirstlane(pool_e);
-      int slot = __builtin_amdgcn_readfirstlane(pool_s);
-      const int nru = __builtin_amdgcn_readfirstlane(nr_out);
-      float* pp = g.pool_part + lane;
-      float run = 0.f;
-#pragma unroll
-      for (int r = 0; r < 32; ++r) {
-        const int reg = (r & 3) + 4 * (r >> 3);
-        if (r < nru) {                                        // (wave-uniform)
-          run += ((r >> 2) & 1) ? acc1[reg] : acc0[reg];
-          if ((E >> r) & 1u) {                                // row r ends its segment (wave-uniform)
-            pp[(int64_t)slot * 64] = run;
-            ++slot;
-            run = 0.f;
-          }
-        }
-      }
-      // the last segment of the tile continues in the next tile: its partial so far
-      if (nru > 0 && !((E >> (nru - 1)) & 1u)) pp[(int64_t)slot * 64] = run;
     }
     if (!has_next) break;
   }
@@ -743,38 +662,27 @@ __global__ __launch_bounds__(NW * 64) void linear64_kernel(Lin64Args g) {
 #undef DESCO_MFMA_HALF_X6
 #undef DESCO_TAB_HALF
 
-template <int KB, int ST, bool X6, bool LD64, bool POOL = false>
+template <int KB, int ST, bool LD64>
 static void shmp_launch_one(const ShmpArgs& g, unsigned grid, hipStream_t st) {
-  constexpr int WST = KB * 64 + 8;
-  constexpr size_t w_floats = X6 ? (size_t)3 * 64 * WST / 2 : (size_t)KB * 64 * 64;
-  constexpr size_t shmem = sizeof(float) * (w_floats + (size_t)NW * WAVE_LDS);
+  constexpr size_t shmem = sizeof(float) * ((size_t)KB * 64 * 64 + (size_t)NW * WAVE_LDS);
   static_assert(shmem <= 160 * 1024, "SHMP layer: LDS budget exceeded");
   static DeviceOnce attr_once;        // function attributes are per device
   if (!attr_once.done()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shmp_layer_f32_kernel<KB, ST, X6, LD64, POOL>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shmp_layer_f32_kernel<KB, ST, LD64>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_once.mark();
   }
-  hipLaunchKernelGGL((shmp_layer_f32_kernel<KB, ST, X6, LD64, POOL>), dim3(grid), dim3(NW * 64), shmem, st, g);
+  hipLaunchKernelGGL((shmp_layer_f32_kernel<KB, ST, LD64>), dim3(grid), dim3(NW * 64), shmem, st, g);
 }
 
-template <int KB, bool X6>
+template <int KB>
 static void shmp_launch_st(const ShmpArgs& g, unsigned grid, hipStream_t st) {
   const bool ld64 = g.ldx == 64 && (g.st == 0 || g.ldy == 64 * g.st);
-  if constexpr (KB == 3 && X6) {
-    if (g.pool_part) {       // count-row launches of the product path (validated by shmp_launch)
-      if (ld64)
-        shmp_launch_one<3, 2, true, true, true>(g, grid, st);
-      else
-        shmp_launch_one<3, 2, true, false, true>(g, grid, st);
-      return;
-    }
-  }
 #define DESCO_ONE(ST_)                                         \
   if (ld64)                                                    \
-    shmp_launch_one<KB, ST_, X6, true>(g, grid, st);           \
+    shmp_launch_one<KB, ST_, true>(g, grid, st);               \
   else                                                         \
-    shmp_launch_one<KB, ST_, X6, false>(g, grid, st);
+    shmp_launch_one<KB, ST_, false>(g, grid, st);
   switch (g.st) {
     case 0: DESCO_ONE(0) break;
     case 1: DESCO_ONE(1) break;
@@ -787,108 +695,6 @@ static void shmp_launch_st(const ShmpArgs& g, unsigned grid, hipStream_t st) {
 #undef DESCO_ONE
 }
 
-// Tile form of the x6 launches: 16-row wave tiles (shmp_layer16.hip) unless DESCO_SHMP_ROWS=32 asks for
-// the 32-row kernel of this file (A/B runs; read once per process).
-static int shmp_tile_rows() {
-  static const int rows = [] {
-    const char* e = getenv("DESCO_SHMP_ROWS");
-    return e && atoi(e) == 32 ? 32 : 16;
-  }();
-  return rows;
-}
-
-static int shmp_launch(const char* who, bool x6, const float* x, int64_t ldx, const int32_t* vrowptr,
-                       const int32_t* vcol, int64_t row0, int64_t num_rows, int slots_stored,
-                       int slots_mfma, int slots_table, const void* weights, const float* bias,
-                       const float* ytab, int64_t ldy, int64_t ytab_row0, float* out, int64_t ldo,
-                       float* out2, int64_t ldo2, int act, float slope, desco_stream_t stream,
-                       const uint32_t* pool_bits = nullptr, const int32_t* pool_slot = nullptr,
-                       float* pool_part = nullptr, const float* wscale = nullptr, float* row_absmax = nullptr,
-                       const float* xself = nullptr, int64_t ldxs = 0, const float* self_coef = nullptr) {
-  if (num_rows == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-  const int max_mfma = x6 ? 2 : 3;
-  const bool pool = pool_part != nullptr;
-  const int tile_rows = wscale ? 16 : x6 ? shmp_tile_rows() : 32;      // (the fp16 form exists for 16-row tiles only)
-  if (pool && (!pool_bits || !pool_slot || row0 % tile_rows || mis16(pool_part) || out2 || !x6 || slots_mfma != 2 ||
-               slots_table != 2))
-    return fail(DESCO_EINVAL, "desco_shmp_layer_pool_bf16x6_f32: bad pooling argument (row0 % tile rows, no out2, "
-                              "slots_mfma == 2, slots_table == 2)");
-  if (xself && (!(x6 && (wscale || shmp_tile_rows() == 16)) || ldxs % 4 || mis16(xself)))
-    return fail(DESCO_EINVAL, "desco_shmp_layer_*: xself is implemented by the 16-row form only (16-byte rows)");
-  if (self_coef && (xself || !pool || !wscale || mis16(self_coef)))
-    return fail(DESCO_EINVAL, "desco_shmp_layer_*: self_coef is implemented by the pooled f16x3 launch only (no xself)");
-  if (!x || (!vrowptr && slots_stored > 0) || !weights || (!out && !pool && !out2) || row0 < 0 || num_rows < 0 || slots_mfma < 0 ||
-      slots_mfma > max_mfma || slots_table < 0 || slots_mfma + slots_table > slots_stored ||
-      slots_stored < 0 || slots_stored > MAXS || (slots_stored == 0 && (slots_mfma || slots_table)) || slots_table > 2 || (slots_table > 0 && !ytab) ||
-      ldx % 4 || (slots_table > 0 && ldy % 4) || mis16(x) || mis16(weights) ||
-      (slots_table > 0 && mis16(ytab)) || x == out || x == out2 ||
-      (out && (mis16(out) || ldo % 4)) || (out2 && (mis16(out2) || ldo2 % 4)))      // float4 stores
-    return fail(DESCO_EINVAL,
-                x6 ? "desco_shmp_layer_bf16x6_f32: bad argument (slots_mfma <= 2, slots_table <= 2)"
-                   : "desco_shmp_layer_f32: bad argument (slots_mfma <= 3, slots_table <= 2)");
-  const int64_t ntiles = (num_rows + NW * WR - 1) / (NW * WR);
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
-  const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
-  ShmpArgs g{x,
-             ldx,
-             vrowptr,
-             vcol,
-             row0,
-             num_rows,
-             slots_stored,
-             slots_mfma,
-             slots_table,
-             x6 ? nullptr : static_cast<const float*>(weights),
-             x6 ? static_cast<const short*>(weights) : nullptr,
-             wscale,
-             bias,
-             ytab,
-             ldy,
-             ytab_row0,
-             out,
-             ldo,
-             out2,
-             ldo2,
-             row_absmax,
-             act,
-             slope,
-             pool_bits,
-             pool_slot,
-             pool_part,
-             tile_rows,
-             xself,
-             ldxs,
-             self_coef};
-  if (!out && !pool && !(x6 && tile_rows == 16))
-    return fail(DESCO_EINVAL, "desco_shmp_layer_*: out == NULL (rows to out2 alone) is implemented by the 16-row form only");
-  hipStream_t st = (hipStream_t)stream;
-  if (x6 && tile_rows == 16) {
-    if (!shmp16_launch(g, cus, stream)) return fail(DESCO_EINVAL, "desco_shmp_layer_bf16x6_f32: shape not built");
-    return launch_status(who);
-  }
-  if (x6) {
-    switch (slots_mfma) {
-      case 0: shmp_launch_st<1, true>(g, grid, st); break;
-      case 1: shmp_launch_st<2, true>(g, grid, st); break;
-      default: shmp_launch_st<3, true>(g, grid, st); break;
-    }
-  } else {
-    switch (slots_mfma) {
-      case 0: shmp_launch_st<1, false>(g, grid, st); break;
-      case 1: shmp_launch_st<2, false>(g, grid, st); break;
-      case 2: shmp_launch_st<3, false>(g, grid, st); break;
-      default: shmp_launch_st<4, false>(g, grid, st); break;
-    }
-  }
-  return launch_status(who);
-}
-
 }  // namespace desco
 
 extern "C" int desco_shmp_layer_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
@@ -897,89 +703,47 @@ extern "C" int desco_shmp_layer_f32(const float* x, int64_t ldx, const int32_t* 
                                     const float* wt, const float* bias, const float* ytab,
                                     int64_t ldy, int64_t ytab_row0, float* out, int64_t ldo,
                                     float* out2, int64_t ldo2, desco_stream_t stream) {
-  return desco::shmp_launch("desco_shmp_layer_f32", false, x, ldx, vrowptr, vcol, row0, num_rows,
-                            slots_stored, slots_mfma, slots_table, wt, bias, ytab, ldy, ytab_row0, out,
-                            ldo, out2, ldo2, DESCO_ACT_RELU, 0.f, stream);
+  using namespace desco;
+  if (num_rows == 0) return 0;
+  ShmpArgs g{};
+  g.x = x;
+  g.ldx = ldx;
+  g.vrowptr = vrowptr;
+  g.vcol = vcol;
+  g.row0 = row0;
+  g.num_rows = num_rows;
+  g.S = slots_stored;
+  g.sm = slots_mfma;
+  g.st = slots_table;
+  g.wt = wt;
+  g.bias = bias;
+  g.ytab = ytab;
+  g.ldy = ldy;
+  g.ytab_row0 = ytab_row0;
+  g.out = out;
+  g.ldo = ldo;
+  g.out2 = out2;
+  g.ldo2 = ldo2;
+  g.act = DESCO_ACT_RELU;
+  if (!shmp_args_ok(g, wt) || slots_mfma > 3 || !out)
+    return fail(DESCO_EINVAL, "desco_shmp_layer_f32: bad argument (slots_mfma <= 3, slots_table <= 2)");
+  const int64_t ntiles = (num_rows + NW * WR - 1) / (NW * WR);
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) == hipSuccess) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+      cus = v;
+  }
+  const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
+  hipStream_t st = (hipStream_t)stream;
+  switch (slots_mfma) {
+    case 0: shmp_launch_st<1>(g, grid, st); break;
+    case 1: shmp_launch_st<2>(g, grid, st); break;
+    case 2: shmp_launch_st<3>(g, grid, st); break;
+    default: shmp_launch_st<4>(g, grid, st); break;
+  }
+  return launch_status("desco_shmp_layer_f32");
 }
-
-extern "C" int desco_shmp_layer_bf16x6_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
-                                           const int32_t* vcol, int64_t row0, int64_t num_rows,
-                                           int slots_stored, int slots_mfma, int slots_table,
-                                           const int16_t* wt_planes, const float* bias,
-                                           const float* ytab, int64_t ldy, int64_t ytab_row0,
-                                           float* out, int64_t ldo, float* out2, int64_t ldo2,
-                                           desco_stream_t stream) {
-  return desco::shmp_launch("desco_shmp_layer_bf16x6_f32", true, x, ldx, vrowptr, vcol, row0,
-                            num_rows, slots_stored, slots_mfma, slots_table, wt_planes, bias, ytab,
-                            ldy, ytab_row0, out, ldo, out2, ldo2, DESCO_ACT_RELU, 0.f, stream);
-}
-
-extern "C" int desco_shmp_layer_pool_bf16x6_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
-                                                const int32_t* vcol, int64_t row0, int64_t num_rows,
-                                                int slots_stored, int slots_mfma, int slots_table,
-                                                const int16_t* wt_planes, const float* bias,
-                                                const float* ytab, int64_t ldy, int64_t ytab_row0,
-                                                float* out, int64_t ldo, const uint32_t* pool_bits,
-                                                const int32_t* pool_slot, float* pool_part,
-                                                desco_stream_t stream) {
-  if (!pool_part)
-    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_pool_bf16x6_f32: pool_part is null");
-  return desco::shmp_launch("desco_shmp_layer_pool_bf16x6_f32", true, x, ldx, vrowptr, vcol, row0,
-                            num_rows, slots_stored, slots_mfma, slots_table, wt_planes, bias, ytab,
-                            ldy, ytab_row0, out, ldo, nullptr, 0, DESCO_ACT_RELU, 0.f, stream,
-                            pool_bits, pool_slot, pool_part);
-}
-
-// The same layer in the three-product fp16 form (16-row tiles): wt_planes[2][64 n][(slots_mfma+1)*64 k] and
-// w_scale[2] = {scale, 1/scale} (device) from desco_split_f16x2_f32; row scales are found in the kernel.
-extern "C" int desco_shmp_layer_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
-                                          const int32_t* vcol, int64_t row0, int64_t num_rows,
-                                          int slots_stored, int slots_mfma, int slots_table,
-                                          const int16_t* wt_planes, const float* w_scale, const float* bias,
-                                          const float* ytab, int64_t ldy, int64_t ytab_row0,
-                                          float* out, int64_t ldo, float* out2, int64_t ldo2,
-                                          float* row_absmax, const float* xself, int64_t ldxs,
-                                          desco_stream_t stream) {
-  if (!w_scale) return desco::fail(DESCO_EINVAL, "desco_shmp_layer_f16x3_f32: w_scale is null");
-  return desco::shmp_launch("desco_shmp_layer_f16x3_f32", true, x, ldx, vrowptr, vcol, row0,
-                            num_rows, slots_stored, slots_mfma, slots_table, wt_planes, bias, ytab,
-                            ldy, ytab_row0, out, ldo, out2, ldo2, DESCO_ACT_RELU, 0.f, stream, nullptr, nullptr,
-                            nullptr, w_scale, row_absmax, xself, ldxs);
-}
-
-extern "C" int desco_shmp_layer_pool_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
-                                               const int32_t* vcol, int64_t row0, int64_t num_rows,
-                                               int slots_stored, int slots_mfma, int slots_table,
-                                               const int16_t* wt_planes, const float* w_scale, const float* bias,
-                                               const float* ytab, int64_t ldy, int64_t ytab_row0,
-                                               float* out, int64_t ldo, const uint32_t* pool_bits,
-                                               const int32_t* pool_slot, float* pool_part,
-                                               desco_stream_t stream) {
-  if (!pool_part || !w_scale)
-    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_pool_f16x3_f32: pool_part / w_scale is null");
-  return desco::shmp_launch("desco_shmp_layer_pool_f16x3_f32", true, x, ldx, vrowptr, vcol, row0,
-                            num_rows, slots_stored, slots_mfma, slots_table, wt_planes, bias, ytab,
-                            ldy, ytab_row0, out, ldo, nullptr, 0, DESCO_ACT_RELU, 0.f, stream,
-                            pool_bits, pool_slot, pool_part, w_scale);
-}
-
-extern "C" int desco_shmp_layer_pool_table_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
-                                                     const int32_t* vcol, int64_t row0, int64_t num_rows,
-                                                     int slots_stored, int slots_mfma, int slots_table,
-                                                     const int16_t* wt_planes, const float* w_scale, const float* bias,
-                                                     const float* ytab, int64_t ldy, int64_t ytab_row0,
-                                                     float* out, int64_t ldo, const uint32_t* pool_bits,
-                                                     const int32_t* pool_slot, float* pool_part,
-                                                     const float* self_coef, desco_stream_t stream) {
-  if (!pool_part || !w_scale || !self_coef)
-    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_pool_table_f16x3_f32: pool_part / w_scale / self_coef is null");
-  return desco::shmp_launch("desco_shmp_layer_pool_table_f16x3_f32", true, x, ldx, vrowptr, vcol, row0,
-                            num_rows, slots_stored, slots_mfma, slots_table, wt_planes, bias, ytab,
-                            ldy, ytab_row0, out, ldo, nullptr, 0, DESCO_ACT_RELU, 0.f, stream,
-                            pool_bits, pool_slot, pool_part, w_scale, nullptr, nullptr, 0, self_coef);
-}
-
-extern "C" int desco_shmp_pool_tile_rows(void) { return desco::shmp_tile_rows(); }
 
 // Row-wise Linear with K = 64 inputs (see linear64_kernel): out[i, 0:64*nb] = act(x[i, 0:64] * W^T + bias),
 // w_planes = nb blocks [3][64 n][64 k].  Two column blocks per pass over x where possible.

@@ -1,14 +1,16 @@
 // Fused SHMP layer, 16-row wave tiles: the same layer as shmp_layer.hip (gnn_model.py:47-70 of the
 // reference: per relation SAGEConv(aggr=add) neighbor sums, root/self Linear, HeteroConv sum, relu) in
-// its bf16 6-product form, built for occupancy instead of tile size.
+// its split forms -- bf16 6-product and fp16 3-product (F16) --, built for occupancy instead of tile size.
+// The entry points of both split forms and their argument checks are at the end of this file.
 //
-// Why a second tiling.  The 32-row kernel runs 8 waves per CU (2 per SIMD): its per-wave LDS (A image,
-// row pointers, 512 staged source ids) fills the 160 KB beside the weight planes.  Its time follows
-// T(w) = a + b / w in the waves per CU (8 -> 4 waves costs 1.44-1.53x): the
-// gather latency is hidden by other waves, not by the two-source steps of one wave.  A wave tile of
-// 16 rows (v_mfma_f32_16x16x32_bf16: four 16-column tiles of the 64 outputs) needs a quarter of the
-// accumulator registers, half the A image and half the staged ids, so 16 waves (4 per SIMD, the
-// 1024-thread block limit) fit beside three weight blocks -- if a wave stays within 128 registers:
+// Why a second tiling.  The 32-row kernel (until round 2 also in the bf16x6 form) runs 8 waves per CU
+// (2 per SIMD): its per-wave LDS (A image, row pointers, 512 staged source ids) fills the 160 KB beside
+// the weights.  Its time follows T(w) = a + b / w in the waves per CU (8 -> 4
+// waves costs 1.44-1.53x): the gather latency is hidden by other waves, not by the two-source steps of
+// one wave.  A wave tile of 16 rows (v_mfma_f32_16x16x32_bf16: four 16-column tiles of the 64 outputs)
+// needs a quarter of the accumulator registers, half the A image and half the staged ids, so 16 waves
+// (4 per SIMD, the 1024-thread block limit) fit beside three weight blocks -- if a wave stays within 128
+// registers:
 //   * wave-uniform bookkeeping (tile, row range, CSR bases) is forced into SGPRs (readfirstlane);
 //   * the next tile's row pointers and source ids go from global memory straight into LDS
 //     (global_load_lds_dword) instead of waiting in registers until the tile switch.
@@ -33,7 +35,6 @@ namespace desco {
 constexpr int WR = 16;        // rows per wave
 constexpr int AH = 36;        // half-K fp32 table image row stride (floats): conflict-free ds_read_b32 / ds_write_b128
 constexpr int APS = 32;       // half-K bf16 plane row stride (shorts, 64 B), chunks XOR-swizzled
-constexpr int MAXS = 4;       // relation slots stored per row
 constexpr int RPN = WR * MAXS + 2;
 // (round 6 sweep on the f16 form with 12 waves, same-box A/B, count-row launch: 5 steps +2.5 %; 14 / 20 / 32 steps -0.9 %
 //  on Syn_1827 shapes and -1.4 % on MSRC-21 + IMDB shapes, COX2 shapes unchanged -- NOT taken: a row of 21..42 sources
@@ -1009,17 +1010,144 @@ static bool shmp16_launch_nw(const ShmpArgs& g, int cus, hipStream_t st) {
   }
 }
 
-// x6 arguments validated by shmp_launch (shmp_layer.hip); g.wplanes set, g.sm <= 2
-bool shmp16_launch(const ShmpArgs& g, int cus, void* stream) {
-  if (!g.wplanes || g.sm < 0 || g.sm > 2 || g.S > MAXS) return false;
+// The split-form entry points below: argument checks, then the launch (wt_planes set; w_scale set for the fp16 form)
+static int shmp16_launch(const char* who, const float* x, int64_t ldx, const int32_t* vrowptr, const int32_t* vcol,
+                         int64_t row0, int64_t num_rows, int slots_stored, int slots_mfma, int slots_table,
+                         const int16_t* wt_planes, const float* w_scale, const float* bias, const float* ytab, int64_t ldy,
+                         int64_t ytab_row0, float* out, int64_t ldo, float* out2, int64_t ldo2, desco_stream_t stream,
+                         const uint32_t* pool_bits = nullptr, const int32_t* pool_slot = nullptr,
+                         float* pool_part = nullptr, float* row_absmax = nullptr, const float* xself = nullptr,
+                         int64_t ldxs = 0, const float* self_coef = nullptr) {
+  if (num_rows == 0) return 0;
+  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  const bool pool = pool_part != nullptr;
+  if (pool && (!pool_bits || !pool_slot || row0 % WR || mis16(pool_part) || out2 || slots_mfma != 2 || slots_table != 2))
+    return fail(DESCO_EINVAL, "desco_shmp_layer_pool_bf16x6_f32: bad pooling argument (row0 % tile rows, no out2, "
+                              "slots_mfma == 2, slots_table == 2)");
+  if (xself && (ldxs % 4 || mis16(xself)))
+    return fail(DESCO_EINVAL, "desco_shmp_layer_*: xself is implemented by the 16-row form only (16-byte rows)");
+  if (self_coef && (xself || !pool || !w_scale || mis16(self_coef)))
+    return fail(DESCO_EINVAL, "desco_shmp_layer_*: self_coef is implemented by the pooled f16x3 launch only (no xself)");
+  ShmpArgs g{};
+  g.x = x;
+  g.ldx = ldx;
+  g.vrowptr = vrowptr;
+  g.vcol = vcol;
+  g.row0 = row0;
+  g.num_rows = num_rows;
+  g.S = slots_stored;
+  g.sm = slots_mfma;
+  g.st = slots_table;
+  g.wplanes = reinterpret_cast<const short*>(wt_planes);
+  g.wscale = w_scale;
+  g.bias = bias;
+  g.ytab = ytab;
+  g.ldy = ldy;
+  g.ytab_row0 = ytab_row0;
+  g.out = out;
+  g.ldo = ldo;
+  g.out2 = out2;
+  g.ldo2 = ldo2;
+  g.row_absmax = row_absmax;
+  g.act = DESCO_ACT_RELU;
+  g.pool_bits = pool_bits;
+  g.pool_slot = pool_slot;
+  g.pool_part = pool_part;
+  g.xself = xself;
+  g.ldxs = ldxs;
+  g.self_coef = self_coef;
+  if (!shmp_args_ok(g, wt_planes) || slots_mfma > 2 || (!out && !pool && !out2))
+    return fail(DESCO_EINVAL, "desco_shmp_layer_bf16x6_f32: bad argument (slots_mfma <= 2, slots_table <= 2)");
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) == hipSuccess) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+      cus = v;
+  }
   // bf16x6 form: 16 waves per block (12 measured 2-6 % slower there: profiles/r2_h_ab_tile_rows.log).  fp16 form: TWELVE,
   // three per SIMD -- a quarter fewer tiles in flight per XCD means a quarter less traffic between two references to a
   // source row, and with half the matrix work per tile the fourth wave per SIMD is not needed to hide latency: Syn_1827
   // shapes 3.68 -> 3.39 ms per count-row launch, MSRC-21 + IMDB 2.93 -> 2.74, COX2 1.325 -> 1.30; 8, 10 and 14 waves are
   // all slower (profiles/r4_m_ab_shmp_waves.log)
-  if (g.wscale) return shmp16_launch_nw<12, true>(g, cus, (hipStream_t)stream);     // fp16 three-product planes
-  return shmp16_launch_nw<16, false>(g, cus, (hipStream_t)stream);
+  const bool built = w_scale ? shmp16_launch_nw<12, true>(g, cus, (hipStream_t)stream)     // fp16 three-product planes
+                             : shmp16_launch_nw<16, false>(g, cus, (hipStream_t)stream);
+  if (!built) return fail(DESCO_EINVAL, "desco_shmp_layer_bf16x6_f32: shape not built");
+  return launch_status(who);
 }
 
 }  // namespace desco
 
+extern "C" int desco_shmp_layer_bf16x6_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
+                                           const int32_t* vcol, int64_t row0, int64_t num_rows,
+                                           int slots_stored, int slots_mfma, int slots_table,
+                                           const int16_t* wt_planes, const float* bias,
+                                           const float* ytab, int64_t ldy, int64_t ytab_row0,
+                                           float* out, int64_t ldo, float* out2, int64_t ldo2,
+                                           desco_stream_t stream) {
+  return desco::shmp16_launch("desco_shmp_layer_bf16x6_f32", x, ldx, vrowptr, vcol, row0, num_rows, slots_stored,
+                              slots_mfma, slots_table, wt_planes, nullptr, bias, ytab, ldy, ytab_row0, out, ldo, out2,
+                              ldo2, stream);
+}
+
+extern "C" int desco_shmp_layer_pool_bf16x6_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
+                                                const int32_t* vcol, int64_t row0, int64_t num_rows,
+                                                int slots_stored, int slots_mfma, int slots_table,
+                                                const int16_t* wt_planes, const float* bias,
+                                                const float* ytab, int64_t ldy, int64_t ytab_row0,
+                                                float* out, int64_t ldo, const uint32_t* pool_bits,
+                                                const int32_t* pool_slot, float* pool_part,
+                                                desco_stream_t stream) {
+  if (!pool_part)
+    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_pool_bf16x6_f32: pool_part is null");
+  return desco::shmp16_launch("desco_shmp_layer_pool_bf16x6_f32", x, ldx, vrowptr, vcol, row0, num_rows, slots_stored,
+                              slots_mfma, slots_table, wt_planes, nullptr, bias, ytab, ldy, ytab_row0, out, ldo, nullptr,
+                              0, stream, pool_bits, pool_slot, pool_part);
+}
+
+// The same layer in the three-product fp16 form (16-row tiles): wt_planes[2][64 n][(slots_mfma+1)*64 k] and
+// w_scale[2] = {scale, 1/scale} (device) from desco_split_f16x2_f32; row scales are found in the kernel.
+extern "C" int desco_shmp_layer_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
+                                          const int32_t* vcol, int64_t row0, int64_t num_rows,
+                                          int slots_stored, int slots_mfma, int slots_table,
+                                          const int16_t* wt_planes, const float* w_scale, const float* bias,
+                                          const float* ytab, int64_t ldy, int64_t ytab_row0,
+                                          float* out, int64_t ldo, float* out2, int64_t ldo2,
+                                          float* row_absmax, const float* xself, int64_t ldxs,
+                                          desco_stream_t stream) {
+  if (!w_scale) return desco::fail(DESCO_EINVAL, "desco_shmp_layer_f16x3_f32: w_scale is null");
+  return desco::shmp16_launch("desco_shmp_layer_f16x3_f32", x, ldx, vrowptr, vcol, row0, num_rows, slots_stored,
+                              slots_mfma, slots_table, wt_planes, w_scale, bias, ytab, ldy, ytab_row0, out, ldo, out2,
+                              ldo2, stream, nullptr, nullptr, nullptr, row_absmax, xself, ldxs);
+}
+
+extern "C" int desco_shmp_layer_pool_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
+                                               const int32_t* vcol, int64_t row0, int64_t num_rows,
+                                               int slots_stored, int slots_mfma, int slots_table,
+                                               const int16_t* wt_planes, const float* w_scale, const float* bias,
+                                               const float* ytab, int64_t ldy, int64_t ytab_row0,
+                                               float* out, int64_t ldo, const uint32_t* pool_bits,
+                                               const int32_t* pool_slot, float* pool_part,
+                                               desco_stream_t stream) {
+  if (!pool_part || !w_scale)
+    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_pool_f16x3_f32: pool_part / w_scale is null");
+  return desco::shmp16_launch("desco_shmp_layer_pool_f16x3_f32", x, ldx, vrowptr, vcol, row0, num_rows, slots_stored,
+                              slots_mfma, slots_table, wt_planes, w_scale, bias, ytab, ldy, ytab_row0, out, ldo, nullptr,
+                              0, stream, pool_bits, pool_slot, pool_part);
+}
+
+extern "C" int desco_shmp_layer_pool_table_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
+                                                     const int32_t* vcol, int64_t row0, int64_t num_rows,
+                                                     int slots_stored, int slots_mfma, int slots_table,
+                                                     const int16_t* wt_planes, const float* w_scale, const float* bias,
+                                                     const float* ytab, int64_t ldy, int64_t ytab_row0,
+                                                     float* out, int64_t ldo, const uint32_t* pool_bits,
+                                                     const int32_t* pool_slot, float* pool_part,
+                                                     const float* self_coef, desco_stream_t stream) {
+  if (!pool_part || !w_scale || !self_coef)
+    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_pool_table_f16x3_f32: pool_part / w_scale / self_coef is null");
+  return desco::shmp16_launch("desco_shmp_layer_pool_table_f16x3_f32", x, ldx, vrowptr, vcol, row0, num_rows,
+                              slots_stored, slots_mfma, slots_table, wt_planes, w_scale, bias, ytab, ldy, ytab_row0, out,
+                              ldo, nullptr, 0, stream, pool_bits, pool_slot, pool_part, nullptr, nullptr, 0, self_coef);
+}
+
+extern "C" int desco_shmp_pool_tile_rows(void) { return desco::WR; }

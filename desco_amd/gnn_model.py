@@ -48,7 +48,7 @@ SHMP_F16X3 = os.environ.get("DESCO_SHMP_F16X3", "1") != "0"
 # False: the general per-layer launches of autograd.ShmpTrunk (its cross-check in the tests)
 SMALL_TRUNK_KERNEL = True
 # True: global_add_pool of the count rows fused into the layer kernel's epilogue (partials per
-# (32-row tile, neighborhood) + a small reduce) instead of one segment_sum pass over X_l per layer
+# (16-row tile, neighborhood) + a small reduce) instead of one segment_sum pass over X_l per layer
 FUSED_POOLING = True
 # ... and the layers' partials reduced by ONE launch at the end of the layer loop (False: one launch per layer)
 POOL_REDUCE_MULTI = os.environ.get("DESCO_POOL_REDUCE_MULTI", "1") != "0"
@@ -438,10 +438,10 @@ def pack_shmp(gnn: BaseGNN, bf16_planes: bool = True) -> dict:
             if bf16_planes and SHMP_BF16X6:
                 # n-major operand planes of the MFMA blocks of the fused layer (K <= 192): fp16 (hi, lo) + one scale
                 # per matrix, or bf16 (hi, mid, lo)
-                f16 = SHMP_F16X3 and ops.pool_tile_rows() == 16
+                split = ops.split_f16_planes if SHMP_F16X3 else ops.split_bf16_planes
                 for name in ("wt_mfma", "wt"):
                     if name in entry and entry[name].shape[0] <= 192:
-                        entry[name + "_x6"] = (ops.split_f16_planes if f16 else ops.split_bf16_planes)(entry[name].t())
+                        entry[name + "_x6"] = split(entry[name].t())
             per_type[t] = entry
         pk["layers"].append(per_type)
     pk["anchor"] = _lin_t(gnn.anchor_mlp[0])
@@ -572,7 +572,7 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
         # one read of X_1 that its segment sum cost)
         pool1 = None
         if (POOL_FIRST_LAYER and FUSED_POOLING and SHMP_BF16X6 and GEMM_BF16X6 and isinstance(batch, NeighborhoodBatch)
-                and Nc > 0 and ops.pool_tile_rows() == 16):
+                and Nc > 0):
             pbits1, pslot1, nslots1 = batch.pool_index()
             pool1 = (pbits1, pslot1, torch.empty((nslots1, H), device=dev))
         # ... and with the table form of the second layer's launches they are not stored either
@@ -707,7 +707,7 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
         seg_ptr = batch.graph_ptr
     if (fuse_post0 and POOL_POST_FUSED and anch is not None and const_input and first == 1 and GEMM_BF16X6
             and "post_nk" in pk and sorted(pool_parts) == list(range(1, core.layer_num + 1)) and core.layer_num <= 8
-            and ops.pool_tile_rows() == 16 and batch.max_count_rows() <= 33):
+            and batch.max_count_rows() <= 33):
         w0, b0 = pk["post_nk"][0]
         return _PostMp0(ops.pool_post(anch, [pool_parts[l] for l in range(1, core.layer_num + 1)], pbits, pslot, seg_ptr,
                                       x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1))

@@ -494,7 +494,7 @@ def _shmp_layer_pool(x, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma,
     yp, ldy = _rows(ytab, "ytab")
     L = _lib.lib()
     fl = 2.0 * num_rows * (slots_mfma + 1) * 64 * 64
-    # x once (+ out once when stored) + indices + the partial rows (about one per 32 rows + one per segment)
+    # x once (+ out once when stored) + indices + the partial rows (about one per 16 rows + one per segment)
     # (table form: the input rows are not read from HBM either -- a few thousand table rows stand for all of them)
     nb = ((0.0 if self_coef is not None else 256.0) + (0.0 if out is None else 256.0)) * num_rows + 4.0 * (
         num_rows * slots_stored + vcol.numel() * num_rows / max((vrowptr.numel() - 1) // max(slots_stored, 1), 1))
@@ -522,9 +522,8 @@ def _shmp_layer_pool(x, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma,
 
 def pool_reduce(part: torch.Tensor, bits: torch.Tensor, slot: torch.Tensor, seg_ptr: torch.Tensor,
                 num_seg: int, extra: Optional[torch.Tensor] = None,
-                out: Optional[torch.Tensor] = None, tile_rows: Optional[int] = None) -> torch.Tensor:
-    """out[b] = sum of segment b's partial rows (left by ``shmp_layer(pool=...)``) + extra[b];
-    ``tile_rows`` = the tile size the index was built for (default: ``pool_tile_rows()``)."""
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b] = sum of segment b's partial rows (left by ``shmp_layer(pool=...)``) + extra[b]."""
     if out is None:
         out = torch.empty((num_seg, 64), device=part.device, dtype=torch.float32)
     op, ldo = _rows(out, "out")
@@ -534,18 +533,16 @@ def pool_reduce(part: torch.Tensor, bits: torch.Tensor, slot: torch.Tensor, seg_
                 256.0 * part.shape[0] + 4.0 * (2 * bits.numel() + num_seg) + 512.0 * num_seg):
         _lib.check(L.desco_pool_reduce_f32(_dev(part, "pool_part"), _dev(bits, "pool_bits", torch.int32),
                                            _dev(slot, "pool_slot", torch.int32),
-                                           _dev(seg_ptr, "seg_ptr", torch.int32), num_seg, ep, lde, op, ldo,
-                                           pool_tile_rows() if tile_rows is None else tile_rows,
+                                           _dev(seg_ptr, "seg_ptr", torch.int32), num_seg, ep, lde, op, ldo, 16,
                                            _stream()), "pool_reduce")
     return out
 
 
-def pool_reduce_multi(parts, bits: torch.Tensor, slot: torch.Tensor, seg_ptr: torch.Tensor, num_seg: int, extras, outs,
-                      tile_rows: Optional[int] = None) -> None:
+def pool_reduce_multi(parts, bits: torch.Tensor, slot: torch.Tensor, seg_ptr: torch.Tensor, num_seg: int, extras,
+                      outs) -> None:
     """``pool_reduce`` for several layers in one launch (desco_pool_reduce_multi_f32, groups of 8): parts[i] -> outs[i]
     (+ extras[i], or None); the layers share the tile index and the segments.  Bit-identical to the single calls."""
     L = _lib.lib()
-    tr = pool_tile_rows() if tile_rows is None else tile_rows
     for i0 in range(0, len(parts), 8):
         ps, es, os_ = parts[i0:i0 + 8], extras[i0:i0 + 8], outs[i0:i0 + 8]
         n = len(ps)
@@ -567,7 +564,7 @@ def pool_reduce_multi(parts, bits: torch.Tensor, slot: torch.Tensor, seg_ptr: to
             _lib.check(L.desco_pool_reduce_multi_f32(n, pa, _dev(bits, "pool_bits", torch.int32),
                                                      _dev(slot, "pool_slot", torch.int32),
                                                      _dev(seg_ptr, "seg_ptr", torch.int32), num_seg, ea, lde or 0, oa, ldo,
-                                                     tr, _stream()), "pool_reduce_multi")
+                                                     16, _stream()), "pool_reduce_multi")
 
 
 def pool_post(anch: torch.Tensor, parts, bits: torch.Tensor, slot: torch.Tensor, seg_ptr: torch.Tensor, x0: torch.Tensor,
@@ -577,7 +574,7 @@ def pool_post(anch: torch.Tensor, parts, bits: torch.Tensor, slot: torch.Tensor,
     ``w_planes`` = split_bf16_planes(W) [3, 64, 64 (L + 1)].  Every segment must span at most three 16-row tiles."""
     B, L = anch.shape[0], len(parts)
     assert tuple(w_planes.shape) == (3, 64, 64 * (L + 1)) and w_planes.is_contiguous() and anch.shape[1] >= 64 * (L + 1)
-    assert x0.is_contiguous() and x0.numel() == 64 and pool_tile_rows() == 16
+    assert x0.is_contiguous() and x0.numel() == 64
     out = torch.empty((B, 64), device=anch.device, dtype=torch.float32)
     ap, lda = _rows(anch, "anch")
     pa = (ctypes.c_void_p * L)(*[_dev(p_, "pool_part") for p_ in parts])
@@ -613,18 +610,18 @@ def post_mp_tail(x: torch.Tensor, w1, b1, w2, b2, w3, b3, out: Optional[torch.Te
 
 def shmp_kernel_name(kb: int, st: int, x6: bool, f16: bool = False) -> str:
     """Profiler key of a fused-layer launch: the kernel family that runs it (16-row wave tiles for
-    the bf16x6 form unless DESCO_SHMP_ROWS=32; always for the fp16 three-product form) and its
-    <weight blocks, table slots>."""
+    the bf16x6 and fp16 three-product forms, 32-row tiles for the f32 form) and its <weight blocks,
+    table slots>."""
     if f16:
         return f"shmp_layer16_kernel<{kb},{st},f16x3>"
-    if x6 and pool_tile_rows() == 16:
+    if x6:
         return f"shmp_layer16_kernel<{kb},{st}>"
-    return f"shmp_layer_f32_kernel<{kb},{st},{'x6' if x6 else 'f32'}>"
+    return f"shmp_layer_f32_kernel<{kb},{st},f32>"
 
 
 def pool_tile_rows() -> int:
-    """Rows per wave tile of the fused layer kernel (16, or 32 with DESCO_SHMP_ROWS=32): the
-    granularity of the fused-pooling index (``NeighborhoodBatch.pool_index``)."""
+    """Rows per wave tile of the fused layer kernel's split forms (16): the granularity of the
+    fused-pooling index (``NeighborhoodBatch.pool_index``)."""
     return int(_lib.lib().desco_shmp_pool_tile_rows())
 
 
@@ -683,7 +680,7 @@ def degree_affine_pool(vrowptr: torch.Tensor, num_rows: int, slots: int, coef: t
                        out: Optional[torch.Tensor], pool: tuple) -> None:
     """``degree_affine`` for rows [0, num_rows) with the rows' segment sums fused in (desco_degree_affine_pool_f32):
     ``pool`` = (pool_bits, pool_slot, pool_part) as for ``shmp_layer(pool=...)`` with 16-row tiles; ``out`` may be None."""
-    assert coef.is_contiguous() and coef.shape == (slots + 1, 64) and pool_tile_rows() == 16
+    assert coef.is_contiguous() and coef.shape == (slots + 1, 64)
     bits, slot, part = pool
     op, ldo = (None, 64) if out is None else _rows(out, "out")
     with _Timed("degree_affine_kernel", 2.0 * num_rows * slots * 64, 256.0 * num_rows + 4.0 * num_rows * (slots + 1)):

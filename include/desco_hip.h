@@ -278,7 +278,7 @@ int desco_gemm_bf16_f32(const float* a1, int64_t lda1, int k1, const float* a2, 
                         int64_t ldc, int64_t m, desco_stream_t stream);
 int desco_round_bf16_f32(const float* w, int64_t count, int16_t* out, desco_stream_t stream);
 
-/* Fused SHMP layer (K2-K7 in one launch; csrc/shmp_layer.hip).  For destination rows i in
+/* Fused SHMP layer (K2-K7 in one launch; csrc/shmp_layer.hip, 32-row wave tiles).  For destination rows i in
  * [row0, row0+num_rows), with sm = slots_mfma <= 3, st = slots_table <= 2, S = slots_stored (sm+st <= S <= 4):
  *   out[i] = relu( sum_{s<sm} (sum_{e in vrow(i*S+s)} x[vcol[e]]) * Wt_s + x[i] * Wt_sm + bias
  *                  + sum_{sm<=s<sm+st} sum_{e in vrow(i*S+s)} ytab[vcol[e]-ytab_row0][(s-sm)*64 : +64] )
@@ -296,8 +296,8 @@ int desco_shmp_layer_f32(const float* x, int64_t ldx, const int32_t* vrowptr, co
                          int64_t ldy, int64_t ytab_row0, float* out, int64_t ldo, float* out2,
                          int64_t ldo2, desco_stream_t stream);
 /* Same layer with the matrix work on the bf16 pipe at fp32 accuracy (the 6-product split of
- * desco_gemm_bf16x6_f32): wt_planes[3][64 n][(slots_mfma+1)*64 k] = desco_split_bf16x3_f32 of the
- * N-MAJOR folded weight (the transpose of desco_shmp_layer_f32's wt).  slots_mfma <= 2. */
+ * desco_gemm_bf16x6_f32; 16-row wave tiles): wt_planes[3][64 n][(slots_mfma+1)*64 k] = desco_split_bf16x3_f32
+ * of the N-MAJOR folded weight (the transpose of desco_shmp_layer_f32's wt).  slots_mfma <= 2. */
 int desco_shmp_layer_bf16x6_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
                                 const int32_t* vcol, int64_t row0, int64_t num_rows,
                                 int slots_stored, int slots_mfma, int slots_table,
@@ -309,8 +309,7 @@ int desco_shmp_layer_bf16x6_f32(const float* x, int64_t ldx, const int32_t* vrow
  * the epilogue: besides (or instead of: out may be NULL, e.g. for the last layer, whose count rows
  * feed nothing but the pooling) storing the produced rows, every wave sums them per segment and
  * writes ONE partial row per (wave tile, segment) to pool_part[slot][0:64].  A wave tile is
- * TR = desco_shmp_pool_tile_rows() rows (16; 32 with DESCO_SHMP_ROWS=32 in the environment, the 32-row
- * form of the kernel kept for A/B runs):
+ * TR = desco_shmp_pool_tile_rows() = 16 rows:
  *   pool_bits[t] bit r = 1  <=>  row TR t + r is the LAST row of its segment (segments = contiguous row
  *                                ranges covering [row0, row0+num_rows); row0 % TR == 0),
  *   pool_slot[t]            =    first slot of tile t (tiles use consecutive slots: one per segment

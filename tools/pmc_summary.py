@@ -24,9 +24,9 @@ def load(path, cname):
             a = [t.strip() for t in k[k.index("<") + 1:k.rindex(">")].split(",")]
             k = f"shmp_layer16_kernel<{a[1]},{a[2]}{',f16x3' if len(a) > 5 and a[5] == 'true' else ''}{',selfdeg' if len(a) > 6 and a[6] == 'true' else ''}>"
         elif k.startswith("shmp_layer_f32_kernel<"):
-            # template <KB, ST, X6, LD64> -> the profiler key of desco_amd/ops.py
+            # template <KB, ST, LD64> -> the profiler key of desco_amd/ops.py
             a = [t.strip() for t in k[k.index("<") + 1:k.rindex(">")].split(",")]
-            k = f"shmp_layer_f32_kernel<{a[0]},{a[1]},{'x6' if a[2] == 'true' else 'f32'}>"
+            k = f"shmp_layer_f32_kernel<{a[0]},{a[1]},f32>"
         else:
             k = k.split("<")[0]
         agg[k][0] += 1

@@ -53,7 +53,7 @@ for f in glob.glob(f"{out}/sq_{key}_p*/**/*counter_collection.csv", recursive=Tr
             k = f"shmp_layer16_kernel<{a[1]},{a[2]}{',f16x3' if len(a) > 5 and a[5] == 'true' else ''}{',selfdeg' if len(a) > 6 and a[6] == 'true' else ''}>"
         elif k.startswith("shmp_layer_f32_kernel<"):
             a = [t.strip() for t in k[k.index("<") + 1:k.rindex(">")].split(",")]
-            k = f"shmp_layer_f32_kernel<{a[0]},{a[1]},{'x6' if a[2] == 'true' else 'f32'}>"
+            k = f"shmp_layer_f32_kernel<{a[0]},{a[1]},f32>"
         else:
             k = k.split("<")[0]
         agg[k][r["Counter_Name"]] += float(r["Counter_Value"])
