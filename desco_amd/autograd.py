@@ -460,6 +460,12 @@ class GossipTrunk(torch.autograd.Function):
     SITE_H1, SITE_H2, SITE_POST = 0, 1, 2
 
     @staticmethod
+    def layer_site(l: int) -> int:
+        """dropout site of h_l (the output of GossipConv l - 1) in a model of any depth: h1 -> 0, h2 -> 1 (post_mp.1
+        is 2), h_l -> l for l >= 3 (GossipTrunkDeep)"""
+        return GossipTrunk.SITE_H1 if l == 1 else GossipTrunk.SITE_H2 if l == 2 else l
+
+    @staticmethod
     def forward(ctx, rowptr, col, n, q, C6, C3, C2, x, g1c, w3, w5, drop, V0, g1, wt1, V1, wtp, Vp, w3t, b3, w5t, b5, w7, b7):
         V0, V1, Vp = V0.contiguous(), V1.contiguous(), Vp.contiguous()
         wt1, wtp, w3t, w5t = wt1.contiguous(), wtp.contiguous(), w3t.contiguous(), w5t.contiguous()
@@ -579,6 +585,114 @@ def _gossip_trunk_backward_x6(ctx, dz5, dwb7, d1, d2, dp):
 
 
 GossipTrunk._backward_x6 = staticmethod(_gossip_trunk_backward_x6)
+
+
+class GossipTrunkDeep(torch.autograd.Function):
+    """GossipTrunk for a model of any depth L (--gossip_layer_num != 2; algebra DESIGN.md 4.2) as ONE autograd node built
+    from the library's un-fused launches: layer 0 in closed form (affine_rows on C6), per layer l >= 1 the gated gather,
+    the product [hh_l | h_l] wt_l and the per-query affine term C3 . V_l with relu and the dropout factor of h_{l+1}, the
+    L-block post_mp.0 as gemm + accumulating gemm_multi launches, then post_mp.3 / .5 / .7.  Backward: the transposed
+    gathers with 1 - g_l, rowdot2 / colsum for the gates, gemm_multi for the input gradients, linear_bwd_w_multi for the
+    weight gradients.  The reference configuration (L = 2) keeps GossipTrunk.
+
+    args: rowptr, col, num_nodes, num_q, C6 [R,6], C3 [R,3], C2 [R,2], x [R], w3, w5 (post_mp.3 / .5 weights [out, in],
+    no gradient), drop (None or (p_layer, p_post)), L, then with gradients: V0 [Q,6,64], w3t, b3, w5t, b5, w7, b7,
+    wtp [64 L, 64] (the post_mp.0 blocks of h_1 .. h_L, K-major), Vp [Q,2,64], and per layer l = 1 .. L-1: g_l [Q],
+    wt_l [128,64], V_l [Q,3,64].  Returns pred [R] = x + post_mp.7(...)."""
+
+    layer_site = staticmethod(GossipTrunk.layer_site)
+
+    @staticmethod
+    def _sites(key, drop, L):
+        if drop is None:
+            return [None] * (L + 1), None
+        d = [None] + [ops.DropSite(key, GossipTrunkDeep.layer_site(l), drop[0]) for l in range(1, L + 1)]
+        return d, ops.DropSite(key, GossipTrunk.SITE_POST, drop[1])
+
+    @staticmethod
+    def forward(ctx, rowptr, col, n, q, C6, C3, C2, x, w3, w5, drop, L, V0, w3t, b3, w5t, b5, w7, b7, wtp, Vp, *lw):
+        V0, Vp, wtp, w3t, w5t = V0.contiguous(), Vp.contiguous(), wtp.contiguous(), w3t.contiguous(), w5t.contiguous()
+        b3, b5, w7 = b3.contiguous(), b5.contiguous(), w7.contiguous()
+        gs = [lw[3 * i].contiguous() for i in range(L - 1)]
+        wts = [lw[3 * i + 1].contiguous() for i in range(L - 1)]
+        Vs = [lw[3 * i + 2].contiguous() for i in range(L - 1)]
+        key = C6.new_empty(0, dtype=torch.int64)
+        if drop is not None:
+            key = ops.rng_next(C6.device)
+        d, dp = GossipTrunkDeep._sites(key, drop, L)
+        hs = [None, ops.affine_rows(None, C6, V0, ops.ACT_RELU, 0.0, d[1])]            # h1 (layer 0, closed form)
+        hhs = [None]
+        for l in range(1, L):
+            hh = ops.gossip_gather(hs[l], rowptr, col, n, q, gs[l - 1])
+            hhs.append(hh)
+            hs.append(ops.affine_rows(ops.gemm(hh, wts[l - 1], a2=hs[l]), C3, Vs[l - 1], ops.ACT_RELU, 0.0, d[l + 1]))
+        zp = ops.gemm(hs[1], wtp[:64].contiguous())                                    # post_mp.0 over [h1 | .. | hL]
+        for l in range(2, L + 1):
+            ops.gemm_multi([dict(a1=hs[l], wt=wtp[64 * (l - 1):64 * l].contiguous(), out=zp, accum=True)])
+        y = ops.affine_rows(zp, C2, Vp, ops.ACT_LEAKY, 0.1, dp)                          # + x tp + zp, .1, .2
+        y3 = ops.gemm(y, w3t, b3, act=ops.ACT_RELU)
+        y5 = ops.gemm(y3, w5t, b5, act=ops.ACT_RELU)
+        pred = ops.affine_scalar(ops.rowdot_add(y5, w7, 0.0, None), add=b7, addv=x)
+        ctx.save_for_backward(rowptr, col, C6, C3, C2, w3.detach(), w5.detach(), wtp, w7, y, y3, y5, key,
+                              *hs[1:], *hhs[1:], *gs, *wts)
+        ctx.n, ctx.q, ctx.drop, ctx.L = n, q, drop, L
+        return pred
+
+    @staticmethod
+    def backward(ctx, dcorr):
+        n, q, L = ctx.n, ctx.q, ctx.L
+        sv = ctx.saved_tensors
+        rowptr, col, C6, C3, C2, w3, w5, wtp, w7, y, y3, y5, key = sv[:13]
+        hs = [None] + list(sv[13:13 + L])
+        hhs = [None] + list(sv[13 + L:13 + L + L - 1])
+        gs = list(sv[12 + 2 * L:12 + 2 * L + L - 1])
+        wts = list(sv[11 + 3 * L:11 + 3 * L + L - 1])
+        d, dp = GossipTrunkDeep._sites(key, ctx.drop, L)
+        R, dev = hs[1].shape[0], hs[1].device
+        dz5, dwb7 = ops.rowdot_bwd(y5, w7, dcorr.contiguous())
+        dz3 = torch.empty((R, 64), device=dev)
+        ops.gemm_multi([dict(a1=dz5, wt=w5, out=dz3, gate=y3, gate_act=ops.ACT_RELU)])
+        dzp = torch.empty((R, 64), device=dev)
+        ops.gemm_multi([dict(a1=dz3, wt=w3, out=dzp, gate=y, gate_act=ops.ACT_LEAKY, gate_slope=0.1, drop=dp)])
+        dVp = ops.affine_rows_bwd(C2, dzp, q)
+        # dA = dZ W^T wants the transposed blocks ([out][in]) of every K-major weight: one copy2d launch per 24
+        wpt = torch.empty((L, 64, 64), device=dev)
+        wlt = torch.empty((max(L - 1, 1), 2, 64, 64), device=dev)
+        cps = [(wtp[64 * l:64 * (l + 1)], wpt[l], True) for l in range(L)]
+        for l in range(L - 1):
+            cps += [(wts[l][:64], wlt[l, 0], True), (wts[l][64:], wlt[l, 1], True)]
+        for c0 in range(0, len(cps), 24):
+            ops.copy2d_multi(cps[c0:c0 + 24])
+        dh = [None] + [torch.empty((R, 64), device=dev) for _ in range(L)]
+        for l in range(1, L + 1):
+            ops.gemm_multi([dict(a1=dzp, wt=wpt[l - 1], out=dh[l])])                 # from post_mp.0
+        dgs, dVs, dzs = [None] * (L - 1), [None] * (L - 1), [None] * L      # dzs[l]: dZ of GossipConv l
+        for l in range(L - 1, 0, -1):                                                # GossipConv l: h_l -> h_{l+1}
+            dz = ops.act_grad(dh[l + 1], hs[l + 1], ops.ACT_RELU, 0.0, d[l + 1])
+            dzs[l] = dz
+            dVs[l - 1] = ops.affine_rows_bwd(C3, dz, q)
+            dhh = torch.empty((R, 64), device=dev)
+            ops.gemm_multi([dict(a1=dz, wt=wlt[l - 1, 0], out=dhh), dict(a1=dz, wt=wlt[l - 1, 1], out=dh[l], accum=True)])
+            # transpose of the gated sum: the same kernel with 1 - g; d out / d g = sum_{j<i} h_j - sum_{j>i} h_j
+            g = gs[l - 1]
+            ops.add_rows(dh[l], ops.gossip_gather(dhh, rowptr, col, n, q, (1.0 - g).contiguous()))
+            dsig = ops.gossip_gather(hs[l], rowptr, col, n, q, None)
+            dgs[l - 1] = ops.colsum(ops.rowdot2(dhh, dsig).view(n, q))
+        dz0 = ops.act_grad(dh[1], hs[1], ops.ACT_RELU, 0.0, d[1])
+        dV0 = ops.affine_rows_bwd(C6, dz0, q)
+        dw5t, db5 = torch.empty((64, 256), device=dev), torch.empty((256,), device=dev)
+        dw3t, db3 = torch.empty((64, 64), device=dev), torch.empty((64,), device=dev)
+        dwtp = torch.empty_like(wtp)
+        dwts = [torch.empty_like(w) for w in wts]
+        probs = [dict(a1=y3, dz=dz5, dwt=dw5t, dbias=db5), dict(a1=y, dz=dz3, dwt=dw3t, dbias=db3)]
+        probs += [dict(a1=hs[l], dz=dzp, dwt=dwtp[64 * (l - 1):64 * l]) for l in range(1, L + 1)]
+        probs += [dict(a1=hhs[l], a2=hs[l], dz=dzs[l], dwt=dwts[l - 1]) for l in range(1, L)]
+        for p0 in range(0, len(probs), 16):
+            ops.linear_bwd_w_multi(probs[p0:p0 + 16])
+        lg = []
+        for l in range(L - 1):
+            lg += [dgs[l], dwts[l], dVs[l]]
+        return (None,) * 12 + (dV0, dw3t, db3, dw5t, db5, dwb7[:256], dwb7[256:257], dwtp, dVp) + tuple(lg)
 
 
 class Mlp(torch.autograd.Function):

@@ -895,12 +895,14 @@ DROPOUT_AT_ZERO = False
 
 def pack_gossip(gnn: BaseGNN, bf16_planes: bool = True) -> dict:
     core = gnn.gnn_core
-    if core.layer_num != 2 or not core.input_pattern_emb or core.input_dim != 1:
+    if core.layer_num < 1 or not core.input_pattern_emb or core.input_dim != 1:
         raise NotImplementedError(
-            "gossip kernels implement the reference configuration: 2 GossipConv layers, "
-            "input_dim 1, query embedding as input (config.py:312-322, main.py:316-325)")
+            "gossip kernels implement GossipConv layers with input_dim 1 and the query embedding as input "
+            "(config.py:312-322, main.py:316-325)")
     pre = core.pre_mp[0]
     pk = {"w_pre": pre.weight[:, 0].contiguous(), "b_pre": pre.bias.contiguous()}
+    if core.layer_num != 2:
+        return _pack_gossip_deep(gnn, pk)
     c0, c1 = core.convs[0], core.convs[1]
     pk["C0"], pk["c0"] = c0.lin_com.weight, c0.lin_com.bias
     pk["D0"], pk["d0"] = c0.lin_update.weight, c0.lin_update.bias
@@ -928,6 +930,140 @@ def pack_gossip(gnn: BaseGNN, bf16_planes: bool = True) -> dict:
                                                             ("fused_w1", "fused_wp", "fused_w3", "fused_w5")])
     pk["qcache"] = None
     return pk
+
+
+def _pack_gossip_deep(gnn: BaseGNN, pk: dict) -> dict:
+    """Operands of a depth-L gossip model (L != 2): per layer l >= 1 the folded weight
+    W_l = [(D_a C)^T; D_b^T]_l as fp16 planes of its n-major form, u_l = D_a c_l and d_l, and the post_mp.0 blocks P0_l
+    of h_1 .. h_L (n-major [64, 64] = the block of the torch weight as it is stored)."""
+    core = gnn.gnn_core
+    L = core.layer_num
+    c0 = core.convs[0]
+    pk["C0"], pk["c0"] = c0.lin_com.weight, c0.lin_com.bias
+    pk["D0"], pk["d0"] = c0.lin_update.weight, c0.lin_update.bias
+    P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
+    pk["P0"], pk["p0"] = P0, p0
+    pk["wsp"] = torch.stack([torch.zeros(H, device=P0.device), _mv(P0[:, H:2 * H], pk["w_pre"])]).contiguous()
+    layers = []
+    for l in range(1, L):
+        c = core.convs[l]
+        Da, Db = c.lin_update.weight[:, :H], c.lin_update.weight[:, H:]
+        w_nk = torch.cat([Da @ c.lin_com.weight, Db], 1).contiguous()               # [64 out, 128 in] = W_l^T
+        layers.append({"w": ops.split_f16_planes(w_nk), "u": _mv(Da, c.lin_com.bias).contiguous(),
+                       "d": c.lin_update.bias.contiguous()})
+    pk["deep"] = layers
+    pk["deep_p"] = [ops.split_f16_planes(P0[:, (l + 1) * H:(l + 2) * H].contiguous()) for l in range(1, L + 1)]
+    if L == 1:      # h1 . P0_1 on the fp32 matrix pipe (no gossip layer to carry it)
+        pk["p1t"] = P0[:, 2 * H:3 * H].t().contiguous()
+    pk["post"] = [_lin_t(gnn.post_mp[i]) for i in (3, 5)]
+    pk["w7"] = gnn.post_mp[7].weight[0].contiguous()
+    pk["b7"] = float(gnn.post_mp[7].bias[0])
+    pk["qcache"] = None
+    return pk
+
+
+def _gossip_query_terms_deep(gnn: BaseGNN, pk: dict, query_emb: torch.Tensor) -> dict:
+    """Per-query operands of a depth-L model: gates g_l, V0 = [p, r, t, z] of the closed-form layer 0 against the row
+    constants (a0, b0, x, 1), V_l = [u_l, g_l u_l, d_l] against C3 = (deg_hi, deg_lo - deg_hi, 1), and the
+    accumulator's start [0, 0, tp, zp] (zp + x tp: the E and pre_mp blocks of post_mp.0)."""
+    key = (query_emb.data_ptr(), query_emb._version, tuple(query_emb.shape))
+    if pk["qcache"] is not None and pk["qcache"][0] == key:
+        return pk["qcache"][1]
+    core = gnn.gnn_core
+    E = query_emb.float()
+    Q = E.shape[0]
+    C0, D0 = pk["C0"], pk["D0"]
+    w_pre, b_pre = pk["w_pre"], pk["b_pre"]
+    q = {"g": [c._gate_value(E).reshape(-1).contiguous() for c in core.convs]}
+    a_q = E @ C0[:, :H].t() + (_mv(C0[:, H:], b_pre) + pk["c0"])
+    v = _mv(C0[:, H:], w_pre)
+    D0a, D0b, D0c = D0[:, :H], D0[:, H:2 * H], D0[:, 2 * H:]
+    p = a_q @ D0a.t()
+    r = _mv(D0a, v).expand(Q, H)
+    t = _mv(D0c, w_pre).expand(Q, H)
+    z = E @ D0b.t() + (_mv(D0c, b_pre) + pk["d0"])
+    q["V0"] = torch.stack([p, r, t, z], 1).contiguous()                               # [Q,4,64]
+    P0 = pk["P0"]
+    zp = E @ P0[:, :H].t() + (_mv(P0[:, H:2 * H], b_pre) + pk["p0"])
+    zero = torch.zeros_like(zp)
+    q["Vacc"] = torch.stack([zero, zero, pk["wsp"][1].expand(Q, H), zp], 1).contiguous()
+    q["V"] = [torch.stack([e["u"].expand(Q, H), g[:, None] * e["u"], e["d"].expand(Q, H)], 1).contiguous()
+              for e, g in zip(pk["deep"], q["g"][1:])]                                 # [Q,3,64] per layer l >= 1
+    q["vzero"] = torch.zeros((1, 3, H), device=E.device)
+    pk["qcache"] = (key, q)
+    return q
+
+
+# rows of the post_mp tail per launch chain of a depth-L pass (its [rows, 256] intermediate is the largest buffer)
+GOSSIP_DEEP_TAIL_ROWS = 1 << 24
+
+
+def _gossip_deep_consts(batch: GossipBatch, x: torch.Tensor):
+    """(C3 [R,3] = (deg_hi, deg_lo - deg_hi, 1), C4 [R,4] whose last column is 1) for x's number of query columns:
+    functions of the CSR and that number alone, made on the first pass over a batch (eagerly: InferencePipeline.capture
+    runs one first) and kept on it."""
+    N, Q = x.shape
+    cache = batch.__dict__.setdefault("_deep_consts", {})
+    if Q not in cache:
+        dev = x.device
+        ones, zeros = torch.ones(Q, device=dev), torch.zeros(Q, device=dev)
+        sa = ops.gossip_scalars(x, batch.rowptr, batch.col, ones, zeros)        # (deg_lo, s_lo, deg_hi, x)
+        deg_lo, deg_hi = sa[:, 0], sa[:, 2]
+        C3 = torch.stack([deg_hi, deg_lo - deg_hi, torch.ones_like(deg_hi)], 1).contiguous()
+        cache[Q] = (C3, torch.ones((N * Q, 4), device=dev))
+    return cache[Q]
+
+
+def gossip_forward_deep(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tensor) -> torch.Tensor:
+    """Inference of a gossip model with L != 2 GossipConv layers: layer 0 in closed form
+    (affine_rows), L - 1 launches of desco_gossip_layer_f16x3_f32 that also accumulate the h_l blocks of post_mp.0,
+    then the post_mp tail.  The layer kernel takes any number of queries (the gates are per row); the per-row scalars
+    of layer 0 (desco_gossip_scalars_f32) take at most 64, so more queries (--use_node_feature) go in column groups."""
+    pk = gnn.packed()
+    with torch.no_grad():
+        q = _gossip_query_terms_deep(gnn, pk, query_emb)
+    x = batch.x
+    N, Q = x.shape
+    if Q != query_emb.shape[0]:
+        raise ValueError("batch.x has a different number of query columns than query_emb rows")
+    if Q <= 64:
+        return _gossip_deep_pass(gnn, pk, batch, x, q)
+    outs = []
+    for q0 in range(0, Q, 64):
+        q1 = min(Q, q0 + 64)
+        qs = {"g": [g[q0:q1].contiguous() for g in q["g"]], "V0": q["V0"][q0:q1].contiguous(),
+              "Vacc": q["Vacc"][q0:q1].contiguous(), "V": [v[q0:q1].contiguous() for v in q["V"]], "vzero": q["vzero"]}
+        outs.append(_gossip_deep_pass(gnn, pk, batch, x[:, q0:q1].contiguous(), qs))
+    return torch.cat(outs, dim=1)
+
+
+def _gossip_deep_pass(gnn: BaseGNN, pk: dict, batch: GossipBatch, x: torch.Tensor, q: dict) -> torch.Tensor:
+    N, Q = x.shape
+    L = gnn.gnn_core.layer_num
+    C3, C4 = _gossip_deep_consts(batch, x)
+    scal4 = ops.gossip_scalars(x, batch.rowptr, batch.col, q["g"][0], q["g"][0])    # (a0, b0, -, x)
+    ops.copy2d_multi([(scal4[:, 0:2], C4[:, 0:2]), (scal4[:, 3:4], C4[:, 2:3])])   # C4 = (a0, b0, x, 1)
+    h = ops.affine_rows(None, C4, q["V0"], ops.ACT_RELU, 0.0)                      # h1 (layer 0)
+    acc = ops.affine_rows(None, C4, q["Vacc"], ops.ACT_NONE, 0.0)                  # zp + x tp
+    if L == 1:
+        ops.gemm_multi([dict(a1=h, wt=pk["p1t"], out=acc, accum=True)])
+    for l in range(1, L):
+        last = l == L - 1
+        h = ops.gossip_layer_f16(h, batch.rowptr, batch.col, N, Q, q["g"][l], C3, q["V"][l - 1], pk["deep"][l - 1]["w"],
+                                 pk["deep_p"][l - 1], acc, pn=pk["deep_p"][l] if last else None)
+    del h
+    (w3, b3), (w5, b5) = pk["post"]
+    R = N * Q
+    xf = x.reshape(-1)
+    out = torch.empty((R,), device=x.device)
+    for r0 in range(0, R, GOSSIP_DEEP_TAIL_ROWS):
+        r1 = min(R, r0 + GOSSIP_DEEP_TAIL_ROWS)
+        y = ops.affine_rows(acc[r0:r1], C3[r0:r1], q["vzero"], ops.ACT_LEAKY, 0.1)   # post_mp.2 (LeakyReLU 0.1)
+        y = ops.gemm(y, w3, b3, act=ops.ACT_RELU)
+        y = ops.gemm(y, w5, b5, act=ops.ACT_RELU)
+        ops.rowdot_add(y, pk["w7"], pk["b7"], add=xf[r0:r1], out=out[r0:r1])          # post_mp.7 + x
+        del y
+    return out.view(N, Q)
 
 
 def _gossip_query_terms(gnn: BaseGNN, pk: dict, query_emb: torch.Tensor) -> dict:
@@ -959,6 +1095,8 @@ def gossip_forward(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tensor) ->
     """All-queries gossip correction + residual: returns pred [N, Q] = x + post_mp(emb)
     (BaseGNN.forward gossip path gnn_model.py:58-103 looped over queries as in
     lightning_model.py:613-628, here batched over the query axis)."""
+    if gnn.gnn_core.layer_num != 2:
+        return gossip_forward_deep(gnn, batch, query_emb)
     pk = gnn.packed()
     with torch.no_grad():
         q = _gossip_query_terms(gnn, pk, query_emb)
@@ -1012,16 +1150,16 @@ def gossip_forward_train(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tens
     (gnn_model.py:236-240): ``pre_mp`` and the query embeddings receive no gradient."""
     from . import autograd as AG
     core = gnn.gnn_core
-    if core.layer_num != 2 or not core.input_pattern_emb or core.input_dim != 1:
-        raise NotImplementedError("gossip training implements the reference configuration only")
+    if core.layer_num < 1 or not core.input_pattern_emb or core.input_dim != 1:
+        raise NotImplementedError("gossip training implements GossipConv layers with input_dim 1 and the query "
+                                  "embedding as input")
     x = batch.x
     N, Q = x.shape
     dev = x.device
     E = query_emb.detach().float().to(dev)
     w_pre, b_pre = core.pre_mp[0].weight[:, 0].detach(), core.pre_mp[0].bias.detach()
-    c0, c1 = core.convs[0], core.convs[1]
+    c0 = core.convs[0]
     C0, cb0, D0, db0 = c0.lin_com.weight, c0.lin_com.bias, c0.lin_update.weight, c0.lin_update.bias
-    C1, cb1, D1, db1 = c1.lin_com.weight, c1.lin_com.bias, c1.lin_update.weight, c1.lin_update.bias
     # ---- constants per (node, query): deg_lo, deg_hi, s_lo, s_hi, x (functions of the batch alone: cached on it) ----
     # (keyed on the tensor object -- kept alive by the cache, so its address cannot be reused -- and its version;
     #  the library's in-place writers of x bump the version: ops.scatter_rows)
@@ -1044,6 +1182,10 @@ def gossip_forward_train(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tens
     p_layer = float(core.dropout or 0.0) if gnn.training else 0.0
     p_post = float(gnn.post_mp[1].p or 0.0) if gnn.training else 0.0
     drop = (p_layer, p_post) if (p_layer > 0.0 or p_post > 0.0 or (DROPOUT_AT_ZERO and gnn.training)) else None
+    if core.layer_num != 2:
+        return _gossip_train_deep(gnn, batch, E, w_pre, b_pre, C6, C3, C2, drop).view(N, Q)
+    c1 = core.convs[1]
+    C1, cb1, D1, db1 = c1.lin_com.weight, c1.lin_com.bias, c1.lin_update.weight, c1.lin_update.bias
     if Q <= 64:
         # The operands folded from the parameters by one kernel each way (autograd.FoldGossip, csrc/train_native.hip;
         # algebra DESIGN.md 4.2), then the whole per-(node, query) pipeline and its backward as one autograd node
@@ -1085,3 +1227,42 @@ def gossip_forward_train(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tens
                                 gnn.post_mp[5].weight.t(), gnn.post_mp[5].bias, gnn.post_mp[7].weight.view(-1),
                                 gnn.post_mp[7].bias)
     return pred.view(N, Q)
+
+
+def _gossip_train_deep(gnn: BaseGNN, batch: GossipBatch, E, w_pre, b_pre, C6, C3, C2, drop) -> torch.Tensor:
+    """Training pass of a depth-L model (L != 2): the operands folded from the parameters with differentiable torch ops
+    (the form of the more-than-64-queries branch, per layer), then autograd.GossipTrunkDeep."""
+    from . import autograd as AG
+    core = gnn.gnn_core
+    L = core.layer_num
+    x = batch.x
+    N, Q = x.shape
+    c0 = core.convs[0]
+    C0, D0 = c0.lin_com.weight, c0.lin_update.weight
+    g0 = c0._gate_value(E).reshape(-1)
+    a_q = E @ C0[:, :H].t() + (_mv(C0[:, H:], b_pre) + c0.lin_com.bias)
+    v = _mv(C0[:, H:], w_pre)
+    D0a, D0b, D0c = D0[:, :H], D0[:, H:2 * H], D0[:, 2 * H:]
+    p = a_q @ D0a.t()
+    r = _mv(D0a, v).expand(Q, H)
+    t = _mv(D0c, w_pre).expand(Q, H)
+    z = E @ D0b.t() + (_mv(D0c, b_pre) + c0.lin_update.bias)
+    V0 = torch.stack([p, g0[:, None] * p, r, g0[:, None] * r, t, z], 1)          # [Q,6,64]
+    lw = []
+    for l in range(1, L):
+        c = core.convs[l]
+        Da, Db = c.lin_update.weight[:, :H], c.lin_update.weight[:, H:]
+        g = c._gate_value(E).reshape(-1)
+        u = _mv(Da, c.lin_com.bias).expand(Q, H)
+        lw += [g, torch.cat([(Da @ c.lin_com.weight).t(), Db.t()], 0),
+               torch.stack([u, g[:, None] * u, c.lin_update.bias.expand(Q, H)], 1)]
+    P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
+    wtp = torch.cat([P0[:, (l + 1) * H:(l + 2) * H].t() for l in range(1, L + 1)], 0)   # [64 L, 64]
+    tp = _mv(P0[:, H:2 * H], w_pre).expand(Q, H)
+    zp = E @ P0[:, :H].t() + (_mv(P0[:, H:2 * H], b_pre) + p0)
+    Vp = torch.stack([tp, zp], 1)                                                   # [Q,2,64]
+    return AG.GossipTrunkDeep.apply(batch.rowptr, batch.col, N, Q, C6, C3, C2, x.reshape(-1),
+                                    gnn.post_mp[3].weight.detach(), gnn.post_mp[5].weight.detach(), drop, L,
+                                    V0, gnn.post_mp[3].weight.t(), gnn.post_mp[3].bias, gnn.post_mp[5].weight.t(),
+                                    gnn.post_mp[5].bias, gnn.post_mp[7].weight.view(-1), gnn.post_mp[7].bias, wtp, Vp,
+                                    *lw)

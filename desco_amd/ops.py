@@ -1015,6 +1015,33 @@ def gossip_scalars(x: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, g0,
     return scal
 
 
+def gossip_layer_f16(h: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, num_nodes: int, num_q: int,
+                     g: torch.Tensor, c3: torch.Tensor, v: torch.Tensor, w: F16Planes, p: F16Planes,
+                     acc: torch.Tensor, pn: Optional[F16Planes] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One gossip layer l >= 1 (desco_gossip_layer_f16x3_f32): returns h_{l+1} = relu([hh | h] W + c3 . v[q]) and adds
+    h P (and h_{l+1} Pn when ``pn`` is given: the last layer) to ``acc`` in place.  h, acc: [N*Q, 64]; c3 [N*Q, 3];
+    v [Q, 3, 64]; w: split_f16_planes of the n-major [64, 128] weight, p / pn of the n-major [64, 64] blocks."""
+    R = num_nodes * num_q
+    assert h.shape == (R, 64) and h.is_contiguous() and acc.shape == (R, 64) and acc.is_contiguous()
+    assert c3.shape == (R, 3) and c3.is_contiguous() and v.shape == (num_q, 3, 64) and g.numel() == num_q
+    assert tuple(w.shape) == (2, 64, 128) and tuple(p.shape) == (2, 64, 64) and (pn is None or tuple(pn.shape) == (2, 64, 64))
+    if out is None:
+        out = torch.empty_like(h)
+    E = col.numel()
+    with _Timed("gossip_layer_kernel", 2.0 * 3 * R * 64 * (128 + 64 + (64 if pn is not None else 0)),
+                R * (256.0 * 4 + 12.0) + 256.0 * E * num_q + 4.0 * (E + num_nodes + 1)):
+        _lib.check(_lib.lib().desco_gossip_layer_f16x3_f32(
+            _dev(h, "h"), _dev(rowptr, "rowptr", torch.int32), _dev(col, "col", torch.int32), num_nodes, num_q,
+            _dev(g.contiguous(), "g"), _dev(c3, "c3"), _dev(v.contiguous(), "v"),
+            _dev(w.planes, "w.planes", torch.int16), _dev(w.scale, "w.scale"),
+            _dev(p.planes, "p.planes", torch.int16), _dev(p.scale, "p.scale"),
+            None if pn is None else _dev(pn.planes, "pn.planes", torch.int16),
+            None if pn is None else _dev(pn.scale, "pn.scale"),
+            _dev(acc, "acc"), _dev(out, "out"), _stream()), "gossip_layer_f16x3")
+    return out
+
+
 # executed MFMA flops per (node, query) row of the fused gossip kernel: K=128,128,64 (N=64), 64 (N=256)
 GOSSIP_FUSED_FLOPS_PER_ROW = 2.0 * 64 * (128 + 128 + 64) + 2.0 * 64 * 256
 
@@ -1103,10 +1130,13 @@ def gossip_fused_f16(scal: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor
     return out
 
 
-def rowdot_add(y: torch.Tensor, w: torch.Tensor, b: float, add: Optional[torch.Tensor]):
-    """out[r] = add[r] + y[r,:] . w + b"""
+def rowdot_add(y: torch.Tensor, w: torch.Tensor, b: float, add: Optional[torch.Tensor],
+               out: Optional[torch.Tensor] = None):
+    """out[r] = add[r] + y[r,:] . w + b   (``out``: a contiguous [R] tensor to write, else a new one)"""
     R, n = y.shape
-    out = torch.empty((R,), device=y.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((R,), device=y.device, dtype=torch.float32)
+    assert out.shape == (R,) and out.is_contiguous()
     yp, ldy = _rows(y, "y")
     L = _lib.lib()
     with _Timed("rowdot_add_kernel", 2.0 * R * n, 4.0 * (R * n + 2 * R)):

@@ -548,6 +548,26 @@ int desco_gossip_fused_f16x3_f32(const float* scal4, const int32_t* rowptr, cons
  * The result does not depend on it bit for bit (every row's sum keeps its own CSR order). */
 int desco_gossip_tile_order(const int32_t* rowptr, int64_t num_nodes, uint8_t* tile_perm, desco_stream_t stream);
 
+/* One GossipConv layer l >= 1 of a gossip model of any depth (--gossip_layer_num != 2), over all
+ * R = num_nodes * num_q rows (node i, query q) = row i * num_q + q, all matrices rows of 64 floats:
+ *   hh[r]   = sum_{j in N(i), CSR order} (j < i ? g[q] : 1 - g[q]) h[j * num_q + q]      (message + aggregate)
+ *   out[r]  = relu([hh[r] | h[r]] W + c3[r, 0:3] . v[q, 0:3, :])                         (lin_com folded into
+ *             lin_update, the per-query affine term: c3 = (deg_hi, deg_lo - deg_hi, 1), v = (u, g u, d))
+ *   acc[r] += h[r] P  (+ out[r] Pn when pn_planes is given: the last layer)               (post_mp.0 blocks)
+ * -- gnn_model.py:255-277, 303-350 of the reference (GossipConv.forward, the layer loop), and the h_l blocks of
+ * post_mp.0 (:44, 102).  W = [(D_a C)^T; D_b^T] [128, 64], P / Pn = the post_mp.0 blocks of h_l / h_{l+1} as [64, 64]
+ * K-major matrices, each passed as the fp16 planes [2][64 (n)][K] of desco_split_f16x2_f32 of its n-major form with
+ * its {scale, 1/scale}; the products run in the three-product f16x3 form (fp32 accuracy).  h, acc, out and the
+ * planes 16-byte aligned; out, acc and h distinct (acc is read and written in place).  Results are bit-reproducible
+ * and do not depend on the launch's tiling (every row's sum keeps its CSR order).  No host sync, no state of its own:
+ * capturable in a hipGraph.  Bytes per row: 256 (h) + 256 per neighbour row + 256 (out) + 512 (acc) + 12 (c3), plus
+ * the CSR. */
+int desco_gossip_layer_f16x3_f32(const float* h, const int32_t* rowptr, const int32_t* col, int64_t num_nodes,
+                                 int num_q, const float* g, const float* c3, const float* v, const int16_t* w_planes,
+                                 const float* w_scale, const int16_t* p_planes, const float* p_scale,
+                                 const int16_t* pn_planes, const float* pn_scale, float* acc, float* out,
+                                 desco_stream_t stream);
+
 /* K21 tail: out[r] = add[r] + sum_c y[r,c]*w[c] + b   (post_mp.7 with output_dim 1, then
  * pred = neigh_pred + gossip_pred, lightning_model.py:622-625) */
 int desco_rowdot_add_f32(const float* y, int64_t ldy, int ncols, const float* w, float b,
