@@ -140,10 +140,14 @@ __device__ __forceinline__ void gemm_split_body(const GemmSplitArgs& g, const in
 #define DESCO_POOL_ROW(j_, r_)                                                                                  \
   {                                                                                                             \
     const int a_ = g.seg_ptr[r_], e_ = g.seg_ptr[(r_) + 1];                                                     \
-    const int t0_ = a_ >> 4, t1_ = (e_ - 1) >> 4, f_ = a_ - (t0_ << 4);                                         \
-    so##j_##0 = (g.pool_slot[t0_] + __popc(g.pool_bits[t0_] & ((1u << f_) - 1u))) * 64;                         \
-    so##j_##1 = t1_ > t0_ ? g.pool_slot[t0_ + 1] * 64 : -1;                                                     \
-    so##j_##2 = t1_ > t0_ + 1 ? g.pool_slot[t0_ + 2] * 64 : -1;                                                 \
+    if (e_ > a_) {                          /* (a segment without rows has no slots: the zero-row path) */      \
+      const int t0_ = a_ >> 4, t1_ = (e_ - 1) >> 4, f_ = a_ - (t0_ << 4);                                       \
+      so##j_##0 = (g.pool_slot[t0_] + __popc(g.pool_bits[t0_] & ((1u << f_) - 1u))) * 64;                       \
+      so##j_##1 = t1_ > t0_ ? g.pool_slot[t0_ + 1] * 64 : -1;                                                   \
+      so##j_##2 = t1_ > t0_ + 1 ? g.pool_slot[t0_ + 2] * 64 : -1;                                               \
+    } else {                                                                                                    \
+      so##j_##0 = so##j_##1 = so##j_##2 = -1;                                                                   \
+    }                                                                                                           \
     nb##j_ = (float)(e_ - a_);                                                                                  \
   }
     DESCO_POOL_ROW(0, r0) DESCO_POOL_ROW(1, r1) DESCO_POOL_ROW(2, r2) DESCO_POOL_ROW(3, r3)
@@ -166,7 +170,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmSplitArgs& g, const in
 // POOLA: the partial rows of chunk kk_ (layer l = kk_ / 64; block 0 has none: its term is rows(b) * x0)
 #define DESCO_LOAD_Q1(d_, j_, P_)                                                             \
   {                                                                                           \
-    d_##j_##0 = *reinterpret_cast<const float4*>((P_) ? (P_) + so##j_##0 : zr_);              \
+    d_##j_##0 = *reinterpret_cast<const float4*>((P_) && so##j_##0 >= 0 ? (P_) + so##j_##0 : zr_);  \
     d_##j_##1 = *reinterpret_cast<const float4*>((P_) && so##j_##1 >= 0 ? (P_) + so##j_##1 : zr_);  \
     d_##j_##2 = *reinterpret_cast<const float4*>((P_) && so##j_##2 >= 0 ? (P_) + so##j_##2 : zr_);  \
   }

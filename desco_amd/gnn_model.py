@@ -513,16 +513,22 @@ def _first_layer_coef(pk, t, su, S, x0, src_of_slot, dev):
     return pk[ck]
 
 
-def _anchor_const_input(pk, gnn, canon, row_bound=None):
-    """anchor_mlp (gnn_model.py:69-73) on emb["canonical"] when the input layer is constant (all-zero node
-    features: x^0 of every canonical row is pre_mp's bias): the first 64-column block of the operand is the
-    same row for every neighborhood, so its product is folded into the bias and the GEMM runs with
-    K = 512 instead of 576 (one ninth of the largest dense product of the pass)."""
+def _anchor_const_input_weights(pk, gnn):
+    """anchor_mlp's weight planes without the first 64 columns and its bias with their product folded in (once per
+    weight version)"""
     if "anchor_nk_const" not in pk:
         w, b = gnn.anchor_mlp[0].weight, gnn.anchor_mlp[0].bias
         x0 = pk["pre"]["canonical"][1]
         _split = ops.split_f16_planes if GEMM_F16X3 else ops.split_bf16_planes
         pk["anchor_nk_const"] = (_split(w[:, H:].contiguous()), (b + _mv(w[:, :H], x0)).contiguous())
+
+
+def _anchor_const_input(pk, gnn, canon, row_bound=None):
+    """anchor_mlp (gnn_model.py:69-73) on emb["canonical"] when the input layer is constant (all-zero node
+    features: x^0 of every canonical row is pre_mp's bias): the first 64-column block of the operand is the
+    same row for every neighborhood, so its product is folded into the bias and the GEMM runs with
+    K = 512 instead of 576 (one ninth of the largest dense product of the pass)."""
+    _anchor_const_input_weights(pk, gnn)
     kw = {"row_scale": row_bound} if (row_bound is not None and isinstance(pk["anchor_nk_const"][0], ops.F16Planes)) else {}
     return _gemm_planes(canon[:, H:], *pk["anchor_nk_const"], act=ops.ACT_LEAKY, slope=0.1, **kw)
 
@@ -536,6 +542,10 @@ FIRST_LAYER_TABLE = os.environ.get("DESCO_FIRST_LAYER_TABLE", "1") != "0"
 # the pooled embeddings [B, 64 (L + 1)] are never written: post_mp.0 forms its operand's chunks from the anchor rows and
 # the fused pooling's partial sums in its load phase (desco_pool_post_bf16x6_f32; neighborhoods of at most 33 count rows)
 POOL_POST_FUSED = os.environ.get("DESCO_POOL_POST_FUSED", "1") != "0"
+
+# ... and with the anchor MLP in the same launch (desco_anchor_pool_post_f16x3_f32): the anchor rows [B, 64 (L + 1)] are
+# never written either (f16x3 anchor on the producer-written row bound, first block folded, L in {2, 5, 8})
+ANCHOR_POST_FUSED = os.environ.get("DESCO_ANCHOR_POST_FUSED", "1") != "0"
 
 
 def shmp_forward(gnn: BaseGNN, batch) -> torch.Tensor:
@@ -695,6 +705,17 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
         else:
             canon = torch.cat([c0] + [xl[Nc:] for xl in X[1:]], dim=1)        # emb["canonical"] [B,P]
         aw, ab = pk["anchor"]
+        pool_post = (fuse_post0 and POOL_POST_FUSED and const_input and first == 1 and GEMM_BF16X6 and "post_nk" in pk
+                     and sorted(pool_parts) == list(range(1, core.layer_num + 1)) and core.layer_num <= 8
+                     and batch.max_count_rows() <= 33)
+        if (pool_post and ANCHOR_POST_FUSED and folded_x0 and canon_max is not None and GEMM_F16X3
+                and core.layer_num in (2, 5, 8)):
+            _anchor_const_input_weights(pk, gnn)
+            aw16, ab16 = pk["anchor_nk_const"]
+            w0, b0 = pk["post_nk"][0]
+            return _PostMp0(ops.anchor_pool_post(canon[:, H:], aw16, ab16, canon_max,
+                                                 [pool_parts[l] for l in range(1, core.layer_num + 1)], pbits, pslot,
+                                                 batch.count_ptr, x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1))
         if folded_x0:
             anch = _anchor_const_input(pk, gnn, canon, row_bound=canon_max)
         elif GEMM_BF16X6:
@@ -705,9 +726,7 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
     else:
         anch = None                                  # query graphs: no canonical node, no anchor
         seg_ptr = batch.graph_ptr
-    if (fuse_post0 and POOL_POST_FUSED and anch is not None and const_input and first == 1 and GEMM_BF16X6
-            and "post_nk" in pk and sorted(pool_parts) == list(range(1, core.layer_num + 1)) and core.layer_num <= 8
-            and batch.max_count_rows() <= 33):
+    if anch is not None and pool_post:
         w0, b0 = pk["post_nk"][0]
         return _PostMp0(ops.pool_post(anch, [pool_parts[l] for l in range(1, core.layer_num + 1)], pbits, pslot, seg_ptr,
                                       x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1))

@@ -587,6 +587,36 @@ def pool_post(anch: torch.Tensor, parts, bits: torch.Tensor, slot: torch.Tensor,
     return out
 
 
+def anchor_pool_post(a: torch.Tensor, anchor_w: "F16Planes", anchor_bias: torch.Tensor, row_scale: torch.Tensor, parts,
+                     bits: torch.Tensor, slot: torch.Tensor, seg_ptr: torch.Tensor, x0: torch.Tensor,
+                     w_planes: torch.Tensor, bias: torch.Tensor, act: int, slope: float) -> torch.Tensor:
+    """``pool_post(gemm_f16x3(a, anchor_w, anchor_bias, act=act, slope=slope, row_scale=row_scale), ...)`` in one launch
+    (desco_anchor_pool_post_f16x3_f32): the anchor rows are never written.  Bit-identical to the two calls.  ``parts`` =
+    the pooled layers' partial arrays (layers 1..L, L in {2, 5, 8}); ``w_planes`` = split_bf16_planes(W0)
+    [3, 64, 64 (L + 1)]; the anchor weight [64 (L + 1), k] with k = 64 L or 64 (L + 1).  Every segment must span at
+    most three 16-row tiles."""
+    B, k = a.shape[0], a.shape[1]
+    L = len(parts)
+    n = 64 * (L + 1)
+    assert isinstance(anchor_w, F16Planes) and tuple(anchor_w.planes.shape) == (2, n, k)
+    assert tuple(w_planes.shape) == (3, 64, n) and w_planes.is_contiguous()
+    assert x0.is_contiguous() and x0.numel() == 64 and anchor_bias.is_contiguous() and anchor_bias.numel() == n
+    out = torch.empty((B, 64), device=a.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    ap, lda = _rows(a, "a")
+    pa = (ctypes.c_void_p * L)(*[_dev(p_, "pool_part") for p_ in parts])
+    with _Timed("anchor_pool_post_kernel", 2.0 * B * k * n + 2.0 * B * 64 * n,
+                4.0 * B * (k + 64 + 1) + sum(256.0 * p_.shape[0] for p_ in parts)):
+        _lib.check(_lib.lib().desco_anchor_pool_post_f16x3_f32(
+            ap, lda, k, _dev(anchor_w.planes, "anchor_w", torch.int16), _dev(anchor_w.scale, "anchor_scale"),
+            _dev(anchor_bias, "anchor_bias"), act, slope, _dev(row_scale, "row_scale"), L,
+            _dev(w_planes, "w_planes", torch.int16), _dev(bias.contiguous(), "bias"), act, slope, _dev(out, "out"), 64, B,
+            _dev(seg_ptr, "seg_ptr", torch.int32), _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32),
+            pa, _dev(x0, "x0"), 16, _stream()), "anchor_pool_post")
+    return out
+
+
 def post_mp_tail(x: torch.Tensor, w1, b1, w2, b2, w3, b3, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """W3 relu(W2 relu(W1 x + b1) + b2) + b3 for the [64 -> 64 -> 256 -> 64] tail of post_mp in one launch
     (desco_post_mp_tail_f16x3_f32); the weights as ``split_f16_planes`` of the [out, in] matrices."""

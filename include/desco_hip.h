@@ -382,11 +382,28 @@ int desco_pool_reduce_multi_f32(int num, const float* const* pool_parts, const u
  *   c[b, 0:64] = act( operand[b, :] * W^T + bias ),  W as desco_split_bf16x3_f32 planes [3][64][64 (L + 1)].
  * anch: [m, >= 64 (L + 1)]; parts: HOST array of the L layers' DEVICE partial arrays; seg_ptr / pool_bits / pool_slot: the
  * fused pooling's index for 16-row tiles.  EVERY SEGMENT MUST LIE IN AT MOST THREE TILES (<= 33 rows; the caller checks:
- * further tiles are ignored).  Saves the write and the read of the pooled [m, 64 (L + 1)] tensor. */
+ * further tiles are ignored); a segment without rows adds no partial rows.  Saves the write and the read of the pooled
+ * [m, 64 (L + 1)] tensor. */
 int desco_pool_post_bf16x6_f32(const float* anch, int64_t lda, int num_layers, const int16_t* w_planes, int n,
                                const float* bias, int act, float slope, float* c, int64_t ldc, int64_t m,
                                const int32_t* seg_ptr, const uint32_t* pool_bits, const int32_t* pool_slot,
                                const float* const* parts, const float* x0, int tile_rows, desco_stream_t stream);
+
+/* The anchor MLP and desco_pool_post_bf16x6_f32 in ONE launch: anch = act(a[:, 0:k] * Wa^T + anchor_bias) on the f16x3
+ * pipe (desco_gemm_f16x3_f32's arithmetic, bit for bit: anchor_planes / anchor_scale from desco_split_f16x2_f32 of the
+ * [64 (L + 1), k] weight, row_scale = a bound of each row's largest |a|), then out[b, 0:64] = post_act( operand[b, :] *
+ * W0^T + post_bias ) with the operand of desco_pool_post_bf16x6_f32 formed from anch (post_planes: desco_split_bf16x3_f32
+ * planes [3][64][64 (L + 1)]).  anch is never written; out is bit-identical to desco_gemm_f16x3_f32 followed by
+ * desco_pool_post_bf16x6_f32.  num_layers L in {2, 5, 8} (the anchor's 64 (L + 1) columns are whole 192-column tiles);
+ * k = 64 L (the constant first block folded into anchor_bias) or 64 (L + 1); tile_rows 16; m < 2^24.  A segment must lie
+ * in at most three 16-row tiles (<= 33 rows: further tiles are ignored); a segment without rows adds no partial rows. */
+int desco_anchor_pool_post_f16x3_f32(const float* a, int64_t lda, int k, const int16_t* anchor_planes,
+                                     const float* anchor_scale, const float* anchor_bias, int act, float slope,
+                                     const float* row_scale, int num_layers, const int16_t* post_planes,
+                                     const float* post_bias, int post_act, float post_slope, float* out, int64_t ldo,
+                                     int64_t m, const int32_t* seg_ptr, const uint32_t* pool_bits,
+                                     const int32_t* pool_slot, const float* const* parts, const float* x0,
+                                     int tile_rows, desco_stream_t stream);
 
 /* post_mp.3 -> ReLU -> post_mp.5 -> ReLU -> post_mp.7 (gnn_model.py:44-53: Linear(64, 64), Linear(64, 256), Linear(256, 64))
  * in one launch:  out[i, 0:64] = W3 relu(W2 relu(W1 x[i, 0:64] + b1) + b2) + b3.  A row is read once and written once;
