@@ -987,3 +987,55 @@ class FoldGossip(torch.autograd.Function):
             g[f"G0_{i}"], g[f"gb0_{i}"] = G["dG0"][i], G["dgb0"][i]
             g[f"g2_{i}"], g[f"gb2_{i}"] = G["dg2"][i].view(1, -1), G["dgb2"][i]
         return (None, None, None) + tuple(g[n] for n in _GF_ORDER)
+
+
+# ---- neighborhood models of other widths than 64 (gnn_model.shmp_forward_train_wide) -----------------------------------
+class GatherSumWide(torch.autograd.Function):
+    """GatherSum for rows of any width W % 4 == 0 up to 256 (desco_csr_gather_sum_wide_f32, both directions)."""
+
+    @staticmethod
+    def forward(ctx, x, vrowptr, vcol, t_rowptr, t_col, num_rows, slots):
+        ctx.save_for_backward(t_rowptr, t_col)
+        ctx.n_src, ctx.width = x.shape[0], x.shape[1]
+        return ops.csr_gather_sum_wide(x.contiguous(), vrowptr, vcol, num_rows, slots)
+
+    @staticmethod
+    def backward(ctx, dagg):
+        t_rowptr, t_col = ctx.saved_tensors
+        d = dagg.contiguous().view(-1, ctx.width)              # [num_rows*slots, W] virtual rows
+        dx = ops.csr_gather_sum_wide(d, t_rowptr, t_col, ctx.n_src, 1)
+        return dx, None, None, None, None, None, None
+
+
+class SegmentSumWide(torch.autograd.Function):
+    """SegmentSum for rows of any width W % 4 == 0 up to 256 (backward: desco_csr_gather_sum_wide_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, seg_ptr, seg_id, ident_ptr, extra):
+        ctx.save_for_backward(seg_id, ident_ptr)
+        ctx.has_extra = extra is not None
+        return ops.segment_sum(x.contiguous(), seg_ptr, seg_ptr.numel() - 1, extra=extra)
+
+    @staticmethod
+    def backward(ctx, dout):
+        seg_id, ident_ptr = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = ops.csr_gather_sum_wide(dout, ident_ptr, seg_id, seg_id.numel(), 1)   # dx[r] = dout[seg(r)]
+        return dx, None, None, None, (dout if ctx.has_extra else None)
+
+
+class CountHeadWide(torch.autograd.Function):
+    """CountHead for hidden widths up to 1024 (desco_count_head_wide_f32; backward desco_count_head_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, t, qh, w2, b2, slope):
+        ctx.save_for_backward(t, qh, w2)
+        ctx.slope = slope
+        return ops.count_head_wide(t, qh, w2, b2, slope, False)
+
+    @staticmethod
+    def backward(ctx, dl):
+        t, qh, w2 = ctx.saved_tensors
+        dt, dqh, dw2 = ops.count_head_bwd(t, qh, w2, ctx.slope, dl)
+        db2 = ops.colsum(dl.contiguous().view(-1, 1)).view(())
+        return dt, dqh, dw2, db2, None

@@ -92,11 +92,27 @@ QUERY_EDGE_TYPES_TCONV = [
 QUERY_EDGE_TYPES_UNION = [("union_node", "union", "union_node")]
 
 
-def _require_hidden(hidden_dim):
-    if hidden_dim != H:
-        raise NotImplementedError(
-            f"desco_amd kernels are specialised for hidden_dim == {H} (reference default, "
-            f"config.py:250); got {hidden_dim}")
+# widths of the neighborhood / query models (--neigh_hidden_dim): H == 64 runs the fused kernels; any other width up to
+# MAX_HIDDEN runs the wide path (shmp_forward_wide) on operands zero-padded to padded_width(H)
+MAX_HIDDEN = 256
+
+
+def padded_width(h: int) -> int:
+    """the width the kernels see: 64 ceil(h / 64)"""
+    return 64 * ((int(h) + 63) // 64)
+
+
+def _require_hidden(hidden_dim, conv_type="SAGE", emb_channels=None):
+    if conv_type == "GOSSIP":
+        if hidden_dim != H:
+            raise NotImplementedError(
+                f"--gossip_hidden_dim must be {H} (the gossip kernels are specialised for it); got {hidden_dim}")
+        if emb_channels is not None and not 1 <= int(emb_channels) <= MAX_HIDDEN:
+            raise NotImplementedError(
+                f"--neigh_hidden_dim (the gossip model's emb_channels) must be in 1..{MAX_HIDDEN}; got {emb_channels}")
+        return
+    if not 1 <= int(hidden_dim) <= MAX_HIDDEN:
+        raise NotImplementedError(f"--neigh_hidden_dim must be in 1..{MAX_HIDDEN}; got {hidden_dim}")
 
 
 class SAGEConv(nn.Module):
@@ -191,7 +207,8 @@ class BaseGNNCore(nn.Module):
 
     def __init__(self, input_dim, hidden_dim, output_dim, args, **kwargs):
         super().__init__()
-        _require_hidden(hidden_dim)
+        _require_hidden(hidden_dim, args.conv_type, kwargs.get("emb_channels"))
+        self.hidden_dim = hidden_dim
         self.dropout = args.dropout
         self.layer_num = args.layer_num
         self.conv_type = args.conv_type
@@ -229,12 +246,13 @@ class BaseGNNCore(nn.Module):
         if self.node_types is not None:
             raise RuntimeError("model is already heterogeneous")
         in_dim = self.pre_mp[0].in_features
-        self.pre_mp = nn.Sequential(nn.ModuleDict({t: nn.Linear(in_dim, H) for t in node_types}))
+        hd = self.hidden_dim
+        self.pre_mp = nn.Sequential(nn.ModuleDict({t: nn.Linear(in_dim, hd) for t in node_types}))
         self.convs = nn.ModuleList([
-            nn.ModuleDict({"__".join(et): SAGEConv(H, H) for et in edge_types})
+            nn.ModuleDict({"__".join(et): SAGEConv(hd, hd) for et in edge_types})
             for _ in range(self.layer_num)])
         self.updates = nn.ModuleList([
-            nn.ModuleDict({t: nn.Linear(2 * H, H) for t in node_types})
+            nn.ModuleDict({t: nn.Linear(2 * hd, hd) for t in node_types})
             for _ in range(self.layer_num)])
         self.node_types, self.edge_types = list(node_types), [tuple(e) for e in edge_types]
         return self
@@ -349,7 +367,8 @@ class BaseGNN(nn.Module):
         ver = self._param_version()
         if self._pack_cache is None or self._pack_cache[0] != ver:
             with torch.no_grad():
-                pk = pack_gossip(self) if self.conv_type == "GOSSIP" else pack_shmp(self)
+                pk = pack_gossip(self) if self.conv_type == "GOSSIP" else \
+                    (pack_shmp_wide(self) if self.is_wide() else pack_shmp(self))
             self._pack_cache = (ver, pk)
         return self._pack_cache[1]
 
@@ -366,9 +385,22 @@ class BaseGNN(nn.Module):
             raise NotImplementedError(
                 "homogeneous SAGE (ablation, hetero_graph=False) is out of the hot path; call "
                 "to_hetero_old()/to_hetero() first (main.py:221-224)")
+        if self.is_wide():
+            # (the padded channels are exactly zero: callers see the true width)
+            return self.forward_padded(data, drop_key)[:, :self.output_dim]
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return shmp_forward_train(self, data, drop_key)
         return shmp_forward(self, data)
+
+    def is_wide(self) -> bool:
+        """True for a SAGE model of another width than 64: it runs the wide path (shmp_forward_wide)"""
+        return self.conv_type != "GOSSIP" and self.gnn_core.hidden_dim != H
+
+    def forward_padded(self, data, drop_key=None) -> torch.Tensor:
+        """wide path: the graph embeddings [B, padded_width(output_dim)] (zero beyond output_dim)"""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return shmp_forward_train_wide(self, data, drop_key)
+        return shmp_forward_wide(self, data)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -906,14 +938,217 @@ def _post_mp_train(AG, pk, gnn, pooled, drop):
 
 
 # -------------------------------------------------------------------------------------------------
+# neighborhood / query models of other widths than 64 (the wide path, DESIGN.md 4.5)
+# -------------------------------------------------------------------------------------------------
+# the wide layers as one fused launch per node-type group and layer (desco_shmp_layer_wide_f16x3_f32); False: the
+# gather (desco_csr_gather_sum_wide_f32) + f16x3 GEMM form, for A/B runs and as the fused kernel's cross-check
+SHMP_WIDE_FUSED = os.environ.get("DESCO_SHMP_WIDE_FUSED", "1") != "0"
+
+
+def _pad_blocks(w: torch.Tensor, h: int, wp: int, nrow: int, ncol: int) -> torch.Tensor:
+    """[nrow h, ncol h] -> [nrow wp, ncol wp]: every h x h block zero-padded on its own (differentiable)"""
+    w4 = w.reshape(nrow, h, ncol, h)
+    return torch.nn.functional.pad(w4, (0, wp - h, 0, 0, 0, wp - h)).reshape(nrow * wp, ncol * wp)
+
+
+def _pad_to(w: torch.Tensor, *shape) -> torch.Tensor:
+    """zero-pad w at the end of every dimension to ``shape`` (differentiable)"""
+    pads = []
+    for d in reversed(range(w.dim())):
+        pads += [0, shape[d] - w.shape[d]]
+    return torch.nn.functional.pad(w, pads)
+
+
+def pack_shmp_wide(gnn: BaseGNN, planes: bool = True) -> dict:
+    """The operands of pack_shmp for a model of width h != 64, zero-padded to wp = padded_width(h) block by block
+    (pre_mp rows, every slot block and the self block of a folded layer weight, every layer block of the anchor and of
+    post_mp.0), so that the padded channels are exactly 0 after every activation.  K-major ([in, out]) matrices;
+    ``planes``: also the fp16 planes of the f16x3 kernels (inference).  Differentiable (training)."""
+    core = gnn.gnn_core
+    h = core.hidden_dim
+    wp = padded_width(h)
+    L = core.layer_num
+    pk = {"h": h, "wp": wp, "pre": {}, "layers": []}
+    for t in core.node_types:
+        lin = core.pre_mp[0][t]
+        pk["pre"][t] = (_pad_to(lin.weight.t(), lin.in_features, wp).contiguous(), _pad_to(lin.bias, wp).contiguous())
+    for l in range(L):
+        per_type = {}
+        for t in core.node_types:
+            U, c = core.updates[l][t].weight, core.updates[l][t].bias
+            Un, Ux = U[:, :h], U[:, h:]
+            keys = core.slot_keys(t)
+            blocks = [(Un @ core.convs[l][k].lin.weight).t() for k in keys]                 # (U_n W_s)^T
+            blocks.append(Ux.t())
+            bsum = sum(core.convs[l][k].lin.bias for k in dict.fromkeys(keys))                # one bias per edge TYPE
+            wt = _pad_blocks(torch.cat(blocks, 0), h, wp, len(blocks), 1).contiguous()      # [(S+1) wp, wp]
+            e = {"wt": wt, "b": _pad_to(_mv(Un, bsum) + c, wp).contiguous(), "slots": len(keys)}
+            if planes:
+                e["w16"] = ops.split_f16_planes(wt.t())
+            per_type[t] = e
+        pk["layers"].append(per_type)
+    if core.node_types != QUERY_NODE_TYPES:
+        aw = gnn.anchor_mlp[0]
+        pk["anchor"] = (_pad_blocks(aw.weight.t(), h, wp, L + 1, L + 1).contiguous(),
+                        torch.nn.functional.pad(aw.bias.view(L + 1, h), (0, wp - h)).reshape(-1).contiguous())
+        if planes:
+            pk["anchor16"] = ops.split_f16_planes(pk["anchor"][0].t())
+    p0 = gnn.post_mp[0]
+    n0 = padded_width(p0.out_features)
+    pk["post"] = [(_pad_to(torch.nn.functional.pad(p0.weight.t().reshape(L + 1, h, -1), (0, 0, 0, wp - h)).reshape(
+        (L + 1) * wp, -1), (L + 1) * wp, n0).contiguous(), _pad_to(p0.bias, n0).contiguous())]
+    for i in (3, 5, 7):
+        m = gnn.post_mp[i]
+        pk["post"].append((_pad_to(m.weight.t(), padded_width(m.in_features), padded_width(m.out_features)).contiguous(),
+                           _pad_to(m.bias, padded_width(m.out_features)).contiguous()))
+    return pk
+
+
+def _wide_groups(batch):
+    if isinstance(batch, NeighborhoodBatch):
+        Nc = batch.num_count
+        return Nc, [("count", 0, Nc, 4), ("canonical", Nc, batch.num_rows, 2)], batch.count_ptr
+    return batch.num_rows, [("union_node", 0, batch.num_rows, 2)], batch.graph_ptr
+
+
+def _wide_zero_feat(gnn: BaseGNN, batch, N: int, dev):
+    """ZeroNodeFeat: the all-zero input rows, made once per batch by this library's fill"""
+    feat = batch.__dict__.get("_zero_feat")
+    if feat is None or feat.shape[1] != gnn.gnn_core.input_dim:
+        feat = batch.__dict__["_zero_feat"] = ops.zeros((N, gnn.gnn_core.input_dim), dev)
+    return feat
+
+
+def shmp_forward_wide(gnn: BaseGNN, batch) -> torch.Tensor:
+    """Inference of a model of width h != 64 (BaseGNN.forward, gnn_model.py:58-109) on the zero-padded operands of
+    pack_shmp_wide -> graph embeddings [B, padded_width(output_dim)]: pre_mp (linear_smallk), per layer and node-type
+    group one desco_shmp_layer_wide_f16x3_f32 launch (the canonical launches also write their column block of the
+    anchor operand), the anchor on the f16x3 GEMM, pooling by segment_sum with the anchor block as `extra`, post_mp on
+    the fp32 GEMM."""
+    pk = gnn.packed()
+    core = gnn.gnn_core
+    wp = pk["wp"]
+    dev = batch.vrowptr.device
+    N, S, B, L = batch.num_rows, batch.slots, batch.num_graphs, core.layer_num
+    Nc, groups, seg_ptr = _wide_groups(batch)
+    nb = isinstance(batch, NeighborhoodBatch)
+    feat = batch.node_feature
+    if feat is None:
+        feat = _wide_zero_feat(gnn, batch, N, dev)
+    x = torch.empty((N, wp), device=dev)
+    for t, r0, r1, _ in groups:
+        if r1 > r0:
+            ops.linear_smallk(feat[r0:r1], *pk["pre"][t], out=x[r0:r1])                # :231
+    canon = torch.empty((B, (L + 1) * wp), device=dev) if nb else None             # emb["canonical"]
+    if nb and N > Nc:
+        ops.copy2d_multi([(x[Nc:], canon[:, :wp])])
+    X = [x]
+    for l in range(L):
+        xn = torch.empty((N, wp), device=dev)
+        cblock = canon[:, (l + 1) * wp:(l + 2) * wp] if nb else None
+        if SHMP_WIDE_FUSED:
+            for t, r0, r1, su in groups:                                               # :262-264, :273
+                if r1 > r0:
+                    e = pk["layers"][l][t]
+                    ops.shmp_layer_wide(X[-1], batch.vrowptr, batch.vcol, S, r0, r1 - r0, su, e["w16"], e["b"], out=xn,
+                                        out2=cblock if t == "canonical" else None)
+        else:
+            agg = ops.csr_gather_sum_wide(X[-1], batch.vrowptr, batch.vcol, N, S)     # [N, S wp]
+            for t, r0, r1, su in groups:
+                if r1 > r0:
+                    e = pk["layers"][l][t]
+                    ops.gemm_f16x3(agg[r0:r1, :su * wp], e["w16"], e["b"], a2=X[-1][r0:r1], act=ops.ACT_RELU,
+                                   out=xn[r0:r1])
+            if nb and N > Nc:
+                ops.copy2d_multi([(xn[Nc:], cblock)])
+        X.append(xn)
+    pooled = torch.empty((B, (L + 1) * wp), device=dev)
+    anch = ops.gemm_f16x3(canon, pk["anchor16"], pk["anchor"][1], act=ops.ACT_LEAKY, slope=0.1) if nb else None
+    for l, xl in enumerate(X):                                                         # :88-89, :107
+        ops.segment_sum(xl[:Nc], seg_ptr, B, extra=None if anch is None else anch[:, l * wp:(l + 1) * wp],
+                        out=pooled[:, l * wp:(l + 1) * wp])
+    (w0, b0), (w3, b3), (w5, b5), (w7, b7) = pk["post"]                                # :44-53
+    h = ops.gemm(pooled, w0, b0, act=ops.ACT_LEAKY, slope=0.1)
+    h = ops.gemm(h, w3, b3, act=ops.ACT_RELU)
+    h = ops.gemm(h, w5, b5, act=ops.ACT_RELU)
+    return ops.gemm(h, w7, b7)
+
+
+# dropout sites of the wide training pass: layer l's rows 2 l, post_mp.1 POST_DROP_SITE
+def wide_layer_drop_site(l: int) -> int:
+    return 2 * l
+
+
+def shmp_forward_train_wide(gnn: BaseGNN, batch, drop_key: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable twin of ``shmp_forward_wide`` -> [B, padded_width(output_dim)]: the per-op autograd composition
+    (SmallKLinear, GatherSumWide, Linear, SegmentSumWide, Linear) on the operands pack_shmp_wide pads with differentiable
+    torch ops, so that the gradients reach the true-width parameters (the padded channels get none).  --neigh_dropout:
+    the counter-based factors of ops.dropout_mask (sites wide_layer_drop_site(l) and POST_DROP_SITE of ``drop_key``)."""
+    from . import autograd as AG
+    import torch.nn.functional as F
+    core = gnn.gnn_core
+    dev = batch.vrowptr.device
+    N, S, L = batch.num_rows, batch.slots, core.layer_num
+    Nc, groups, seg_ptr = _wide_groups(batch)
+    nb = isinstance(batch, NeighborhoodBatch)
+    p_layer = float(core.dropout or 0.0) if gnn.training else 0.0
+    p_post = float(gnn.post_mp[1].p or 0.0) if gnn.training else 0.0
+    if (p_layer > 0.0 or p_post > 0.0) and drop_key is None:
+        drop_key = ops.rng_next(dev)
+    pk = pack_shmp_wide(gnn, planes=False)
+    wp = pk["wp"]
+    feat = batch.node_feature
+    if feat is None:
+        feat = _wide_zero_feat(gnn, batch, N, dev)
+    ti = batch.train_index()
+    x = torch.cat([AG.SmallKLinear.apply(feat[r0:r1], *pk["pre"][t]) for t, r0, r1, _ in groups], 0)
+    X = [x]
+    for l in range(L):
+        agg = AG.GatherSumWide.apply(X[-1], batch.vrowptr, batch.vcol, ti["t_rowptr"], ti["t_col"], N, S)
+        parts = []
+        for t, r0, r1, su in groups:
+            e = pk["layers"][l][t]
+            parts.append(AG.Linear.apply(agg[r0:r1, :su * wp], X[-1][r0:r1], e["wt"], e["b"], ops.ACT_RELU, 0.0))
+        xl = torch.cat(parts, 0)
+        if p_layer > 0.0:                                                              # gnn_model.py:274
+            xl = xl * ops.dropout_mask(ops.DropSite(drop_key, wide_layer_drop_site(l), p_layer), N, wp)
+        X.append(xl)
+    if nb:
+        canon = torch.cat([xl[Nc:] for xl in X], dim=1)
+        aw, ab = pk["anchor"]
+        anch = AG.Linear.apply(canon, None, aw, ab, ops.ACT_LEAKY, 0.1)
+        pooled = torch.cat([AG.SegmentSumWide.apply(xl[:Nc], seg_ptr, ti["seg_id"], ti["ident_ptr"],
+                                                    anch[:, l * wp:(l + 1) * wp].contiguous())
+                            for l, xl in enumerate(X)], dim=1)
+    else:
+        pooled = torch.cat([AG.SegmentSumWide.apply(xl, seg_ptr, ti["seg_id"], ti["ident_ptr"], None) for xl in X], dim=1)
+    (w0, b0), (w3, b3), (w5, b5), (w7, b7) = pk["post"]
+    h = AG.Linear.apply(pooled, None, w0, b0, ops.ACT_NONE, 0.0)
+    if p_post > 0.0:                                                                   # post_mp.1 (gnn_model.py:46)
+        h = h * ops.dropout_mask(ops.DropSite(drop_key, POST_DROP_SITE, p_post), h.shape[0], h.shape[1])
+    h = F.leaky_relu(h, 0.1)
+    h = AG.Linear.apply(h, None, w3, b3, ops.ACT_RELU, 0.0)
+    h = AG.Linear.apply(h, None, w5, b5, ops.ACT_RELU, 0.0)
+    return AG.Linear.apply(h, None, w7, b7, ops.ACT_NONE, 0.0)
+
+
+# -------------------------------------------------------------------------------------------------
 # gossip path
 # -------------------------------------------------------------------------------------------------
 # test switch: run the dropout form of the training kernels at p = 0 too (must not change a bit: factor 1 everywhere)
 DROPOUT_AT_ZERO = False
 
 
+def gossip_emb_width(core: BaseGNNCore) -> int:
+    """width of the query embeddings a gossip model reads (emb_channels = --neigh_hidden_dim, main.py:145).  The layer-0
+    input is [E | pre_mp(x)], so E's width decides where the pre_mp and h_l column blocks of lin_com / lin_update of layer
+    0 and of post_mp.0 start; H (the module constant) is the gossip model's own width."""
+    return int(core.kwargs.get("emb_channels", H))
+
+
 def pack_gossip(gnn: BaseGNN, bf16_planes: bool = True) -> dict:
     core = gnn.gnn_core
+    He = gossip_emb_width(core)
     if core.layer_num < 1 or not core.input_pattern_emb or core.input_dim != 1:
         raise NotImplementedError(
             "gossip kernels implement GossipConv layers with input_dim 1 and the query embedding as input "
@@ -932,8 +1167,8 @@ def pack_gossip(gnn: BaseGNN, bf16_planes: bool = True) -> dict:
     pk["d1"] = c1.lin_update.bias.contiguous()
     P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
     pk["P0"], pk["p0"] = P0, p0
-    pk["wtp"] = torch.cat([P0[:, 2 * H:3 * H].t(), P0[:, 3 * H:4 * H].t()], 0).contiguous()
-    pk["wsp"] = torch.stack([torch.zeros(H, device=P0.device), _mv(P0[:, H:2 * H], pk["w_pre"])]).contiguous()
+    pk["wtp"] = torch.cat([P0[:, He + H:He + 2 * H].t(), P0[:, He + 2 * H:He + 3 * H].t()], 0).contiguous()
+    pk["wsp"] = torch.stack([torch.zeros(H, device=P0.device), _mv(P0[:, He:He + H], pk["w_pre"])]).contiguous()
     pk["post"] = [_lin_t(gnn.post_mp[i]) for i in (3, 5)]
     pk["w7"] = gnn.post_mp[7].weight[0].contiguous()
     pk["b7"] = float(gnn.post_mp[7].bias[0])
@@ -956,13 +1191,14 @@ def _pack_gossip_deep(gnn: BaseGNN, pk: dict) -> dict:
     W_l = [(D_a C)^T; D_b^T]_l as fp16 planes of its n-major form, u_l = D_a c_l and d_l, and the post_mp.0 blocks P0_l
     of h_1 .. h_L (n-major [64, 64] = the block of the torch weight as it is stored)."""
     core = gnn.gnn_core
+    He = gossip_emb_width(core)
     L = core.layer_num
     c0 = core.convs[0]
     pk["C0"], pk["c0"] = c0.lin_com.weight, c0.lin_com.bias
     pk["D0"], pk["d0"] = c0.lin_update.weight, c0.lin_update.bias
     P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
     pk["P0"], pk["p0"] = P0, p0
-    pk["wsp"] = torch.stack([torch.zeros(H, device=P0.device), _mv(P0[:, H:2 * H], pk["w_pre"])]).contiguous()
+    pk["wsp"] = torch.stack([torch.zeros(H, device=P0.device), _mv(P0[:, He:He + H], pk["w_pre"])]).contiguous()
     layers = []
     for l in range(1, L):
         c = core.convs[l]
@@ -971,9 +1207,9 @@ def _pack_gossip_deep(gnn: BaseGNN, pk: dict) -> dict:
         layers.append({"w": ops.split_f16_planes(w_nk), "u": _mv(Da, c.lin_com.bias).contiguous(),
                        "d": c.lin_update.bias.contiguous()})
     pk["deep"] = layers
-    pk["deep_p"] = [ops.split_f16_planes(P0[:, (l + 1) * H:(l + 2) * H].contiguous()) for l in range(1, L + 1)]
+    pk["deep_p"] = [ops.split_f16_planes(P0[:, He + l * H:He + (l + 1) * H].contiguous()) for l in range(1, L + 1)]
     if L == 1:      # h1 . P0_1 on the fp32 matrix pipe (no gossip layer to carry it)
-        pk["p1t"] = P0[:, 2 * H:3 * H].t().contiguous()
+        pk["p1t"] = P0[:, He + H:He + 2 * H].t().contiguous()
     pk["post"] = [_lin_t(gnn.post_mp[i]) for i in (3, 5)]
     pk["w7"] = gnn.post_mp[7].weight[0].contiguous()
     pk["b7"] = float(gnn.post_mp[7].bias[0])
@@ -989,21 +1225,22 @@ def _gossip_query_terms_deep(gnn: BaseGNN, pk: dict, query_emb: torch.Tensor) ->
     if pk["qcache"] is not None and pk["qcache"][0] == key:
         return pk["qcache"][1]
     core = gnn.gnn_core
+    He = gossip_emb_width(core)
     E = query_emb.float()
     Q = E.shape[0]
     C0, D0 = pk["C0"], pk["D0"]
     w_pre, b_pre = pk["w_pre"], pk["b_pre"]
     q = {"g": [c._gate_value(E).reshape(-1).contiguous() for c in core.convs]}
-    a_q = E @ C0[:, :H].t() + (_mv(C0[:, H:], b_pre) + pk["c0"])
-    v = _mv(C0[:, H:], w_pre)
-    D0a, D0b, D0c = D0[:, :H], D0[:, H:2 * H], D0[:, 2 * H:]
+    a_q = E @ C0[:, :He].t() + (_mv(C0[:, He:], b_pre) + pk["c0"])
+    v = _mv(C0[:, He:], w_pre)
+    D0a, D0b, D0c = D0[:, :H], D0[:, H:H + He], D0[:, H + He:]
     p = a_q @ D0a.t()
     r = _mv(D0a, v).expand(Q, H)
     t = _mv(D0c, w_pre).expand(Q, H)
     z = E @ D0b.t() + (_mv(D0c, b_pre) + pk["d0"])
     q["V0"] = torch.stack([p, r, t, z], 1).contiguous()                               # [Q,4,64]
     P0 = pk["P0"]
-    zp = E @ P0[:, :H].t() + (_mv(P0[:, H:2 * H], b_pre) + pk["p0"])
+    zp = E @ P0[:, :He].t() + (_mv(P0[:, He:He + H], b_pre) + pk["p0"])
     zero = torch.zeros_like(zp)
     q["Vacc"] = torch.stack([zero, zero, pk["wsp"][1].expand(Q, H), zp], 1).contiguous()
     q["V"] = [torch.stack([e["u"].expand(Q, H), g[:, None] * e["u"], e["d"].expand(Q, H)], 1).contiguous()
@@ -1091,21 +1328,22 @@ def _gossip_query_terms(gnn: BaseGNN, pk: dict, query_emb: torch.Tensor) -> dict
     if pk["qcache"] is not None and pk["qcache"][0] == key:
         return pk["qcache"][1]
     core = gnn.gnn_core
+    He = gossip_emb_width(core)
     E = query_emb.float()
     C0, D0 = pk["C0"], pk["D0"]
     w_pre, b_pre = pk["w_pre"], pk["b_pre"]
     q = {}
     q["g0"] = core.convs[0]._gate_value(E).reshape(-1).contiguous()          # gnn_model.py:340
     q["g1"] = core.convs[1]._gate_value(E).reshape(-1).contiguous()
-    a_q = E @ C0[:, :H].t() + (_mv(C0[:, H:], b_pre) + pk["c0"])             # lin_com(h0) const part
-    v = _mv(C0[:, H:], w_pre)
-    D0a, D0b, D0c = D0[:, :H], D0[:, H:2 * H], D0[:, 2 * H:]
+    a_q = E @ C0[:, :He].t() + (_mv(C0[:, He:], b_pre) + pk["c0"])             # lin_com(h0) const part
+    v = _mv(C0[:, He:], w_pre)
+    D0a, D0b, D0c = D0[:, :H], D0[:, H:H + He], D0[:, H + He:]
     q["p"] = (a_q @ D0a.t()).contiguous()
     q["r"] = _mv(D0a, v).contiguous()
     q["t"] = _mv(D0c, w_pre).contiguous()
     q["z"] = (E @ D0b.t() + (_mv(D0c, b_pre) + pk["d0"])).contiguous()
     P0 = pk["P0"]
-    q["zp"] = (E @ P0[:, :H].t() + (_mv(P0[:, H:2 * H], b_pre) + pk["p0"])).contiguous()     # [Q,64]
+    q["zp"] = (E @ P0[:, :He].t() + (_mv(P0[:, He:He + H], b_pre) + pk["p0"])).contiguous()     # [Q,64]
     pk["qcache"] = (key, q)
     return q
 
@@ -1169,6 +1407,7 @@ def gossip_forward_train(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tens
     (gnn_model.py:236-240): ``pre_mp`` and the query embeddings receive no gradient."""
     from . import autograd as AG
     core = gnn.gnn_core
+    He = gossip_emb_width(core)
     if core.layer_num < 1 or not core.input_pattern_emb or core.input_dim != 1:
         raise NotImplementedError("gossip training implements GossipConv layers with input_dim 1 and the query "
                                   "embedding as input")
@@ -1205,7 +1444,7 @@ def gossip_forward_train(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tens
         return _gossip_train_deep(gnn, batch, E, w_pre, b_pre, C6, C3, C2, drop).view(N, Q)
     c1 = core.convs[1]
     C1, cb1, D1, db1 = c1.lin_com.weight, c1.lin_com.bias, c1.lin_update.weight, c1.lin_update.bias
-    if Q <= 64:
+    if Q <= 64 and He == H:
         # The operands folded from the parameters by one kernel each way (autograd.FoldGossip, csrc/train_native.hip;
         # algebra DESIGN.md 4.2), then the whole per-(node, query) pipeline and its backward as one autograd node
         # (autograd.GossipTrunk): the step launches nothing but this library's kernels.
@@ -1220,12 +1459,13 @@ def gossip_forward_train(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tens
                                     V0, g1, wt1, V1, wtp, Vp, w3t, gnn.post_mp[3].bias, w5t, gnn.post_mp[5].bias,
                                     gnn.post_mp[7].weight.view(-1), gnn.post_mp[7].bias)
         return pred.view(N, Q)
-    # ---- operands folded from the parameters with differentiable torch ops (more than 64 queries) ---------------------
+    # ---- operands folded from the parameters with differentiable torch ops (more than 64 queries, or query embeddings
+    #      of another width than 64) -------------------------------------------------------------------------------------
     g0 = c0._gate_value(E).reshape(-1)
     g1 = c1._gate_value(E).reshape(-1)
-    a_q = E @ C0[:, :H].t() + (_mv(C0[:, H:], b_pre) + cb0)
-    v = _mv(C0[:, H:], w_pre)
-    D0a, D0b, D0c = D0[:, :H], D0[:, H:2 * H], D0[:, 2 * H:]
+    a_q = E @ C0[:, :He].t() + (_mv(C0[:, He:], b_pre) + cb0)
+    v = _mv(C0[:, He:], w_pre)
+    D0a, D0b, D0c = D0[:, :H], D0[:, H:H + He], D0[:, H + He:]
     p = a_q @ D0a.t()
     r = _mv(D0a, v).expand(Q, H)
     t = _mv(D0c, w_pre).expand(Q, H)
@@ -1236,9 +1476,9 @@ def gossip_forward_train(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tens
     u = _mv(D1a, cb1).expand(Q, H)
     V1 = torch.stack([u, g1[:, None] * u, db1.expand(Q, H)], 1)                     # [Q,3,64]
     P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
-    wtp = torch.cat([P0[:, 2 * H:3 * H].t(), P0[:, 3 * H:4 * H].t()], 0)
-    tp = _mv(P0[:, H:2 * H], w_pre).expand(Q, H)
-    zp = E @ P0[:, :H].t() + (_mv(P0[:, H:2 * H], b_pre) + p0)
+    wtp = torch.cat([P0[:, He + H:He + 2 * H].t(), P0[:, He + 2 * H:He + 3 * H].t()], 0)
+    tp = _mv(P0[:, He:He + H], w_pre).expand(Q, H)
+    zp = E @ P0[:, :He].t() + (_mv(P0[:, He:He + H], b_pre) + p0)
     Vp = torch.stack([tp, zp], 1)                                                   # [Q,2,64]
     pred = AG.GossipTrunk.apply(batch.rowptr, batch.col, N, Q, C6, C3, C2, x.reshape(-1), (1.0 - g1).detach().contiguous(),
                                 gnn.post_mp[3].weight.detach(), gnn.post_mp[5].weight.detach(), drop,
@@ -1253,15 +1493,16 @@ def _gossip_train_deep(gnn: BaseGNN, batch: GossipBatch, E, w_pre, b_pre, C6, C3
     (the form of the more-than-64-queries branch, per layer), then autograd.GossipTrunkDeep."""
     from . import autograd as AG
     core = gnn.gnn_core
+    He = gossip_emb_width(core)
     L = core.layer_num
     x = batch.x
     N, Q = x.shape
     c0 = core.convs[0]
     C0, D0 = c0.lin_com.weight, c0.lin_update.weight
     g0 = c0._gate_value(E).reshape(-1)
-    a_q = E @ C0[:, :H].t() + (_mv(C0[:, H:], b_pre) + c0.lin_com.bias)
-    v = _mv(C0[:, H:], w_pre)
-    D0a, D0b, D0c = D0[:, :H], D0[:, H:2 * H], D0[:, 2 * H:]
+    a_q = E @ C0[:, :He].t() + (_mv(C0[:, He:], b_pre) + c0.lin_com.bias)
+    v = _mv(C0[:, He:], w_pre)
+    D0a, D0b, D0c = D0[:, :H], D0[:, H:H + He], D0[:, H + He:]
     p = a_q @ D0a.t()
     r = _mv(D0a, v).expand(Q, H)
     t = _mv(D0c, w_pre).expand(Q, H)
@@ -1276,9 +1517,9 @@ def _gossip_train_deep(gnn: BaseGNN, batch: GossipBatch, E, w_pre, b_pre, C6, C3
         lw += [g, torch.cat([(Da @ c.lin_com.weight).t(), Db.t()], 0),
                torch.stack([u, g[:, None] * u, c.lin_update.bias.expand(Q, H)], 1)]
     P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
-    wtp = torch.cat([P0[:, (l + 1) * H:(l + 2) * H].t() for l in range(1, L + 1)], 0)   # [64 L, 64]
-    tp = _mv(P0[:, H:2 * H], w_pre).expand(Q, H)
-    zp = E @ P0[:, :H].t() + (_mv(P0[:, H:2 * H], b_pre) + p0)
+    wtp = torch.cat([P0[:, He + l * H:He + (l + 1) * H].t() for l in range(1, L + 1)], 0)   # [64 L, 64]
+    tp = _mv(P0[:, He:He + H], w_pre).expand(Q, H)
+    zp = E @ P0[:, :He].t() + (_mv(P0[:, He:He + H], b_pre) + p0)
     Vp = torch.stack([tp, zp], 1)                                                   # [Q,2,64]
     return AG.GossipTrunkDeep.apply(batch.rowptr, batch.col, N, Q, C6, C3, C2, x.reshape(-1),
                                     gnn.post_mp[3].weight.detach(), gnn.post_mp[5].weight.detach(), drop, L,

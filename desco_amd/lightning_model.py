@@ -22,7 +22,7 @@ from . import ops
 from .optim import Adam
 from .batch import GossipBatch, NeighborhoodBatch, QueryBatch
 from .data import graph_atlas_plus
-from .gnn_model import (BaseGNN, H, QUERY_EDGE_TYPES_TCONV, QUERY_EDGE_TYPES_UNION,
+from .gnn_model import (BaseGNN, H, _pad_to, padded_width, QUERY_EDGE_TYPES_TCONV, QUERY_EDGE_TYPES_UNION,
                         QUERY_NODE_TYPES, TARGET_EDGE_TYPES_TCONV, TARGET_EDGE_TYPES_UNION,
                         TARGET_NODE_TYPES)
 
@@ -126,6 +126,8 @@ class _LightningLike(nn.Module):
                 m._pack_cache = None
         self._head_cache = None
         self._qemb_cache = None
+        self.__dict__.pop("_qemb_pad_cache", None)          # (the wide path's: padded query embeddings, head operands)
+        self.__dict__.pop("_head_wide_cache", None)
 
 
 # training: run the query model's trunk on a second HIP stream beside the target batch's (train_forward)
@@ -199,6 +201,8 @@ class NeighborhoodCountingModel(_LightningLike):
     def get_query_emb(self) -> torch.Tensor:                                # :311-316
         """[Q, 64] query embeddings.  The reference recomputes them on every batch (:204-207);
         they only depend on the weights, so they are cached per weight version."""
+        if self.emb_model_query.is_wide():       # (a view of the zero-padded embeddings: [Q, hidden_dim])
+            return self._query_emb_padded()[:, :self.hidden_dim]
         qb = self._queries()
         ver = self.emb_model_query._param_version()
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.emb_model_query.parameters()):
@@ -207,6 +211,63 @@ class NeighborhoodCountingModel(_LightningLike):
             with torch.no_grad():
                 self._qemb_cache = ((ver, id(qb)), self.emb_model_query(qb))
         return self._qemb_cache[1]
+
+    # ---- models of other widths than 64 (the wide path, gnn_model.shmp_forward_wide) ------------------------------
+    def _query_emb_padded(self) -> torch.Tensor:
+        """[Q, padded_width(hidden_dim)] query embeddings of the wide path, cached per weight version at inference"""
+        qb = self._queries()
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.emb_model_query.parameters()):
+            return self.emb_model_query.forward_padded(qb)
+        key = (self.emb_model_query._param_version(), id(qb))
+        c = self.__dict__.get("_qemb_pad_cache")
+        if c is None or c[0] != key:
+            with torch.no_grad():
+                c = self.__dict__["_qemb_pad_cache"] = (key, self.emb_model_query.forward_padded(qb))
+        return c[1]
+
+    def _head_wide_operands(self):
+        """count_model.0's target and query halves as K-major [wp, hid_p] matrices, its bias and count_model.2's weight
+        [hid_p], zero-padded (wp = padded_width(hidden_dim), hid_p = padded_width(4 hidden_dim)); differentiable"""
+        h = self.hidden_dim
+        W1, b1 = self.count_model[0].weight, self.count_model[0].bias
+        wp, hid = padded_width(h), padded_width(W1.shape[0])
+        return (_pad_to(W1[:, :h].t(), wp, hid).contiguous(), _pad_to(W1[:, h:].t(), wp, hid).contiguous(),
+                _pad_to(b1, hid).contiguous(), _pad_to(self.count_model[2].weight[0], hid).contiguous())
+
+    def _logits_wide(self, batch, exp2: bool) -> torch.Tensor:
+        emb_q = self._query_emb_padded()
+        emb_t = self.emb_model.forward_padded(batch)
+        ver = tuple((p.data_ptr(), p._version) for p in self.count_model.parameters())
+        c = self.__dict__.get("_head_wide_cache")
+        if c is None or c[0] != ver or c[1] is not emb_q or c[2] != emb_q._version:
+            with torch.no_grad():
+                wt_t, wt_q, b1, w2 = self._head_wide_operands()
+                c = self.__dict__["_head_wide_cache"] = (ver, emb_q, emb_q._version, wt_t, ops.gemm(emb_q, wt_q, b1), w2,
+                                                        float(self.count_model[2].bias[0]))
+        _, _, _, wt_t, Qh, w2, b2 = c
+        T = ops.gemm(emb_t, wt_t)
+        slope = self.count_model[1].negative_slope
+        out = getattr(batch, "out_buf", None) if exp2 else None
+        if out is None:
+            out = torch.empty((T.shape[0], Qh.shape[0]), device=T.device)
+        # (more than 32 queries: groups of 32, each written into its columns of the one result)
+        for q0 in range(0, Qh.shape[0], 32):
+            ops.count_head_wide(T, Qh[q0:q0 + 32], w2, b2, slope, exp2, out=out[:, q0:q0 + 32])
+        return out
+
+    def _train_forward_wide(self, batch, kq, kt) -> torch.Tensor:
+        from . import autograd as AG
+        emb_q = self.emb_model_query.forward_padded(self._queries(), drop_key=kq)
+        emb_t = self.emb_model.forward_padded(batch, drop_key=kt)
+        wt_t, wt_q, b1, w2 = self._head_wide_operands()
+        T = AG.Linear.apply(emb_t, None, wt_t, None, ops.ACT_NONE, 0.0)
+        Qh = AG.Linear.apply(emb_q, None, wt_q, b1, ops.ACT_NONE, 0.0)
+        b2 = self.count_model[2].bias.view(())
+        slope = self.count_model[1].negative_slope
+        logits = torch.cat([AG.CountHeadWide.apply(T, Qh[q0:q0 + 32].contiguous(), w2, b2, slope)
+                            for q0 in range(0, Qh.shape[0], 32)], dim=1)
+        y = batch.y if batch.y.dtype == torch.float32 else batch.y.float()
+        return AG.Loss.apply(logits, y, 0)
 
     # ---- forward ---------------------------------------------------------------------------------
     def _head_pack(self):
@@ -223,6 +284,8 @@ class NeighborhoodCountingModel(_LightningLike):
         return self._head_cache[1]
 
     def _logits(self, batch: NeighborhoodBatch, exp2: bool) -> torch.Tensor:
+        if self.emb_model.is_wide():
+            return self._logits_wide(batch, exp2)
         emb_q = self.get_query_emb()
         emb_t = self.emb_model(batch)
         hp = self._head_pack()
@@ -290,6 +353,8 @@ class NeighborhoodCountingModel(_LightningLike):
         kq = kt = None
         if self.training and self.device.type == "cuda" and float(self.emb_model.gnn_core.dropout or 0.0) > 0.0:
             kq, kt = ops.rng_next(self.device), ops.rng_next(self.device)
+        if self.emb_model.is_wide():
+            return self._train_forward_wide(batch, kq, kt)
         if OVERLAP_QUERY_TRUNK and self.device.type == "cuda" and not D.hooks_active():
             # the query model's trunk is ~100 launches on 135 rows: forward (and, through autograd, backward) on a
             # second stream, beside the target batch's launches instead of in front of them (also inside a hipGraph

@@ -1662,3 +1662,69 @@ def dropout_mask(drop: DropSite, num_rows: int, num_cols: int) -> torch.Tensor:
         _lib.check(L.desco_dropout_mask_f32(ctypes.byref(d), num_rows, num_cols, _dev(out, "out"), num_cols, _stream()),
                    "dropout_mask")
     return out
+
+
+# ---- neighborhood models of other widths than 64 (csrc/shmp_wide.hip) ----------------------------------
+def csr_gather_sum_wide(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, num_rows: int, slots: int,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """agg[i, s*W:(s+1)*W] = sum over virtual row i*slots+s of x[vcol[e], 0:W] for W = x.shape[1] (W % 4 == 0, <= 256),
+    in CSR order -> [num_rows, slots*W]"""
+    width = x.shape[1]
+    if out is None:
+        out = torch.empty((num_rows, slots * width), device=x.device, dtype=torch.float32)
+    assert out.is_contiguous() and tuple(out.shape) == (num_rows, slots * width)
+    xp, ldx = _rows(x, "x")
+    nb = 4.0 * width * (x.shape[0] + num_rows * slots) + 4.0 * (vcol.numel() + num_rows * slots + 1)
+    with _Timed("csr_gather_sum_wide_kernel", float(vcol.numel()) * width, nb):
+        if vcol.numel() == 0:       # (read only below an edge: any int32 device pointer, no fill launched)
+            vcol = vrowptr
+        _lib.check(_lib.lib().desco_csr_gather_sum_wide_f32(xp, ldx, _dev(vrowptr, "vrowptr", torch.int32),
+                                                           _dev(vcol, "vcol", torch.int32), num_rows, slots, width,
+                                                           _dev(out, "out"), width, _stream()), "csr_gather_sum_wide")
+    return out
+
+
+def shmp_layer_wide(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, vslots: int, row0: int, num_rows: int,
+                    slots: int, w: "F16Planes", bias: torch.Tensor, out: Optional[torch.Tensor] = None,
+                    out2: Optional[torch.Tensor] = None) -> None:
+    """relu([sum slot 0 | ... | sum slot S-1 | x[r]] Wt + bias) for rows [row0, row0 + num_rows) of width Wp =
+    x.shape[1] (desco_shmp_layer_wide_f16x3_f32; the CSR has ``vslots`` virtual rows per row, the first ``slots`` are
+    used); ``w`` = split_f16_planes(Wt.T) [2, Wp, (S+1) Wp].  Writes rows
+    row0.. of ``out`` and / or rows 0.. of ``out2`` (a view with unit inner stride, e.g. a column block)."""
+    width = x.shape[1]
+    assert isinstance(w, F16Planes) and tuple(w.shape) == (2, width, (slots + 1) * width)
+    xp, ldx = _rows(x, "x")
+    op, ldo = (None, 0) if out is None else _rows(out, "out")
+    o2, ld2 = (None, 0) if out2 is None else _rows(out2, "out2")
+    kk = (slots + 1) * width
+    nb = 4.0 * width * (num_rows * (2 + (out is not None) + (out2 is not None))) + 4.0 * (num_rows * slots + 1)
+    with _Timed("shmp_layer_wide_kernel", 2.0 * num_rows * kk * width, nb):
+        if vcol.numel() == 0:       # (read only below an edge: any int32 device pointer, no fill launched)
+            vcol = vrowptr
+        _lib.check(_lib.lib().desco_shmp_layer_wide_f16x3_f32(
+            xp, ldx, _dev(vrowptr, "vrowptr", torch.int32), _dev(vcol, "vcol", torch.int32), int(vslots), int(row0), int(num_rows),
+            slots, width, _dev(w.planes, "w", torch.int16), _dev(w.scale, "w_scale"), _dev(bias.contiguous(), "bias"),
+            op, ldo, o2, ld2, _stream()), "shmp_layer_wide")
+
+
+def count_head_wide(t: torch.Tensor, qh: torch.Tensor, w2: torch.Tensor, b2, slope: float,
+                    exp2_minus_1: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``count_head`` for hidden widths up to 1024 (desco_count_head_wide_f32; hid % 64 == 0, <= 32 queries).
+    ``out``: optional [B, Q] destination with unit inner stride (e.g. a column slice of a wider result)."""
+    B, hid = t.shape
+    Q = qh.shape[0]
+    if out is None:
+        out = torch.empty((B, Q), device=t.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, Q) or (Q > 1 and out.stride(1) != 1):
+        raise ValueError("count_head_wide: `out` must be a [B, Q] tensor with unit inner stride")
+    tp, ldt = _rows(t, "t")
+    qp, ldq = _rows(qh, "qh")
+    op, ldo = _rows(out, "out")
+    with _Timed("count_head_wide_kernel", 4.0 * B * Q * hid, 4.0 * (B * hid + Q * hid + B * Q)):
+        b2_dev = None
+        if isinstance(b2, torch.Tensor):
+            b2_dev, b2 = _dev(b2.detach().reshape(1).contiguous(), "b2"), 0.0
+        _lib.check(_lib.lib().desco_count_head_wide_f32(tp, ldt, qp, ldq, hid, _dev(w2.contiguous(), "w2"), b2, b2_dev,
+                                                       slope, int(exp2_minus_1), op, ldo, B, Q, _stream()),
+                   "count_head_wide")
+    return out

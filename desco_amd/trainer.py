@@ -202,6 +202,10 @@ class Trainer:
         # (dropout does not stand in the way of replay: the masks are functions of a (seed, step) pair in device memory
         #  that a captured launch advances -- ops.rng_next -- so every replay draws the next mask)
         use_graphs = self.graph_capture and self.device.type == "cuda"
+        if use_graphs and any(getattr(m, "is_wide", lambda: False)() for m in model.modules()):
+            # (the wide path's training step -- --neigh_hidden_dim != 64 -- is not validated under capture)
+            raise NotImplementedError("--graph_capture supports --neigh_hidden_dim 64 only; train a model of another "
+                                      "width without it")
         # shuffle=False (main.py:195): the batch stream is the same every epoch, so the device-resident
         # batches (and their backward indices) are built once.  Data parallel: optimisation step k
         # consumes the `world` consecutive batches [k*world, (k+1)*world), one per rank, weighted by

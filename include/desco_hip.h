@@ -585,6 +585,34 @@ int desco_gossip_layer_f16x3_f32(const float* h, const int32_t* rowptr, const in
                                  const int16_t* pn_planes, const float* pn_scale, float* acc, float* out,
                                  desco_stream_t stream);
 
+/* Neighborhood models of other widths than 64 (--neigh_hidden_dim = H in 1..256, csrc/shmp_wide.hip).  The host pads
+ * every H-wide block of the folded operands with zeros to width = 64 ceil(H / 64) in {64, 128, 192, 256}.
+ *
+ * One SAGE layer of one node-type group, fused: for rows r in [row0, row0 + num_rows) of the virtual-row CSR (vslots
+ * virtual rows per row, vrowptr indexed by r * vslots + s, vcol = rows of x; the first `slots` of them are used),
+ *   y[r] = relu([sum slot 0 | ... | sum slot S-1 | x[r]] Wt + bias)          Wt [(slots + 1) width, width]
+ * with Wt passed as w_planes [2][width][(slots + 1) width] / w_scale = desco_split_f16x2_f32 of Wt^T; the products run
+ * in the three-product f16x3 form (one power-of-two scale per (row, K-block), fp32 accumulation).  y[r] goes to
+ * out[r * ldo] (absolute row; may be NULL) and to out2[(r - row0) * ld2] (relative row; may be NULL), at least one of
+ * them.  slots in {2, 4}, slots <= vslots <= 4; x and the planes 16-byte aligned, ldx % 4 == 0; out / out2 must not be x.  Every row's
+ * neighbours are summed in CSR order: results are bit-reproducible and do not depend on the tiling.  Capturable. */
+int desco_shmp_layer_wide_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr, const int32_t* vcol,
+                                    int vslots, int64_t row0, int64_t num_rows, int slots, int width, const int16_t* w_planes,
+                                    const float* w_scale, const float* bias, float* out, int64_t ldo, float* out2,
+                                    int64_t ld2, desco_stream_t stream);
+
+/* out[(v * slots + s) * ldo + 0 : width] = sum_{e in vrow v * slots + s} x[vcol[e] * ldx + 0 : width] in CSR order, for
+ * num_rows rows of slots in {1, 2, 4} virtual rows each; width % 4 == 0, width <= 256; x and out 16-byte aligned,
+ * ldx, ldo multiples of 4 and >= width. */
+int desco_csr_gather_sum_wide_f32(const float* x, int64_t ldx, const int32_t* vrowptr, const int32_t* vcol,
+                                  int64_t num_rows, int slots, int width, float* out, int64_t ldo, desco_stream_t stream);
+
+/* desco_count_head_f32 (same arguments and results, exp2_minus_1 and b2_dev included) for hid % 64 == 0, hid <= 1024;
+ * num_q <= 32; t 16-byte aligned, ldt % 4 == 0, ldt and ldq >= hid, ldo >= num_q. */
+int desco_count_head_wide_f32(const float* t, int64_t ldt, const float* qh, int64_t ldq, int hid, const float* w2,
+                              float b2, const float* b2_dev, float slope, int exp2_minus_1, float* out, int64_t ldo,
+                              int64_t num_b, int num_q, desco_stream_t stream);
+
 /* K21 tail: out[r] = add[r] + sum_c y[r,c]*w[c] + b   (post_mp.7 with output_dim 1, then
  * pred = neigh_pred + gossip_pred, lightning_model.py:622-625) */
 int desco_rowdot_add_f32(const float* y, int64_t ldy, int ncols, const float* w, float b,
