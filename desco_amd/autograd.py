@@ -40,23 +40,6 @@ def set_precision(p: str) -> None:
 
 
 
-class GatherSum(torch.autograd.Function):
-    """agg = csr_gather_sum(x); backward = gather over the transposed index (csr_t)."""
-
-    @staticmethod
-    def forward(ctx, x, vrowptr, vcol, t_rowptr, t_col, num_rows, slots):
-        ctx.save_for_backward(t_rowptr, t_col)
-        ctx.n_src = x.shape[0]
-        return ops.csr_gather_sum(x.contiguous(), vrowptr, vcol, num_rows, slots)
-
-    @staticmethod
-    def backward(ctx, dagg):
-        t_rowptr, t_col = ctx.saved_tensors
-        d = dagg.contiguous().view(-1, 64)                     # [num_rows*slots, 64] virtual rows
-        dx = ops.csr_gather_sum(d, t_rowptr, t_col, ctx.n_src, 1)
-        return dx, None, None, None, None, None, None
-
-
 class Linear(torch.autograd.Function):
     """c = act([a1 | a2] @ wt + bias);  wt is [(k1+k2), n] (a differentiable function of params)."""
 
@@ -360,23 +343,6 @@ class SmallKLinear(torch.autograd.Function):
             # a [K, n] product over M rows: K column-sums
             dwt = torch.stack([ops.colsum(dout * feat[:, k:k + 1]) for k in range(feat.shape[1])])
         return None, dwt, ops.colsum(dout)
-
-
-class SegmentSum(torch.autograd.Function):
-    """out[b] = sum_{rows of b} x + extra[b]; backward = broadcast (gather by segment id)."""
-
-    @staticmethod
-    def forward(ctx, x, seg_ptr, seg_id, ident_ptr, extra):
-        ctx.save_for_backward(seg_id, ident_ptr)
-        ctx.has_extra = extra is not None
-        return ops.segment_sum(x.contiguous(), seg_ptr, seg_ptr.numel() - 1, extra=extra)
-
-    @staticmethod
-    def backward(ctx, dout):
-        seg_id, ident_ptr = ctx.saved_tensors
-        dout = dout.contiguous()
-        dx = ops.csr_gather_sum(dout, ident_ptr, seg_id, seg_id.numel(), 1)   # dx[r] = dout[seg(r)]
-        return dx, None, None, None, (dout if ctx.has_extra else None)
 
 
 class CountHead(torch.autograd.Function):
@@ -991,7 +957,8 @@ class FoldGossip(torch.autograd.Function):
 
 # ---- neighborhood models of other widths than 64 (gnn_model.shmp_forward_train_wide) -----------------------------------
 class GatherSumWide(torch.autograd.Function):
-    """GatherSum for rows of any width W % 4 == 0 up to 256 (desco_csr_gather_sum_wide_f32, both directions)."""
+    """agg = csr_gather_sum_wide(x) for rows of any width W % 4 == 0 up to 256; backward = gather over the transposed
+    index (csr_t).  desco_csr_gather_sum_wide_f32 both ways."""
 
     @staticmethod
     def forward(ctx, x, vrowptr, vcol, t_rowptr, t_col, num_rows, slots):
@@ -1008,7 +975,8 @@ class GatherSumWide(torch.autograd.Function):
 
 
 class SegmentSumWide(torch.autograd.Function):
-    """SegmentSum for rows of any width W % 4 == 0 up to 256 (backward: desco_csr_gather_sum_wide_f32)."""
+    """out[b] = sum_{rows of b} x + extra[b] for rows of any width W % 4 == 0 up to 256; backward = broadcast (gather by
+    segment id, desco_csr_gather_sum_wide_f32)."""
 
     @staticmethod
     def forward(ctx, x, seg_ptr, seg_id, ident_ptr, extra):

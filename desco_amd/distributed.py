@@ -467,8 +467,7 @@ class GradBuckets:
     trunk (autograd.ShmpTrunk, default) the gradients of ALL SHMP-layer weights appear at once, at the end of the
     trunk's backward, so only the head / post-MLP buckets overlap compute; the layer buckets (most of the 5.24 MB)
     are issued behind the trunk.  At 5 MB per step against ~5 ms of kernels that exposes < 0.1 ms per step over
-    xGMI; per-op autograd (gnn_model.FUSED_TRAIN_TRUNK = False) restores the overlap at
-    1.5x the step time.
+    xGMI.
     ``finish()`` issues the buckets whose parameters received no gradient (the never-used
     query-side ``anchor_mlp``, SURVEY A10: DDP's find_unused_parameters semantics, they reduce
     zeros) and waits.  After the first step those parameters are moved into ONE last bucket, so that

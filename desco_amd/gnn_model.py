@@ -25,10 +25,6 @@ from . import ops
 from .batch import GossipBatch, NeighborhoodBatch, QueryBatch
 
 H = 64
-# one fused gather+MFMA launch per destination type and layer (False: gather kernel + GEMM)
-FUSED_SHMP_LAYER = True
-# scalars pre-pass + one on-chip kernel for the whole gossip network (False: 7 launches via HBM)
-FUSED_GOSSIP = True
 # the fused gossip pass in the three-product fp16 form (csrc/gossip_f16.hip); False: the six-product bf16 kernel
 # (csrc/gossip_fused.hip), kept as its cross-check
 GOSSIP_F16X3 = os.environ.get("DESCO_GOSSIP_F16X3", "1") != "0"
@@ -44,25 +40,13 @@ SHMP_BF16X6 = True
 # ... in the three-product fp16 form with per-row power-of-two scales (csrc/shmp_layer16.hip, F16 instantiations); needs
 # SHMP_BF16X6 and 16-row wave tiles
 SHMP_F16X3 = os.environ.get("DESCO_SHMP_F16X3", "1") != "0"
-# training: the query model's trunk (<= 144 rows) as one single-workgroup launch per direction (csrc/shmp_small.hip);
-# False: the general per-layer launches of autograd.ShmpTrunk (its cross-check in the tests)
-SMALL_TRUNK_KERNEL = True
-# True: global_add_pool of the count rows fused into the layer kernel's epilogue (partials per
-# (16-row tile, neighborhood) + a small reduce) instead of one segment_sum pass over X_l per layer
-FUSED_POOLING = True
-# ... and the layers' partials reduced by ONE launch at the end of the layer loop (False: one launch per layer)
-POOL_REDUCE_MULTI = os.environ.get("DESCO_POOL_REDUCE_MULTI", "1") != "0"
-# ... and the closed-form first layer's count launch leaves its partial sums too (desco_degree_affine_pool_f32) instead
-# of a segment-sum pass over the rows it has just written
+# the closed-form first layer's count launch leaves pooled partial sums (desco_degree_affine_pool_f32) like the fused
+# layer launches do, instead of a segment-sum pass over the rows it has just written
 POOL_FIRST_LAYER = os.environ.get("DESCO_POOL_FIRST_LAYER", "1") != "0"
 # the canonical rows of every layer are stored ONCE, in their column block of the anchor operand [B, 64 (L + 1)]: the
 # canonical launches read their own rows from there (desco_shmp_layer_f16x3_f32: xself) and the table products too,
 # instead of from a second copy behind the count rows of X_l (False: both copies, rounds 2-5)
 CANON_ROWS_ONCE = os.environ.get("DESCO_CANON_ROWS_ONCE", "1") != "0"
-# Training: the SHMP layer loop + anchor + pooling as ONE autograd node whose forward and backward are C-ABI
-# launches on its own buffers (autograd.ShmpTrunk); False: one autograd Function per op (round 2; kept for
-# --neigh_dropout > 0 and as the cross-check of the fused node's gradients)
-FUSED_TRAIN_TRUNK = True
 # degree-balanced row order inside the fused gossip kernel's 128-node tiles (desco_gossip_tile_order); results are
 # bit-identical with and without it
 GOSSIP_TILE_ORDER = os.environ.get("DESCO_GOSSIP_TILE_ORDER", "1") != "0"
@@ -589,39 +573,42 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
     """The pooled embeddings [B, 64 (L+1)] of BaseGNN.forward before post_mp (gnn_model.py:58-107)."""
     pk = gnn.packed()
     core = gnn.gnn_core
+    L = core.layer_num
     dev = batch.vrowptr.device
-    N, S = batch.num_rows, batch.slots
-    if isinstance(batch, NeighborhoodBatch):
+    N, S, B = batch.num_rows, batch.slots, batch.num_graphs
+    P = H * (L + 1)
+    nb = isinstance(batch, NeighborhoodBatch)
+    if nb:
         Nc = batch.num_count
         groups = [("count", 0, Nc, 4), ("canonical", Nc, N, 2)]
     else:
         Nc = N
         groups = [("union_node", 0, N, 2)]
-    feat = batch.node_feature
-    const_input = feat is None and FUSED_SHMP_LAYER and core.layer_num >= 1
-    tab1 = table1 = None
+    f16 = GEMM_BF16X6 and GEMM_F16X3 and SHMP_BF16X6 and SHMP_F16X3
+    # ZeroNodeFeat (workload.py:431-440): pre_mp(x) is its bias, identical for every node of a type, so X_0 is never
+    # materialised and layer 0 is a degree-affine map (desco_hip.h)
+    const_input = batch.node_feature is None and L >= 1
+    # fused pooling: the count launches leave partial neighborhood sums, reduced after the anchor MLP
+    fpool = SHMP_BF16X6 and GEMM_BF16X6 and nb and Nc > 0
+    # canonical rows only in the anchor operand: the f16x3 fused path with its direct column-block writes
+    canon_once = CANON_ROWS_ONCE and const_input and nb and f16 and N > Nc > 0
+    # the count rows' first-layer launch leaves their pooled partial sums like the fused layers' launches do (round 6:
+    # saves the one read of X_1 that its segment sum cost)
+    pool1 = POOL_FIRST_LAYER and const_input and fpool
+    # ... and with the table form of the second layer's launches they are not stored either (tab1: the table index)
+    tab1 = None
+    if (FIRST_LAYER_TABLE and pool1 and canon_once and L >= 2 and "wt_tab" in pk["layers"][1]["count"]
+            and isinstance(pk["layers"][1]["count"].get("wt_mfma_x6"), ops.F16Planes)):
+        tab1 = batch.degree_table_index()
+    pool_parts = {}
+    if fpool:
+        pbits, pslot, nslots = batch.pool_index()
     if const_input:
-        # ZeroNodeFeat (workload.py:431-440): pre_mp(x) is its bias, identical for every node of a
-        # type, so X_0 is never materialised and layer 0 is a degree-affine map (desco_hip.h).
         x0 = {t: pk["pre"][t][1] for t, *_ in groups}
-        src_of_slot = (lambda t, s: ("count" if s < 2 else "canonical")) if len(groups) == 2 else \
-            (lambda t, s: t)
+        src_of_slot = (lambda t, s: ("count" if s < 2 else "canonical")) if nb else (lambda t, s: t)
         xn = torch.empty((N, H), device=dev)
-        # (canonical rows only in the anchor operand: the f16x3 fused path with its direct column-block writes)
-        canon_once = (CANON_ROWS_ONCE and isinstance(batch, NeighborhoodBatch) and GEMM_BF16X6 and GEMM_F16X3
-                      and SHMP_BF16X6 and SHMP_F16X3 and N > Nc > 0)
-        # the count rows' launch leaves their pooled partial sums like the fused layers' launches do (round 6: saves the
-        # one read of X_1 that its segment sum cost)
-        pool1 = None
-        if (POOL_FIRST_LAYER and FUSED_POOLING and SHMP_BF16X6 and GEMM_BF16X6 and isinstance(batch, NeighborhoodBatch)
-                and Nc > 0):
-            pbits1, pslot1, nslots1 = batch.pool_index()
-            pool1 = (pbits1, pslot1, torch.empty((nslots1, H), device=dev))
-        # ... and with the table form of the second layer's launches they are not stored either
-        if (FIRST_LAYER_TABLE and pool1 is not None and canon_once and core.layer_num >= 2 and SHMP_F16X3
-                and "wt_tab" in pk["layers"][1]["count"]
-                and isinstance(pk["layers"][1]["count"].get("wt_mfma_x6"), ops.F16Planes)):
-            tab1 = batch.degree_table_index()
+        if pool1:
+            pool_parts[1] = torch.empty((nslots, H), device=dev)
         if tab1 is not None:
             coef_c = _first_layer_coef(pk, "count", 4, S, x0, src_of_slot, dev)
             table1 = torch.empty((tab1[0].numel() // S, H), device=dev)
@@ -631,15 +618,15 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
             if r1 <= r0:
                 continue
             coef = _first_layer_coef(pk, t, su, S, x0, src_of_slot, dev)
-            if pool1 is not None and t == "count" and r0 == 0:
-                ops.degree_affine_pool(batch.vrowptr, r1, S, coef, ops.ACT_RELU, 0.0, xn, pool1)
+            if pool1 and t == "count":
+                ops.degree_affine_pool(batch.vrowptr, r1, S, coef, ops.ACT_RELU, 0.0, xn, (pbits, pslot, pool_parts[1]))
             elif t == "canonical" and canon_once:
                 pass                                   # (written below, straight into the anchor operand's block 1)
             else:
                 ops.degree_affine(batch.vrowptr, r0, r1 - r0, S, coef, ops.ACT_RELU, 0.0, xn)
         X = [None, xn]
-        first = 1
     else:
+        feat = batch.node_feature
         if feat is None:
             feat = torch.zeros((N, core.input_dim), device=dev)
         x = torch.empty((N, H), device=dev)
@@ -647,134 +634,101 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
             wt, b = pk["pre"][t]
             ops.linear_smallk(feat[r0:r1], wt, b, out=x[r0:r1])               # :231
         X = [x]
-        first = 0
-        canon_once = False
-    B = batch.num_graphs
-    P = H * (core.layer_num + 1)
-    # emb["canonical"] [B, P] (operand of the anchor MLP): the fused canonical launches write their
-    # column block directly (out2), so no concatenation pass is needed
-    direct_canon = FUSED_SHMP_LAYER and isinstance(batch, NeighborhoodBatch)
-    canon = torch.empty((B, P), device=dev) if direct_canon else None
+    first = len(X) - 1
+    # emb["canonical"] [B, P] (operand of the anchor MLP): the canonical launches write their column block directly
+    # (out2), so no concatenation pass is needed
+    canon = torch.empty((B, P), device=dev) if nb else None
     # per-row bound of the anchor operand, left by the launches that write its column blocks (saves the f16x3 GEMM's
     # pre-pass over the operand): only when every block comes from such a launch (constant input, fp16 layer form)
-    canon_max = None
-    if direct_canon and const_input and GEMM_BF16X6 and GEMM_F16X3 and SHMP_BF16X6 and SHMP_F16X3 and first == 1:
-        canon_max = torch.empty((B,), device=dev)
-    if direct_canon and const_input and first == 1:
+    canon_max = torch.empty((B,), device=dev) if (nb and const_input and f16) else None
+    if nb and const_input:
         # the closed-form first layer once more for the canonical rows, straight into its column block of the anchor
         # operand (a 1/9-size launch of our own instead of a strided torch copy per pass); it WRITES the row bound the
         # canonical launches below accumulate into, so it runs before them
         t, r0, r1, su = groups[1]
         ops.degree_affine(batch.vrowptr, r0, r1 - r0, S, _first_layer_coef(pk, t, su, S, x0, src_of_slot, dev),
                           ops.ACT_RELU, 0.0, canon[:, H:2 * H], out_row0=0, row_absmax=canon_max)
-    # fused pooling: the count launches leave partial neighborhood sums, reduced after the anchor MLP
-    fpool = (FUSED_POOLING and FUSED_SHMP_LAYER and SHMP_BF16X6 and GEMM_BF16X6
-             and isinstance(batch, NeighborhoodBatch) and Nc > 0)
-    pool_parts = {}
-    if fpool:
-        pbits, pslot, nslots = batch.pool_index()
-        if const_input and first == 1 and pool1 is not None:
-            pool_parts[1] = pool1[2]
-    for l in range(first, core.layer_num):
-        last = l == core.layer_num - 1
+    for l in range(first, L):                                              # :262-264, :273, :389-395
+        last = l == L - 1
         # the last layer's count rows feed nothing but the pooling: with fused pooling they are
         # never stored (the canonical rows still are, they sit at the end of the same tensor)
         xn = torch.empty((N, H), device=dev)
         # layer input, column ids and (count rows) self index of this layer's launches: X_l itself, or -- for the second
         # layer when X_1's count rows exist as a table of distinct rows only -- that table
         x_src, vcol_l, coef_l = X[-1], batch.vcol, None
-        if const_input and first == 1 and l == 1 and tab1 is not None:
+        if l == 1 and tab1 is not None:
             x_src, vcol_l, coef_l = table1, tab1[2], coef_c
-        if FUSED_SHMP_LAYER:
-            for t, r0, r1, su in groups:                                   # :262-264, :273, :389-395
-                if r1 <= r0:
-                    continue
-                e = pk["layers"][l][t]
-                if "wt_tab" in e:
-                    crows = canon[:, l * H:(l + 1) * H] if canon_once else X[-1][Nc:]     # canonical rows of X_l
-                    ytab = (ops.linear64(crows, e["wt_tab_l64"]) if GEMM_BF16X6 else
-                            ops.gemm(crows, e["wt_tab"]))                 # canonical rows x [W2|W3]
-                    pool = None
-                    if fpool and "wt_mfma_x6" in e:
-                        pool_parts[l + 1] = torch.empty((nslots, H), device=dev)
-                        pool = (pbits, pslot, pool_parts[l + 1])
-                    ops.shmp_layer(x_src, batch.vrowptr, vcol_l, r0, r1 - r0, S, 2,
-                                   e.get("wt_mfma_x6", e["wt_mfma"]) if SHMP_BF16X6 else e["wt_mfma"],
-                                   e["b"], None if (pool is not None and last) else xn, ytab=ytab,
-                                   ytab_row0=Nc, pool=pool, self_coef=coef_l)
-                else:
-                    once = canon_once and t == "canonical" and isinstance(e.get("wt_x6"), ops.F16Planes)
-                    ops.shmp_layer(x_src, batch.vrowptr, vcol_l, r0, r1 - r0, S, su,
-                                   e.get("wt_x6", e["wt"]) if SHMP_BF16X6 else e["wt"], e["b"], None if once else xn,
-                                   out2=(canon[:, (l + 1) * H:(l + 2) * H]
-                                         if direct_canon and t == "canonical" else None),
-                                   row_absmax=canon_max if (direct_canon and t == "canonical" and
-                                                            isinstance(e.get("wt_x6"), ops.F16Planes)) else None,
-                                   xself=canon[:, l * H:(l + 1) * H] if once else None)
-        else:
-            agg = ops.csr_gather_sum(X[-1], batch.vrowptr, batch.vcol, N, S)   # [N, S*64]
-            for t, r0, r1, su in groups:
-                if r1 > r0:
-                    e = pk["layers"][l][t]
-                    ops.gemm(agg[r0:r1, :su * H], e["wt"], e["b"], a2=X[-1][r0:r1],
-                             act=ops.ACT_RELU, out=xn[r0:r1])
+        for t, r0, r1, su in groups:
+            if r1 <= r0:
+                continue
+            e = pk["layers"][l][t]
+            if "wt_tab" in e:
+                crows = canon[:, l * H:(l + 1) * H] if canon_once else X[-1][Nc:]     # canonical rows of X_l
+                ytab = (ops.linear64(crows, e["wt_tab_l64"]) if GEMM_BF16X6 else
+                        ops.gemm(crows, e["wt_tab"]))                     # canonical rows x [W2|W3]
+                pool = None
+                if fpool and "wt_mfma_x6" in e:
+                    pool_parts[l + 1] = torch.empty((nslots, H), device=dev)
+                    pool = (pbits, pslot, pool_parts[l + 1])
+                ops.shmp_layer(x_src, batch.vrowptr, vcol_l, r0, r1 - r0, S, 2,
+                               e.get("wt_mfma_x6", e["wt_mfma"]) if SHMP_BF16X6 else e["wt_mfma"],
+                               e["b"], None if (pool is not None and last) else xn, ytab=ytab,
+                               ytab_row0=Nc, pool=pool, self_coef=coef_l)
+            else:
+                canonical, w16 = t == "canonical", isinstance(e.get("wt_x6"), ops.F16Planes)
+                once = canon_once and canonical and w16
+                ops.shmp_layer(x_src, batch.vrowptr, vcol_l, r0, r1 - r0, S, su,
+                               e.get("wt_x6", e["wt"]) if SHMP_BF16X6 else e["wt"], e["b"], None if once else xn,
+                               out2=canon[:, (l + 1) * H:(l + 2) * H] if canonical else None,
+                               row_absmax=canon_max if (canonical and w16) else None,
+                               xself=canon[:, l * H:(l + 1) * H] if once else None)
         X.append(xn)
-        if fpool and direct_canon and l >= 1 and l in pool_parts:
+        if l in pool_parts:
             # layer l's rows have been consumed (their pooled sums sit in pool_parts[l], their canonical
             # rows in `canon`): release them -- a block then holds three [N, 64] tensors instead of nine,
             # which is what lets InferencePipeline run blocks of tens of millions of rows
             X[l] = _RELEASED
-    pooled = torch.empty((B, P), device=dev)
-    if isinstance(batch, NeighborhoodBatch):
-        c0 = x0["canonical"].expand(B, H) if const_input else X[0][Nc:]
-        folded_x0 = GEMM_BF16X6 and const_input and direct_canon and first == 1    # (_anchor_const_input: K = 512)
-        if direct_canon:
-            if not folded_x0:
-                canon[:, :H] = c0
-            for l in range(1, first + 1):        # layers produced outside the fused launches
-                if not (const_input and l == 1):     # (that one was written above, before the layer loop)
-                    canon[:, l * H:(l + 1) * H] = X[l][Nc:]
-        else:
-            canon = torch.cat([c0] + [xl[Nc:] for xl in X[1:]], dim=1)        # emb["canonical"] [B,P]
-        aw, ab = pk["anchor"]
-        pool_post = (fuse_post0 and POOL_POST_FUSED and const_input and first == 1 and GEMM_BF16X6 and "post_nk" in pk
-                     and sorted(pool_parts) == list(range(1, core.layer_num + 1)) and core.layer_num <= 8
-                     and batch.max_count_rows() <= 33)
-        if (pool_post and ANCHOR_POST_FUSED and folded_x0 and canon_max is not None and GEMM_F16X3
-                and core.layer_num in (2, 5, 8)):
+    if nb:
+        folded_x0 = GEMM_BF16X6 and const_input    # (_anchor_const_input: K = 512)
+        if not folded_x0:
+            canon[:, :H] = x0["canonical"].expand(B, H) if const_input else X[0][Nc:]
+        seg_ptr = batch.count_ptr
+        pool_post = (fuse_post0 and POOL_POST_FUSED and const_input and GEMM_BF16X6 and "post_nk" in pk
+                     and sorted(pool_parts) == list(range(1, L + 1)) and L <= 8 and batch.max_count_rows() <= 33)
+        if pool_post and ANCHOR_POST_FUSED and canon_max is not None and L in (2, 5, 8):
             _anchor_const_input_weights(pk, gnn)
             aw16, ab16 = pk["anchor_nk_const"]
             w0, b0 = pk["post_nk"][0]
             return _PostMp0(ops.anchor_pool_post(canon[:, H:], aw16, ab16, canon_max,
-                                                 [pool_parts[l] for l in range(1, core.layer_num + 1)], pbits, pslot,
-                                                 batch.count_ptr, x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1))
+                                                 [pool_parts[l] for l in range(1, L + 1)], pbits, pslot,
+                                                 seg_ptr, x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1))
         if folded_x0:
             anch = _anchor_const_input(pk, gnn, canon, row_bound=canon_max)
         elif GEMM_BF16X6:
             anch = _gemm_planes(canon, *pk["anchor_nk"], act=ops.ACT_LEAKY, slope=0.1)
         else:
+            aw, ab = pk["anchor"]
             anch = ops.gemm(canon, aw, ab, act=ops.ACT_LEAKY, slope=0.1)   # :69-73
-        seg_ptr = batch.count_ptr
+        if pool_post:
+            w0, b0 = pk["post_nk"][0]
+            return _PostMp0(ops.pool_post(anch, [pool_parts[l] for l in range(1, L + 1)], pbits, pslot, seg_ptr,
+                                          x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1))
     else:
         anch = None                                  # query graphs: no canonical node, no anchor
         seg_ptr = batch.graph_ptr
-    if anch is not None and pool_post:
-        w0, b0 = pk["post_nk"][0]
-        return _PostMp0(ops.pool_post(anch, [pool_parts[l] for l in range(1, core.layer_num + 1)], pbits, pslot, seg_ptr,
-                                      x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1))
-    if pool_parts and POOL_REDUCE_MULTI:
+    pooled = torch.empty((B, P), device=dev)
+    if pool_parts:
         # the layers' partial sums, reduced together: one launch for (up to eight of) them instead of one per layer
         ls = sorted(pool_parts)
         ops.pool_reduce_multi([pool_parts[l] for l in ls], pbits, pslot, seg_ptr, B,
                               [None if anch is None else anch[:, l * H:(l + 1) * H] for l in ls],
                               [pooled[:, l * H:(l + 1) * H] for l in ls])
     for l, xl in enumerate(X):                                             # :88-89, :107
+        if l in pool_parts:
+            continue
         extra = None if anch is None else anch[:, l * H:(l + 1) * H]
         out_l = pooled[:, l * H:(l + 1) * H]
-        if l in pool_parts:
-            if not POOL_REDUCE_MULTI:
-                ops.pool_reduce(pool_parts[l], pbits, pslot, seg_ptr, B, extra=extra, out=out_l)
-        elif xl is None:     # constant X_0: the segment sum is (rows in segment) * x0
+        if xl is None:       # constant X_0: the segment sum is (rows in segment) * x0
             t0 = groups[0][0]
             ck = ("pool0_coef", t0)
             if ck not in pk:
@@ -827,114 +781,65 @@ POST_DROP_SITE = 200      # dropout site of post_mp.1 (the layers use 2 l + row 
 
 
 def shmp_forward_train(gnn: BaseGNN, batch, drop_key: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Differentiable twin of ``shmp_forward`` (same math, un-fused kernels, autograd Functions from
-    desco_amd.autograd; every forward and backward op is a C-ABI kernel launch).  ``drop_key``: the (seed, step) key of
-    this pass's dropout (ops.rng_next), drawn here when None -- callers that run two models on two streams draw both
-    keys first, on one stream (NeighborhoodCountingModel.train_forward)."""
+    """Differentiable twin of ``shmp_forward`` (same math; every forward and backward op is a C-ABI kernel launch of
+    desco_amd.autograd).  ``drop_key``: the (seed, step) key of this pass's dropout (ops.rng_next), drawn here when
+    None -- callers that run two models on two streams draw both keys first, on one stream
+    (NeighborhoodCountingModel.train_forward)."""
     from . import autograd as AG
     core = gnn.gnn_core
     dev = batch.vrowptr.device
     N, S = batch.num_rows, batch.slots
-    import torch.nn.functional as F
     # --neigh_dropout > 0 (default 0.0, config.py:251): F.dropout after every layer's relu (gnn_model.py:274) and the
     # nn.Dropout of post_mp.1 (:46), in training mode: counter-based factors inside the fused nodes' epilogues
     # (autograd.ShmpTrunk / ShmpTrunkSmall / Mlp), as in the gossip model
     p_layer = float(core.dropout or 0.0) if gnn.training else 0.0
     p_post = float(gnn.post_mp[1].p or 0.0) if gnn.training else 0.0
     drop = p_layer > 0.0 or p_post > 0.0
-    if isinstance(batch, NeighborhoodBatch):
+    has_anchor = isinstance(batch, NeighborhoodBatch)
+    if has_anchor:
         Nc = batch.num_count
         groups = [("count", 0, Nc, 4), ("canonical", Nc, N, 2)]
-        seg_ptr = batch.count_ptr
     else:
-        Nc = N
         groups = [("union_node", 0, N, 2)]
-        seg_ptr = batch.graph_ptr
     feat = batch.node_feature
     if feat is None:
         feat = batch.__dict__.get("_zero_feat")          # ZeroNodeFeat: a constant of the batch, made once
         if feat is None or feat.shape[1] != core.input_dim:
             feat = batch.__dict__["_zero_feat"] = torch.zeros((N, core.input_dim), device=dev)
-    small = (SMALL_TRUNK_KERNEL and not isinstance(batch, NeighborhoodBatch) and S == 2 and core.layer_num >= 1
-             and 0 < N <= ops.shmp_trunk_small_max_rows())
+    # the query graphs (<= 144 rows): the whole trunk in one launch per direction (autograd.ShmpTrunkSmall; only its
+    # per-graph kernels carry the dropout factors)
+    small = not has_anchor and S == 2 and core.layer_num >= 1 and 0 < N <= ops.shmp_trunk_small_max_rows()
     if small and drop and not AG.ShmpTrunkSmall.per_graph(batch):
-        small = False                                   # (only the per-graph kernels carry the dropout factors)
-    if FUSED_TRAIN_TRUNK and all(len(core.slot_keys(t)) == su for t, _, _, su in groups):
-        if drop and drop_key is None:
-            drop_key = ops.rng_next(dev)
-        ldrop = (drop_key, p_layer) if p_layer > 0.0 else None
-        # The whole layer loop + anchor + pooling as one autograd node (autograd.ShmpTrunk) on weights folded in
-        # stacked form.  Everything between the parameters and that node is this library's kernels too (round 5): the
-        # folding reads the parameters through an address table (autograd.FoldShmp), the K-major copies of pre_mp /
-        # anchor_mlp / post_mp are one copy2d launch (autograd.TransposedMany), pre_mp writes one buffer (PreLinear).
-        has_anchor = isinstance(batch, NeighborhoodBatch)
-        lins = [core.pre_mp[0][t] for t, *_ in groups] + ([gnn.anchor_mlp[0]] if has_anchor else []) + \
-               [gnn.post_mp[i] for i in (0, 3, 5, 7)]
-        wts = AG.TransposedMany.apply(*[m.weight for m in lins])
-        ng = len(groups)
-        pre = []
-        for g in range(ng):
-            pre += [wts[g], lins[g].bias]
-        x = AG.PreLinear.apply(feat, groups, *pre)
-        flat = [wts[ng], gnn.anchor_mlp[0].bias] if has_anchor else []
-        for t, *_ in groups:
-            flat += list(fold_shmp_native(gnn, t))
-        if small and len(groups) == 1:
-            # the query graphs (135 rows): the whole trunk in one launch per direction (one workgroup per graph)
-            pooled = AG.ShmpTrunkSmall.apply(x, batch, ldrop, *flat)
-        else:
-            pooled = AG.ShmpTrunk.apply(x, batch, groups, has_anchor, ldrop, *flat)
-        pw = wts[ng + (1 if has_anchor else 0):]
-        post = {"post": [(pw[j], gnn.post_mp[i].bias) for j, i in enumerate((0, 3, 5, 7))]}
-        pdrop = ops.DropSite(drop_key, POST_DROP_SITE, p_post) if p_post > 0.0 else None
-        return _post_mp_train(AG, post, gnn, pooled, pdrop)
-    pk = pack_shmp(gnn, bf16_planes=False)   # differentiable folding: grads reach the raw parameters
-    ti = batch.train_index()
-    x = torch.cat([AG.SmallKLinear.apply(feat[r0:r1], *pk["pre"][t]) for t, r0, r1, _ in groups], 0)
-    X = [x]
-    for l in range(core.layer_num):
-        agg = AG.GatherSum.apply(X[-1], batch.vrowptr, batch.vcol, ti["t_rowptr"], ti["t_col"], N, S)
-        parts = []
-        for t, r0, r1, su in groups:
-            e = pk["layers"][l][t]
-            parts.append(AG.Linear.apply(agg[r0:r1, :su * H], X[-1][r0:r1], e["wt"], e["b"],
-                                         ops.ACT_RELU, 0.0))
-        xl = torch.cat(parts, 0)
-        if drop:                                                           # gnn_model.py:274
-            xl = F.dropout(xl, p=core.dropout, training=True)
-        X.append(xl)
-    if isinstance(batch, NeighborhoodBatch):
-        canon = torch.cat([xl[Nc:] for xl in X], dim=1)
-        aw, ab = pk["anchor"]
-        anch = AG.Linear.apply(canon, None, aw, ab, ops.ACT_LEAKY, 0.1)
-        pooled = torch.cat([AG.SegmentSum.apply(xl[:Nc], seg_ptr, ti["seg_id"], ti["ident_ptr"],
-                                                anch[:, l * H:(l + 1) * H].contiguous())
-                            for l, xl in enumerate(X)], dim=1)
+        small = False
+    if drop and drop_key is None:
+        drop_key = ops.rng_next(dev)
+    ldrop = (drop_key, p_layer) if p_layer > 0.0 else None
+    # The whole layer loop + anchor + pooling as one autograd node (autograd.ShmpTrunk) on weights folded in
+    # stacked form.  Everything between the parameters and that node is this library's kernels too (round 5): the
+    # folding reads the parameters through an address table (autograd.FoldShmp), the K-major copies of pre_mp /
+    # anchor_mlp / post_mp are one copy2d launch (autograd.TransposedMany), pre_mp writes one buffer (PreLinear).
+    lins = [core.pre_mp[0][t] for t, *_ in groups] + ([gnn.anchor_mlp[0]] if has_anchor else []) + \
+           [gnn.post_mp[i] for i in (0, 3, 5, 7)]
+    wts = AG.TransposedMany.apply(*[m.weight for m in lins])
+    ng = len(groups)
+    pre = []
+    for g in range(ng):
+        pre += [wts[g], lins[g].bias]
+    x = AG.PreLinear.apply(feat, groups, *pre)
+    flat = [wts[ng], gnn.anchor_mlp[0].bias] if has_anchor else []
+    for t, *_ in groups:
+        flat += list(fold_shmp_native(gnn, t))
+    if small:
+        pooled = AG.ShmpTrunkSmall.apply(x, batch, ldrop, *flat)
     else:
-        pooled = torch.cat([AG.SegmentSum.apply(xl, seg_ptr, ti["seg_id"], ti["ident_ptr"], None)
-                            for xl in X], dim=1)
-    return _post_mp_train(AG, pk, gnn, pooled, drop)
-
-
-def _post_mp_train(AG, pk, gnn, pooled, drop):
-    """post_mp of a training pass.  ``drop``: None / False (no dropout), an ops.DropSite (post_mp.1 as the counter-based
-    factor inside the fused node), or True (the per-op cross-check path: torch's F.dropout)."""
-    import torch.nn.functional as F
-    (w0, b0), (w3, b3), (w5, b5), (w7, b7) = pk["post"]
-    if not drop or isinstance(drop, ops.DropSite):
-        # the four Linears and their backward as one autograd node (activation derivatives in the GEMM epilogues, one
-        # launch pair for all weight gradients)
-        return AG.Mlp.apply(pooled, ((ops.ACT_LEAKY, 0.1), (ops.ACT_RELU, 0.0), (ops.ACT_RELU, 0.0), (ops.ACT_NONE, 0.0)),
-                            tuple(gnn.post_mp[i].weight for i in (0, 3, 5, 7)), drop if drop else None,
-                            w0, b0, w3, b3, w5, b5, w7, b7)
-    if drop:                                                               # post_mp.1 (gnn_model.py:46)
-        h = AG.Linear.apply(pooled, None, w0, b0, ops.ACT_NONE, 0.0)
-        h = F.leaky_relu(F.dropout(h, p=gnn.post_mp[1].p, training=True), 0.1)
-    else:
-        h = AG.Linear.apply(pooled, None, w0, b0, ops.ACT_LEAKY, 0.1)
-    h = AG.Linear.apply(h, None, w3, b3, ops.ACT_RELU, 0.0)
-    h = AG.Linear.apply(h, None, w5, b5, ops.ACT_RELU, 0.0)
-    return AG.Linear.apply(h, None, w7, b7, ops.ACT_NONE, 0.0)
+        pooled = AG.ShmpTrunk.apply(x, batch, groups, has_anchor, ldrop, *flat)
+    pw = wts[ng + (1 if has_anchor else 0):]
+    post = [v for j, i in enumerate((0, 3, 5, 7)) for v in (pw[j], gnn.post_mp[i].bias)]
+    pdrop = ops.DropSite(drop_key, POST_DROP_SITE, p_post) if p_post > 0.0 else None
+    # post_mp: the four Linears and their backward as one autograd node (activation derivatives in the GEMM epilogues,
+    # one launch pair for all weight gradients)
+    return AG.Mlp.apply(pooled, ((ops.ACT_LEAKY, 0.1), (ops.ACT_RELU, 0.0), (ops.ACT_RELU, 0.0), (ops.ACT_NONE, 0.0)),
+                        tuple(gnn.post_mp[i].weight for i in (0, 3, 5, 7)), pdrop, *post)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1154,26 +1059,21 @@ def pack_gossip(gnn: BaseGNN, bf16_planes: bool = True) -> dict:
             "gossip kernels implement GossipConv layers with input_dim 1 and the query embedding as input "
             "(config.py:312-322, main.py:316-325)")
     pre = core.pre_mp[0]
-    pk = {"w_pre": pre.weight[:, 0].contiguous(), "b_pre": pre.bias.contiguous()}
+    pk = {"w_pre": pre.weight[:, 0].contiguous(), "b_pre": pre.bias.contiguous(),
+          "post": [_lin_t(gnn.post_mp[i]) for i in (3, 5)], "w7": gnn.post_mp[7].weight[0].contiguous(),
+          "b7": float(gnn.post_mp[7].bias[0]), "qcache": None}
     if core.layer_num != 2:
         return _pack_gossip_deep(gnn, pk)
-    c0, c1 = core.convs[0], core.convs[1]
-    pk["C0"], pk["c0"] = c0.lin_com.weight, c0.lin_com.bias
-    pk["D0"], pk["d0"] = c0.lin_update.weight, c0.lin_update.bias
+    c1 = core.convs[1]
     D1 = c1.lin_update.weight
     D1a, D1b = D1[:, :H], D1[:, H:]
-    pk["wt1"] = torch.cat([(D1a @ c1.lin_com.weight).t(), D1b.t()], 0).contiguous()   # [128,64]
-    pk["ws1"] = torch.stack([_mv(D1a, c1.lin_com.bias), torch.zeros_like(c1.lin_com.bias)]).contiguous()
+    wt1 = torch.cat([(D1a @ c1.lin_com.weight).t(), D1b.t()], 0).contiguous()   # [128,64]
+    pk["u1"] = _mv(D1a, c1.lin_com.bias)
     pk["d1"] = c1.lin_update.bias.contiguous()
-    P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
-    pk["P0"], pk["p0"] = P0, p0
-    pk["wtp"] = torch.cat([P0[:, He + H:He + 2 * H].t(), P0[:, He + 2 * H:He + 3 * H].t()], 0).contiguous()
-    pk["wsp"] = torch.stack([torch.zeros(H, device=P0.device), _mv(P0[:, He:He + H], pk["w_pre"])]).contiguous()
-    pk["post"] = [_lin_t(gnn.post_mp[i]) for i in (3, 5)]
-    pk["w7"] = gnn.post_mp[7].weight[0].contiguous()
-    pk["b7"] = float(gnn.post_mp[7].bias[0])
-    pk["fused_w1"] = pk["wt1"].t().contiguous()                 # [64,128]
-    pk["fused_wp"] = pk["wtp"].t().contiguous()                 # [64,128]
+    P0 = gnn.post_mp[0].weight
+    wtp = torch.cat([P0[:, He + H:He + 2 * H].t(), P0[:, He + 2 * H:He + 3 * H].t()], 0).contiguous()
+    pk["fused_w1"] = wt1.t().contiguous()                       # [64,128]
+    pk["fused_wp"] = wtp.t().contiguous()                       # [64,128]
     pk["fused_w3"] = gnn.post_mp[3].weight.contiguous()         # [64,64]  (already [out, in])
     pk["fused_w5"] = gnn.post_mp[5].weight.contiguous()         # [256,64]
     if bf16_planes:     # bf16 planes (hi, mid, lo) of the n-major matrices: the fused kernel's operands
@@ -1182,23 +1082,17 @@ def pack_gossip(gnn: BaseGNN, bf16_planes: bool = True) -> dict:
         # ... and the fp16 (hi, lo) weight stream of the three-product kernel
         pk["wstream"], pk["winv"] = ops.gossip_f16_stream(*[ops.split_f16_planes(pk[k]) for k in
                                                             ("fused_w1", "fused_wp", "fused_w3", "fused_w5")])
-    pk["qcache"] = None
     return pk
 
 
 def _pack_gossip_deep(gnn: BaseGNN, pk: dict) -> dict:
-    """Operands of a depth-L gossip model (L != 2): per layer l >= 1 the folded weight
-    W_l = [(D_a C)^T; D_b^T]_l as fp16 planes of its n-major form, u_l = D_a c_l and d_l, and the post_mp.0 blocks P0_l
-    of h_1 .. h_L (n-major [64, 64] = the block of the torch weight as it is stored)."""
+    """Operands of a depth-L gossip model (L != 2) beyond pack_gossip's head ``pk``: per layer l >= 1 the
+    folded weight W_l = [(D_a C)^T; D_b^T]_l as fp16 planes of its n-major form, u_l = D_a c_l and d_l, and the
+    post_mp.0 blocks P0_l of h_1 .. h_L (n-major [64, 64] = the block of the torch weight as it is stored)."""
     core = gnn.gnn_core
     He = gossip_emb_width(core)
     L = core.layer_num
-    c0 = core.convs[0]
-    pk["C0"], pk["c0"] = c0.lin_com.weight, c0.lin_com.bias
-    pk["D0"], pk["d0"] = c0.lin_update.weight, c0.lin_update.bias
-    P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
-    pk["P0"], pk["p0"] = P0, p0
-    pk["wsp"] = torch.stack([torch.zeros(H, device=P0.device), _mv(P0[:, He:He + H], pk["w_pre"])]).contiguous()
+    P0 = gnn.post_mp[0].weight
     layers = []
     for l in range(1, L):
         c = core.convs[l]
@@ -1210,11 +1104,29 @@ def _pack_gossip_deep(gnn: BaseGNN, pk: dict) -> dict:
     pk["deep_p"] = [ops.split_f16_planes(P0[:, He + l * H:He + (l + 1) * H].contiguous()) for l in range(1, L + 1)]
     if L == 1:      # h1 . P0_1 on the fp32 matrix pipe (no gossip layer to carry it)
         pk["p1t"] = P0[:, He + H:He + 2 * H].t().contiguous()
-    pk["post"] = [_lin_t(gnn.post_mp[i]) for i in (3, 5)]
-    pk["w7"] = gnn.post_mp[7].weight[0].contiguous()
-    pk["b7"] = float(gnn.post_mp[7].bias[0])
-    pk["qcache"] = None
     return pk
+
+
+def _gossip_layer0_terms(core: BaseGNNCore, post0: nn.Linear, E: torch.Tensor, w_pre: torch.Tensor,
+                         b_pre: torch.Tensor):
+    """The per-query terms of a gossip pass, from the query embeddings E [Q, He] and pre_mp's weight
+    column / bias: the gates g_l [Q] of every layer; p, z [Q, 64] and r, t [64] of the closed-form layer 0
+    (h1 = relu(a0 p + b0 r + x t + z) per row, a0 / b0 the gated degree sums); zp [Q, 64] and tp [64] of post_mp.0's
+    E and pre_mp blocks (zp + x tp).  Differentiable; the callers stack and expand them into their operand layouts."""
+    He = gossip_emb_width(core)
+    c0 = core.convs[0]
+    C0, D0, P0 = c0.lin_com.weight, c0.lin_update.weight, post0.weight
+    g = [c._gate_value(E).reshape(-1) for c in core.convs]                              # gnn_model.py:340
+    a_q = E @ C0[:, :He].t() + (_mv(C0[:, He:], b_pre) + c0.lin_com.bias)                # lin_com(h0) const part
+    v = _mv(C0[:, He:], w_pre)
+    D0a, D0b, D0c = D0[:, :H], D0[:, H:H + He], D0[:, H + He:]
+    p = a_q @ D0a.t()
+    r = _mv(D0a, v)
+    t = _mv(D0c, w_pre)
+    z = E @ D0b.t() + (_mv(D0c, b_pre) + c0.lin_update.bias)
+    tp = _mv(P0[:, He:He + H], w_pre)
+    zp = E @ P0[:, :He].t() + (_mv(P0[:, He:He + H], b_pre) + post0.bias)
+    return g, p, r, t, z, tp, zp
 
 
 def _gossip_query_terms_deep(gnn: BaseGNN, pk: dict, query_emb: torch.Tensor) -> dict:
@@ -1224,25 +1136,13 @@ def _gossip_query_terms_deep(gnn: BaseGNN, pk: dict, query_emb: torch.Tensor) ->
     key = (query_emb.data_ptr(), query_emb._version, tuple(query_emb.shape))
     if pk["qcache"] is not None and pk["qcache"][0] == key:
         return pk["qcache"][1]
-    core = gnn.gnn_core
-    He = gossip_emb_width(core)
     E = query_emb.float()
     Q = E.shape[0]
-    C0, D0 = pk["C0"], pk["D0"]
-    w_pre, b_pre = pk["w_pre"], pk["b_pre"]
-    q = {"g": [c._gate_value(E).reshape(-1).contiguous() for c in core.convs]}
-    a_q = E @ C0[:, :He].t() + (_mv(C0[:, He:], b_pre) + pk["c0"])
-    v = _mv(C0[:, He:], w_pre)
-    D0a, D0b, D0c = D0[:, :H], D0[:, H:H + He], D0[:, H + He:]
-    p = a_q @ D0a.t()
-    r = _mv(D0a, v).expand(Q, H)
-    t = _mv(D0c, w_pre).expand(Q, H)
-    z = E @ D0b.t() + (_mv(D0c, b_pre) + pk["d0"])
-    q["V0"] = torch.stack([p, r, t, z], 1).contiguous()                               # [Q,4,64]
-    P0 = pk["P0"]
-    zp = E @ P0[:, :He].t() + (_mv(P0[:, He:He + H], b_pre) + pk["p0"])
+    g, p, r, t, z, tp, zp = _gossip_layer0_terms(gnn.gnn_core, gnn.post_mp[0], E, pk["w_pre"], pk["b_pre"])
+    q = {"g": [gl.contiguous() for gl in g]}
+    q["V0"] = torch.stack([p, r.expand(Q, H), t.expand(Q, H), z], 1).contiguous()     # [Q,4,64]
     zero = torch.zeros_like(zp)
-    q["Vacc"] = torch.stack([zero, zero, pk["wsp"][1].expand(Q, H), zp], 1).contiguous()
+    q["Vacc"] = torch.stack([zero, zero, tp.expand(Q, H), zp], 1).contiguous()
     q["V"] = [torch.stack([e["u"].expand(Q, H), g[:, None] * e["u"], e["d"].expand(Q, H)], 1).contiguous()
               for e, g in zip(pk["deep"], q["g"][1:])]                                 # [Q,3,64] per layer l >= 1
     q["vzero"] = torch.zeros((1, 3, H), device=E.device)
@@ -1327,23 +1227,9 @@ def _gossip_query_terms(gnn: BaseGNN, pk: dict, query_emb: torch.Tensor) -> dict
     key = (query_emb.data_ptr(), query_emb._version, tuple(query_emb.shape))
     if pk["qcache"] is not None and pk["qcache"][0] == key:
         return pk["qcache"][1]
-    core = gnn.gnn_core
-    He = gossip_emb_width(core)
-    E = query_emb.float()
-    C0, D0 = pk["C0"], pk["D0"]
-    w_pre, b_pre = pk["w_pre"], pk["b_pre"]
-    q = {}
-    q["g0"] = core.convs[0]._gate_value(E).reshape(-1).contiguous()          # gnn_model.py:340
-    q["g1"] = core.convs[1]._gate_value(E).reshape(-1).contiguous()
-    a_q = E @ C0[:, :He].t() + (_mv(C0[:, He:], b_pre) + pk["c0"])             # lin_com(h0) const part
-    v = _mv(C0[:, He:], w_pre)
-    D0a, D0b, D0c = D0[:, :H], D0[:, H:H + He], D0[:, H + He:]
-    q["p"] = (a_q @ D0a.t()).contiguous()
-    q["r"] = _mv(D0a, v).contiguous()
-    q["t"] = _mv(D0c, w_pre).contiguous()
-    q["z"] = (E @ D0b.t() + (_mv(D0c, b_pre) + pk["d0"])).contiguous()
-    P0 = pk["P0"]
-    q["zp"] = (E @ P0[:, :He].t() + (_mv(P0[:, He:He + H], b_pre) + pk["p0"])).contiguous()     # [Q,64]
+    (g0, g1), *terms = _gossip_layer0_terms(gnn.gnn_core, gnn.post_mp[0], query_emb.float(), pk["w_pre"], pk["b_pre"])
+    q = dict(zip(("p", "r", "t", "z", "tp", "zp"), (v.contiguous() for v in terms)))
+    q["g0"], q["g1"] = g0.contiguous(), g1.contiguous()
     pk["qcache"] = (key, q)
     return q
 
@@ -1361,42 +1247,29 @@ def gossip_forward(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tensor) ->
     N, Q = x.shape
     if Q != query_emb.shape[0]:
         raise ValueError("batch.x has a different number of query columns than query_emb rows")
-    if FUSED_GOSSIP:
-        (w3, b3), (w5, b5) = pk["post"]
-        outs = []
-        # the scalars pre-pass maps one lane to one query: more than 64 queries (the labelled queries
-        # of --use_node_feature) go in column groups
-        for q0 in range(0, Q, 64):
-            q1 = min(q0 + 64, Q)
-            sl = (lambda t: t) if (q0 == 0 and q1 == Q) else (lambda t: t[q0:q1].contiguous())
-            xs = x if (q0 == 0 and q1 == Q) else x[:, q0:q1].contiguous()
-            scal4 = ops.gossip_scalars(xs, batch.rowptr, batch.col, sl(q["g0"]), sl(q["g1"]))
-            v = {"g1": sl(q["g1"]), "p": sl(q["p"]), "z": sl(q["z"]), "zp": sl(q["zp"]), "r": q["r"],
-                 "t": q["t"], "u": pk["ws1"][0], "tp": pk["wsp"][1], "d1": pk["d1"],
-                 # the fused kernel takes n-major ([out, in]) weight blocks
-                 "w1s": pk["fused_w1s"], "wps": pk["fused_wps"], "w3s": pk["fused_w3s"], "b3": b3,
-                 "w5s": pk["fused_w5s"], "b5": b5, "w7": pk["w7"], "b7": pk["b7"]}
-            tperm = batch.tile_perm if GOSSIP_TILE_ORDER else None
-            if GOSSIP_F16X3:
-                v["wstream"], v["winv"] = pk["wstream"], pk["winv"]
-                outs.append(ops.gossip_fused_f16(scal4, batch.rowptr, batch.col, N, q1 - q0, v, batch.work_queue,
-                                                 tile_perm=tperm,
-                                                 out=getattr(batch, "out_buf", None) if (q0 == 0 and q1 == Q) else None))
-            else:
-                outs.append(ops.gossip_fused(scal4, batch.rowptr, batch.col, N, q1 - q0, v, tile_perm=tperm))
-        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
-    h1, scal = ops.gossip_layer0(x, batch.rowptr, batch.col, q["g0"], q["g1"], q["p"], q["r"],
-                                 q["t"], q["z"])                                  # layer 0
-    hh = ops.gossip_gather(h1, batch.rowptr, batch.col, N, Q, q["g1"])           # layer 1 aggregate
-    h2 = ops.gemm(hh, pk["wt1"], pk["d1"], a2=h1, act=ops.ACT_RELU, s=scal, ws=pk["ws1"])
-    y = ops.gemm(h1, pk["wtp"], q["zp"], a2=h2, act=ops.ACT_LEAKY, slope=0.1, s=scal,
-                 ws=pk["wsp"])                                                    # post_mp.0
-    del hh
     (w3, b3), (w5, b5) = pk["post"]
-    y = ops.gemm(y, w3, b3, act=ops.ACT_RELU)
-    y = ops.gemm(y, w5, b5, act=ops.ACT_RELU)
-    out = ops.rowdot_add(y, pk["w7"], pk["b7"], add=x.reshape(-1))               # post_mp.7 + x
-    return out.view(N, Q)
+    outs = []
+    # the scalars pre-pass maps one lane to one query: more than 64 queries (the labelled queries
+    # of --use_node_feature) go in column groups
+    for q0 in range(0, Q, 64):
+        q1 = min(q0 + 64, Q)
+        sl = (lambda t: t) if (q0 == 0 and q1 == Q) else (lambda t: t[q0:q1].contiguous())
+        xs = x if (q0 == 0 and q1 == Q) else x[:, q0:q1].contiguous()
+        scal4 = ops.gossip_scalars(xs, batch.rowptr, batch.col, sl(q["g0"]), sl(q["g1"]))
+        v = {"g1": sl(q["g1"]), "p": sl(q["p"]), "z": sl(q["z"]), "zp": sl(q["zp"]), "r": q["r"],
+             "t": q["t"], "u": pk["u1"], "tp": q["tp"], "d1": pk["d1"],
+             # the fused kernel takes n-major ([out, in]) weight blocks
+             "w1s": pk["fused_w1s"], "wps": pk["fused_wps"], "w3s": pk["fused_w3s"], "b3": b3,
+             "w5s": pk["fused_w5s"], "b5": b5, "w7": pk["w7"], "b7": pk["b7"]}
+        tperm = batch.tile_perm if GOSSIP_TILE_ORDER else None
+        if GOSSIP_F16X3:
+            v["wstream"], v["winv"] = pk["wstream"], pk["winv"]
+            outs.append(ops.gossip_fused_f16(scal4, batch.rowptr, batch.col, N, q1 - q0, v, batch.work_queue,
+                                             tile_perm=tperm,
+                                             out=getattr(batch, "out_buf", None) if (q0 == 0 and q1 == Q) else None))
+        else:
+            outs.append(ops.gossip_fused(scal4, batch.rowptr, batch.col, N, q1 - q0, v, tile_perm=tperm))
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
 
 def gossip_forward_train(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tensor) -> torch.Tensor:
@@ -1461,25 +1334,16 @@ def gossip_forward_train(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tens
         return pred.view(N, Q)
     # ---- operands folded from the parameters with differentiable torch ops (more than 64 queries, or query embeddings
     #      of another width than 64) -------------------------------------------------------------------------------------
-    g0 = c0._gate_value(E).reshape(-1)
-    g1 = c1._gate_value(E).reshape(-1)
-    a_q = E @ C0[:, :He].t() + (_mv(C0[:, He:], b_pre) + cb0)
-    v = _mv(C0[:, He:], w_pre)
-    D0a, D0b, D0c = D0[:, :H], D0[:, H:H + He], D0[:, H + He:]
-    p = a_q @ D0a.t()
-    r = _mv(D0a, v).expand(Q, H)
-    t = _mv(D0c, w_pre).expand(Q, H)
-    z = E @ D0b.t() + (_mv(D0c, b_pre) + db0)
+    (g0, g1), p, r, t, z, tp, zp = _gossip_layer0_terms(core, gnn.post_mp[0], E, w_pre, b_pre)
+    r, t = r.expand(Q, H), t.expand(Q, H)
     V0 = torch.stack([p, g0[:, None] * p, r, g0[:, None] * r, t, z], 1)          # [Q,6,64]
     D1a, D1b = D1[:, :H], D1[:, H:]
     wt1 = torch.cat([(D1a @ C1).t(), D1b.t()], 0)
     u = _mv(D1a, cb1).expand(Q, H)
     V1 = torch.stack([u, g1[:, None] * u, db1.expand(Q, H)], 1)                     # [Q,3,64]
-    P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
+    P0 = gnn.post_mp[0].weight
     wtp = torch.cat([P0[:, He + H:He + 2 * H].t(), P0[:, He + 2 * H:He + 3 * H].t()], 0)
-    tp = _mv(P0[:, He:He + H], w_pre).expand(Q, H)
-    zp = E @ P0[:, :He].t() + (_mv(P0[:, He:He + H], b_pre) + p0)
-    Vp = torch.stack([tp, zp], 1)                                                   # [Q,2,64]
+    Vp = torch.stack([tp.expand(Q, H), zp], 1)                                      # [Q,2,64]
     pred = AG.GossipTrunk.apply(batch.rowptr, batch.col, N, Q, C6, C3, C2, x.reshape(-1), (1.0 - g1).detach().contiguous(),
                                 gnn.post_mp[3].weight.detach(), gnn.post_mp[5].weight.detach(), drop,
                                 V0, g1, wt1, V1, wtp, Vp, gnn.post_mp[3].weight.t(), gnn.post_mp[3].bias,
@@ -1497,30 +1361,19 @@ def _gossip_train_deep(gnn: BaseGNN, batch: GossipBatch, E, w_pre, b_pre, C6, C3
     L = core.layer_num
     x = batch.x
     N, Q = x.shape
-    c0 = core.convs[0]
-    C0, D0 = c0.lin_com.weight, c0.lin_update.weight
-    g0 = c0._gate_value(E).reshape(-1)
-    a_q = E @ C0[:, :He].t() + (_mv(C0[:, He:], b_pre) + c0.lin_com.bias)
-    v = _mv(C0[:, He:], w_pre)
-    D0a, D0b, D0c = D0[:, :H], D0[:, H:H + He], D0[:, H + He:]
-    p = a_q @ D0a.t()
-    r = _mv(D0a, v).expand(Q, H)
-    t = _mv(D0c, w_pre).expand(Q, H)
-    z = E @ D0b.t() + (_mv(D0c, b_pre) + c0.lin_update.bias)
-    V0 = torch.stack([p, g0[:, None] * p, r, g0[:, None] * r, t, z], 1)          # [Q,6,64]
+    g, p, r, t, z, tp, zp = _gossip_layer0_terms(core, gnn.post_mp[0], E, w_pre, b_pre)
+    r, t = r.expand(Q, H), t.expand(Q, H)
+    V0 = torch.stack([p, g[0][:, None] * p, r, g[0][:, None] * r, t, z], 1)      # [Q,6,64]
     lw = []
     for l in range(1, L):
         c = core.convs[l]
         Da, Db = c.lin_update.weight[:, :H], c.lin_update.weight[:, H:]
-        g = c._gate_value(E).reshape(-1)
         u = _mv(Da, c.lin_com.bias).expand(Q, H)
-        lw += [g, torch.cat([(Da @ c.lin_com.weight).t(), Db.t()], 0),
-               torch.stack([u, g[:, None] * u, c.lin_update.bias.expand(Q, H)], 1)]
-    P0, p0 = gnn.post_mp[0].weight, gnn.post_mp[0].bias
+        lw += [g[l], torch.cat([(Da @ c.lin_com.weight).t(), Db.t()], 0),
+               torch.stack([u, g[l][:, None] * u, c.lin_update.bias.expand(Q, H)], 1)]
+    P0 = gnn.post_mp[0].weight
     wtp = torch.cat([P0[:, He + l * H:He + (l + 1) * H].t() for l in range(1, L + 1)], 0)   # [64 L, 64]
-    tp = _mv(P0[:, He:He + H], w_pre).expand(Q, H)
-    zp = E @ P0[:, :He].t() + (_mv(P0[:, He:He + H], b_pre) + p0)
-    Vp = torch.stack([tp, zp], 1)                                                   # [Q,2,64]
+    Vp = torch.stack([tp.expand(Q, H), zp], 1)                                      # [Q,2,64]
     return AG.GossipTrunkDeep.apply(batch.rowptr, batch.col, N, Q, C6, C3, C2, x.reshape(-1),
                                     gnn.post_mp[3].weight.detach(), gnn.post_mp[5].weight.detach(), drop, L,
                                     V0, gnn.post_mp[3].weight.t(), gnn.post_mp[3].bias, gnn.post_mp[5].weight.t(),

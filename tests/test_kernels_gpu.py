@@ -387,6 +387,31 @@ def test_fused_pooling_equals_segment_sum(num_rows, seg_kind):
     _close(got, exact, rtol=1e-5, atol=1e-4 * max(1, max(lens)) ** 0.5)
 
 
+def test_pool_reduce_multi_changes_no_bit():
+    """desco_pool_reduce_multi_f32 (the layers' partial sums reduced by one launch per group of 8) == one
+    desco_pool_reduce_f32 per layer, bit for bit, with and without the extra rows, on strided column blocks as the model
+    uses them; 7 layers (one group) and 11 (two groups); tile index of a real batch (golden graphs + random families)."""
+    from desco_amd.batch import NeighborhoodBatch
+    from desco_amd.graphs import GraphSet
+    from desco_amd.partition import build_partition
+    from helpers import golden_graphs, random_family_graphs
+    part = build_partition(GraphSet.from_edge_lists(golden_graphs(max_n=60) + random_family_graphs(3, 40)), 4)
+    batch = NeighborhoodBatch(part, DEV)
+    bits, slot, nslots = batch.pool_index()
+    B, seg = batch.num_graphs, batch.count_ptr
+    for layers in (7, 11):
+        g = torch.Generator().manual_seed(layers)
+        parts = [torch.randn(nslots, 64, generator=g).to(DEV) for _ in range(layers)]
+        anch = torch.randn(B, 64 * layers, generator=g).to(DEV)
+        for with_extra in (False, True):
+            extras = [anch[:, l * 64:(l + 1) * 64] if with_extra else None for l in range(layers)]
+            multi = torch.full((B, 64 * layers), float("nan"), device=DEV)
+            ops.pool_reduce_multi(parts, bits, slot, seg, B, extras, [multi[:, l * 64:(l + 1) * 64] for l in range(layers)])
+            for l in range(layers):
+                one = ops.pool_reduce(parts[l], bits, slot, seg, B, extra=extras[l])
+                assert torch.isfinite(one).all() and torch.equal(multi[:, l * 64:(l + 1) * 64], one), (layers, with_extra, l)
+
+
 @pytest.mark.parametrize("m,k1,k2,n", [(1, 64, 0, 64), (300, 128, 64, 128), (1000, 576, 0, 576), (4097, 64, 0, 192)])
 def test_gemm_bf16_rounds_operands_to_nearest_even(m, k1, k2, n):
     """bf16 training GEMM == exact product of the RNE-bf16-rounded operands (fp32 accumulation)."""

@@ -291,10 +291,9 @@ def test_repeated_runs_are_bitwise_identical(setup):
             assert torch.equal(out[k], v), k
 
 
-def test_fused_gossip_equals_unfused_incl_hubs(setup):
-    """The on-chip gossip kernel vs the 7-launch path on a graph set with hub nodes whose tile
+def test_fused_gossip_vs_oracle_incl_hubs(setup):
+    """The on-chip gossip kernel vs the CPU oracle on a graph set with hub nodes whose tile
     holds more neighbour records than one staging pass (ECAP = 768)."""
-    import desco_amd.gnn_model as GM
     nm, gm, qids, queries = setup
     rng = np.random.default_rng(5)
     hub_n = 1500
@@ -303,17 +302,13 @@ def test_fused_gossip_equals_unfused_incl_hubs(setup):
     graphs = golden_graphs(max_n=60)[:6] + [hub] + golden_graphs(max_n=60)[6:9]
     gs = GraphSet.from_edge_lists(graphs)
     x = torch.from_numpy(rng.gamma(1.0, 4.0, size=(gs.num_nodes, len(queries)))).float()
-    gm.set_query_emb(nm.get_query_emb())
+    qemb = nm.get_query_emb()
+    gm.set_query_emb(qemb)
     batch = GossipBatch(gs, DEV, x=x)
-    try:
-        GM.FUSED_GOSSIP = True
-        fused = gm.graph_to_count(batch)
-        GM.FUSED_GOSSIP = False
-        unfused = gm.graph_to_count(batch)
-    finally:
-        GM.FUSED_GOSSIP = True
-    report("gossip fused vs unfused", fused - batch.x, unfused - batch.x)
-    assert_logits_close("gossip fused vs unfused", fused - batch.x, unfused - batch.x)
+    fused = gm.graph_to_count(batch).cpu()
+    ref = OM.gossip_graph_to_count(cpu_sd(gm), x, batch.edge_index.numpy(), qemb.cpu(), 2)
+    report("gossip fused vs oracle", fused - x, ref - x)
+    assert_logits_close("gossip fused vs oracle", fused - x, ref - x)
 
 
 def test_gossip_f16x3_equals_bf16x6_incl_hubs_and_ragged_tiles(setup):
@@ -409,19 +404,15 @@ def test_gossip_tile_order_is_a_permutation_and_changes_no_bit(setup):
     assert torch.equal(a, b)
 
 
-def test_unfused_shmp_equals_fused(setup):
-    import desco_amd.gnn_model as GM
-    nm, *_ = setup
-    part = build_partition(GraphSet.from_edge_lists(golden_graphs(max_n=60)), 4)
-    batch = NeighborhoodBatch(part, DEV)
-    try:
-        GM.FUSED_SHMP_LAYER = False
-        a = nm._logits(batch, exp2=False)
-    finally:
-        GM.FUSED_SHMP_LAYER = True
+def test_fused_shmp_layers_vs_oracle(setup):
+    nm, _, qids, queries = setup
+    graphs = golden_graphs(max_n=60)
+    batch = NeighborhoodBatch(build_partition(GraphSet.from_edge_lists(graphs), 4), DEV)
     with torch.no_grad():
-        b = nm._logits(batch, exp2=False)
-    assert_logits_close("layer-by-layer vs fused SHMP layer", a, b)
+        got = nm._logits(batch, exp2=False)
+    _, _, neighs = OP.neighborhood_dataset(graphs, 4)
+    ref, _ = OM.neighborhood_logits(cpu_sd(nm), OP.neighborhood_batch(neighs), OP.query_batch(queries), emulate_quirk=False)
+    assert_logits_close("fused SHMP layers vs oracle", got, ref)
 
 
 def test_neighborhood_training_loss_and_gradients(setup):
@@ -1056,24 +1047,6 @@ def test_empty_loss_and_replaced_parameters(setup):
         nm.emb_model.gnn_core.updates[3]["count"].weight.mul_(0.5)
     g2 = grads()
     assert not torch.equal(g2["emb_model.gnn_core.updates.3.count.weight"], g1["emb_model.gnn_core.updates.3.count.weight"])
-
-
-def test_pool_reduce_in_one_launch_changes_no_bit(setup):
-    """gnn_model.POOL_REDUCE_MULTI: the seven pooled layers' partial sums reduced by one launch
-    (desco_pool_reduce_multi_f32) instead of one launch per layer -- same arithmetic per layer, identical logits."""
-    import desco_amd.gnn_model as GM
-    nm, *_ = setup
-    part = build_partition(GraphSet.from_edge_lists(golden_graphs(max_n=60) + random_family_graphs(3, 40)), 4)
-    batch = NeighborhoodBatch(part, DEV)
-    outs = []
-    for multi in (True, False):
-        GM.POOL_REDUCE_MULTI = multi
-        try:
-            with torch.no_grad():
-                outs.append(nm._logits(batch, exp2=False).clone())
-        finally:
-            GM.POOL_REDUCE_MULTI = True
-    assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
 
 
 def test_first_layer_pooling_fused_into_its_launch(setup):
