@@ -543,6 +543,21 @@ extern "C" int desco_gemm_bf16x6_f32(const float* a1, int64_t lda1, int k1, cons
                      stream);
 }
 
+namespace desco {
+const char* dropout_check(const desco_dropout* d, int64_t num_rows, int64_t num_cols);   // dropout.hip
+
+// the site / shape limits of a dropout descriptor (the kernels build the Philox counter as col | site << 24 in 32 bits:
+// an unchecked site 256 would draw site 0's mask): 0 without a key or when it passes
+static int drop_desc_check(const char* who, const desco_gemm_desc& d) {
+  if (!d.drop.key) return 0;
+  if (const char* why = dropout_check(&d.drop, d.m, d.n)) {
+    std::string msg = std::string(who) + ": " + why;
+    return fail(DESCO_EINVAL, msg.c_str());
+  }
+  return 0;
+}
+}  // namespace desco
+
 // One descriptor of desco_gemm_f32_multi's form on the bf16x6 pipe (training: the gossip step's forward and input-gradient
 // products, with the activation-derivative gate and the dropout factor in the epilogue)
 extern "C" int desco_gemm_bf16x6_desc_f32(const desco_gemm_desc* d, const int16_t* w_planes, int ws_rows,
@@ -551,6 +566,7 @@ extern "C" int desco_gemm_bf16x6_desc_f32(const desco_gemm_desc* d, const int16_
   if (d->accum || (d->gate && (d->ldg < d->n)) || ws_rows < 1 || d->m >= ((int64_t)1 << 31))
     return desco::fail(DESCO_EINVAL, "desco_gemm_bf16x6_desc_f32: accum is not supported; gate rows shorter than n; "
                                      "ws_rows >= 1; m < 2^31");
+  if (int rc = desco::drop_desc_check("desco_gemm_bf16x6_desc_f32", *d)) return rc;
   const desco::DropArgs drop{d->drop.key, d->drop.site, d->drop.threshold, d->drop.scale};
   return gemm_planes("desco_gemm_bf16x6_desc_f32: bad argument (k%32, n%64, 16-byte alignment)", 3, d->a1, d->lda1,
                      d->k1, d->a2, d->lda2, d->k2, w_planes, d->n, d->bias, d->bias_rows, d->s, d->ns, d->ws, d->act,
@@ -660,6 +676,7 @@ static int gemm_planes_multi(int np, int num, const desco_gemm_desc* descs, cons
         (d.gate && d.ldg < d.n))
       return fail(DESCO_EINVAL, "desco_gemm_bf16x6_multi_f32: bad descriptor (k%32, n%64, 16-byte alignment, no scalar "
                                 "tail / accum / per-row bias)");
+    if (int rc = drop_desc_check(np == 3 ? "desco_gemm_bf16x6_multi_f32" : "desco_gemm_bf16_multi_f32", d)) return rc;
     const int64_t gm = (d.m + 127) / 128;
     const int ny = d.n / 64;
     const int64_t nb = ((gm + 7) / 8) * 8 * ny;

@@ -292,7 +292,8 @@ extern "C" int desco_affine_rows_dropout_f32(const float* base, const float* c, 
 extern "C" int desco_affine_rows_bwd_f32(const float* c, int ks, const float* dz, int qv,
                                          int64_t num_rows, float* dv, float* workspace,
                                          desco_stream_t stream) {
-  if (!c || !dz || !dv || !workspace || ks < 1 || ks > 8 || qv < 1 || num_rows < 0 ||
+  // (no rows: c / dz are never read -- torch hands its empty tensors over as NULL -- and dv comes out zero)
+  if ((num_rows > 0 && (!c || !dz)) || !dv || !workspace || ks < 1 || ks > 8 || qv < 1 || num_rows < 0 ||
       num_rows % qv)
     return fail(DESCO_EINVAL, "desco_affine_rows_bwd_f32: bad argument");
   const int64_t num_i = num_rows / qv;

@@ -676,7 +676,8 @@ extern "C" int desco_count_head_bwd_f32(const float* t, int64_t ldt, const float
                                         int64_t lddl, int64_t num_b, int num_q, float* dt,
                                         int64_t lddt, float* dqh, float* dw2, float* workspace,
                                         desco_stream_t stream) {
-  if (!t || !qh || !w2 || !dl || !dt || !dqh || !dw2 || !workspace || num_b < 0 || num_q < 1 ||
+  // (an empty batch reads no row of t / dl and writes none of dt: torch hands its empty tensors over as NULL)
+  if ((num_b > 0 && (!t || !dl || !dt)) || !qh || !w2 || !dqh || !dw2 || !workspace || num_b < 0 || num_q < 1 ||
       hid <= 0)
     return fail(DESCO_EINVAL, "desco_count_head_bwd_f32: bad argument");
   hipStream_t st = (hipStream_t)stream;

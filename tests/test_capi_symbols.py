@@ -161,3 +161,42 @@ def test_round6_entry_points_validate_their_arguments():
     assert b"desco_act_grad_dropout_f32" in L.desco_last_error()
     g = (_lib.GemmDesc * 1)()
     assert ctypes.sizeof(_lib.GemmDesc) % 8 == 0 and _lib.GemmDesc.drop.offset % 8 == 0
+
+
+def test_training_entry_points_validate_their_arguments():
+    """Training-step entry points: each limit below comes back as DESCO_EINVAL naming the entry point, before any HIP call.
+    Every other argument is valid, so the one limit named is what each call trips on."""
+    L = _lib.lib()
+    buf = np.zeros(64 * 1024, np.float32)
+    p = buf.ctypes.data
+    assert p % 16 == 0
+
+    def rejects(name, rc):
+        assert rc == -1, name
+        assert name.encode() in L.desco_last_error(), (name, L.desco_last_error())
+        assert L.desco_rng_next(None, None, None) == -1          # (resets the message for the next case)
+
+    rejects("desco_affine_rows_bwd_f32", L.desco_affine_rows_bwd_f32(p, 3, p, 29, 29 * 5 + 1, p, p, None))  # rows % qv
+    rejects("desco_affine_rows_bwd_f32", L.desco_affine_rows_bwd_f32(p, 9, p, 29, 29 * 5, p, p, None))      # ks = 9
+    rejects("desco_count_head_wide_f32", L.desco_count_head_wide_f32(p, 96, p, 96, 96, p, 0.0, None, 0.01, 0, p, 4, 10, 4,
+                                                                     None))                              # hid = 96
+    rejects("desco_count_head_wide_f32", L.desco_count_head_wide_f32(p, 64, p, 64, 64, p, 0.0, None, 0.01, 0, p, 33, 10, 33,
+                                                                     None))                              # num_q = 33
+    rejects("desco_loss_f32", L.desco_loss_f32(p, p, 0, 0, p, p, p, None))                                # count 0
+    rejects("desco_loss_f32", L.desco_loss_f32(p, p, 0, 1, p, p, p, None))
+    table = np.zeros(64, np.int64)
+    rejects("desco_fold_shmp_fwd_f32", L.desco_fold_shmp_fwd_f32(table.ctypes.data, 1, 5, 1, p, p, None))  # slots = 5
+    prm, out = _lib.GossipFoldParams(), _lib.GossipFoldOut()
+    for n, _ in _lib.GossipFoldParams._fields_:
+        if n == "num_q":
+            continue
+        v = getattr(prm, n)
+        if isinstance(v, ctypes.Array):
+            for i in range(len(v)):
+                v[i] = p
+        else:
+            setattr(prm, n, p)
+    for n, _ in _lib.GossipFoldOut._fields_:
+        setattr(out, n, p)
+    prm.num_q = 65
+    rejects("desco_gossip_fold_fwd_f32", L.desco_gossip_fold_fwd_f32(ctypes.byref(prm), ctypes.byref(out), None))

@@ -1252,3 +1252,97 @@ def test_first_layer_rows_as_a_table_changes_no_bit(setup):
     assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
     # too many distinct tuples for the cap: the materialised path runs
     assert NeighborhoodBatch(part, DEV).degree_table_index(max_rows=3) is None
+
+
+def test_without_tconv_training_matches_oracle(setup):
+    """--use_tconv off, training: loss and every parameter gradient vs torch autograd through the oracle composed as in
+    test_without_tconv_matches_oracle (union edge types for both models, then head_logits and the training criterion).
+    Only this setting ties two slots of a row to one weight, the branch of fold_shmp_bwd that sums their gradients."""
+    from desco_amd.lightning_model import NeighborhoodCountingModel
+    from helpers import neigh_args
+    _, _, qids, queries = setup
+    torch.manual_seed(5)
+    nm = NeighborhoodCountingModel(1, 64, neigh_args(use_tconv=False)).to_hetero_old(False, False)
+    with torch.no_grad():
+        for p in nm.parameters():
+            if p.dim() == 2:
+                p.mul_(1.3)
+    nm = nm.to(DEV)
+    nm.set_queries(qids)
+    graphs = golden_graphs(max_n=41)[:12]
+    part = build_partition(GraphSet.from_edge_lists(graphs), 4)
+    g = torch.Generator().manual_seed(6)
+    y = torch.floor(torch.rand(part.num_neigh, len(queries), generator=g) ** 3 * 40)
+    batch = NeighborhoodBatch(part, DEV, y=y)
+    nm.zero_grad()
+    loss = nm.train_forward(batch, 0)
+    loss.backward()
+    sd = {k: v.detach().cpu().clone().requires_grad_(True) for k, v in nm.state_dict().items()}
+    _, _, neighs = OP.neighborhood_dataset(graphs, 4)
+    union_types = (("count", "union", "canonical"), ("canonical", "union", "count"), ("count", "union", "count"))
+    ob = OP.neighborhood_batch(neighs, tconv=False)
+    qb = OP.query_batch(queries, tconv=False)
+    emb_q = OM.base_gnn_hetero(sd, "emb_model_query", qb, ("union_node",), (("union_node", "union", "union_node"),), 8)
+    emb_t = OM.base_gnn_hetero(sd, "emb_model", ob, OP.NODE_TYPES, union_types, 8, emulate_quirk=False)
+    ref_loss = OM.train_loss_from_logits(OM.head_logits(sd, emb_t, emb_q), y)
+    ref_loss.backward()
+    report("no-tconv train loss", loss.detach().reshape(1), ref_loss.detach().reshape(1))
+    assert_loss_close("no-tconv train loss", loss.detach(), ref_loss.detach())
+    worst, checked = 0.0, 0
+    for name, p in nm.named_parameters():
+        ref = sd[name].grad
+        if ref is None:
+            assert p.grad is None or float(p.grad.abs().max()) == 0.0, name
+            continue
+        assert p.grad is not None, name
+        worst = max(worst, assert_grad_close(name, p.grad, ref))
+        checked += 1
+    assert checked > 20
+    print(f"[parity] no-tconv training: worst relative gradient error over {checked} tensors: {worst:.3e}")
+
+
+def test_gossip_training_on_a_multi_slab_batch(setup):
+    """Gossip training on 3119 nodes with hub rows (the Syn_1827-shaped block with its dense 704-node graph, plus three
+    680-node G(n, m) graphs): more than 1024 nodes, so affine_rows_bwd reduces several slabs (the golden batches run
+    one).  Loss and every gradient vs torch autograd through the oracle."""
+    from desco_amd import synthetic
+    nm, _, qids, queries = setup
+    _, gm = make_models(seed=0)
+    gm = gm.to(DEV)
+    full = synthetic.syn_1827_shaped(60)
+    sizes = np.diff(full.graph_ptr)
+    keep = [g for g in np.argsort(sizes)[::-1] if sizes[g] <= 160][:4]
+    keep.append(int(np.argsort(sizes)[::-1][1]))
+    graphs = [full.edge_lists()[g] for g in sorted(keep)]
+    rng = np.random.default_rng(77)
+    graphs += [synthetic._force_connected(*synthetic._gnm(680, 2100, rng), rng) for _ in range(3)]
+    gs = GraphSet.from_edge_lists(graphs)
+    deg = np.diff(gs.rowptr)
+    assert gs.num_nodes >= 3000 and int(deg.max()) >= 4 * int(np.median(deg)), (gs.num_nodes, int(deg.max()))
+    print(f"[shape] gossip multi-slab batch: {gs.num_nodes} nodes ({(gs.num_nodes + 1023) // 1024} slabs of affine_rows_bwd), "
+          f"degree median {int(np.median(deg))}, max {int(deg.max())}")
+    g = torch.Generator().manual_seed(8)
+    x = torch.rand(gs.num_nodes, len(queries), generator=g) * 20
+    y = torch.floor(torch.rand(gs.num_nodes, len(queries), generator=g) * 25)
+    qemb = nm.get_query_emb()
+    gm.set_query_emb(qemb)
+    batch = GossipBatch(gs, DEV, x=x, y=y)
+    gm.zero_grad()
+    loss = gm.train_forward(batch, 0)
+    loss.backward()
+    sd = {k: v.detach().cpu().clone().requires_grad_(True) for k, v in gm.state_dict().items()}
+    ref_loss = OM.gossip_loss(sd, x, y, batch.edge_index.numpy(), qemb.cpu(), 2)
+    ref_loss.backward()
+    report("gossip multi-slab train loss", loss.detach().reshape(1), ref_loss.detach().reshape(1))
+    assert_loss_close("gossip multi-slab train loss", loss.detach(), ref_loss.detach())
+    worst, checked = 0.0, 0
+    for name, p in gm.named_parameters():
+        ref = sd[name].grad
+        if ref is None or float(ref.abs().max()) == 0.0:
+            assert p.grad is None or float(p.grad.abs().max()) == 0.0, name
+            continue
+        assert p.grad is not None, name
+        worst = max(worst, assert_grad_close(name, p.grad, ref, tol=GOSSIP_GRAD_TOL))
+        checked += 1
+    assert checked > 10
+    print(f"[parity] gossip multi-slab training: worst relative gradient error over {checked} tensors: {worst:.3e}")
