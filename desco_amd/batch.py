@@ -101,12 +101,40 @@ class NeighborhoodBatch(_TrainIndexMixin):
     def _seg_ptr_device(self):
         return self.count_ptr
 
+    def _pool_on_device(self) -> bool:
+        """The pooling index is built by desco_pool_index_dev only when this batch holds a device ``count_ptr`` on a
+        cuda device (``DESCO_DEVICE_PROLOGUE=0`` / ``device_prologue = False``: the numpy path on the host copy)."""
+        cp = self.__dict__.get("count_ptr")
+        on = self.__dict__.get("device_prologue")
+        if on is None:
+            import os
+            on = os.environ.get("DESCO_DEVICE_PROLOGUE", "1") != "0"
+        return bool(on) and isinstance(cp, torch.Tensor) and cp.is_cuda
+
+    def _pool_dev(self):
+        """(bits, slot, num_slots, largest, smallest neighborhood) from the device; one read-back, cached"""
+        r = self.__dict__.get("_pool_dev_result")
+        if r is None:
+            from . import ops
+            B = int(self.count_ptr.numel()) - 1
+            nc = self.__dict__.get("num_count")
+            if nc is None:
+                nc = self.part.num_count
+            bits, slot, totals = ops.pool_index_dev(self.count_ptr, B, nc)
+            ns, mx, mn, _ = totals.tolist() if B else (0, 0, 1, 0)
+            r = self.__dict__["_pool_dev_result"] = (bits, slot, int(ns), int(mx), int(mn))
+        return r
+
     def max_count_rows(self) -> int:
-        """the largest number of count rows of a neighborhood of this batch (host data, cached)"""
+        """the largest number of count rows of a neighborhood of this batch (cached)"""
         m = self.__dict__.get("_max_count_rows")
         if m is None:
-            d = np.diff(self.part.count_ptr)
-            m = self.__dict__["_max_count_rows"] = int(d.max()) if len(d) else 0
+            if self._pool_on_device():
+                m = self._pool_dev()[3]
+            else:
+                d = np.diff(self.part.count_ptr)
+                m = int(d.max()) if len(d) else 0
+            self.__dict__["_max_count_rows"] = m
         return m
 
     def pool_index(self):
@@ -114,6 +142,13 @@ class NeighborhoodBatch(_TrainIndexMixin):
         per 16-row wave tile of the layer kernel, the bitmap of count rows that END a neighborhood and the first partial
         slot of the tile (a tile uses one slot per neighborhood that has a row in it)."""
         idx = self.__dict__.get("_pool_index")
+        if idx is None and self._pool_on_device():
+            bits, slot, ns, _, mn = self._pool_dev()
+            if mn <= 0:
+                raise ValueError("fused pooling needs at least one count row per neighborhood")
+            if ns >= 2 ** 31:
+                raise ValueError("too many pooling slots for int32")
+            idx = self.__dict__["_pool_index"] = (bits, slot, ns)
         if idx is None:
             TR = 16
             cp = self.part.count_ptr.astype(np.int64)

@@ -848,6 +848,90 @@ def segment_ids(seg_ptr: torch.Tensor, num_rows: int) -> torch.Tensor:
     return out
 
 
+def partition_slice_dev(count_ptr: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, count_orig: torch.Tensor,
+                        num_neigh: int, num_count: int, b0: int, b1: int, block_count: int, block_edges: int):
+    """(count_ptr, count_orig, vrowptr, vcol) of neighborhoods [b0, b1) as a self-contained block, on the device
+    (desco_partition_dev_slice); ``block_count`` / ``block_edges`` are the block's sizes, read back by the caller."""
+    dev, nb = count_ptr.device, b1 - b0
+    i32 = dict(device=dev, dtype=torch.int32)
+    if nb <= 0:
+        return torch.zeros(1, **i32), torch.empty(0, **i32), torch.zeros(1, **i32), torch.empty(0, **i32)
+    cp = torch.empty(nb + 1, **i32)
+    co = torch.empty(block_count, **i32)
+    vr = torch.empty(4 * (block_count + nb) + 1, **i32)
+    vc = torch.empty(block_edges, **i32)
+    p = lambda t, n: _dev(t, n, torch.int32) if t.numel() else None
+    _lib.check(_lib.lib().desco_partition_dev_slice(
+        _dev(count_ptr, "count_ptr", torch.int32), _dev(vrowptr, "vrowptr", torch.int32), p(vcol, "vcol"),
+        p(count_orig, "count_orig"), num_neigh, num_count, b0, b1, block_count, block_edges,
+        _dev(cp, "count_ptr_out", torch.int32), p(co, "count_orig_out"), _dev(vr, "vrowptr_out", torch.int32),
+        p(vc, "vcol_out"), _stream()), "partition_slice_dev")
+    return cp, co, vr, vc
+
+
+def partition_degree_sort_dev(count_ptr: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor,
+                              count_orig: torch.Tensor, num_neigh: int, num_count: int, num_edges: int,
+                              neigh_index: Optional[torch.Tensor] = None, num_blocks: int = 0):
+    """(count_orig, vrowptr, vcol) with the count rows of every neighborhood degree-sorted, on the device: bit-identical
+    to ``desco_partition_degree_sort``.  ``neigh_index`` [B,2] int64 (its column 1 is the direction key) or None (the
+    index b); ``num_blocks``: workgroups per launch, 0 = the library's choice."""
+    dev = count_ptr.device
+    i32 = dict(device=dev, dtype=torch.int32)
+    co, vr, vc = torch.empty(num_count, **i32), torch.empty(4 * (num_count + num_neigh) + 1, **i32), \
+        torch.empty(num_edges, **i32)
+    if num_neigh == 0:
+        return co, vr.zero_(), vc
+    L = _lib.lib()
+    ws = torch.empty((int(L.desco_partition_dev_degree_sort_workspace(num_count, num_edges)) + 7) // 8,
+                     device=dev, dtype=torch.int64)
+    p = lambda t, n: _dev(t, n, torch.int32) if t.numel() else None
+    key = None
+    if neigh_index is not None:
+        if neigh_index.shape != (num_neigh, 2) or not neigh_index.is_contiguous():
+            raise ValueError("partition_degree_sort_dev: neigh_index must be a contiguous [num_neigh, 2] tensor")
+        key = _dev(neigh_index, "neigh_index", torch.int64) + 8
+    _lib.check(L.desco_partition_dev_degree_sort(
+        _dev(count_ptr, "count_ptr", torch.int32), num_neigh, num_count, num_edges,
+        _dev(vrowptr, "vrowptr", torch.int32), p(vcol, "vcol"), p(count_orig, "count_orig"), key, 2,
+        p(co, "count_orig_out"), _dev(vr, "vrowptr_out", torch.int32), p(vc, "vcol_out"),
+        _dev(ws, "workspace", torch.int64) if ws.numel() else None, num_blocks, _stream()),
+        "partition_degree_sort_dev")
+    return co, vr, vc
+
+
+def pool_index_dev(count_ptr: torch.Tensor, num_neigh: int, num_count: int):
+    """(pool_bits, pool_slot, totals) of the fused pooling, on the device (desco_pool_index_dev): ``totals`` is a device
+    int64 [4] = (num_slots, largest, smallest number of count rows of a neighborhood, 0) that the caller reads back."""
+    dev = count_ptr.device
+    tiles = (num_count + pool_tile_rows() - 1) // pool_tile_rows()
+    bits = torch.empty(tiles, device=dev, dtype=torch.int32)
+    slot = torch.empty(tiles, device=dev, dtype=torch.int32)
+    # (an empty batch launches nothing: its totals are the zero fill)
+    totals = (torch.empty if num_neigh else torch.zeros)(4, device=dev, dtype=torch.int64)
+    _lib.check(_lib.lib().desco_pool_index_dev(
+        _dev(count_ptr, "count_ptr", torch.int32), num_neigh, num_count,
+        _dev(bits, "pool_bits", torch.int32) if tiles else None,
+        _dev(slot, "pool_slot", torch.int32) if tiles else None, _dev(totals, "totals", torch.int64), _stream()),
+        "pool_index_dev")
+    return bits, slot, totals
+
+
+def neigh_rows_dev(neigh_index: torch.Tensor, graph_ptr: torch.Tensor, num_graphs: int):
+    """(scatter_index [B], neigh_graph_ptr [G+1]) int32 from the device ``neigh_index`` [B,2] int64 and ``graph_ptr``
+    [G+1] int64 (desco_neigh_rows_dev)."""
+    dev, B = graph_ptr.device, neigh_index.shape[0]
+    scatter = torch.empty(B, device=dev, dtype=torch.int32)
+    # (no neighborhood: nothing is launched and the segment pointer is the zero fill)
+    ngp = (torch.empty if B else torch.zeros)(num_graphs + 1, device=dev, dtype=torch.int32)
+    if B and not neigh_index.is_contiguous():
+        raise ValueError("neigh_rows_dev: neigh_index must be contiguous")
+    _lib.check(_lib.lib().desco_neigh_rows_dev(
+        _dev(neigh_index, "neigh_index", torch.int64) if B else None, B, _dev(graph_ptr, "graph_ptr", torch.int64),
+        num_graphs, _dev(scatter, "scatter_index", torch.int32) if B else None,
+        _dev(ngp, "neigh_graph_ptr", torch.int32), _stream()), "neigh_rows_dev")
+    return scatter, ngp
+
+
 def round_bf16(w: torch.Tensor) -> torch.Tensor:
     """int16 tensor of w's shape: round-to-nearest-even bf16 bit patterns (weight operand of
     ``gemm_bf16``)."""

@@ -7,7 +7,6 @@ replaces the reference's list of per-neighborhood ``HeteroData`` objects plus th
 from __future__ import annotations
 
 import ctypes
-from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -28,25 +27,73 @@ SLOT_EDGE_TYPES_CANON_DST = (
 )
 
 
-@dataclass
+_ARRAY_FIELDS = ("neigh_index", "indicator", "count_ptr", "count_orig", "vrowptr", "vcol")
+
+
 class NeighborhoodPartition:
-    """Host arrays for B canonical neighborhoods (see include/desco_hip.h for the layout)."""
-    neigh_index: np.ndarray     # int64 [B,2]  (graph id, node id in graph) == nx_neighs_index
-    indicator: np.ndarray       # bool  [num_nodes]                       == nx_neighs_indicator
-    count_ptr: np.ndarray       # int32 [B+1]
-    count_orig: np.ndarray      # int32 [N_c] global node id of each count row
-    vrowptr: np.ndarray         # int32 [4*(N_c+B)+1]
-    vcol: np.ndarray            # int32 [E]
-    depth: int = 4
-    quirk_batch: int = 0
+    """The arrays of B canonical neighborhoods (see include/desco_hip.h for the layout):
+
+        neigh_index  int64 [B,2]  (graph id, node id in graph) == nx_neighs_index
+        indicator    bool  [num_nodes]                         == nx_neighs_indicator
+        count_ptr    int32 [B+1]
+        count_orig   int32 [N_c]  global node id of each count row
+        vrowptr      int32 [4*(N_c+B)+1]
+        vcol         int32 [E]
+
+    Built from numpy arrays it is a plain host container.  Built on the device (``from_device_arrays``: what
+    ``build_partition_device``, ``slice_device`` and ``degree_sorted_device`` return) the six arrays live in
+    ``device_arrays`` and every field above is a HOST VIEW that is downloaded the first time it is read and then kept
+    (``downloads`` counts them per field); the sizes come from the totals the builder read back, so ``num_neigh``,
+    ``num_count``, ``num_rows`` and ``num_edges`` never download anything."""
+
+    def __init__(self, neigh_index, indicator, count_ptr, count_orig, vrowptr, vcol, depth: int = 4,
+                 quirk_batch: int = 0):
+        self._host = {"neigh_index": neigh_index, "indicator": indicator, "count_ptr": count_ptr,
+                      "count_orig": count_orig, "vrowptr": vrowptr, "vcol": vcol}
+        self.depth = depth
+        self.quirk_batch = quirk_batch
+        self.device_arrays = None
+        self._sizes = None
+        self.downloads = {f: 0 for f in _ARRAY_FIELDS}
+
+    @classmethod
+    def from_device_arrays(cls, device_arrays: dict, num_neigh: int, num_count: int, num_edges: int, depth: int = 4,
+                           quirk_batch: int = 0) -> "NeighborhoodPartition":
+        """A device-resident partition: ``device_arrays`` holds ``device`` and one tensor per field (``indicator`` as
+        uint8); the three sizes are what the builder read back."""
+        missing = [f for f in ("device",) + _ARRAY_FIELDS if f not in device_arrays]
+        if missing:
+            raise ValueError(f"from_device_arrays: missing {missing}")
+        self = cls.__new__(cls)
+        self._host = {}
+        self.depth, self.quirk_batch = depth, quirk_batch
+        self.device_arrays = device_arrays
+        self._sizes = (int(num_neigh), int(num_count), int(num_edges))
+        self.downloads = {f: 0 for f in _ARRAY_FIELDS}
+        return self
+
+    def _host_view(self, name):
+        a = self._host.get(name)
+        if a is None and name not in self._host:
+            a = self.device_arrays[name].cpu().numpy()
+            if name == "indicator":
+                a = a.astype(bool)
+            self._host[name] = a
+            self.downloads[name] += 1
+        return a
+
+    def __repr__(self):
+        return (f"NeighborhoodPartition(num_neigh={self.num_neigh}, num_count={self.num_count}, "
+                f"num_edges={self.num_edges}, depth={self.depth}, quirk_batch={self.quirk_batch}, "
+                f"device={'no' if self.device_arrays is None else self.device_arrays['device']})")
 
     @property
     def num_neigh(self) -> int:
-        return len(self.count_ptr) - 1
+        return self._sizes[0] if self._sizes is not None else len(self.count_ptr) - 1
 
     @property
     def num_count(self) -> int:
-        return int(self.count_ptr[-1])
+        return self._sizes[1] if self._sizes is not None else int(self.count_ptr[-1])
 
     @property
     def num_rows(self) -> int:
@@ -54,7 +101,7 @@ class NeighborhoodPartition:
 
     @property
     def num_edges(self) -> int:
-        return int(self.vrowptr[-1])
+        return self._sizes[2] if self._sizes is not None else int(self.vrowptr[-1])
 
     def __len__(self):
         return self.num_neigh
@@ -128,6 +175,62 @@ class NeighborhoodPartition:
             neigh_index=self.neigh_index, indicator=self.indicator, count_ptr=self.count_ptr, count_orig=co2,
             vrowptr=vr2, vcol=vc2, depth=self.depth, quirk_batch=self.quirk_batch)
 
+    # ---- device-resident twins (csrc/batch_dev.hip) ------------------------------------------
+    def _device_arrays(self, what: str) -> dict:
+        da = self.device_arrays
+        if da is None or any(f not in da for f in _ARRAY_FIELDS):
+            raise RuntimeError(f"{what} needs a partition built on the device (build_partition_device); "
+                               "there is no host fallback -- use the host method of the same name")
+        return da
+
+    def slice_device(self, b0: int, b1: int) -> "NeighborhoodPartition":
+        """``slice(b0, b1)`` computed on the device (desco_partition_dev_slice), the result device-resident; the whole
+        range is this object itself (no copy).  Reads back the block's sizes (one small transfer)."""
+        import torch
+        from . import ops
+        da = self._device_arrays("slice_device")
+        B, Nc = self.num_neigh, self.num_count
+        b0, b1 = max(0, b0), min(B, b1)
+        b1 = max(b0, b1)
+        if b0 == 0 and b1 == B:
+            return self
+        nc = ne = 0
+        if b1 > b0:
+            cp, v = da["count_ptr"], da["vrowptr"]
+            if "count_ptr" in self._host:
+                c0, c1 = int(self._host["count_ptr"][b0]), int(self._host["count_ptr"][b1])
+            else:
+                c0, c1 = torch.stack((cp[b0], cp[b1])).tolist()
+            e = torch.stack((v[4 * c0], v[4 * c1], v[4 * (Nc + b0)], v[4 * (Nc + b1)])).tolist()
+            nc, ne = c1 - c0, (e[1] - e[0]) + (e[3] - e[2])
+        cp2, co2, vr2, vc2 = ops.partition_slice_dev(da["count_ptr"], da["vrowptr"], da["vcol"], da["count_orig"],
+                                                     B, Nc, b0, b1, nc, ne)
+        out = NeighborhoodPartition.from_device_arrays(
+            {"device": da["device"], "count_ptr": cp2, "vrowptr": vr2, "vcol": vc2, "count_orig": co2,
+             "neigh_index": da["neigh_index"][b0:b1], "indicator": da["indicator"]},
+            b1 - b0, nc, ne, self.depth, self.quirk_batch)
+        if "indicator" in self._host:
+            out._host["indicator"] = self._host["indicator"]
+        return out
+
+    def degree_sorted_device(self, num_blocks: int = 0) -> "NeighborhoodPartition":
+        """``degree_sorted()`` computed on the device (desco_partition_dev_degree_sort), bit-identical to it; the
+        result is device-resident and shares ``count_ptr`` / ``neigh_index`` / ``indicator`` with this object."""
+        from . import ops
+        da = self._device_arrays("degree_sorted_device")
+        if self.num_count == 0:
+            return self
+        B, Nc, E = self.num_neigh, self.num_count, self.num_edges
+        co2, vr2, vc2 = ops.partition_degree_sort_dev(da["count_ptr"], da["vrowptr"], da["vcol"], da["count_orig"],
+                                                      B, Nc, E, da["neigh_index"].contiguous(), num_blocks)
+        out = NeighborhoodPartition.from_device_arrays(
+            {"device": da["device"], "count_ptr": da["count_ptr"], "vrowptr": vr2, "vcol": vc2, "count_orig": co2,
+             "neigh_index": da["neigh_index"], "indicator": da["indicator"]}, B, Nc, E, self.depth, self.quirk_batch)
+        for f in ("count_ptr", "neigh_index", "indicator"):      # host views already downloaded stay shared
+            if f in self._host:
+                out._host[f] = self._host[f]
+        return out
+
     # ---- PyG-convention view (tests / interop) ---------------------------------------------
     def edge_index_dict(self) -> Dict[Tuple[str, str, str], np.ndarray]:
         """The six typed ``edge_index`` arrays of the collated HeteroData batch (PyG convention:
@@ -147,6 +250,20 @@ class NeighborhoodPartition:
             m = (dst >= Nc) & (slot == s)
             out[et] = np.stack([src[m], dst[m] - Nc])
         return out
+
+
+def _host_field(name):
+    def get(self):
+        return self._host_view(name)
+
+    def set_(self, value):
+        self._host[name] = value
+    return property(get, set_)
+
+
+for _f in _ARRAY_FIELDS:
+    setattr(NeighborhoodPartition, _f, _host_field(_f))
+del _f
 
 
 def build_partition(graphs: GraphSet, depth: int = 4, quirk_batch: int = 0,
@@ -181,9 +298,8 @@ def build_partition_device(graphs: GraphSet, depth: int = 4, device="cuda",
                            num_waves: int = 0) -> NeighborhoodPartition:
     """Same result as ``build_partition`` (quirk_batch = 0), computed on the GPU by
     desco_partition_dev_* (csrc/partition_dev.hip).  The flat CSR is produced in
-    device memory; the returned object also carries host copies (the host-side API of
-    NeighborhoodPartition) and keeps the device tensors in ``device_arrays`` so that
-    ``NeighborhoodBatch`` does not upload them again.  Graphs too large for the per-wave LDS
+    device memory and stays there: the returned object keeps all six arrays in ``device_arrays`` (so that
+    ``NeighborhoodBatch`` does not upload them again) and downloads a host view of a field only when it is read.  Graphs too large for the per-wave LDS
     workspace raise ``ValueError`` (use ``build_partition``)."""
     import torch
     L = _lib.lib()
@@ -230,8 +346,6 @@ def build_partition_device(graphs: GraphSet, depth: int = 4, device="cuda",
                                           indicator.data_ptr(), count_ptr.data_ptr(),
                                           count_orig.data_ptr(), vrowptr.data_ptr(), vcol.data_ptr(), st),
                "desco_partition_dev_fill")
-    part = NeighborhoodPartition(neigh_index.cpu().numpy(), indicator.cpu().numpy().astype(bool),
-                                 count_ptr.cpu().numpy(), count_orig.cpu().numpy(),
-                                 vrowptr.cpu().numpy(), vcol.cpu().numpy(), depth, 0)
-    part.device_arrays = {"device": dev, "count_ptr": count_ptr, "vrowptr": vrowptr, "vcol": vcol}
-    return part
+    return NeighborhoodPartition.from_device_arrays(
+        {"device": dev, "count_ptr": count_ptr, "vrowptr": vrowptr, "vcol": vcol, "neigh_index": neigh_index,
+         "indicator": indicator, "count_orig": count_orig, "graph_ptr": gp}, B, Nc, Ec + Ek, depth, 0)

@@ -14,7 +14,7 @@ import torch
 
 from . import gnn_model as GMOD
 from . import ops
-from .batch import GossipBatch, NeighborhoodBatch
+from .batch import GossipBatch, NeighborhoodBatch, _norm_device
 from .graphs import GraphSet
 from .partition import NeighborhoodPartition, build_partition, build_partition_device
 
@@ -40,8 +40,12 @@ class InferencePipeline:
                  partition: Optional[NeighborhoodPartition] = None,
                  partition_backend: str = "device", rank: Optional[int] = None,
                  world: Optional[int] = None, graph_replay_rows: int = 400_000,
-                 chunks: Optional[int] = None, degree_sort: Optional[bool] = None):
-        """``degree_sort`` (default on; ``DESCO_DEGREE_SORT=0`` turns it off for A/B runs): the count rows of every
+                 chunks: Optional[int] = None, degree_sort: Optional[bool] = None,
+                 device_prologue: Optional[bool] = None):
+        """``device_prologue`` (default on; ``DESCO_DEVICE_PROLOGUE=0`` turns it off for A/B runs): when the partition
+        was built on the device, the blocks are cut, degree-sorted and indexed there too (csrc/batch_dev.hip) and the
+        large arrays never visit the host; off = the host routines on downloaded copies, with the same results.
+        ``degree_sort`` (default on; ``DESCO_DEGREE_SORT=0`` turns it off for A/B runs): the count rows of every
         neighborhood of a block are re-ordered by their number of count -> count sources
         (``NeighborhoodPartition.degree_sorted``), which saves gather steps in the layer kernel on dense shapes; the
         order inside a neighborhood is not observable in any result except through fp32 summation order.
@@ -91,7 +95,6 @@ class InferencePipeline:
             graphs, self.graph_range = D.shard_graphs(graphs, self.rank, self.world, Q0, device, depth, agree)
         self.graphs = graphs
         self._chunk_cuts = chunk_cuts
-        from .batch import _norm_device
         self.device = _norm_device(device)
         device = self.device
         if device.type == "cuda":
@@ -125,35 +128,59 @@ class InferencePipeline:
         self.partition = partition
         part = self.partition
         self.num_queries = None
-        # neighborhood blocks by row budget
-        rows_per_neigh = np.diff(part.count_ptr).astype(np.int64) + 1
-        per_graph = np.bincount(part.neigh_index[:, 0], minlength=graphs.num_graphs)
-        ngp = np.concatenate([[0], np.cumsum(per_graph)]).astype(np.int64)     # neighborhoods are ordered by graph
-        if self._chunk_cuts is None:
-            cuts = _split_by_budget(rows_per_neigh, max_neigh_rows)
-        else:       # a block never crosses a chunk boundary, and is cut by the budget from the chunk's start
-            cuts = [0]
-            for ga, gb in zip(self._chunk_cuts[:-1], self._chunk_cuts[1:]):
-                a, b = int(ngp[ga]), int(ngp[gb])
-                if b > a:
-                    cuts += [a + c for c in _split_by_budget(rows_per_neigh[a:b], max_neigh_rows)[1:]]
         import os as _os
         if degree_sort is None:
             degree_sort = _os.environ.get("DESCO_DEGREE_SORT", "1") != "0"
         self.degree_sort = bool(degree_sort)
-        self.neigh_batches = [
-            NeighborhoodBatch(part.slice(b0, b1).degree_sorted(num_threads) if self.degree_sort else part.slice(b0, b1),
-                              device)
-            for b0, b1 in zip(cuts[:-1], cuts[1:]) if b1 > b0]
-        # neighborhood b -> node row of the gossip x matrix (apply_neighborhood_count)
-        rows = graphs.graph_ptr[part.neigh_index[:, 0]] + part.neigh_index[:, 1]
-        self.scatter_index = torch.from_numpy(rows.astype(np.int32)).to(device)
-        # neighborhoods are ordered by graph: segment pointer for aggregate_neighborhood_count
-        self.neigh_graph_ptr = torch.from_numpy(ngp.astype(np.int32)).to(device)
+        if device_prologue is None:
+            device_prologue = _os.environ.get("DESCO_DEVICE_PROLOGUE", "1") != "0"
+        da = getattr(part, "device_arrays", None)
+        self.device_prologue = bool(device_prologue) and self.partition_backend == "device" and da is not None \
+            and _norm_device(da["device"]) == device and "graph_ptr" in da
+        B, G = part.num_neigh, graphs.num_graphs
+        if self.device_prologue:
+            # neighborhood b -> node row of the gossip x matrix (apply_neighborhood_count), and the segment pointer of
+            # aggregate_neighborhood_count (neighborhoods are ordered by graph), from the device neigh_index
+            self.scatter_index, self.neigh_graph_ptr = ops.neigh_rows_dev(da["neigh_index"], da["graph_ptr"], G)
+            if self._chunk_cuts is None and part.num_rows <= max_neigh_rows:
+                cuts = [0, B]                   # one block: nothing to decide, nothing downloaded
+            else:                               # only the two small arrays that decide the cuts reach the host
+                cuts = self._block_cuts(part.count_ptr, self.neigh_graph_ptr.cpu().numpy().astype(np.int64),
+                                        max_neigh_rows)
+            blocks = [part.slice_device(b0, b1) for b0, b1 in zip(cuts[:-1], cuts[1:]) if b1 > b0]
+            if self.degree_sort:
+                blocks = [blk.degree_sorted_device() for blk in blocks]
+        else:
+            per_graph = np.bincount(part.neigh_index[:, 0], minlength=G)
+            ngp = np.concatenate([[0], np.cumsum(per_graph)]).astype(np.int64)     # neighborhoods are ordered by graph
+            cuts = self._block_cuts(part.count_ptr, ngp, max_neigh_rows)
+            blocks = [part.slice(b0, b1).degree_sorted(num_threads) if self.degree_sort else part.slice(b0, b1)
+                      for b0, b1 in zip(cuts[:-1], cuts[1:]) if b1 > b0]
+            # neighborhood b -> node row of the gossip x matrix (apply_neighborhood_count)
+            rows = graphs.graph_ptr[part.neigh_index[:, 0]] + part.neigh_index[:, 1]
+            self.scatter_index = torch.from_numpy(rows.astype(np.int32)).to(device)
+            # neighborhoods are ordered by graph: segment pointer for aggregate_neighborhood_count
+            self.neigh_graph_ptr = torch.from_numpy(ngp.astype(np.int32)).to(device)
+        self.neigh_batches = [NeighborhoodBatch(blk, device) for blk in blocks]
+        for b in self.neigh_batches:
+            b.device_prologue = self.device_prologue
         self.node_graph_ptr = torch.from_numpy(graphs.graph_ptr.astype(np.int32)).to(device)
         # gossip blocks by (node x query) row budget, cut on graph boundaries
         self._gossip_cuts_budget = max_gossip_rows
         self.gossip_batches = None
+
+    def _block_cuts(self, count_ptr: np.ndarray, ngp: np.ndarray, max_neigh_rows: int) -> List[int]:
+        """Neighborhood blocks by row budget: cut points over the neighborhoods (``ngp`` = neighborhoods before each
+        graph, for the chunk boundaries)."""
+        rows_per_neigh = np.diff(count_ptr).astype(np.int64) + 1
+        if self._chunk_cuts is None:
+            return _split_by_budget(rows_per_neigh, max_neigh_rows)
+        cuts = [0]      # a block never crosses a chunk boundary, and is cut by the budget from the chunk's start
+        for ga, gb in zip(self._chunk_cuts[:-1], self._chunk_cuts[1:]):
+            a, b = int(ngp[ga]), int(ngp[gb])
+            if b > a:
+                cuts += [a + c for c in _split_by_budget(rows_per_neigh[a:b], max_neigh_rows)[1:]]
+        return cuts
 
     def _ensure_gossip_batches(self, Q: int):
         if self.gossip_batches is not None and self.num_queries == Q:

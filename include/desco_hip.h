@@ -120,6 +120,47 @@ int desco_partition_dev_fill(const int64_t* graph_ptr, const int32_t* node_graph
                              int32_t* count_orig, int32_t* vrowptr, int32_t* vcol,
                              desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DEVICE: from the device partition to the arrays a batch's kernels read (csrc/batch_dev.hip).  Integer kernels that
+ * reproduce the host routines bit for bit; all pointers are device pointers, every entry point launches on `stream`,
+ * never allocates and never synchronises.  num_neigh == 0 (for the slice: b0 == b1) returns 0 and launches nothing.
+ *
+ * desco_partition_dev_slice: neighborhoods [b0, b1) of a partition (num_neigh neighborhoods, num_count count rows) as a
+ *   block of their own (NeighborhoodPartition.slice): count_ptr_out[b1-b0+1] re-based, count_orig_out[block_count],
+ *   vrowptr_out[4(block_count + b1-b0)+1] = the count rows' then the canonical rows' pointers re-based, vcol_out
+ *   [block_edges] re-labelled.  block_count = count_ptr[b1] - count_ptr[b0] and block_edges = (vrowptr[4 c1] -
+ *   vrowptr[4 c0]) + (vrowptr[4(N_c+b1)] - vrowptr[4(N_c+b0)]) are read back by the caller, who allocates the outputs.
+ *
+ * desco_partition_dev_degree_sort: the device twin of desco_partition_degree_sort (same keys, same stable order, vcol
+ *   re-labelled and ascending inside every (row, slot) segment of any length).  num_count = count_ptr[num_neigh],
+ *   num_edges = vrowptr[4(num_count + num_neigh)].  neigh_key: int64 read at neigh_key[b * neigh_key_stride] (column 1
+ *   of neigh_index: pointer + 1, stride 2), NULL = the index b.  workspace: at least
+ *   desco_partition_dev_degree_sort_workspace(num_count, num_edges) bytes, 8-byte aligned; it also holds the keys of
+ *   a neighborhood too large for the workgroup's LDS (more than 4608 rows), which is sorted there, slower, with the
+ *   same result.  num_blocks: workgroups per launch, 0 = chosen by the library (the result does not depend on it).
+ *
+ * desco_pool_index_dev: pool_bits / pool_slot [ceil(num_count / 16)] of the fused pooling (per 16-row tile: bitmap of
+ *   the count rows that end a neighborhood, first partial slot) and totals4 = (num_slots, largest, smallest number of
+ *   count rows of a neighborhood, 0).  A smallest number of 0 means the index is not usable.
+ *
+ * desco_neigh_rows_dev: scatter_index[b] = graph_ptr[neigh_index[b][0]] + neigh_index[b][1] and neigh_graph_ptr[g] =
+ *   neighborhoods of the graphs before g (g = 0..num_graphs; neighborhoods are ordered by graph).
+ * ------------------------------------------------------------------------------------------ */
+int desco_partition_dev_slice(const int32_t* count_ptr, const int32_t* vrowptr, const int32_t* vcol,
+                              const int32_t* count_orig, int64_t num_neigh, int64_t num_count, int64_t b0, int64_t b1,
+                              int64_t block_count, int64_t block_edges, int32_t* count_ptr_out,
+                              int32_t* count_orig_out, int32_t* vrowptr_out, int32_t* vcol_out, desco_stream_t stream);
+size_t desco_partition_dev_degree_sort_workspace(int64_t num_count, int64_t num_edges);
+int desco_partition_dev_degree_sort(const int32_t* count_ptr, int64_t num_neigh, int64_t num_count, int64_t num_edges,
+                                    const int32_t* vrowptr, const int32_t* vcol, const int32_t* count_orig,
+                                    const int64_t* neigh_key, int64_t neigh_key_stride, int32_t* count_orig_out,
+                                    int32_t* vrowptr_out, int32_t* vcol_out, void* workspace, int num_blocks,
+                                    desco_stream_t stream);
+int desco_pool_index_dev(const int32_t* count_ptr, int64_t num_neigh, int64_t num_count, int32_t* pool_bits,
+                         int32_t* pool_slot, int64_t* totals4, desco_stream_t stream);
+int desco_neigh_rows_dev(const int64_t* neigh_index, int64_t num_neigh, const int64_t* graph_ptr, int64_t num_graphs,
+                         int32_t* scatter_index, int32_t* neigh_graph_ptr, desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
