@@ -92,6 +92,20 @@ def test_round4_entry_points_validate_their_arguments():
     assert L.desco_gemm_f16x3_f32 is not None and L.desco_row_absmax_f32 is not None
 
 
+def test_gossip_scalars_refuses_query_counts_outside_1_to_64():
+    """desco_gossip_scalars_f32 maps one lane to one query: num_q = 0 and 65 are refused on the host, before any launch,
+    with every pointer valid and aligned (so that the query count is the only thing wrong), naming the entry point."""
+    L = _lib.lib()
+    buf = np.zeros(64, np.float32)
+    idx = np.zeros(4, np.int32)
+    aligned = buf.ctypes.data + (-buf.ctypes.data % 16)          # scal4 has to be 16-byte aligned
+    for num_q in (0, 65, -1):
+        L.desco_gemm_f32_multi(5, None, None)                   # (another entry point's message in between)
+        assert L.desco_gossip_scalars_f32(buf.ctypes.data, num_q, idx.ctypes.data, idx.ctypes.data, 1, num_q,
+                                          buf.ctypes.data, buf.ctypes.data, aligned, None) == -1
+        assert b"desco_gossip_scalars_f32" in L.desco_last_error()
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from desco_amd import ops

@@ -129,7 +129,9 @@ def test_deep_gossip_more_than_64_queries():
 
 
 def test_gossip_layer_kernel_repeats_bit_for_bit():
-    """The layer kernel on the hub shape, 20 launches: identical output and accumulator every time."""
+    """The layer kernel on the hub shape, 20 launches: identical output and accumulator every time.  (Its values are
+    checked per element against fp64 in tests/test_gossip_kernels_gpu.py::test_gossip_layer_against_fp64, this shape
+    included.)"""
     gs = syn_hub_graphs()
     Q = 29
     batch = GossipBatch(gs, DEV, x=torch.zeros(gs.num_nodes, Q))
@@ -152,25 +154,6 @@ def test_gossip_layer_kernel_repeats_bit_for_bit():
     same = all(torch.equal(o, outs[0]) for o in outs) and all(torch.equal(a, accs[0]) for a in accs)
     print(f"[repeat] gossip_layer_f16x3 x20 on {R} rows: bit-identical={same}")
     assert same
-    # and against an fp64 evaluation of the same formula on the host
-    hc, rp, cl = h.double().cpu(), batch.rowptr.cpu().long(), batch.col.cpu().long()
-    hh = torch.zeros(R, 64, dtype=torch.float64)
-    gc = gate.double().cpu()
-    for i in range(N):
-        for e in range(int(rp[i]), int(rp[i + 1])):
-            j = int(cl[e])
-            wgt = gc if j < i else 1 - gc
-            hh[i * Q:(i + 1) * Q] += wgt[:, None] * hc[j * Q:(j + 1) * Q]
-    wf = lambda pl: (pl.planes[0].view(torch.float16).double() + pl.planes[1].view(torch.float16).double()).cpu() \
-        / float(pl.scale[0])
-    qi = torch.arange(R) % Q
-    ref = torch.cat([hh, hc], 1) @ wf(w).t() + (c3.double().cpu()[:, :, None] * v.double().cpu()[qi]).sum(1)
-    ref = ref.clamp_min(0)
-    ref_acc = acc0.double().cpu() + hc @ wf(p).t() + ref @ wf(pn).t()
-    report("gossip_layer out", outs[0].cpu(), ref.float())
-    report("gossip_layer acc", accs[0].cpu(), ref_acc.float())
-    assert_logits_close("gossip_layer out", outs[0].cpu(), ref.float(), tol=1e-5)
-    assert_logits_close("gossip_layer acc", accs[0].cpu(), ref_acc.float(), tol=1e-5)
 
 
 def test_pipeline_eager_and_replay_agree_at_depth_3(nm):

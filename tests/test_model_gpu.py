@@ -14,6 +14,7 @@ from desco_amd.partition import build_partition  # noqa: E402
 from oracle import model as OM  # noqa: E402
 from oracle import partition as OP  # noqa: E402
 
+from gossip_reference import check_tile_order  # noqa: E402
 from helpers import (GOSSIP_GRAD_TOL, LOGIT_TOL, assert_counts_close, assert_grad_close, assert_logits_close,  # noqa: E402
                      assert_loss_close, cpu_sd, golden_graphs, make_models, random_family_graphs, report,
                      standard_queries)
@@ -382,17 +383,8 @@ def test_gossip_tile_order_is_a_permutation_and_changes_no_bit(setup):
     graphs = golden_graphs(max_n=60)[:8] + [hub, (5, [(0, 1)])] + golden_graphs(max_n=60)[8:12]
     gs = GraphSet.from_edge_lists(graphs)
     batch = GossipBatch(gs, DEV, x=torch.from_numpy(rng.gamma(1.0, 4.0, size=(gs.num_nodes, len(queries)))).float())
-    perm = batch.tile_perm.cpu().numpy().astype(np.int64).reshape(-1, 128)
-    assert perm.shape[0] == (gs.num_nodes + 127) // 128 and gs.num_nodes % 128 != 0
-    assert (np.sort(perm, axis=1) == np.arange(128)).all()
-    deg = np.zeros(perm.shape[0] * 128, np.int64)
-    deg[:gs.num_nodes] = np.diff(gs.rowptr)
-    for t in range(perm.shape[0]):
-        d = deg[128 * t + perm[t]].reshape(8, 8, 2)            # [wave][pair][half]
-        pair_cost = d.max(2)                                    # lock-stepped halves
-        order = np.concatenate([pair_cost[:, g] if g % 2 == 0 else pair_cost[::-1, g] for g in range(8)])
-        assert (np.diff(order) <= 0).all(), "pairs must be dealt in snake order of decreasing cost"
-        assert (d[:, :, 0] >= d[:, :, 1]).all()
+    assert gs.num_nodes % 128 != 0
+    check_tile_order(batch.tile_perm.cpu().numpy(), gs.rowptr, gs.num_nodes)
     gm.set_query_emb(nm.get_query_emb())
     try:
         GM.GOSSIP_TILE_ORDER = True
