@@ -24,6 +24,7 @@
 // query).  Adjacency tests read per-graph bitset rows (built by a
 // first kernel from the CSR).  Integer work, bit-exact against the host enumerator.
 #include "common_device.hpp"
+#include "groundtruth_label.hpp"
 
 namespace desco {
 
@@ -182,6 +183,30 @@ namespace {
 inline int gt_pair_bit(int a, int b) { return b * (b - 1) / 2 + a; }   // a < b
 }
 
+// The bitset rows of both device enumerators (this one and groundtruth_label_dev.hip).
+int desco::gt_build_bitsets(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col,
+                            const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                            int64_t num_words, int64_t num_nodes, int64_t num_entries, void* stream,
+                            const char* who) {
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(bits, 0, (size_t)num_words * 8, s) != hipSuccess)
+    return launch_status((std::string(who) + ": memset").c_str());
+  if (num_entries == 0) return 0;
+  const int64_t blocks = (num_entries + GT_THREADS - 1) / GT_THREADS;
+  if (blocks > INT32_MAX) return fail(DESCO_EINVAL, (std::string(who) + ": too many edges").c_str());
+  GtArgs a{};
+  a.graph_ptr = graph_ptr;
+  a.rowptr = rowptr;
+  a.col = col;
+  a.node_graph = node_graph;
+  a.bit_off = bit_off;
+  a.bits = reinterpret_cast<unsigned long long*>(bits);
+  a.num_nodes = num_nodes;
+  a.num_entries = num_entries;
+  hipLaunchKernelGGL(gt_bits_kernel, dim3((unsigned)blocks), dim3(GT_THREADS), 0, s, a);
+  return launch_status(who);
+}
+
 // HOST helper: the class table the device kernel reads.
 extern "C" int desco_canonical_class_table(const int32_t* q_nodes, const int32_t* q_edge_ptr,
                                            const int32_t* q_edges, int num_queries, int16_t* table,
@@ -248,16 +273,16 @@ extern "C" int desco_canonical_counts_dev(const int64_t* graph_ptr, int64_t num_
       num_queries < 0 || num_queries > GT_MAXQ || (num_entries > 0 && !col))
     return fail(DESCO_EINVAL, "desco_canonical_counts_dev: bad argument (queries of 2..5 nodes, at most 32)");
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(bits, 0, (size_t)num_words * 8, s) != hipSuccess ||
-      hipMemsetAsync(out, 0, (size_t)num_nodes * num_queries * 8, s) != hipSuccess)
+  if (hipMemsetAsync(out, 0, (size_t)num_nodes * num_queries * 8, s) != hipSuccess)
     return launch_status("desco_canonical_counts_dev: memset");
-  if (num_entries == 0) return 0;
-  const int64_t blocks = (num_entries + GT_THREADS - 1) / GT_THREADS;
   const int64_t wblocks = (num_entries + GT_THREADS / 64 - 1) / (GT_THREADS / 64);
   if (wblocks > INT32_MAX) return fail(DESCO_EINVAL, "desco_canonical_counts_dev: too many edges");
+  if (const int rc = gt_build_bitsets(graph_ptr, rowptr, col, node_graph, bit_off, bits, num_words, num_nodes,
+                                      num_entries, stream, "desco_canonical_counts_dev"))
+    return rc;
+  if (num_entries == 0) return 0;
   GtArgs a{graph_ptr, rowptr, col, node_graph, bit_off, reinterpret_cast<unsigned long long*>(bits),
            cls, kmax, num_queries, num_nodes, num_entries, reinterpret_cast<unsigned long long*>(out)};
-  hipLaunchKernelGGL(gt_bits_kernel, dim3((unsigned)blocks), dim3(GT_THREADS), 0, s, a);
   hipLaunchKernelGGL(gt_count_kernel, dim3((unsigned)wblocks), dim3(GT_THREADS), 0, s, a);
   return launch_status("desco_canonical_counts_dev");
 }

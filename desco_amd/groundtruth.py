@@ -98,11 +98,230 @@ def canonical_counts(graphs: GraphSet, queries: Sequence, num_threads: int = 0,
     return torch.from_numpy(out).double()
 
 
-def canonical_counts_labelled(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat") -> torch.Tensor:
-    """Canonical counts of LABELLED queries (--use_node_feature): the reference's own procedure,
-    networkx VF2 with ``node_match`` on the feature (workload.py:327-348) divided by the labelled
-    symmetry factor (data.py:61-68).  The native enumerators count unlabelled patterns; labelled
-    ground truth is an offline, one-time step and stays on the host like the reference's."""
+# ---- labelled queries (--use_node_feature) ---------------------------------------------------------------------------
+# Limits of the native paths (include/desco_hip.h).  Host: label ids of 8 bits, queries of 2..6 nodes.  Device:
+# label ids of 4 bits, queries of 2..5 nodes, and a direct lookup table of sum_k 2^(k(k-1)/2) A^k int32 entries that
+# must fit the budget below: 256 MiB, the size of the MI355X's Infinity Cache, so that the few entries a graph set
+# touches are served on chip (A = 8 with 5-node queries is 134 MB, A = 9 242 MB; A = 10 goes to the host path, as
+# does anything wider than 16 labels).
+_HOST_LABEL_LIMIT = 256
+_DEVICE_LABEL_LIMIT = 16
+_DEVICE_LABEL_TABLE_LIMIT_BYTES = 256 << 20
+# the device path counts per labelled CLASS into [nodes, C] int64 and expands to [nodes, Q] (int64, and its double
+# copy on the way to the host): they live on the device for one chunk of whole graphs at a time, chosen so that
+# 8 (C + 2 Q) bytes per node stay below this budget (a single graph above it is a chunk of its own)
+_DEVICE_LABEL_CHUNK_BYTES = 1 << 30
+# name of the backend that served the last canonical_counts_labelled call ("vf2", "host" or "device")
+last_labelled_backend = None
+
+
+class _Labelled:
+    """Label ids, flattened queries and labelled isomorphism classes of one call."""
+
+    def __init__(self, graphs: GraphSet, queries: Sequence, key: str):
+        if graphs.node_feat is None:
+            raise ValueError("labelled ground truth needs GraphSet.node_feat")
+        self.nan = False
+        ids = {}                      # feature row as a tuple of floats -> id: float equality, as the VF2 node_match
+        # (-0.0 == 0.0 and hash alike; NaN never equals anything -> VF2 path)
+        nf = graphs.node_feat.astype(np.float64) + 0.0
+        self.nan |= bool(np.isnan(nf).any())
+        if nf.shape[0]:
+            uniq, inv = np.unique(nf, axis=0, return_inverse=True)
+            remap = np.array([ids.setdefault(tuple(r.tolist()), len(ids)) for r in uniq], dtype=np.int32)
+            self.node_labels = np.ascontiguousarray(remap[np.asarray(inv).reshape(-1)], dtype=np.int32)
+        else:
+            self.node_labels = np.zeros(0, dtype=np.int32)
+        flat, q_labels = [], []
+        for q in queries:
+            nodes = list(q.nodes)
+            idx = {v: i for i, v in enumerate(nodes)}
+            flat.append((len(nodes), [(idx[a], idx[b]) for a, b in q.edges()]))
+            for v in nodes:
+                f = tuple(float(x) for x in np.asarray(q.nodes[v][key]).reshape(-1))
+                self.nan |= any(x != x for x in f)
+                q_labels.append(ids.setdefault(f, len(ids)))
+        self.num_labels = max(len(ids), 1)
+        self.flat, self.q_nodes, self.q_edge_ptr, self.q_edges = _flatten_queries(flat)
+        self.q_labels = np.array(q_labels, dtype=np.int32)
+        self.num_queries = len(flat)
+        self.kmin = int(self.q_nodes.min()) if len(flat) else 2
+        self.kmax = int(self.q_nodes.max()) if len(flat) else 2
+        self.class_of_query, self.num_classes = None, 0
+
+    def host_limit(self):
+        """None when the native host path takes this input, else the limit it is outside of."""
+        if self.nan:
+            return "features contain NaN (never equal to anything): only the VF2 path reproduces that"
+        if self.num_labels > _HOST_LABEL_LIMIT:
+            return f"{self.num_labels} distinct labels: the native paths take at most {_HOST_LABEL_LIMIT}"
+        if self.kmin < 2 or self.kmax > 6:
+            return "the native host path takes queries of 2..6 nodes"
+        return None
+
+    def table_bytes(self):
+        return 4 * sum((1 << (k * (k - 1) // 2)) * self.num_labels ** k for k in range(2, self.kmax + 1))
+
+    def device_limit(self, graphs: GraphSet):
+        """None when the device path takes this input, else the limit it is outside of."""
+        if self.host_limit():
+            return self.host_limit()
+        if self.kmax > 5:
+            return "the device path takes labelled queries of 2..5 nodes"
+        if self.num_labels > _DEVICE_LABEL_LIMIT:
+            return f"{self.num_labels} distinct labels: the device path takes at most {_DEVICE_LABEL_LIMIT}"
+        if self.table_bytes() > _DEVICE_LABEL_TABLE_LIMIT_BYTES:
+            return (f"the lookup table for {self.num_labels} labels and {self.kmax}-node queries takes "
+                    f"{self.table_bytes()} bytes, above the budget of {_DEVICE_LABEL_TABLE_LIMIT_BYTES}")
+        n = np.diff(graphs.graph_ptr).astype(np.int64)
+        if int((n * ((n + 63) // 64)).sum()) > _DEVICE_BITSET_LIMIT_WORDS:
+            return "the adjacency bitsets are above the device path's limit"
+        return None
+
+    def _qargs(self):
+        return (self.q_nodes.ctypes.data, self.q_edge_ptr.ctypes.data,
+                self.q_edges.ctypes.data if len(self.q_edges) else None, self.q_labels.ctypes.data,
+                self.num_queries, self.num_labels)
+
+    def classes(self):
+        if self.class_of_query is None:
+            coq = np.zeros(self.num_queries, dtype=np.int32)
+            c, kmax = ctypes.c_int(0), ctypes.c_int(0)
+            _lib.check(_lib.lib().desco_canonical_label_classes(*self._qargs(), coq.ctypes.data, ctypes.byref(c),
+                                                                ctypes.byref(kmax)), "desco_canonical_label_classes")
+            self.class_of_query, self.num_classes = coq, int(c.value)
+        return self.class_of_query
+
+    def table(self):
+        coq = self.classes()
+        L = _lib.lib()
+        entries = int(L.desco_canonical_label_table_size(self.kmax, self.num_labels))
+        if entries < 0:
+            _lib.check(-1, "desco_canonical_label_table_size")
+        table = np.empty(entries, dtype=np.int32)
+        _lib.check(L.desco_canonical_label_table(*self._qargs(), coq.ctypes.data, self.num_classes, self.kmax,
+                                                 table.ctypes.data, entries), "desco_canonical_label_table")
+        return table
+
+
+def _labelled_host(graphs: GraphSet, lab: _Labelled, num_threads: int) -> torch.Tensor:
+    coq = lab.classes()
+    out = np.zeros((graphs.num_nodes, lab.num_classes), dtype=np.int64)
+    _lib.check(_lib.lib().desco_canonical_counts_labelled(
+        graphs.graph_ptr.ctypes.data, graphs.num_graphs, graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
+        lab.node_labels.ctypes.data, lab.num_labels, *lab._qargs()[:5], coq.ctypes.data, lab.num_classes,
+        num_threads, out.ctypes.data), "desco_canonical_counts_labelled")
+    return torch.from_numpy(out)[:, torch.from_numpy(coq).long()].double()
+
+
+def _labelled_device_chunks(graphs: GraphSet, lab: _Labelled, dev, chunk_bytes=None):
+    """Yields (first node, end node, [nodes, Q] int64 counts on ``dev``) for consecutive chunks of whole graphs."""
+    L = _lib.lib()
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
+    table = t(lab.table(), np.int32)
+    coq = t(lab.classes(), np.int64)
+    C, Q, G = lab.num_classes, lab.num_queries, graphs.num_graphs
+    budget = _DEVICE_LABEL_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    max_nodes = max(budget // (8 * (C + 2 * Q)), 1)
+    g0 = 0
+    while g0 < G:
+        g1 = g0 + 1
+        while g1 < G and graphs.graph_ptr[g1 + 1] - graphs.graph_ptr[g0] <= max_nodes:
+            g1 += 1
+        sub = graphs if (g0, g1) == (0, G) else graphs.subset(g0, g1)
+        n0, n1 = int(graphs.graph_ptr[g0]), int(graphs.graph_ptr[g1])
+        g0 = g1
+        if n1 == n0:
+            continue
+        n = np.diff(sub.graph_ptr).astype(np.int64)
+        bit_off = np.concatenate([[0], np.cumsum(n * ((n + 63) // 64))]).astype(np.int64)
+        graph_ptr, rowptr = t(sub.graph_ptr, np.int64), t(sub.rowptr, np.int64)
+        col, node_graph = t(sub.col, np.int32), t(sub.node_graph_ids(), np.int32)
+        labels, bit_off_d = t(lab.node_labels[n0:n1], np.int32), t(bit_off[:-1], np.int64)
+        bits = torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev)
+        out = torch.empty((n1 - n0, C), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.desco_canonical_counts_labelled_dev(
+                graph_ptr.data_ptr(), sub.num_graphs, n1 - n0, rowptr.data_ptr(), int(sub.col.shape[0]),
+                col.data_ptr() if col.numel() else None, node_graph.data_ptr(), bit_off_d.data_ptr(),
+                bits.data_ptr(), int(bit_off[-1]), labels.data_ptr(), lab.num_labels, table.data_ptr(),
+                table.numel(), lab.kmax, C, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                "desco_canonical_counts_labelled_dev")
+        yield n0, n1, out.index_select(1, coq)
+
+
+def _require_device(lab: _Labelled, graphs: GraphSet):
+    limit = lab.device_limit(graphs)
+    if limit:
+        raise RuntimeError("canonical_counts_labelled: device path: " + limit)
+
+
+def canonical_counts_labelled_device(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat",
+                                     device="cuda", chunk_bytes=None) -> torch.Tensor:
+    """The counts of ``canonical_counts_labelled`` computed on the MI355X (csrc/groundtruth_label_dev.hip): labelled
+    queries of 2..5 nodes, any number of them, duplicates (isomorphic labelled copies) included, at most 16 distinct
+    labels and a lookup table within ``_DEVICE_LABEL_TABLE_LIMIT_BYTES``; raises RuntimeError naming the limit
+    otherwise.  Returns a [num_nodes, num_queries] int64 tensor on ``device``.  The per-class intermediate is
+    produced in node chunks of at most ``chunk_bytes`` (default ``_DEVICE_LABEL_CHUNK_BYTES``); the chunking does
+    not change the result."""
+    lab = _Labelled(graphs, queries, node_feat_key)
+    _require_device(lab, graphs)
+    dev = torch.device(device)
+    out = torch.zeros((graphs.num_nodes, lab.num_queries), dtype=torch.int64, device=dev)
+    if graphs.num_nodes and lab.num_queries:
+        for n0, n1, counts in _labelled_device_chunks(graphs, lab, dev, chunk_bytes):
+            out[n0:n1] = counts
+    return out
+
+
+def canonical_counts_labelled(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat",
+                              backend: str = "auto", num_threads: int = 0) -> torch.Tensor:
+    """Canonical counts of LABELLED queries (--use_node_feature): [num_nodes, num_queries] double tensor on the CPU,
+    count[v][q] = #{S : max(S) = v, G[S] connected, G[S] with its node labels isomorphic to labelled query q} --
+    the reference's VF2 with ``node_match`` on the feature (workload.py:327-348) divided by the labelled symmetry
+    factor (data.py:61-68).  ``queries``: networkx graphs whose nodes carry ``node_feat_key``; two nodes match iff
+    their feature vectors are equal as lists of floats.  Isomorphic labelled copies (the reference's expansion is
+    full of them) get equal columns.
+
+    ``backend``: "vf2" (the reference's procedure in Python, the yardstick of the tests), "host" (OpenMP enumerator,
+    queries of 2..6 nodes, ``num_threads`` threads), "device" (HIP kernel; raises RuntimeError naming the limit the
+    input is outside of, see ``canonical_counts_labelled_device``) or "auto": the device when a GPU is present and
+    the input fits it, else the host enumerator, else (features with NaN, more than 256 distinct labels) VF2.
+    ``last_labelled_backend`` names the one that served the call."""
+    global last_labelled_backend
+    if backend not in ("vf2", "host", "device", "auto"):
+        raise ValueError(f"unknown backend {backend!r}")
+    if backend == "vf2":
+        last_labelled_backend = "vf2"
+        return _canonical_counts_labelled_vf2(graphs, queries, node_feat_key)
+    lab = _Labelled(graphs, queries, node_feat_key)
+    if backend == "device":
+        _require_device(lab, graphs)
+    elif backend == "auto":
+        if lab.host_limit():
+            backend = "vf2"
+        else:
+            backend = "device" if torch.cuda.is_available() and not lab.device_limit(graphs) else "host"
+    if backend == "vf2":
+        last_labelled_backend = "vf2"
+        return _canonical_counts_labelled_vf2(graphs, queries, node_feat_key)
+    if backend == "host" and lab.host_limit():
+        raise RuntimeError("canonical_counts_labelled: host path: " + lab.host_limit())
+    out = torch.zeros((graphs.num_nodes, lab.num_queries), dtype=torch.double)
+    if graphs.num_nodes and lab.num_queries:
+        if backend == "host":
+            out = _labelled_host(graphs, lab, num_threads)
+        else:
+            for n0, n1, counts in _labelled_device_chunks(graphs, lab, torch.device("cuda")):
+                out[n0:n1] = counts.double().cpu()
+    last_labelled_backend = backend
+    return out
+
+
+def _canonical_counts_labelled_vf2(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat") -> torch.Tensor:
+    """The reference's own procedure: networkx VF2 with ``node_match`` on the feature (workload.py:327-348)
+    divided by the labelled symmetry factor (data.py:61-68).  One matcher per (query, graph) in Python: the
+    reference every native path is tested against, and the path for features that contain NaN."""
     import networkx as nx
     if graphs.node_feat is None:
         raise ValueError("labelled ground truth needs GraphSet.node_feat")

@@ -231,7 +231,8 @@ class Workload:
             eye = [t for t in np.eye(self.node_feat_len).tolist()]
             qs = [g for q in qs for g in add_node_feat_to_networkx(q, eye, self.node_feat_key)]
         if self.use_node_feat:
-            truth = canonical_counts_labelled(self.dataset, qs, self.node_feat_key)
+            truth = canonical_counts_labelled(self.dataset, qs, self.node_feat_key, backend="auto",
+                                              num_threads=max(num_workers, 0))
         else:
             truth = canonical_counts(self.dataset, qs, num_threads=max(num_workers, 0))
         self.canonical_count_truth = truth

@@ -190,6 +190,52 @@ int desco_canonical_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int
                                int64_t num_words, const int16_t* cls, int kmax, int num_queries,
                                int64_t* out, desco_stream_t stream);
 
+/* LABELLED queries (--use_node_feature): out[v][c] = #{S : max(S) = v, G[S] connected, and G[S] with its node
+ * labels isomorphic to the labelled queries of class c} -- the reference's VF2 with node_match on the feature
+ * (workload.py:327-348) divided by the labelled symmetry factor (data.py:61-68).  Node and query labels are integer
+ * ids 0..num_labels-1 (the caller maps equal feature rows to equal ids).  Query q is given as in
+ * desco_canonical_counts plus its labels q_labels[o_q .. o_q + q_nodes[q] - 1], o_q = q_nodes[0] + .. + q_nodes[q-1].
+ * The reference's expansion (utils.py:258-272) contains labelled copies that are isomorphic to each other, so any
+ * number of queries and duplicates are accepted everywhere below and counting is per labelled isomorphism CLASS:
+ * the caller expands out[:, class_of_query[q]] to query columns.
+ *
+ * HOST helper: class_of_query[num_queries] (classes are numbered 0..*num_classes-1 in the order of their first
+ * query) and *kmax = the largest query.  Queries of 2..6 nodes, num_labels <= 256. */
+int desco_canonical_label_classes(const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges,
+                                  const int32_t* q_labels, int num_queries, int num_labels,
+                                  int32_t* class_of_query, int* num_classes, int* kmax);
+/* HOST enumerator (csrc/groundtruth_label.cpp; ESU rooted at the maximum id, OpenMP over graphs): labels [N] int32,
+ * class_of_query / num_classes from the helper above, queries of 2..6 nodes, num_labels <= 256.
+ * out: int64 [N][num_classes], zeroed and filled by the call.  No nodes or no queries: returns 0, touches nothing. */
+int desco_canonical_counts_labelled(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                    const int32_t* col, const int32_t* labels, int num_labels,
+                                    const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges,
+                                    const int32_t* q_labels, int num_queries, const int32_t* class_of_query,
+                                    int num_classes, int num_threads, int64_t* out);
+/* The same counts on the GPU (csrc/groundtruth_label_dev.hip): queries of 2..5 nodes and num_labels <= 16 (label
+ * ids of 4 bits), any number of queries.  The kernel classifies a found k-subset with ONE read of a direct table:
+ * entry  off[k] + mask * A^k + sum_j label_j * A^j  (A = num_labels; mask as in desco_canonical_class_table, labels in
+ * subset order; off[2] = 0, off[k+1] = off[k] + 2^(k(k-1)/2) * A^k) holds the class or -1.
+ * HOST helpers: desco_canonical_label_table_size = number of int32 entries for queries up to kmax nodes (-1 with a
+ * message outside 2..5 nodes / 1..16 labels; 1024 * A^5 entries dominate at kmax = 5: 67 MB at A = 7, 134 MB at
+ * A = 8 -- the caller decides what it affords, at most 2^31 - 1 entries); desco_canonical_label_table fills
+ * table[table_entries] with every relabeling of every class. */
+int64_t desco_canonical_label_table_size(int kmax, int num_labels);
+int desco_canonical_label_table(const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges,
+                                const int32_t* q_labels, int num_queries, int num_labels,
+                                const int32_t* class_of_query, int num_classes, int kmax, int32_t* table,
+                                int64_t table_entries);
+/* DEVICE: the arguments of desco_canonical_counts_dev, then labels [N] int32 (ids 0..num_labels-1; a node with an
+ * id outside that range matches nothing), the table above and its size; all device pointers.
+ * out: int64 [N][num_classes], zeroed and filled by the call (64-bit integer atomics: bit-identical from run to
+ * run).  Enqueues on `stream`, does not allocate or synchronise.  No nodes or no classes: returns 0. */
+int desco_canonical_counts_labelled_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                        const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                        const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                        int64_t num_words, const int32_t* labels, int num_labels,
+                                        const int32_t* table, int64_t table_entries, int kmax, int num_classes,
+                                        int64_t* out, desco_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DEVICE kernels
  * ------------------------------------------------------------------------------------------ */
