@@ -183,10 +183,17 @@ __global__ __launch_bounds__(NT) void shmp_small_bwd_kernel(const BwdArgs g) {
       float* dw = g.dwt + (int64_t)l * KA * 64 + col4;
 #pragma unroll
       for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(dw + (kg + 64 * j) * 64) = acc[j];
-      if (t < 64) {
+      {
+        // db_l = column sums of dZ: 16 lanes per column take rows r, r + 16, .. each and meet in a shuffle tree (one
+        // chain of n additions per column loses n ulps where the fp32 evaluation of the same sum loses a few)
+        const int lane = t & 63, c = (t >> 6) * 4 + (lane & 3), r = lane >> 2;
         float s = 0.f;
-        for (int i = 0; i < n; ++i) s += G[i * 64 + t];
-        g.dbias[l * 64 + t] = s;
+        for (int i = r; i < n; i += 16) s += G[i * 64 + c];
+        s += __shfl_xor(s, 4, 64);
+        s += __shfl_xor(s, 8, 64);
+        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 32, 64);
+        if (r == 0) g.dbias[l * 64 + c] = s;
       }
     }
     __syncthreads();                                      // A consumed: D goes into its place
@@ -242,8 +249,8 @@ constexpr size_t kShmem = sizeof(float) * (size_t)NMAX * (64 + KA);
 //             graph; the 4 k groups of a wave are added with two shuffles, the 12 waves through LDS in wave order.
 //   backward  D = dZ Wt^T straight from Wt (thread (k, quarter of the 64 columns): 64 contiguous bytes; the 4 quarters of
 //             a k sit in adjacent lanes: two shuffles) -- no transposed weight copy; dZ_l goes to a workspace from which
-//             a second launch, one workgroup per (layer, 16 weight rows), forms dWt_l = A_l^T dZ_l over ALL rows in row
-//             order (the one-workgroup kernel's order) with A_l gathered on the fly, and db_l.
+//             a second launch, one workgroup per (layer, 16 weight rows), forms dWt_l = A_l^T dZ_l over ALL rows (128-row
+//             chunks in row order, chunk sums added up) with A_l gathered on the fly, and db_l.
 constexpr int GT = 768;       // threads per graph workgroup: 12 waves
 constexpr int GMAX = 8;       // rows per graph
 
@@ -436,7 +443,9 @@ __global__ __launch_bounds__(GT) void shmp_graphs_bwd_kernel(const GBwdArgs g) {
 #undef SG_LOADW
 }
 
-// dWt[l][16 kb + kk][:] = sum_i A_l[i][16 kb + kk] dZ_l[i][:] over all rows i in row order; db[l] = colsum dZ_l
+// dWt[l][16 kb + kk][:] = sum_i A_l[i][16 kb + kk] dZ_l[i][:] over all rows i, db[l] = colsum dZ_l.  Both are summed chunk
+// by chunk (128 rows in row order, then the chunk's sum joins the total), the bias inside a chunk by 4 lanes per column
+// with rows r, r + 4, ..: a batch of thousands of rows adds chains of 128 + chunks terms, not of all its rows.
 struct GBwdWArgs {
   const float* x0;
   const float* xall;
@@ -459,6 +468,7 @@ __global__ __launch_bounds__(256) void shmp_graphs_bwd_w_kernel(const GBwdWArgs 
   const float* dz = g.dz_all + (int64_t)l * g.n * 64;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   float bs = 0.f;
+  const int bc = (t >> 6) * 16 + (t & 15), br = (t & 63) >> 4;             // bias: column, first row of the chunk
   for (int64_t i0 = 0; i0 < g.n; i0 += CH) {
     const int m = (int)((g.n - i0) < CH ? (g.n - i0) : CH);
     __syncthreads();
@@ -478,12 +488,21 @@ __global__ __launch_bounds__(256) void shmp_graphs_bwd_w_kernel(const GBwdWArgs 
       Ab[i * 16 + (u & 15)] = a;
     }
     __syncthreads();
-    for (int i = 0; i < m; ++i) f4fma(acc, Ab[i * 16 + kk], *reinterpret_cast<const float4*>(Z + i * 64 + col4));
-    if (kb == 0 && t < 64)
-      for (int i = 0; i < m; ++i) bs += Z[i * 64 + t];
+    float4 part = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = 0; i < m; ++i) f4fma(part, Ab[i * 16 + kk], *reinterpret_cast<const float4*>(Z + i * 64 + col4));
+    acc.x += part.x; acc.y += part.y; acc.z += part.z; acc.w += part.w;
+    if (kb == 0) {
+      float ps = 0.f;
+      for (int i = br; i < m; i += 4) ps += Z[i * 64 + bc];
+      bs += ps;
+    }
   }
   *reinterpret_cast<float4*>(g.dwt + ((int64_t)l * KA + 16 * kb + kk) * 64 + col4) = acc;
-  if (kb == 0 && t < 64) g.dbias[l * 64 + t] = bs;
+  if (kb == 0) {
+    bs += __shfl_xor(bs, 16, 64);
+    bs += __shfl_xor(bs, 32, 64);
+    if (br == 0) g.dbias[l * 64 + bc] = bs;
+  }
 }
 
 }  // namespace small

@@ -1263,6 +1263,12 @@ def rowdot_add(y: torch.Tensor, w: torch.Tensor, b: float, add: Optional[torch.T
 # ------------------------------------------------------------------------------------------------
 # backward-pass entry points (csrc/train_ops.hip)
 # ------------------------------------------------------------------------------------------------
+def _edges_or(idx: torch.Tensor, other: torch.Tensor) -> torch.Tensor:
+    """An edge index of a batch WITHOUT edges is an empty tensor, whose pointer is null -- which the trunk entry points
+    refuse.  It is read only below an edge, so any int32 device pointer stands in (as in csr_gather_sum_wide)."""
+    return idx if idx.numel() else other
+
+
 def shmp_trunk_small_max_rows() -> int:
     return int(_lib.lib().desco_shmp_trunk_small_max_rows())
 
@@ -1273,6 +1279,7 @@ def shmp_trunk_small_fwd(x0, vrowptr, vcol, wt, bias, seg_ptr, num_seg):
     assert x0.is_contiguous() and wt.is_contiguous() and bias.is_contiguous() and tuple(wt.shape) == (L, 192, 64)
     xall = torch.empty((L, n, 64), device=x0.device, dtype=torch.float32)
     pooled = torch.empty((num_seg, 64 * (L + 1)), device=x0.device, dtype=torch.float32)
+    vcol = _edges_or(vcol, vrowptr)
     with _Timed("shmp_small_fwd_kernel", 2.0 * n * 192 * 64 * L, 4.0 * (L * 192 * 64 + (L + 1) * n * 64)):
         _lib.check(_lib.lib().desco_shmp_trunk_small_fwd_f32(
             _dev(x0, "x0"), _dev(vrowptr, "vrowptr", torch.int32), _dev(vcol, "vcol", torch.int32), n, L, _dev(wt, "wt"),
@@ -1290,6 +1297,7 @@ def shmp_trunk_small_bwd(x0, xall, vrowptr, vcol, t_rowptr, t_col_s1, seg_id, wt
     dbias = torch.empty((L, 64), device=dev, dtype=torch.float32)
     dx0 = torch.empty((n, 64), device=dev, dtype=torch.float32)
     dp, ldp = _rows(dpooled, "dpooled")
+    vcol, t_col_s1 = _edges_or(vcol, vrowptr), _edges_or(t_col_s1, vrowptr)
     with _Timed("shmp_small_bwd_kernel", 6.0 * n * 192 * 64 * L, 4.0 * (3 * L * 192 * 64 + (L + 1) * n * 64)):
         _lib.check(_lib.lib().desco_shmp_trunk_small_bwd_f32(
             _dev(x0, "x0"), _dev(xall, "xall"), _dev(vrowptr, "vrowptr", torch.int32), _dev(vcol, "vcol", torch.int32),
@@ -1311,6 +1319,7 @@ def shmp_trunk_graphs_fwd(x0, vrowptr, vcol, wt, bias, seg_ptr, num_seg, drop: "
     assert x0.is_contiguous() and wt.is_contiguous() and bias.is_contiguous() and tuple(wt.shape) == (L, 192, 64)
     xall = torch.empty((L, n, 64), device=x0.device, dtype=torch.float32)
     pooled = torch.empty((num_seg, 64 * (L + 1)), device=x0.device, dtype=torch.float32)
+    vcol = _edges_or(vcol, vrowptr)
     with _Timed("shmp_graphs_fwd_kernel", 2.0 * n * 192 * 64 * L, 4.0 * (num_seg * L * 192 * 64 + (L + 1) * n * 64)):
         _lib.check(_lib.lib().desco_shmp_trunk_graphs_fwd_f32(
             _dev(x0, "x0"), _dev(vrowptr, "vrowptr", torch.int32), _dev(vcol, "vcol", torch.int32), n, L, _dev(wt, "wt"),
@@ -1330,6 +1339,7 @@ def shmp_trunk_graphs_bwd(x0, xall, vrowptr, vcol, t_rowptr, t_col_s1, seg_ptr, 
     dx0 = torch.empty((n, 64), device=dev, dtype=torch.float32)
     ws = torch.empty((L, n, 64), device=dev, dtype=torch.float32)
     dp, ldp = _rows(dpooled, "dpooled")
+    vcol, t_col_s1 = _edges_or(vcol, vrowptr), _edges_or(t_col_s1, vrowptr)
     with _Timed("shmp_graphs_bwd_kernel", 6.0 * n * 192 * 64 * L, 4.0 * (2 * num_seg * L * 192 * 64 + (L + 1) * n * 64),
                 launches=2):
         _lib.check(_lib.lib().desco_shmp_trunk_graphs_bwd_f32(

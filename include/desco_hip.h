@@ -808,8 +808,9 @@ int desco_shmp_trunk_small_bwd_f32(const float* x0, const float* xall, const int
 /* round 6: the same trunk with ONE WORKGROUP PER GRAPH (segment), for batches whose graphs have at most
  * desco_shmp_trunk_graphs_max_rows() (8) rows each -- the 29 query graphs (3..5 nodes; lightning_model.py:204-207): the
  * graphs are independent of each other, so 29 workgroups stream the layers' weights side by side instead of one
- * workgroup walking 135 rows behind one weight stream.  Arguments as the _small_ entry points; rows of a segment beyond
- * the limit are ignored (the caller checks its segment sizes); the backward takes wt itself ([L][192][64], no transposed
+ * workgroup walking 135 rows behind one weight stream.  Arguments as the _small_ entry points.  PRECONDITION: every
+ * segment has at most desco_shmp_trunk_graphs_max_rows() rows -- the entry points do not check it, and rows of a segment
+ * beyond the limit are silently left out (autograd.ShmpTrunkSmall.per_graph is the caller's check); the backward takes wt itself ([L][192][64], no transposed
  * copy), seg_ptr instead of seg_id, and a workspace of num_layers * num_rows * 64 floats; no limit on num_rows.
  * drop (NULL: none): F.dropout behind every layer's relu (gnn_model.py:274) -- layer l's rows are multiplied by the
  * factor of (row, col) of site drop->site + 2 l; the backward then takes mask_scale = drop->scale (1 without). */

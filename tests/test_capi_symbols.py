@@ -214,3 +214,50 @@ def test_training_entry_points_validate_their_arguments():
         setattr(out, n, p)
     prm.num_q = 65
     rejects("desco_gossip_fold_fwd_f32", L.desco_gossip_fold_fwd_f32(ctypes.byref(prm), ctypes.byref(out), None))
+
+
+def test_per_graph_trunk_entry_points_validate_their_arguments():
+    """desco_shmp_trunk_graphs_fwd_f32 / _bwd_f32: each call below is wrong in ONE way (every other argument valid and
+    16-byte aligned) and comes back as DESCO_EINVAL naming the entry point, before any HIP call."""
+    L = _lib.lib()
+    buf = np.zeros(64 * 1024, np.float32)
+    idx = np.zeros(64, np.int32)
+    p, q = buf.ctypes.data, idx.ctypes.data
+    assert p % 16 == 0
+    key = np.zeros(2, np.uint64)
+    layers, ldp = 3, 64 * 4
+
+    def drop(site, k=key.ctypes.data):
+        d = _lib.Dropout()
+        d.key, d.site, d.threshold, d.scale = k, site, 1 << 30, 4.0 / 3.0
+        return ctypes.byref(d)
+
+    def rejects(name, rc):
+        assert rc == -1, name
+        assert name.encode() in L.desco_last_error(), (name, L.desco_last_error())
+        assert L.desco_rng_next(None, None, None) == -1          # (resets the message for the next case)
+
+    def fwd(x0=p, rows=8, nl=layers, wt=p, bias=p, d=None, xall=p, pooled=p, ld=ldp):
+        return L.desco_shmp_trunk_graphs_fwd_f32(x0, q, q, rows, nl, wt, bias, q, 2, d, xall, pooled, ld, None)
+
+    def bwd(x0=p, xall=p, nl=layers, wt=p, dp=p, ld=ldp, dwt=p, ws=p):
+        return L.desco_shmp_trunk_graphs_bwd_f32(x0, xall, q, q, q, q, q, 2, 8, nl, wt, dp, ld, 1.0, dwt, p, p, ws, None)
+
+    name = "desco_shmp_trunk_graphs_fwd_f32"
+    rejects(name, fwd(x0=None))                                  # a null pointer
+    rejects(name, fwd(pooled=None))
+    rejects(name, fwd(ld=ldp - 4))                               # ldp < 64 (L + 1)
+    rejects(name, fwd(ld=ldp + 2))                               # ldp % 4
+    rejects(name, fwd(xall=p + 4))                               # a misaligned pointer
+    rejects(name, fwd(nl=0))
+    rejects(name, fwd(d=drop(256 - 2 * layers)))                 # site + 2 L >= 256
+    rejects(name, fwd(d=drop(5, None)))                          # a descriptor without a key
+    assert fwd(rows=0) == 0                                      # nothing to do
+    name = "desco_shmp_trunk_graphs_bwd_f32"
+    rejects(name, bwd(x0=None))
+    rejects(name, bwd(ws=None))
+    rejects(name, bwd(ld=ldp - 4))
+    rejects(name, bwd(ld=ldp + 2))
+    rejects(name, bwd(dp=p + 4))
+    rejects(name, bwd(nl=0))
+    assert L.desco_shmp_trunk_graphs_max_rows() == 8
