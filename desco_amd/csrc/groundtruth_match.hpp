@@ -1,0 +1,35 @@
+// The match plan shared by the pattern-guided ground-truth matchers (groundtruth_match.cpp on the host,
+// groundtruth_match_dev.hip on the GPU).  A plan is a flat int32 array:
+//
+//   plan[0] = number of queries Q, plan[1] = number of anchors A, then A records of GTM_REC int32 each, sorted by
+//   query.  One record = one anchor = one orbit of the query's automorphism group: the query node (the orbit's
+//   smallest) that is mapped to the root v while every other image stays below v.
+//
+//   rec[GTM_QUERY]       query index (the column of `out` the record counts into)
+//   rec[GTM_K]           number of query nodes k, 2..16
+//   rec[GTM_ANCHOR]      the anchor (= rec[GTM_NODE])
+//   rec[GTM_DIVISOR]     what a count of maps is divided by to give subsets: 1, because the order constraints
+//                        below leave exactly one map per subset (kept in the format so that a reader can assert it)
+//   rec[GTM_NODE + i]    query node matched at position i; position 0 is the anchor, and every later node is
+//                        adjacent to an earlier one (a connected matching order)
+//   rec[GTM_PARENT + i]  i >= 1: the earlier position whose image's adjacency row supplies the candidates of i
+//   rec[GTM_ADJ + i]     bit j (j < i): the image of i must be adjacent to the image of j; a clear bit j < i means
+//                        it must NOT be (induced matching)
+//   rec[GTM_LT + i]      bit j (j < i): image(i) < image(j)   } symmetry breaking (Grochow-Kellis) inside the
+//   rec[GTM_GT + i]      bit j (j < i): image(i) > image(j)   } stabiliser of the anchor
+#pragma once
+#include <stdint.h>
+
+namespace desco {
+
+constexpr int GTM_KMAX = 16;
+constexpr int GTM_HEAD = 2;
+constexpr int GTM_QUERY = 0, GTM_K = 1, GTM_ANCHOR = 2, GTM_DIVISOR = 3;
+constexpr int GTM_NODE = 4, GTM_PARENT = 20, GTM_ADJ = 36, GTM_LT = 52, GTM_GT = 68;
+constexpr int GTM_REC = 84;
+
+// groundtruth_match.cpp: is `plan` (host memory) a well-formed plan for num_queries queries?  Both matchers index
+// with its fields, so they refuse anything else.  Returns 0 or DESCO_EINVAL with the message set.
+int match_plan_check(const char* who, const int32_t* plan, int64_t plan_entries, int num_queries);
+
+}  // namespace desco

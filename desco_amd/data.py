@@ -36,12 +36,13 @@ def gen_query_ids(query_size: List[int]) -> List[int]:
 def graph_atlas_plus(atlas_id: int) -> nx.Graph:
     """Atlas graph by id (workload.py:1128-1671).  The reference additionally hard-codes 60 large
     (8-14 node) patterns under ids 8000-14001; those literals are not reproduced -- pass such
-    patterns explicitly through ``queries=[nx.Graph, ...]``."""
+    patterns explicitly through ``queries=[nx.Graph, ...]``: queries of up to 16 nodes get exact native
+    ground truth (``groundtruth.canonical_counts``, the matcher of csrc/groundtruth_match.cpp)."""
     if atlas_id < 1253:
         return nx.graph_atlas(atlas_id)
     raise NotImplementedError(
         f"atlas id {atlas_id}: the reference's hand-coded 8-14 node patterns are not bundled; "
-        "pass them via queries=[...]")
+        "pass them via queries=[...] (patterns of up to 16 nodes get exact native ground truth there)")
 
 
 def add_node_feat_to_networkx(graph: nx.Graph, node_feats, node_feat_key: str = "feat"):

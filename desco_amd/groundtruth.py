@@ -78,10 +78,23 @@ def canonical_counts_device(graphs: GraphSet, queries: Sequence, device="cuda") 
 def canonical_counts(graphs: GraphSet, queries: Sequence, num_threads: int = 0,
                      backend: str = "auto") -> torch.Tensor:
     """[num_nodes, num_queries] float tensor of canonical counts (the reference stores doubles).
-    ``queries``: networkx graphs or (n, edges) pairs, connected, 2..6 nodes.
-    ``backend``: "host" (OpenMP enumerator), "device" (HIP kernel), or "auto": the device when a GPU
-    is present and the queries fit its path (2..5 nodes, <= 32, distinct classes), else the host."""
+    ``queries``: networkx graphs or (n, edges) pairs, connected, 2..16 nodes.
+    ``backend``: "host" (OpenMP), "device" (HIP kernels), "auto", or "vf2" (the reference's procedure in Python:
+    the yardstick of the tests and the way out for queries above 16 nodes).
+    Columns of queries with at most 6 nodes go to the ESU enumerators -- "auto": the device when a GPU is present
+    and the queries fit its path (2..5 nodes, <= 32, distinct classes), else the host.  Columns of larger queries
+    go to the matcher (``canonical_counts_match``) with the same ``backend``; the results are joined in query order."""
+    if backend == "vf2":
+        return _canonical_counts_vf2(graphs, queries)
     flat, q_nodes, q_edge_ptr, q_edges = _flatten_queries(queries)
+    large = [i for i, k in enumerate(q_nodes) if k > 6]
+    if large:
+        small = [i for i, k in enumerate(q_nodes) if k <= 6]
+        out = torch.zeros((graphs.num_nodes, len(flat)), dtype=torch.double)
+        out[:, large] = canonical_counts_match(graphs, [flat[i] for i in large], backend, num_threads)
+        if small:
+            out[:, small] = canonical_counts(graphs, [flat[i] for i in small], num_threads, backend)
+        return out
     if backend == "device" or (backend == "auto" and _device_eligible(graphs, q_nodes)):
         try:
             return canonical_counts_device(graphs, queries).cpu().double()
@@ -96,6 +109,130 @@ def canonical_counts(graphs: GraphSet, queries: Sequence, num_threads: int = 0,
                                         q_edges.ctypes.data if len(q_edges) else None, len(flat),
                                         num_threads, out.ctypes.data), "desco_canonical_counts")
     return torch.from_numpy(out).double()
+
+
+# ---- large queries: the pattern-guided matcher ------------------------------------------------------------------------
+# One device launch covers the CSR entries of a slice; a slice holds so many entries that entries x anchors (= waves)
+# stays at this bound, so that no single kernel carries the whole of an unbounded search
+_MATCH_SLICE_WAVES = 1 << 18
+# name of the backend that served the last canonical_counts_match call ("host" or "device")
+last_match_backend = None
+
+
+def match_plan(queries: Sequence) -> np.ndarray:
+    """The matcher's plan of ``queries`` (desco_canonical_match_plan, include/desco_hip.h): int32, plan[0] = number of
+    queries, plan[1] = number of anchors, then one record of 84 entries per anchor.  Raises RuntimeError naming the
+    limit for queries outside 2..16 nodes, disconnected queries and loops."""
+    _, q_nodes, q_edge_ptr, q_edges = _flatten_queries(queries)
+    L = _lib.lib()
+    qargs = (q_nodes.ctypes.data, q_edge_ptr.ctypes.data, q_edges.ctypes.data if len(q_edges) else None, len(q_nodes))
+    entries = int(L.desco_canonical_match_plan_size(*qargs))
+    if entries < 0:
+        _lib.check(-1, "desco_canonical_match_plan_size")
+    plan = np.zeros(entries, dtype=np.int32)
+    _lib.check(L.desco_canonical_match_plan(*qargs, plan.ctypes.data, entries), "desco_canonical_match_plan")
+    return plan
+
+
+def _bitset_words(graphs: GraphSet) -> np.ndarray:
+    n = np.diff(graphs.graph_ptr).astype(np.int64)
+    return n * ((n + 63) // 64)
+
+
+def canonical_counts_match_device(graphs: GraphSet, queries: Sequence, device="cuda",
+                                  slice_entries=None) -> torch.Tensor:
+    """The counts of ``canonical_counts_match`` computed on the MI355X (csrc/groundtruth_match_dev.hip).  Returns a
+    [num_nodes, num_queries] int64 tensor on ``device``.  The CSR entries are cut into slices of ``slice_entries``
+    (default: ``_MATCH_SLICE_WAVES`` waves per launch), one launch each, and the stream is synchronised and the
+    status checked after every slice; the slicing does not change the result."""
+    plan = match_plan(queries)
+    Q, A = int(plan[0]), int(plan[1])
+    dev = torch.device(device)
+    words = _bitset_words(graphs)
+    bit_off = np.concatenate([[0], np.cumsum(words)]).astype(np.int64)
+    N, G, E = graphs.num_nodes, graphs.num_graphs, int(graphs.col.shape[0])
+    out = torch.zeros((N, Q), dtype=torch.int64, device=dev)
+    if N == 0 or Q == 0:
+        return out
+    if slice_entries is None:
+        slice_entries = max(_MATCH_SLICE_WAVES // max(A, 1), 1)
+    slice_entries = int(slice_entries)
+    if slice_entries < 1:
+        raise ValueError("slice_entries must be positive")
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
+    graph_ptr, rowptr = t(graphs.graph_ptr, np.int64), t(graphs.rowptr, np.int64)
+    col, node_graph = t(graphs.col, np.int32), t(graphs.node_graph_ids(), np.int32)
+    bit_off_d, plan_d = t(bit_off[:-1] if G else bit_off, np.int64), t(plan, np.int32)
+    bits = torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        e0 = 0
+        while True:
+            e1 = min(e0 + slice_entries, E)
+            _lib.check(L.desco_canonical_counts_match_dev(
+                graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), E, col.data_ptr() if col.numel() else None,
+                node_graph.data_ptr(), bit_off_d.data_ptr(), bits.data_ptr(), int(bit_off[-1]), plan.ctypes.data,
+                plan_d.data_ptr(), len(plan), Q, e0, e1, out.data_ptr(), stream.cuda_stream),
+                "desco_canonical_counts_match_dev")
+            stream.synchronize()                # a fault of this slice surfaces here, before the next is enqueued
+            e0 = e1
+            if e0 >= E:
+                break
+    return out
+
+
+def canonical_counts_match(graphs: GraphSet, queries: Sequence, backend: str = "auto",
+                           num_threads: int = 0, slice_entries=None) -> torch.Tensor:
+    """Canonical counts by the pattern-guided induced-subgraph matcher: [num_nodes, num_queries] double tensor on the
+    CPU, count[v][q] = #{S : max(S) = v, G[S] isomorphic to q} as ``canonical_counts``.  Its work follows the query
+    instead of the number of connected k-subsets, so it takes queries of 2..16 nodes (small ones too, to be checked
+    against ESU), any number of them, isomorphic duplicates included.
+    ``backend``: "host" (OpenMP over graphs, ``num_threads`` threads), "device" (HIP kernel, ``slice_entries`` as in
+    ``canonical_counts_match_device``) or "auto": the device when a GPU is present and the adjacency bitsets fit
+    ``_DEVICE_BITSET_LIMIT_WORDS``, else the host.  ``last_match_backend`` names the one that served the call."""
+    global last_match_backend
+    if backend not in ("host", "device", "auto"):
+        raise ValueError(f"unknown backend {backend!r}")
+    if backend == "auto":
+        fits = int(_bitset_words(graphs).sum()) <= _DEVICE_BITSET_LIMIT_WORDS
+        backend = "device" if torch.cuda.is_available() and fits else "host"
+    last_match_backend = backend
+    if backend == "device":
+        return canonical_counts_match_device(graphs, queries, slice_entries=slice_entries).cpu().double()
+    plan = match_plan(queries)
+    out = np.zeros((graphs.num_nodes, int(plan[0])), dtype=np.int64)
+    _lib.check(_lib.lib().desco_canonical_counts_match(
+        graphs.graph_ptr.ctypes.data, graphs.num_graphs, graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
+        plan.ctypes.data, len(plan), int(plan[0]), num_threads, out.ctypes.data), "desco_canonical_counts_match")
+    return torch.from_numpy(out).double()
+
+
+def _canonical_counts_vf2(graphs: GraphSet, queries: Sequence) -> torch.Tensor:
+    """The reference's own procedure for unlabelled queries: networkx VF2, one match per isomorphism keyed by
+    ``max(vmap.keys())`` (workload.py:327-348), divided by the query's automorphism count (data.py:61-67).  Any query
+    size; minutes where the native paths take milliseconds."""
+    import networkx as nx
+    flat, _, _, _ = _flatten_queries(queries)
+    GM = nx.algorithms.isomorphism.GraphMatcher
+    targets = []
+    for n, edges in graphs.edge_lists():
+        t = nx.Graph()
+        t.add_nodes_from(range(n))
+        t.add_edges_from(edges)
+        targets.append(t)
+    out = torch.zeros((graphs.num_nodes, len(flat)), dtype=torch.double)
+    for qi, (k, edges) in enumerate(flat):
+        q = nx.Graph()
+        q.add_nodes_from(range(k))
+        q.add_edges_from(edges)
+        sym = sum(1 for _ in GM(q, q).subgraph_isomorphisms_iter())
+        for g, t in enumerate(targets):
+            base = int(graphs.graph_ptr[g])
+            for vmap in GM(t, q).subgraph_isomorphisms_iter():
+                out[base + max(vmap.keys()), qi] += 1
+        out[:, qi] /= sym
+    return out
 
 
 # ---- labelled queries (--use_node_feature) ---------------------------------------------------------------------------

@@ -236,6 +236,45 @@ int desco_canonical_counts_labelled_dev(const int64_t* graph_ptr, int64_t num_gr
                                         const int32_t* table, int64_t table_entries, int kmax, int num_classes,
                                         int64_t* out, desco_stream_t stream);
 
+/* LARGE queries (2..16 nodes): a pattern-guided induced-subgraph matcher next to the ESU enumerators above, whose
+ * class tables of 2^(k(k-1)/2) masks stop at 6 nodes.  Same definition: out[v][q] = #{S : max(S) = v, G[S] isomorphic
+ * to q}.  Queries as in desco_canonical_counts: connected, loop-free, any number, isomorphic duplicates allowed (equal
+ * columns); anything else is DESCO_EINVAL with a message naming the limit.
+ *
+ * HOST helpers (csrc/groundtruth_match.cpp): the PLAN of a query set, a flat int32 array -- plan[0] = num_queries,
+ * plan[1] = number of anchors A, then A records of 84 int32, sorted by query.  A record is one anchor: the query node
+ * that is mapped to the root v while every other image stays below v, one per orbit of the query's automorphism
+ * group.  rec[0] = query, rec[1] = k, rec[2] = anchor, rec[3] = divisor of the map count (always 1: see below),
+ * rec[4 + i] = query node at position i of a connected matching order (position 0 = the anchor), rec[20 + i] = the
+ * earlier position whose image's adjacency row supplies the candidates of position i, rec[36 + i] = mask of the
+ * earlier positions whose images must be adjacent to i's (the other earlier positions must NOT be), rec[52 + i] /
+ * rec[68 + i] = masks of the earlier positions whose image must be above / below i's: symmetry-breaking order
+ * constraints (Grochow-Kellis) inside the anchor's stabiliser, which leave exactly one map per subset.
+ * desco_canonical_match_plan_size = number of int32 entries (-1 with a message), desco_canonical_match_plan fills
+ * plan[plan_entries]. */
+int64_t desco_canonical_match_plan_size(const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges,
+                                        int num_queries);
+int desco_canonical_match_plan(const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges,
+                               int num_queries, int32_t* plan, int64_t plan_entries);
+/* HOST matcher (OpenMP over graphs, per-graph adjacency bitset rows, depth-first over the plan).
+ * out: int64 [N][num_queries], zeroed and filled by the call. */
+int desco_canonical_counts_match(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                 const int32_t* col, const int32_t* plan, int64_t plan_entries, int num_queries,
+                                 int num_threads, int64_t* out);
+/* DEVICE matcher (csrc/groundtruth_match_dev.hip): the device arguments of desco_canonical_counts_dev, then the plan
+ * twice -- plan_host (validated here: the kernel indexes with its fields) and its device copy plan_dev -- and the
+ * slice [entry_begin, entry_end) of CSR entries this call covers: one wave per (entry (v, u0) with u0 < v, record).
+ * The work of a large query on a dense graph is unbounded, so the caller cuts [0, num_entries) into slices, in
+ * ascending order, and checks every status; the call with entry_begin = 0 zeroes out and builds the bitset rows,
+ * every call adds its slice's counts into out: int64 [N][num_queries] (64-bit integer atomics: bit-identical from
+ * run to run and for every slicing).  Enqueues on `stream`, does not allocate or synchronise. */
+int desco_canonical_counts_match_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                     const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                     const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                     int64_t num_words, const int32_t* plan_host, const int32_t* plan_dev,
+                                     int64_t plan_entries, int num_queries, int64_t entry_begin, int64_t entry_end,
+                                     int64_t* out, desco_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DEVICE kernels
  * ------------------------------------------------------------------------------------------ */
