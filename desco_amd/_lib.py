@@ -89,6 +89,11 @@ SIGNATURES = {
     "desco_canonical_counts_match": (c_int, [vp, i64, vp, vp, vp, i64, i32, i32, vp]),
     "desco_canonical_counts_match_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, i32, i64, i64,
                                                  vp, vp]),
+    "desco_canonical_match_plan_labelled_size": (i64, [vp, vp, vp, vp, i32]),
+    "desco_canonical_match_plan_labelled": (c_int, [vp, vp, vp, vp, i32, vp, i64, vp, vp]),
+    "desco_canonical_counts_match_labelled": (c_int, [vp, i64, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "desco_canonical_counts_match_labelled_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64,
+                                                          i32, i64, i64, vp, vp]),
     "desco_linear_smallk_f32": (c_int, [vp, i64, i32, vp, vp, vp, i64, i64, i32, vp]),
     "desco_csr_gather_sum_f32": (c_int, [vp, i64, vp, vp, i64, i32, vp, vp]),
     "desco_gemm_f32": (c_int, [vp, i64, i32, vp, i64, i32, vp, i32, vp, i32, vp, i32, vp, i32, f32,

@@ -19,6 +19,16 @@
 // constraints: every subset is visited ONCE, no division is needed (a star K1,6 does not carry its 720
 // automorphisms), and GTM_DIVISOR is 1.  Automorphisms are never listed (K1,15 has 15! of them): orbits come
 // from a backtracking search for ONE automorphism that fixes the chosen nodes and maps x to y.
+//
+// LABELLED queries (--use_node_feature; desco_canonical_match_plan_labelled_size, desco_canonical_match_plan_labelled,
+// desco_canonical_counts_match_labelled): every node carries an int32 label id and a map must preserve it.  The same
+// argument holds with Aut(q) replaced by the LABEL-PRESERVING automorphisms: anchors are one per orbit of that
+// (smaller) group and the order constraints break only it, so an asymmetrically labelled P7 has 7 anchors and no
+// constraint, and an all-equal labelling gives the unlabelled records.  The reference's expansion of a query into
+// F^k labelled copies is full of copies isomorphic to each other, so the labelled plan is built over labelled
+// isomorphism CLASSES (numbered by first query; the caller expands out[:, class_of_query]), its records carry the
+// label of every position and are sorted by (label of position 0, label of position 1) with a bucket table behind
+// them (groundtruth_match.hpp): a root and its first neighbour select the one bucket whose records can match.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -41,6 +51,7 @@ using namespace desco;
 struct Query {
   int k = 0;
   uint32_t adj[GTM_KMAX] = {0};        // adjacency row bitmasks
+  int32_t lab[GTM_KMAX] = {0};         // label ids (all 0: an unlabelled query)
   int deg(int a) const { return __builtin_popcount(adj[a]); }
   bool has(int a, int b) const { return adj[a] >> b & 1; }
 };
@@ -74,13 +85,15 @@ const char* read_query(const int32_t* q_nodes, const int32_t* q_edge_ptr, const 
   return nullptr;
 }
 
-// Is there an automorphism g of q with g(src[t]) = dst[t] for t < m?  Backtracking over a connected order.
+// Is there an isomorphism g from q onto p (edges and labels preserved; p = q: an automorphism) with g(src[t]) = dst[t]
+// for t < m?  Backtracking over a connected order.  q and p have the same number of nodes.
 struct AutoSearch {
   const Query& q;
+  const Query& p;
   int order[GTM_KMAX], img[GTM_KMAX], m;
   uint32_t used = 0;
 
-  AutoSearch(const Query& q_, const int* src, const int* dst, int m_) : q(q_), m(m_) {
+  AutoSearch(const Query& q_, const Query& p_, const int* src, const int* dst, int m_) : q(q_), p(p_), m(m_) {
     uint32_t placed = 0;
     int n = 0;
     for (int t = 0; t < m; ++t) {
@@ -99,9 +112,9 @@ struct AutoSearch {
     }
   }
   bool fits(int t, int y) const {
-    if ((used >> y & 1) || q.deg(order[t]) != q.deg(y)) return false;
+    if ((used >> y & 1) || q.deg(order[t]) != p.deg(y) || q.lab[order[t]] != p.lab[y]) return false;
     for (int s = 0; s < t; ++s)
-      if (q.has(order[s], order[t]) != q.has(img[s], y)) return false;
+      if (q.has(order[s], order[t]) != p.has(img[s], y)) return false;
     return true;
   }
   bool go(int t) {
@@ -126,26 +139,27 @@ struct AutoSearch {
   }
 };
 
-// orbit of x (as a bitmask) under the automorphisms that fix every node of fixed[0..m-1]
+// orbit of x (as a bitmask) under the (label-preserving) automorphisms that fix every node of fixed[0..m-1]
 uint32_t orbit_of(const Query& q, const int* fixed, int m, int x) {
   int src[GTM_KMAX + 1], dst[GTM_KMAX + 1];
   for (int t = 0; t < m; ++t) src[t] = dst[t] = fixed[t];
   uint32_t orb = 1u << x;
   src[m] = x;
   for (int y = 0; y < q.k; ++y) {
-    if (y == x || q.deg(y) != q.deg(x)) continue;
+    if (y == x || q.deg(y) != q.deg(x) || q.lab[y] != q.lab[x]) continue;
     bool is_fixed = false;
     for (int t = 0; t < m; ++t) is_fixed |= fixed[t] == y;
     if (is_fixed) continue;
     dst[m] = y;
-    AutoSearch s(q, src, dst, m + 1);
+    AutoSearch s(q, q, src, dst, m + 1);
     if (s.go(0)) orb |= 1u << y;
   }
   return orb;
 }
 
-// Appends the records of query `qi` to `plan` (one per orbit of Aut(q)).
-void plan_query(const Query& q, int qi, std::vector<int32_t>& plan) {
+// Appends the records of query `qi` to `plan` (one per orbit of Aut(q)), `rec_size` entries each: GTM_REC, or
+// GTML_REC with the label of every position.
+void plan_query(const Query& q, int qi, std::vector<int32_t>& plan, int rec_size = GTM_REC) {
   const int k = q.k;
   uint32_t covered = 0;
   for (int a = 0; a < k; ++a) {
@@ -189,7 +203,7 @@ void plan_query(const Query& q, int qi, std::vector<int32_t>& plan) {
     }
 
     const size_t r = plan.size();
-    plan.resize(r + GTM_REC, 0);
+    plan.resize(r + rec_size, 0);
     int32_t* rec = plan.data() + r;
     rec[GTM_QUERY] = qi;
     rec[GTM_K] = k;
@@ -210,6 +224,7 @@ void plan_query(const Query& q, int qi, std::vector<int32_t>& plan) {
       rec[GTM_ADJ + i] = (int32_t)adj;
       rec[GTM_LT + i] = (int32_t)lt;
       rec[GTM_GT + i] = (int32_t)gt;
+      if (rec_size == GTML_REC) rec[GTML_LABEL + i] = q.lab[x];
     }
   }
 }
@@ -230,7 +245,97 @@ int build_plan(const char* who, const int32_t* q_nodes, const int32_t* q_edge_pt
   return 0;
 }
 
-// One graph's matcher state.
+const char* kLabelLimit = ": label ids must be non-negative";
+
+// Invariant of a labelled query under isomorphism: equal for isomorphic queries (the filter in front of AutoSearch).
+uint64_t mix64(uint64_t x) {
+  x += 0x9e3779b97f4a7c15ull;
+  x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+  x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+uint64_t invariant(const Query& q) {
+  uint64_t own[GTM_KMAX], sum = mix64((uint64_t)q.k);
+  for (int a = 0; a < q.k; ++a) own[a] = mix64(((uint64_t)(uint32_t)q.lab[a] << 8) | (uint64_t)q.deg(a));
+  for (int a = 0; a < q.k; ++a) {
+    uint64_t around = 0;
+    for (int b = 0; b < q.k; ++b)
+      if (q.has(a, b)) around += own[b];
+    sum += mix64(own[a] ^ mix64(around));                        // (sums: independent of the node numbering)
+  }
+  return sum;
+}
+
+bool isomorphic(const Query& a, const Query& b) {
+  if (a.k != b.k) return false;
+  AutoSearch s(a, b, nullptr, nullptr, 0);
+  return s.go(0);
+}
+
+// The labelled plan (groundtruth_match.hpp) of the queries, class_of_query and the number of classes.
+int build_plan_labelled(const char* who, const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges,
+                        const int32_t* q_labels, int num_queries, std::vector<int32_t>& plan,
+                        std::vector<int32_t>& class_of_query) {
+  if (!q_nodes || !q_edge_ptr || num_queries < 0 || (num_queries > 0 && !q_labels))
+    return fail(DESCO_EINVAL, (std::string(who) + ": bad argument").c_str());
+  std::vector<Query> reps;                                       // the first query of every class
+  std::vector<uint64_t> rep_inv;
+  class_of_query.assign((size_t)num_queries, 0);
+  int64_t off = 0;
+  for (int q = 0; q < num_queries; ++q) {
+    Query qq;
+    if (const char* why = read_query(q_nodes, q_edge_ptr, q_edges, q, qq))
+      return fail(DESCO_EINVAL, (std::string(who) + why).c_str());
+    for (int a = 0; a < qq.k; ++a) {
+      qq.lab[a] = q_labels[off + a];
+      if (qq.lab[a] < 0) return fail(DESCO_EINVAL, (std::string(who) + kLabelLimit).c_str());
+    }
+    off += qq.k;
+    const uint64_t inv = invariant(qq);
+    int c = -1;
+    for (size_t r = 0; r < reps.size() && c < 0; ++r)
+      if (rep_inv[r] == inv && isomorphic(qq, reps[r])) c = (int)r;
+    if (c < 0) {
+      c = (int)reps.size();
+      reps.push_back(qq);
+      rep_inv.push_back(inv);
+    }
+    class_of_query[q] = c;
+  }
+  std::vector<int32_t> recs;
+  for (size_t c = 0; c < reps.size(); ++c) plan_query(reps[c], (int)c, recs, GTML_REC);
+  const int num_recs = (int)(recs.size() / GTML_REC);
+  std::vector<int> order((size_t)num_recs);
+  for (int a = 0; a < num_recs; ++a) order[a] = a;
+  auto key = [&](int a) {
+    const int32_t* rec = recs.data() + (size_t)a * GTML_REC;
+    return ((int64_t)rec[GTML_LABEL] << 32) | (int64_t)rec[GTML_LABEL + 1];
+  };
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key(a) < key(b); });
+  plan.assign(GTML_HEAD, 0);
+  std::vector<int32_t> buckets;
+  int largest = 0;
+  for (int i = 0; i < num_recs; ++i) {
+    const int32_t* rec = recs.data() + (size_t)order[i] * GTML_REC;
+    plan.insert(plan.end(), rec, rec + GTML_REC);
+    if (i == 0 || key(order[i]) != key(order[i - 1])) {
+      const int32_t b[GTML_BUCKET] = {rec[GTML_LABEL], rec[GTML_LABEL + 1], i, i};
+      buckets.insert(buckets.end(), b, b + GTML_BUCKET);
+    }
+    int32_t* b = buckets.data() + buckets.size() - GTML_BUCKET;
+    b[3] = i + 1;
+    largest = std::max(largest, b[3] - b[2]);
+  }
+  plan.insert(plan.end(), buckets.begin(), buckets.end());
+  plan[0] = (int32_t)reps.size();
+  plan[1] = num_recs;
+  plan[2] = (int32_t)(buckets.size() / GTML_BUCKET);
+  plan[3] = largest;
+  return 0;
+}
+
+// One graph's matcher state.  LAB: the labelled matcher, which tests a candidate's label before its adjacency bits.
+template <bool LAB>
 struct Matcher {
   int64_t base;
   const int64_t* rowptr;
@@ -238,6 +343,7 @@ struct Matcher {
   const uint64_t* bits;
   int words, v;
   const int32_t* rec;
+  const int32_t* lab;                  // LAB: this graph's node labels
   int k;
   int img[GTM_KMAX];
   int64_t found;
@@ -245,6 +351,7 @@ struct Matcher {
   bool adj(int a, int b) const { return bits[(size_t)a * words + (b >> 6)] >> (b & 63) & 1; }
 
   bool fits(int level, int u) const {
+    if (LAB && lab[u] != rec[GTML_LABEL + level]) return false;
     const uint32_t want = (uint32_t)rec[GTM_ADJ + level], lt = (uint32_t)rec[GTM_LT + level],
                    gt = (uint32_t)rec[GTM_GT + level];
     for (int j = 0; j < level; ++j) {
@@ -322,6 +429,84 @@ int desco::match_plan_check(const char* who, const int32_t* plan, int64_t plan_e
   return 0;
 }
 
+extern "C" int64_t desco_canonical_match_plan_labelled_size(const int32_t* q_nodes, const int32_t* q_edge_ptr,
+                                                            const int32_t* q_edges, const int32_t* q_labels,
+                                                            int num_queries) {
+  try {
+    std::vector<int32_t> plan, coq;
+    if (build_plan_labelled("desco_canonical_match_plan_labelled_size", q_nodes, q_edge_ptr, q_edges, q_labels,
+                            num_queries, plan, coq))
+      return -1;
+    return (int64_t)plan.size();
+  } catch (const std::bad_alloc&) {
+    fail(DESCO_ENOMEM, "desco_canonical_match_plan_labelled_size: out of memory");
+    return -1;
+  }
+}
+
+extern "C" int desco_canonical_match_plan_labelled(const int32_t* q_nodes, const int32_t* q_edge_ptr,
+                                                   const int32_t* q_edges, const int32_t* q_labels, int num_queries,
+                                                   int32_t* plan, int64_t plan_entries, int32_t* class_of_query,
+                                                   int* num_classes) {
+  try {
+    std::vector<int32_t> p, coq;
+    if (const int rc = build_plan_labelled("desco_canonical_match_plan_labelled", q_nodes, q_edge_ptr, q_edges,
+                                           q_labels, num_queries, p, coq))
+      return rc;
+    if (!num_classes || (num_queries > 0 && !class_of_query))
+      return fail(DESCO_EINVAL, "desco_canonical_match_plan_labelled: bad argument");
+    if (!plan || plan_entries != (int64_t)p.size())
+      return fail(DESCO_EINVAL,
+                  "desco_canonical_match_plan_labelled: plan_entries is not desco_canonical_match_plan_labelled_size");
+    std::memcpy(plan, p.data(), p.size() * sizeof(int32_t));
+    if (num_queries > 0) std::memcpy(class_of_query, coq.data(), coq.size() * sizeof(int32_t));
+    *num_classes = p[0];
+    return 0;
+  } catch (const std::bad_alloc&) {
+    return fail(DESCO_ENOMEM, "desco_canonical_match_plan_labelled: out of memory");
+  }
+}
+
+// The same for a labelled plan: head, record fields, labels, the sort by (label 0, label 1) and the bucket table, which
+// must be exactly the runs of equal (label 0, label 1) in the records.
+int desco::match_plan_labelled_check(const char* who, const int32_t* plan, int64_t plan_entries, int num_classes) {
+  const std::string w(who);
+  if (!plan || plan_entries < GTML_HEAD || plan[0] != num_classes || plan[1] < 0 || plan[2] < 0 || plan[2] > plan[1] ||
+      plan_entries != GTML_HEAD + (int64_t)plan[1] * GTML_REC + (int64_t)plan[2] * GTML_BUCKET)
+    return fail(DESCO_EINVAL, (w + ": not a plan of desco_canonical_match_plan_labelled for these queries").c_str());
+  const int32_t* buckets = plan + GTML_HEAD + (int64_t)plan[1] * GTML_REC;
+  int b = -1, largest = 0;
+  for (int a = 0; a < plan[1]; ++a) {
+    const int32_t* rec = plan + GTML_HEAD + (int64_t)a * GTML_REC;
+    const int k = rec[GTM_K];
+    bool ok = rec[GTM_QUERY] >= 0 && rec[GTM_QUERY] < num_classes && k >= 2 && k <= GTM_KMAX && rec[GTM_DIVISOR] == 1;
+    for (int i = 0; ok && i < k; ++i) ok = rec[GTML_LABEL + i] >= 0;
+    for (int i = 1; ok && i < k; ++i) {
+      const uint32_t below = (1u << i) - 1u;
+      const int p = rec[GTM_PARENT + i];
+      ok = p >= 0 && p < i && ((uint32_t)rec[GTM_ADJ + i] >> p & 1) && !((uint32_t)rec[GTM_ADJ + i] & ~below) &&
+           !((uint32_t)rec[GTM_LT + i] & ~below) && !((uint32_t)rec[GTM_GT + i] & ~below);
+    }
+    if (ok) {                                                    // the bucket this record belongs to
+      const int32_t l0 = rec[GTML_LABEL], l1 = rec[GTML_LABEL + 1];
+      if (b < 0 || buckets[b * GTML_BUCKET] != l0 || buckets[b * GTML_BUCKET + 1] != l1) {
+        ++b;
+        const int32_t* nb = buckets + (int64_t)b * GTML_BUCKET;
+        ok = b < plan[2] && nb[0] == l0 && nb[1] == l1 && nb[2] == a && nb[3] > a && nb[3] <= plan[1] &&
+             (b == 0 || nb[-GTML_BUCKET] < l0 || (nb[-GTML_BUCKET] == l0 && nb[-GTML_BUCKET + 1] < l1)) &&
+             (b == 0 || nb[-GTML_BUCKET + 3] == a);
+        if (ok) largest = std::max(largest, nb[3] - nb[2]);
+      } else {
+        ok = a < buckets[b * GTML_BUCKET + 3];
+      }
+    }
+    if (!ok) return fail(DESCO_EINVAL, (w + ": malformed plan record").c_str());
+  }
+  if (b + 1 != plan[2] || largest != plan[3] || (b >= 0 && buckets[b * GTML_BUCKET + 3] != plan[1]))
+    return fail(DESCO_EINVAL, (w + ": malformed plan buckets").c_str());
+  return 0;
+}
+
 extern "C" int desco_canonical_counts_match(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
                                             const int32_t* col, const int32_t* plan, int64_t plan_entries,
                                             int num_queries, int num_threads, int64_t* out) {
@@ -357,7 +542,7 @@ extern "C" int desco_canonical_counts_match(const int64_t* graph_ptr, int64_t nu
           const int w = (int)(col[e] - base);
           bits[(size_t)u * words + (w >> 6)] |= (uint64_t)1 << (w & 63);
         }
-      Matcher m;
+      Matcher<false> m;
       m.base = base;
       m.rowptr = rowptr;
       m.col = col;
@@ -380,5 +565,70 @@ extern "C" int desco_canonical_counts_match(const int64_t* graph_ptr, int64_t nu
     return 0;
   } catch (const std::bad_alloc&) {
     return fail(DESCO_ENOMEM, "desco_canonical_counts_match: out of memory");
+  }
+}
+
+extern "C" int desco_canonical_counts_match_labelled(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                                     const int32_t* col, const int32_t* labels, const int32_t* plan,
+                                                     int64_t plan_entries, int num_classes, int num_threads,
+                                                     int64_t* out) {
+  const char* who = "desco_canonical_counts_match_labelled";
+  if (!graph_ptr || !rowptr || !out || num_graphs < 0 || num_classes < 0 || (graph_ptr[num_graphs] > 0 && !labels))
+    return fail(DESCO_EINVAL, "desco_canonical_counts_match_labelled: bad argument");
+  if (const int rc = match_plan_labelled_check(who, plan, plan_entries, num_classes)) return rc;
+  try {
+    const int64_t total = graph_ptr[num_graphs];
+    std::memset(out, 0, sizeof(int64_t) * (size_t)total * (size_t)num_classes);
+    const int num_recs = plan[1];
+    if (num_classes == 0 || num_recs == 0) return 0;
+#ifdef _OPENMP
+    const int nt = num_threads > 0 ? num_threads : omp_get_max_threads();
+#else
+    const int nt = 1;
+    (void)num_threads;
+#endif
+    bool oom = false;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+    for (int64_t g = 0; g < num_graphs; ++g) {
+      const int64_t base = graph_ptr[g], n = graph_ptr[g + 1] - base;
+      const int words = (int)((n + 63) / 64);
+      std::vector<uint64_t> bits;
+      try {
+        bits.assign((size_t)n * words, 0);
+      } catch (const std::bad_alloc&) {
+#pragma omp atomic write
+        oom = true;
+        continue;
+      }
+      for (int64_t u = 0; u < n; ++u)
+        for (int64_t e = rowptr[base + u]; e < rowptr[base + u + 1]; ++e) {
+          const int w = (int)(col[e] - base);
+          bits[(size_t)u * words + (w >> 6)] |= (uint64_t)1 << (w & 63);
+        }
+      Matcher<true> m;
+      m.base = base;
+      m.rowptr = rowptr;
+      m.col = col;
+      m.bits = bits.data();
+      m.words = words;
+      m.lab = labels + base;
+      for (int v = 1; v < (int)n; ++v) {
+        if (rowptr[base + v] == rowptr[base + v + 1]) continue;
+        m.v = v;
+        m.img[0] = v;
+        for (int a = 0; a < num_recs; ++a) {
+          m.rec = plan + GTML_HEAD + (int64_t)a * GTML_REC;
+          if (m.rec[GTML_LABEL] != m.lab[v]) continue;           // the root's label retires the record at once
+          m.k = m.rec[GTM_K];
+          m.found = 0;
+          m.extend(1);
+          out[(base + v) * num_classes + m.rec[GTM_QUERY]] += m.found;
+        }
+      }
+    }
+    if (oom) return fail(DESCO_ENOMEM, "desco_canonical_counts_match_labelled: out of memory");
+    return 0;
+  } catch (const std::bad_alloc&) {
+    return fail(DESCO_ENOMEM, "desco_canonical_counts_match_labelled: out of memory");
   }
 }

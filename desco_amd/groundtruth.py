@@ -255,13 +255,14 @@ last_labelled_backend = None
 class _Labelled:
     """Label ids, flattened queries and labelled isomorphism classes of one call."""
 
-    def __init__(self, graphs: GraphSet, queries: Sequence, key: str):
-        if graphs.node_feat is None:
+    def __init__(self, graphs, queries: Sequence, key: str):
+        """``graphs``: a GraphSet with node_feat, or None (query labels only: ``match_plan_labelled``)."""
+        if graphs is not None and graphs.node_feat is None:
             raise ValueError("labelled ground truth needs GraphSet.node_feat")
         self.nan = False
         ids = {}                      # feature row as a tuple of floats -> id: float equality, as the VF2 node_match
         # (-0.0 == 0.0 and hash alike; NaN never equals anything -> VF2 path)
-        nf = graphs.node_feat.astype(np.float64) + 0.0
+        nf = (graphs.node_feat.astype(np.float64) if graphs is not None else np.zeros((0, 1))) + 0.0
         self.nan |= bool(np.isnan(nf).any())
         if nf.shape[0]:
             uniq, inv = np.unique(nf, axis=0, return_inverse=True)
@@ -424,7 +425,10 @@ def canonical_counts_labelled(graphs: GraphSet, queries: Sequence, node_feat_key
     queries of 2..6 nodes, ``num_threads`` threads), "device" (HIP kernel; raises RuntimeError naming the limit the
     input is outside of, see ``canonical_counts_labelled_device``) or "auto": the device when a GPU is present and
     the input fits it, else the host enumerator, else (features with NaN, more than 256 distinct labels) VF2.
-    ``last_labelled_backend`` names the one that served the call."""
+    ``last_labelled_backend`` names the one that served the call.
+    Columns of queries with 7..16 nodes go to the labelled matcher (``canonical_counts_match_labelled``) with the same
+    ``backend`` and the results are joined in query order; a call made only of such queries sets
+    ``last_labelled_backend`` to the matcher's backend.  Above 16 nodes "auto" uses VF2 and "host" / "device" raise."""
     global last_labelled_backend
     if backend not in ("vf2", "host", "device", "auto"):
         raise ValueError(f"unknown backend {backend!r}")
@@ -432,6 +436,27 @@ def canonical_counts_labelled(graphs: GraphSet, queries: Sequence, node_feat_key
         last_labelled_backend = "vf2"
         return _canonical_counts_labelled_vf2(graphs, queries, node_feat_key)
     lab = _Labelled(graphs, queries, node_feat_key)
+    large = [i for i, k in enumerate(lab.q_nodes) if k > 6]
+    if large and not (backend == "auto" and (lab.nan or lab.kmax > 16)):
+        # columns above 6 nodes go to the labelled matcher with the same backend, the others where they always went
+        if lab.nan:
+            raise RuntimeError(f"canonical_counts_labelled: {backend} path: " + lab.host_limit())
+        if lab.kmax > 16:
+            raise RuntimeError(f"canonical_counts_labelled: {backend} path: the native paths take labelled queries "
+                               "of 2..16 nodes (backend=\"vf2\" takes larger ones)")
+        queries = list(queries)
+        small = [i for i, k in enumerate(lab.q_nodes) if k <= 6]
+        out = torch.zeros((graphs.num_nodes, lab.num_queries), dtype=torch.double)
+        if small:
+            out[:, small] = canonical_counts_labelled(graphs, [queries[i] for i in small], node_feat_key, backend,
+                                                      num_threads)
+        out[:, large] = canonical_counts_match_labelled(graphs, [queries[i] for i in large], node_feat_key, backend,
+                                                        num_threads)
+        if not small:
+            last_labelled_backend = last_labelled_match_backend
+        return out
+    if large:
+        backend = "vf2"                         # "auto" with NaN features or a query above 16 nodes
     if backend == "device":
         _require_device(lab, graphs)
     elif backend == "auto":
@@ -453,6 +478,156 @@ def canonical_counts_labelled(graphs: GraphSet, queries: Sequence, node_feat_key
                 out[n0:n1] = counts.double().cpu()
     last_labelled_backend = backend
     return out
+
+
+# ---- labelled queries of 7..16 nodes: the matcher with labels ---------------------------------------------------------
+# name of the backend that served the last canonical_counts_match_labelled call ("host" or "device")
+last_labelled_match_backend = None
+# offsets into the labelled plan (csrc/groundtruth_match.hpp)
+_GTML_HEAD, _GTML_REC, _GTML_LABEL, _GTML_BUCKET = 4, 100, 84, 4
+
+
+def _match_plan_labelled(lab: _Labelled):
+    L = _lib.lib()
+    qargs = lab._qargs()[:5]
+    entries = int(L.desco_canonical_match_plan_labelled_size(*qargs))
+    if entries < 0:
+        _lib.check(-1, "desco_canonical_match_plan_labelled_size")
+    plan = np.zeros(entries, dtype=np.int32)
+    coq = np.zeros(lab.num_queries, dtype=np.int32)
+    c = ctypes.c_int(0)
+    _lib.check(L.desco_canonical_match_plan_labelled(*qargs, plan.ctypes.data, entries, coq.ctypes.data,
+                                                     ctypes.byref(c)), "desco_canonical_match_plan_labelled")
+    return plan, coq
+
+
+def match_plan_labelled(queries: Sequence, node_feat_key: str = "feat"):
+    """The labelled matcher's plan of ``queries`` (networkx graphs whose nodes carry ``node_feat_key``) and
+    class_of_query (desco_canonical_match_plan_labelled, include/desco_hip.h): ``(plan, class_of_query)``, int32.
+    plan[0] = number of labelled isomorphism classes, plan[1] = number of records, plan[2] = number of buckets,
+    plan[3] = the largest bucket, then records of 100 entries (the 84 of ``match_plan`` with the class as query, then
+    the label id of every position) sorted by the labels of positions 0 and 1, then buckets of 4 entries.  Label ids
+    number the distinct feature vectors of the queries in order of appearance.  Raises RuntimeError naming the limit
+    for queries outside 2..16 nodes, disconnected queries and loops."""
+    lab = _Labelled(None, queries, node_feat_key)
+    if lab.nan:
+        raise RuntimeError("match_plan_labelled: features contain NaN (never equal to anything)")
+    return _match_plan_labelled(lab)
+
+
+def _plan_buckets(plan: np.ndarray) -> np.ndarray:
+    """[B, 4] view of the plan's buckets: label 0, label 1, first record, end record."""
+    return plan[_GTML_HEAD + int(plan[1]) * _GTML_REC:].reshape(-1, _GTML_BUCKET)
+
+
+def labelled_match_waves(graphs: GraphSet, lab_or_labels, plan: np.ndarray):
+    """(launched, live) waves of the device labelled matcher for this input: it launches the largest bucket per CSR
+    entry; live are the (entry (v, u0) with u0 < v, record of the bucket of their labels) pairs."""
+    labels = lab_or_labels.node_labels if isinstance(lab_or_labels, _Labelled) else np.asarray(lab_or_labels)
+    E = int(graphs.col.shape[0])
+    launched = E * int(plan[3])
+    rows = np.repeat(np.arange(graphs.num_nodes, dtype=np.int64), np.diff(graphs.rowptr))
+    below = graphs.col < rows
+    size = {(int(b[0]), int(b[1])): int(b[3] - b[2]) for b in _plan_buckets(plan)}
+    pairs, counts = np.unique(np.stack([labels[rows[below]], labels[graphs.col[below]]], axis=1), axis=0,
+                              return_counts=True) if below.any() else (np.zeros((0, 2), np.int64), np.zeros(0, np.int64))
+    live = sum(int(n) * size.get((int(a), int(b)), 0) for (a, b), n in zip(pairs, counts))
+    return launched, live
+
+
+def _labelled_match_device(graphs: GraphSet, lab: _Labelled, dev, slice_entries=None):
+    """([num_nodes, num_classes] int64 counts on ``dev``, class_of_query)"""
+    plan, coq = _match_plan_labelled(lab)
+    C, largest = int(plan[0]), int(plan[3])
+    words = _bitset_words(graphs)
+    bit_off = np.concatenate([[0], np.cumsum(words)]).astype(np.int64)
+    N, G, E = graphs.num_nodes, graphs.num_graphs, int(graphs.col.shape[0])
+    if N == 0 or lab.num_queries == 0:
+        return torch.zeros((N, C), dtype=torch.int64, device=dev), coq
+    if slice_entries is None:           # waves per launch = entries x largest bucket, whatever the number of records
+        slice_entries = max(_MATCH_SLICE_WAVES // max(largest, 1), 1)
+    slice_entries = int(slice_entries)
+    if slice_entries < 1:
+        raise ValueError("slice_entries must be positive")
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
+    graph_ptr, rowptr = t(graphs.graph_ptr, np.int64), t(graphs.rowptr, np.int64)
+    col, node_graph = t(graphs.col, np.int32), t(graphs.node_graph_ids(), np.int32)
+    bit_off_d, plan_d = t(bit_off[:-1] if G else bit_off, np.int64), t(plan, np.int32)
+    labels = t(lab.node_labels, np.int32)
+    bits = torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev)
+    out = torch.zeros((N, C), dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        e0 = 0
+        while True:
+            e1 = min(e0 + slice_entries, E)
+            _lib.check(L.desco_canonical_counts_match_labelled_dev(
+                graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), E, col.data_ptr() if col.numel() else None,
+                node_graph.data_ptr(), bit_off_d.data_ptr(), bits.data_ptr(), int(bit_off[-1]), labels.data_ptr(),
+                plan.ctypes.data, plan_d.data_ptr(), len(plan), C, e0, e1, out.data_ptr(), stream.cuda_stream),
+                "desco_canonical_counts_match_labelled_dev")
+            stream.synchronize()                # a fault of this slice surfaces here, before the next is enqueued
+            e0 = e1
+            if e0 >= E:
+                break
+    return out, coq
+
+
+def _require_no_nan(lab: _Labelled, who: str):
+    if lab.nan:
+        raise RuntimeError(f"{who}: features contain NaN (never equal to anything): only the VF2 path reproduces that")
+
+
+def canonical_counts_match_labelled_device(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat",
+                                           device="cuda", slice_entries=None) -> torch.Tensor:
+    """The counts of ``canonical_counts_match_labelled`` computed on the MI355X (csrc/groundtruth_match_dev.hip, the
+    labelled instantiation).  Returns a [num_nodes, num_queries] int64 tensor on ``device``.  Each labelled class is
+    matched once and its column copied to every query of the class.  The CSR entries are cut into slices of
+    ``slice_entries`` (default: ``_MATCH_SLICE_WAVES`` waves per launch, a wave being one (entry, record slot of the
+    largest label bucket) pair), one launch each, synchronised and checked; the slicing does not change the result."""
+    lab = _Labelled(graphs, queries, node_feat_key)
+    _require_no_nan(lab, "canonical_counts_match_labelled_device")
+    dev = torch.device(device)
+    out, coq = _labelled_match_device(graphs, lab, dev, slice_entries)
+    return out.index_select(1, torch.from_numpy(coq).long().to(dev))
+
+
+def canonical_counts_match_labelled(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat",
+                                    backend: str = "auto", num_threads: int = 0, slice_entries=None) -> torch.Tensor:
+    """Labelled canonical counts (as ``canonical_counts_labelled``) by the pattern-guided matcher: [num_nodes,
+    num_queries] double tensor on the CPU.  Labelled queries of 2..16 nodes (small ones too, to be checked against the
+    labelled ESU path), any number of them, any number of distinct labels; isomorphic labelled copies are matched once.
+    ``backend``: "host" (OpenMP over graphs, ``num_threads`` threads), "device" (HIP kernel) or "auto": the device when
+    a GPU is present and the adjacency bitsets fit ``_DEVICE_BITSET_LIMIT_WORDS``, else the host.
+    ``last_labelled_match_backend`` names the one that served the call.  Features with NaN are refused (VF2 only)."""
+    global last_labelled_match_backend
+    if backend not in ("host", "device", "auto"):
+        raise ValueError(f"unknown backend {backend!r}")
+    lab = _Labelled(graphs, queries, node_feat_key)
+    _require_no_nan(lab, "canonical_counts_match_labelled")
+    if backend == "auto":
+        fits = int(_bitset_words(graphs).sum()) <= _DEVICE_BITSET_LIMIT_WORDS
+        backend = "device" if torch.cuda.is_available() and fits else "host"
+    last_labelled_match_backend = backend
+    if backend == "device":
+        # expanded to query columns and converted on the device, in row chunks within the labelled paths' byte budget
+        # (int64 + double copy of a chunk), each copied straight into its rows of the result
+        dev = torch.device("cuda")
+        out, coq = _labelled_match_device(graphs, lab, dev, slice_entries)
+        coq_d = torch.from_numpy(coq).long().to(dev)
+        res = torch.empty((graphs.num_nodes, lab.num_queries), dtype=torch.double)
+        rows = max(_DEVICE_LABEL_CHUNK_BYTES // (16 * max(lab.num_queries, 1)), 1)
+        for n0 in range(0, graphs.num_nodes, rows):
+            res[n0:n0 + rows].copy_(out[n0:n0 + rows].index_select(1, coq_d).double())
+        return res
+    plan, coq = _match_plan_labelled(lab)
+    out = np.zeros((graphs.num_nodes, int(plan[0])), dtype=np.int64)
+    _lib.check(_lib.lib().desco_canonical_counts_match_labelled(
+        graphs.graph_ptr.ctypes.data, graphs.num_graphs, graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
+        lab.node_labels.ctypes.data, plan.ctypes.data, len(plan), int(plan[0]), num_threads, out.ctypes.data),
+        "desco_canonical_counts_match_labelled")
+    return torch.from_numpy(out)[:, torch.from_numpy(coq).long()].double()
 
 
 def _canonical_counts_labelled_vf2(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat") -> torch.Tensor:

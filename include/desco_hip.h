@@ -275,6 +275,44 @@ int desco_canonical_counts_match_dev(const int64_t* graph_ptr, int64_t num_graph
                                      int64_t plan_entries, int num_queries, int64_t entry_begin, int64_t entry_end,
                                      int64_t* out, desco_stream_t stream);
 
+/* LABELLED LARGE queries (--use_node_feature, 2..16 nodes): the matcher above with a label id on every query node
+ * and on every graph node; a map must preserve labels as well as edges and non-edges.  Label ids are any
+ * non-negative int32 (the matcher compares ids: no alphabet limit); q_labels is laid out as in
+ * desco_canonical_label_classes.  Two queries are one CLASS iff a bijection between them preserves edges and labels;
+ * classes are numbered in the order of their first query and the plan is built over classes, so each is matched once
+ * however many isomorphic copies the reference's F^k expansion holds: the caller expands out[:, class_of_query[q]].
+ *
+ * The labelled PLAN: plan[0] = num_classes, plan[1] = number of records A, plan[2] = number of buckets B, plan[3] = the
+ * size of the largest bucket, then A records of 100 int32, then B buckets of 4 int32.  A record is the 84-entry record
+ * above -- rec[0] = the class, one record per orbit of the LABEL-PRESERVING automorphism group, order constraints
+ * that break only that group (divisor 1) -- followed by rec[84 + i] = the label of position i.  Records are sorted by
+ * (label of position 0, label of position 1), then class; bucket = (label 0, label 1, first record, end record) of one
+ * run, ascending.  desco_canonical_match_plan_labelled_size = number of int32 entries (-1 with a message);
+ * desco_canonical_match_plan_labelled fills plan[plan_entries], class_of_query[num_queries] and *num_classes. */
+int64_t desco_canonical_match_plan_labelled_size(const int32_t* q_nodes, const int32_t* q_edge_ptr,
+                                                 const int32_t* q_edges, const int32_t* q_labels, int num_queries);
+int desco_canonical_match_plan_labelled(const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges,
+                                        const int32_t* q_labels, int num_queries, int32_t* plan, int64_t plan_entries,
+                                        int32_t* class_of_query, int* num_classes);
+/* HOST labelled matcher (OpenMP over graphs): labels [N] int32; a candidate's label is tested before its adjacency
+ * bits.  A node whose label no query position carries matches nothing.  out: int64 [N][num_classes], zeroed and
+ * filled by the call. */
+int desco_canonical_counts_match_labelled(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                          const int32_t* col, const int32_t* labels, const int32_t* plan,
+                                          int64_t plan_entries, int num_classes, int num_threads, int64_t* out);
+/* DEVICE labelled matcher (csrc/groundtruth_match_dev.hip): the arguments of desco_canonical_counts_match_dev plus the
+ * device labels [N], with the labelled plan.  One wave per (CSR entry (v, u0) of the slice, j < largest bucket): the
+ * wave takes the j-th record of the bucket of (labels[v], labels[u0]) or retires, so a slice launches
+ * (entry_end - entry_begin) * plan[3] waves whatever the number of records.  Slices, zeroing, atomics and the
+ * no-allocation / no-synchronisation rule as desco_canonical_counts_match_dev; out: int64 [N][num_classes]. */
+int desco_canonical_counts_match_labelled_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                              const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                              const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                              int64_t num_words, const int32_t* labels, const int32_t* plan_host,
+                                              const int32_t* plan_dev, int64_t plan_entries, int num_classes,
+                                              int64_t entry_begin, int64_t entry_end, int64_t* out,
+                                              desco_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DEVICE kernels
  * ------------------------------------------------------------------------------------------ */
