@@ -6,11 +6,19 @@ is still running -- desco_amd.distributed)."""
 from __future__ import annotations
 
 import os
+import warnings
 from typing import List, Optional
 
 import torch
 
 from . import distributed as D
+
+
+# the one wording of why --neigh_tune_bs / --gossip_tune_bs do nothing (README)
+TUNE_BS_NOT_EXECUTED = (
+    "auto_scale_batch_size (--neigh_tune_bs / --gossip_tune_bs) is not executed: Lightning's scaler grows the batch until "
+    "the allocator fails, which is not something to do on a shared card, and what the flag sets in the reference is "
+    "ambiguous (model.batch_size and the datamodule's own batch_size both exist there); the batch size stays as given")
 
 
 class ModelCheckpoint:
@@ -88,7 +96,8 @@ class Trainer:
     def __init__(self, max_epochs: int = 1, accelerator: str = "gpu", devices=None,
                  default_root_dir: str = ".", callbacks=None, strategy: Optional[str] = None,
                  grad_reduce: str = "mean", precision: str = "fp32", graph_capture: bool = False,
-                 num_buckets: int = 4, verbose: bool = False, **unused):
+                 num_buckets: int = 4, verbose: bool = False, auto_lr_find: bool = False,
+                 auto_scale_batch_size=False, **unused):
         # precision: "fp32" | "bf16" (Lightning's "32" / "bf16-mixed" spellings accepted): matrix
         # products of the training step in fp32 or bf16 MFMA (desco_amd.autograd.set_precision)
         self.precision = precision
@@ -103,6 +112,9 @@ class Trainer:
         self.grad_reduce = grad_reduce      # "mean" (neighborhood loss) or "sum" (gossip loss)
         self.num_buckets = num_buckets
         self.verbose = verbose              # print the monitored validation loss per epoch (rank 0)
+        # auto_lr_find / auto_scale_batch_size (main.py:211-212, --*_tune_lr / --*_tune_bs): what tune() does before fit
+        self.auto_lr_find = bool(auto_lr_find)
+        self.auto_scale_batch_size = auto_scale_batch_size
         self.device = D.local_device(devices, accelerator)
         if self.device.type == "cuda":
             # the C ABI launches on the CURRENT device / stream: bind this process to its GPU
@@ -187,6 +199,35 @@ class Trainer:
             model.invalidate_caches()
 
     # ---- API ----------------------------------------------------------------------------------
+    def tune(self, model, datamodule=None, lr_find_kwargs=None) -> dict:
+        """``pl.Trainer.tune`` as main.py:237-240, 351-354 call it before ``fit``.  With ``auto_lr_find`` the
+        learning-rate range test (desco_amd.tuner.lr_find) runs, its suggestion becomes ``model.lr`` and the record goes
+        to ``<default_root_dir>/lr_find.csv``; returns ``{"lr_find": LRFinderResult}``.  Data parallel: the reference
+        tunes on its one-device trainer before the "ddp" fit; here rank 0 sweeps alone over the full batch stream (no
+        buckets, no hooks, no collective inside the sweep) and the other ranks -- which get ``{"lr_find": None}`` --
+        wait for its suggestion.  ``auto_scale_batch_size`` is not executed: see the warning below."""
+        if self.auto_scale_batch_size:
+            warnings.warn(TUNE_BS_NOT_EXECUTED)
+        if not self.auto_lr_find:
+            return {}
+        from . import tuner
+        kw = dict(lr_find_kwargs or {})
+        kw.pop("update_attr", None)
+        skips = {k: kw[k] for k in ("skip_begin", "skip_end") if k in kw}
+        multi = D.collectives_on()
+        result = None
+        if self._rank0():
+            result = tuner.lr_find(self, model, datamodule, update_attr=not multi, **kw)
+            os.makedirs(self.root, exist_ok=True)
+            result.to_csv(os.path.join(self.root, "lr_find.csv"))
+            lr = result.suggestion(**skips)
+            print(f"lr_find: {len(result.raw_loss)} steps{' (stopped early)' if result.stopped_early else ''}, "
+                  f"suggested learning rate {lr}", flush=True)
+        if multi:
+            lr, _ = D.broadcast_object((lr, result.stopped_early) if self._rank0() else None)
+            tuner.apply_lr(model, lr)
+        return {"lr_find": result}
+
     def fit(self, model, datamodule):
         from . import autograd as AG
         AG.set_precision(self.precision)

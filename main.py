@@ -103,7 +103,9 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
                             default_root_dir=args_neighborhood.model_path, callbacks=[neigh_ckpt],
                             strategy=strategy, grad_reduce="mean", verbose=True,
                             precision=getattr(args_opt, "precision", "fp32"),
-                            graph_capture=getattr(args_opt, "graph_capture", False))
+                            graph_capture=getattr(args_opt, "graph_capture", False),
+                            auto_lr_find=getattr(args_neighborhood, "tune_lr", False),
+                            auto_scale_batch_size=getattr(args_neighborhood, "tune_bs", False))
     if train_neighborhood and neighborhood_checkpoint is None:
         neigh_model = NeighborhoodCountingModel(input_dim=args_neighborhood.input_dim,
                                                 hidden_dim=args_neighborhood.hidden_dim,
@@ -117,6 +119,8 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
     neigh_model.to(neigh_trainer.device)
     neigh_model.set_queries(query_ids=query_ids, queries=nx_queries, transform=transform)
     if train_neighborhood:
+        if neigh_trainer.auto_lr_find or neigh_trainer.auto_scale_batch_size:          # main.py:237-240
+            neigh_trainer.tune(model=neigh_model, datamodule=neigh_loader)
         neigh_trainer.fit(model=neigh_model, datamodule=neigh_loader)
         print("best neighborhood model path: ", neigh_ckpt.best_model_path)
         neigh_model = NeighborhoodCountingModel.load_from_checkpoint(neigh_ckpt.best_model_path)
@@ -155,10 +159,14 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
         gossip_trainer = Trainer(max_epochs=args_gossip.epoch_num, accelerator="gpu", devices=devices,
                                  default_root_dir=args_gossip.model_path, callbacks=[gossip_ckpt],
                                  strategy=strategy, grad_reduce="sum", verbose=True,
-                                 precision=getattr(args_opt, "precision", "fp32"))
+                                 precision=getattr(args_opt, "precision", "fp32"),
+                                 auto_lr_find=getattr(args_gossip, "tune_lr", False),
+                                 auto_scale_batch_size=getattr(args_gossip, "tune_bs", False))
         gossip_model.to(gossip_trainer.device)
         gossip_model.set_query_emb(neigh_model.get_query_emb())
         if train_gossip:
+            if gossip_trainer.auto_lr_find or gossip_trainer.auto_scale_batch_size:    # main.py:351-354
+                gossip_trainer.tune(model=gossip_model, datamodule=gossip_loader)
             gossip_trainer.fit(model=gossip_model, datamodule=gossip_loader)
             print("best gossip model path: ", gossip_ckpt.best_model_path)
             gossip_model = GossipCountingModel.load_from_checkpoint(gossip_ckpt.best_model_path)
