@@ -568,42 +568,51 @@ def pool_reduce_multi(parts, bits: torch.Tensor, slot: torch.Tensor, seg_ptr: to
 
 
 def pool_post(anch: torch.Tensor, parts, bits: torch.Tensor, slot: torch.Tensor, seg_ptr: torch.Tensor, x0: torch.Tensor,
-              w_planes: torch.Tensor, bias: torch.Tensor, act: int, slope: float) -> torch.Tensor:
+              w_planes: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: float = 0.0,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(pooled @ W^T + bias) [B, 64] with pooled = [anch block 0 + rows * x0 | anch block l + segment sums of parts[l-1]]
     formed inside the product (desco_pool_post_bf16x6_f32): ``parts`` = the pooled layers' partial arrays (layers 1..L),
-    ``w_planes`` = split_bf16_planes(W) [3, 64, 64 (L + 1)].  Every segment must span at most three 16-row tiles."""
+    ``w_planes`` = split_bf16_planes(W) [3, 64, 64 (L + 1)].  Every segment must span at most three 16-row tiles.
+    ``out`` [B, 64] (optional): any row stride >= 64 and any alignment (a misaligned one is stored element by element)."""
     B, L = anch.shape[0], len(parts)
     assert tuple(w_planes.shape) == (3, 64, 64 * (L + 1)) and w_planes.is_contiguous() and anch.shape[1] >= 64 * (L + 1)
     assert x0.is_contiguous() and x0.numel() == 64
-    out = torch.empty((B, 64), device=anch.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((B, 64), device=anch.device, dtype=torch.float32)
+    assert tuple(out.shape) == (B, 64)
+    op, ldo = _rows(out, "out")
     ap, lda = _rows(anch, "anch")
     pa = (ctypes.c_void_p * L)(*[_dev(p_, "pool_part") for p_ in parts])
     with _Timed("gemm_split_kernel", 2.0 * B * 64 * 64 * (L + 1),
                 4.0 * B * 64 * (L + 2) + sum(256.0 * p_.shape[0] for p_ in parts)):
         _lib.check(_lib.lib().desco_pool_post_bf16x6_f32(
-            ap, lda, L, _dev(w_planes, "w_planes", torch.int16), 64, _dev(bias.contiguous(), "bias"), act, slope,
-            _dev(out, "out"), 64, B, _dev(seg_ptr, "seg_ptr", torch.int32), _dev(bits, "pool_bits", torch.int32),
+            ap, lda, L, _dev(w_planes, "w_planes", torch.int16), 64, _opt(None if bias is None else bias.contiguous(), "bias"),
+            act, slope, op, ldo, B, _dev(seg_ptr, "seg_ptr", torch.int32), _dev(bits, "pool_bits", torch.int32),
             _dev(slot, "pool_slot", torch.int32), pa, _dev(x0, "x0"), 16, _stream()), "pool_post")
     return out
 
 
 def anchor_pool_post(a: torch.Tensor, anchor_w: "F16Planes", anchor_bias: torch.Tensor, row_scale: torch.Tensor, parts,
                      bits: torch.Tensor, slot: torch.Tensor, seg_ptr: torch.Tensor, x0: torch.Tensor,
-                     w_planes: torch.Tensor, bias: torch.Tensor, act: int, slope: float) -> torch.Tensor:
+                     w_planes: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: float = 0.0,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``pool_post(gemm_f16x3(a, anchor_w, anchor_bias, act=act, slope=slope, row_scale=row_scale), ...)`` in one launch
     (desco_anchor_pool_post_f16x3_f32): the anchor rows are never written.  Bit-identical to the two calls.  ``parts`` =
     the pooled layers' partial arrays (layers 1..L, L in {2, 5, 8}); ``w_planes`` = split_bf16_planes(W0)
     [3, 64, 64 (L + 1)]; the anchor weight [64 (L + 1), k] with k = 64 L or 64 (L + 1).  Every segment must span at
-    most three 16-row tiles."""
+    most three 16-row tiles.  ``out`` [B, 64] (optional): any row stride >= 64 and any alignment."""
     B, k = a.shape[0], a.shape[1]
     L = len(parts)
     n = 64 * (L + 1)
     assert isinstance(anchor_w, F16Planes) and tuple(anchor_w.planes.shape) == (2, n, k)
     assert tuple(w_planes.shape) == (3, 64, n) and w_planes.is_contiguous()
     assert x0.is_contiguous() and x0.numel() == 64 and anchor_bias.is_contiguous() and anchor_bias.numel() == n
-    out = torch.empty((B, 64), device=a.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((B, 64), device=a.device, dtype=torch.float32)
+    assert tuple(out.shape) == (B, 64)
     if B == 0:
         return out
+    op, ldo = _rows(out, "out")
     ap, lda = _rows(a, "a")
     pa = (ctypes.c_void_p * L)(*[_dev(p_, "pool_part") for p_ in parts])
     with _Timed("anchor_pool_post_kernel", 2.0 * B * k * n + 2.0 * B * 64 * n,
@@ -611,7 +620,8 @@ def anchor_pool_post(a: torch.Tensor, anchor_w: "F16Planes", anchor_bias: torch.
         _lib.check(_lib.lib().desco_anchor_pool_post_f16x3_f32(
             ap, lda, k, _dev(anchor_w.planes, "anchor_w", torch.int16), _dev(anchor_w.scale, "anchor_scale"),
             _dev(anchor_bias, "anchor_bias"), act, slope, _dev(row_scale, "row_scale"), L,
-            _dev(w_planes, "w_planes", torch.int16), _dev(bias.contiguous(), "bias"), act, slope, _dev(out, "out"), 64, B,
+            _dev(w_planes, "w_planes", torch.int16), _opt(None if bias is None else bias.contiguous(), "bias"), act, slope,
+            op, ldo, B,
             _dev(seg_ptr, "seg_ptr", torch.int32), _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32),
             pa, _dev(x0, "x0"), 16, _stream()), "anchor_pool_post")
     return out
