@@ -272,7 +272,6 @@ extern "C" int desco_anchor_pool_post_f16x3_f32(const float* a, int64_t lda, int
   if (m == 0) return 0;
   if (m > (int64_t)(1 << 24))
     return fail(DESCO_EINVAL, "desco_anchor_pool_post_f16x3_f32: more than 2^24 segments (slot offsets are 31 bits)");
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   const int n = 64 * (num_layers + 1);
   if (m < 0 || !a || !anchor_planes || !anchor_scale || !row_scale || !post_planes || !out || !seg_ptr || !pool_bits ||
       !pool_slot || !parts || !x0 || num_layers < 1 || num_layers > 8 || n % kApBN || (k != n && k != n - 64) ||
@@ -298,13 +297,8 @@ extern "C" int desco_anchor_pool_post_f16x3_f32(const float* a, int64_t lda, int
       return fail(DESCO_EINVAL, "desco_anchor_pool_post_f16x3_f32: NULL / misaligned partial array");
     q.part[l] = parts[l - 1];
   }
-  static DeviceOnce attr_once;
-  if (!attr_once.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(anchor_pool_post_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kApLdsBytes);
-    if (e != hipSuccess) return fail((int)e, "desco_anchor_pool_post_f16x3_f32: cannot size LDS");
-    attr_once.mark();
-  }
+  if (hipError_t e = size_dynamic_lds<anchor_pool_post_kernel>((int)kApLdsBytes); e != hipSuccess)
+    return fail((int)e, "desco_anchor_pool_post_f16x3_f32: cannot size LDS");
   const int64_t blocks = (m + kApBM - 1) / kApBM;
   hipLaunchKernelGGL(anchor_pool_post_kernel, dim3((unsigned)blocks), dim3(2 * kApBM), kApLdsBytes, (hipStream_t)stream, q);
   return launch_status("desco_anchor_pool_post_f16x3_f32");

@@ -13,6 +13,8 @@ constexpr int kH = DESCO_H;
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
+using bf16x8 = __attribute__((ext_vector_type(8))) short;      // MFMA operand: 8 bf16 bit patterns
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;    // MFMA operand: 8 fp16
 
 inline int launch_status(const char* what) {
   hipError_t e = hipGetLastError();

@@ -174,13 +174,8 @@ static int launch_gemm_f16x3(const GemmF16Args& g, hipStream_t stream) {
   constexpr size_t stage_bytes = (size_t)(2 * BM * FST + 2 * BN * FST) * sizeof(short);
   constexpr size_t epi_bytes = (size_t)(BM / 32) * 32 * 32 * WN * sizeof(float);
   constexpr size_t lds_bytes = (stage_bytes > epi_bytes ? stage_bytes : epi_bytes) + BM * sizeof(float);
-  static DeviceOnce attr_once;
-  if (!attr_once.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16x3_kernel<WN, BM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "desco_gemm_f16x3_f32: cannot size LDS");
-    attr_once.mark();
-  }
+  if (hipError_t e = size_dynamic_lds<gemm_f16x3_kernel<WN, BM>>((int)lds_bytes); e != hipSuccess)
+    return fail((int)e, "desco_gemm_f16x3_f32: cannot size LDS");
   const int64_t gm = (g.m + BM - 1) / BM;
   const int ny = g.n / BN;
   const int64_t blocks = ((gm + 7) / 8) * 8 * ny;
@@ -196,7 +191,6 @@ using namespace desco;
 extern "C" int desco_row_absmax_f32(const float* a1, int64_t lda1, int k1, const float* a2, int64_t lda2, int k2,
                                    int64_t m, float* row_scale, desco_stream_t stream) {
   if (m == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (m < 0 || !a1 || !row_scale || k1 <= 0 || k1 % 4 || k2 < 0 || k2 % 4 || (k2 > 0 && !a2) || lda1 % 4 ||
       (k2 > 0 && lda2 % 4) || mis16(a1) || (k2 > 0 && mis16(a2)))
     return fail(DESCO_EINVAL, "desco_row_absmax_f32: bad argument (k % 4, 16-byte alignment)");
@@ -213,7 +207,6 @@ extern "C" int desco_gemm_f16x3_f32(const float* a1, int64_t lda1, int k1, const
                                     float* c, int64_t ldc, int64_t m, const float* row_scale,
                                     desco_stream_t stream) {
   if (m == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (m < 0 || !a1 || !w_planes || !w_scale || !row_scale || !c || k1 <= 0 || k1 % FBK || k2 < 0 || k2 % FBK ||
       n <= 0 || n % 64 || (k2 > 0 && !a2) || ns < 0 || ns > 4 || (ns > 0 && (!s || !ws)) ||
       (bias && bias_rows < 1) || lda1 % 4 || (k2 > 0 && lda2 % 4) || mis16(a1) || (k2 > 0 && mis16(a2)) ||

@@ -28,8 +28,6 @@ struct GemmF16Args {
   const float* row_scale;  // [m] bound of each row's largest |a| (desco_row_absmax_f32 or the producer of A)
 };
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
 constexpr int FBK = 32, FST = 32;              // K chunk; plane row stride in halves (64 B, no padding)
 // same swizzle as gemm_split.hip: 16-byte chunk c of plane row r sits at chunk c ^ ((r >> 3) & 3)
 __device__ __forceinline__ int gf16_chunk(const int row, const int c) { return ((c ^ (row >> 3)) & 3) << 3; }

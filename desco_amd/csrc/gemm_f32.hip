@@ -223,7 +223,6 @@ const char* dropout_check(const desco_dropout* d, int64_t num_rows, int64_t num_
 
 static const char* gemm_f32_check(const desco::GemmArgs& g) {
   using namespace desco;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (g.m < 0 || !g.a1 || !g.wt || !g.c || g.k1 <= 0 || g.k1 % BK || g.k2 < 0 || g.k2 % BK || g.n <= 0 || g.n % BN ||
       (g.k2 > 0 && !g.a2) || g.ns < 0 || g.ns > 4 || (g.ns > 0 && (!g.s || !g.ws)) || (g.bias && g.bias_rows < 1) ||
       g.lda1 % 4 || (g.k2 > 0 && g.lda2 % 4) || mis16(g.a1) || (g.k2 > 0 && mis16(g.a2)) || mis16(g.wt))
@@ -271,7 +270,6 @@ extern "C" int desco_gemm_f32(const float* a1, int64_t lda1, int k1, const float
                               float* c, int64_t ldc, int64_t m, desco_stream_t stream) {
   using namespace desco;
   if (m == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (m < 0 || !a1 || !wt || !c || k1 <= 0 || k1 % BK || k2 < 0 || k2 % BK || n <= 0 || n % BN ||
       (k2 > 0 && !a2) || ns < 0 || ns > 4 || (ns > 0 && (!s || !ws)) || (bias && bias_rows < 1) ||
       lda1 % 4 || (k2 > 0 && lda2 % 4) || mis16(a1) || (k2 > 0 && mis16(a2)) || mis16(wt))

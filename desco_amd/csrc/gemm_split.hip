@@ -58,8 +58,6 @@ struct GemmSplitArgs {
 
 __device__ __attribute__((aligned(16))) float gs_zero_row[64] = {};
 
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-
 #define GS_SPLIT(a_, b_, h_, m_, l_) split2_bf16x3(a_, b_, h_, m_, l_)
 
 constexpr int SBK = 32, SST = 32;              // SST: plane row stride in bf16 (64 B, no padding)
@@ -479,13 +477,8 @@ static int launch_gemm_split_bm(const GemmSplitArgs& g, hipStream_t stream) {
   constexpr size_t stage_bytes = (size_t)(NP * BM * SST + NP * BN * SST) * sizeof(short);
   constexpr size_t epi_bytes = (size_t)(BM / 32) * 32 * 32 * WN * sizeof(float);   // one [32][32 WN] image per wave
   constexpr size_t lds_bytes = stage_bytes > epi_bytes ? stage_bytes : epi_bytes;
-  static DeviceOnce attr_once;        // function attributes are per device
-  if (!attr_once.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<WN, NP, BM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "desco_gemm_bf16x6_f32: cannot size LDS");
-    attr_once.mark();
-  }
+  if (hipError_t e = size_dynamic_lds<gemm_split_kernel<WN, NP, BM>>((int)lds_bytes); e != hipSuccess)
+    return fail((int)e, "desco_gemm_bf16x6_f32: cannot size LDS");
   const int64_t gm = (g.m + BM - 1) / BM;
   const int ny = g.n / BN;
   const int64_t blocks = ((gm + 7) / 8) * 8 * ny;
@@ -513,7 +506,6 @@ static int gemm_planes(const char* who, int np, const float* a1, int64_t lda1, i
                        desco::DropArgs drop = desco::DropArgs{nullptr, 0u, 0u, 1.f}, int ws_rows = 1) {
   using namespace desco;
   if (m == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (m < 0 || !a1 || !w || !c || k1 <= 0 || k1 % SBK || k2 < 0 || k2 % SBK || n <= 0 ||
       n % 64 || (k2 > 0 && !a2) || ns < 0 || ns > 4 || (ns > 0 && (!s || !ws)) ||
       (bias && bias_rows < 1) || lda1 % 4 || (k2 > 0 && lda2 % 4) || mis16(a1) ||
@@ -664,7 +656,6 @@ static int gemm_planes_multi(int np, int num, const desco_gemm_desc* descs, cons
   if (num == 0) return 0;
   if (num < 0 || num > kSplitMulti || !descs || !planes)
     return fail(DESCO_EINVAL, "desco_gemm_bf16x6_multi_f32: 1..4 descriptors");
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   GemmSplitMulti q{};
   int nq = 0, blocks = 0;
   for (int i = 0; i < num; ++i) {
@@ -697,16 +688,9 @@ static int gemm_planes_multi(int np, int num, const desco_gemm_desc* descs, cons
   constexpr size_t stage_bytes = (size_t)(3 * BM * SST + 3 * BN * SST) * sizeof(short);      // (sized for three planes)
   constexpr size_t epi_bytes = (size_t)(BM / 32) * 32 * 32 * sizeof(float);
   constexpr size_t lds_bytes = stage_bytes > epi_bytes ? stage_bytes : epi_bytes;
-  static DeviceOnce attr_once;
-  if (!attr_once.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_multi_kernel<3, BM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_multi_kernel<1, BM>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "desco_gemm_bf16x6_multi_f32: cannot size LDS");
-    attr_once.mark();
-  }
+  const hipError_t e = np == 3 ? size_dynamic_lds<gemm_split_multi_kernel<3, BM>>((int)lds_bytes)
+                               : size_dynamic_lds<gemm_split_multi_kernel<1, BM>>((int)lds_bytes);
+  if (e != hipSuccess) return fail((int)e, "desco_gemm_bf16x6_multi_f32: cannot size LDS");
   if (np == 3)
     hipLaunchKernelGGL((gemm_split_multi_kernel<3, BM>), dim3((unsigned)blocks), dim3(2 * BM), lds_bytes,
                        (hipStream_t)stream, q);
@@ -728,7 +712,6 @@ extern "C" int desco_pool_post_bf16x6_f32(const float* anch, int64_t lda, int nu
   using namespace desco;
   if (m == 0) return 0;
   if (m > (int64_t)(1 << 24)) return fail(DESCO_EINVAL, "desco_pool_post_bf16x6_f32: more than 2^24 segments (slot offsets are 31 bits)");
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (m < 0 || !anch || !w_planes || !c || num_layers < 1 || num_layers > 8 || n != 64 || !seg_ptr || !pool_bits ||
       !pool_slot || !parts || !x0 || tile_rows != 16 || lda % 4 || lda < 64 * (num_layers + 1) || mis16(anch) ||
       mis16(w_planes) || mis16(x0))
@@ -743,13 +726,8 @@ extern "C" int desco_pool_post_bf16x6_f32(const float* anch, int64_t lda, int nu
   constexpr size_t stage_bytes = (size_t)(3 * BM * SST + 3 * 64 * SST) * sizeof(short);
   constexpr size_t epi_bytes = (size_t)(BM / 32) * 32 * 32 * sizeof(float);
   constexpr size_t lds_bytes = stage_bytes > epi_bytes ? stage_bytes : epi_bytes;
-  static DeviceOnce attr_once;
-  if (!attr_once.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<1, 3, BM, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "desco_pool_post_bf16x6_f32: cannot size LDS");
-    attr_once.mark();
-  }
+  if (hipError_t e = size_dynamic_lds<gemm_split_kernel<1, 3, BM, true>>((int)lds_bytes); e != hipSuccess)
+    return fail((int)e, "desco_pool_post_bf16x6_f32: cannot size LDS");
   const int64_t gm = (m + BM - 1) / BM;
   const int64_t blocks = ((gm + 7) / 8) * 8;
   if (blocks > INT32_MAX) return fail(DESCO_EINVAL, "desco_pool_post_bf16x6_f32: m too large");

@@ -159,10 +159,7 @@ __global__ __launch_bounds__(256) void affine_rows_bwd_kernel(const float* __res
   for (int k = 0; k < 8; ++k) acc[k] = 0.f;
   // sixteen rows of the class in flight per wave (round 6: one row per iteration was one memory round trip per
   // iteration -- 0.25 ms per call for 0.26 GB); rows beyond the slab re-read its last row with weight 0
-#ifndef DESCO_ARB_ROWS
-#define DESCO_ARB_ROWS 16     // (8: 0.34 ms per step for the three calls, 16: 0.29)
-#endif
-  constexpr int U = DESCO_ARB_ROWS;
+  constexpr int U = 16;         // (8: 0.34 ms per step for the three calls, 16: 0.29)
   for (int64_t i = i_beg + wave; i < i_end; i += 4 * U) {
     float d[U], cw[U];
     int64_t r[U];
@@ -241,8 +238,7 @@ extern "C" int desco_gossip_gather_f32(const float* h, const int32_t* rowptr, co
                                        int64_t num_nodes, int num_q, const float* g, float* out,
                                        desco_stream_t stream) {
   if (num_nodes == 0) return 0;
-  if (!h || !rowptr || !out || num_nodes < 0 || num_q < 1 || (reinterpret_cast<uintptr_t>(h) & 15) ||
-      (reinterpret_cast<uintptr_t>(out) & 15))
+  if (!h || !rowptr || !out || num_nodes < 0 || num_q < 1 || mis16(h) || mis16(out))
     return fail(DESCO_EINVAL, "desco_gossip_gather_f32: bad argument (h / out 16-byte aligned)");
   const int64_t blocks = (num_nodes * num_q + 15) / 16;
   if (blocks > INT32_MAX) return fail(DESCO_EINVAL, "desco_gossip_gather_f32: too many rows");

@@ -74,7 +74,6 @@ struct Args {
   unsigned grid_blocks;     // gridDim.x (set by the launcher)
 };
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
@@ -483,8 +482,6 @@ extern "C" int desco_gossip_fused_f16x3_f32(const float* scal4, const int32_t* r
                                             desco_stream_t stream) {
   using namespace gf16;
   if (num_nodes == 0) return 0;
-  auto mis16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) != 0; };
-  auto mis8 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 7) != 0; };
   if (!scal4 || !rowptr || !g1 || !p || !z || !zp || !r || !t || !u || !tp || !d1 || !wstream || !winv || !b3 || !b5 ||
       !w7 || !out || !queue || num_nodes < 0 || num_q < 1 || num_q > 65535 || mis16(scal4) || mis16(wstream) ||
       mis16(p) || mis16(z) || mis16(r) || mis16(t) || mis8(queue))
@@ -494,21 +491,10 @@ extern "C" int desco_gossip_fused_f16x3_f32(const float* scal4, const int32_t* r
   Args a{reinterpret_cast<const float4*>(scal4), rowptr, col, num_nodes, num_q, g1, p, z, zp, r, t, u, tp, d1,
          reinterpret_cast<const short*>(wstream), winv, b3, b5, w7, b7, out, tile_perm,
          reinterpret_cast<unsigned long long*>(queue)};
-  static DeviceOnce attr_once;
-  if (!attr_once.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gossip_fused_f16_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_WAVE);
-    if (e != hipSuccess) return fail((int)e, "desco_gossip_fused_f16x3_f32: cannot size LDS");
-    attr_once.mark();
-  }
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
+  if (hipError_t e = size_dynamic_lds<gossip_fused_f16_kernel>((int)LDS_WAVE); e != hipSuccess)
+    return fail((int)e, "desco_gossip_fused_f16x3_f32: cannot size LDS");
   const int64_t units = groups * ((num_q + WQ - 1) / WQ);
-  const int64_t blocks = (units + 7) / 8;
-  const unsigned grid = (unsigned)(blocks < (int64_t)cus ? blocks : (int64_t)cus);
+  const unsigned grid = persistent_grid((units + 7) / 8);
   a.grid_blocks = grid;
   hipLaunchKernelGGL(gossip_fused_f16_kernel, dim3(grid), dim3(GNT), LDS_WAVE, (hipStream_t)stream, a, groups);
   return launch_status("desco_gossip_fused_f16x3_f32");

@@ -158,8 +158,6 @@ __global__ __launch_bounds__(128) void gossip_tile_order_kernel(const int32_t* _
   perm[(int64_t)blockIdx.x * 128 + 16 * w + 2 * grp + (t & 1)] = (uint8_t)(key[t] & 0xffu);
 }
 
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-
 // element offset of (row, k) inside a [rows][64] bf16 plane with swizzled 16-byte chunks
 __device__ __forceinline__ int gf_pidx(const int row, const int k) {
   return row * 64 + ((((k >> 3) ^ (row >> 1)) & 7) << 3) + (k & 7);
@@ -187,7 +185,6 @@ __device__ __forceinline__ int gf_pidx(const int row, const int k) {
 // tile, j = node tile.  Lane (r16 = lane & 15, q4 = lane >> 4) holds, per 32-deep k step t and plane,
 // W[32 wn + 16 i + r16][32 t + 8 q4 + 0..7] and X[32 wm + 16 j + r16][32 t + 8 q4 + 0..7] (16-byte
 // fragments), and after the MFMAs D^T[feature 32 wn + 16 i + 4 q4 + e][node 32 wm + 16 j + r16].
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 #define GF_M16(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_, b_, c_, 0, 0, 0);
 // the six products (smallest terms first) of one weight tile w_ with both node tiles of x_
 #define GF_MM(c0_, c1_, w_, x_)                                       \
@@ -562,9 +559,6 @@ __global__ __launch_bounds__(GNT) void gossip_fused_kernel(GossipFusedArgs g, in
     // No barrier here: what the next item's publish overwrites is either read by the SAME thread above (srow[tid]) or was
     // last read before the barrier in front of block 8 (rp, tperm, the staging area in WB1, zp_q) or before the one above
     // (WB0: block 8); red is not written again before ten more barriers, and the ticket is read behind the next one.
-#ifdef GF_END_BARRIER
-    __syncthreads();
-#endif
   }
   if (tid == 0 && atomicAdd(g.queue + 1, 1ull) == gridDim.x - 1) {      // last block out: leave the slot clean
     g.queue[0] = 0;
@@ -598,8 +592,7 @@ extern "C" int desco_gossip_scalars_f32(const float* x, int64_t ldx, const int32
                                         const float* g0, const float* g1, float* scal4,
                                         desco_stream_t stream) {
   if (num_nodes == 0) return 0;
-  if (!x || !rowptr || !g0 || !g1 || !scal4 || num_nodes < 0 || num_q < 1 || num_q > 64 ||
-      (reinterpret_cast<uintptr_t>(scal4) & 15))
+  if (!x || !rowptr || !g0 || !g1 || !scal4 || num_nodes < 0 || num_q < 1 || num_q > 64 || mis16(scal4))
     return fail(DESCO_EINVAL, "desco_gossip_scalars_f32: bad argument (1 <= num_q <= 64)");
   const int64_t per_block = num_q <= 32 ? 8 : 4;          // (a half wave per node when the queries fit one)
   const int64_t blocks = (num_nodes + per_block - 1) / per_block;
@@ -631,8 +624,6 @@ extern "C" int desco_gossip_fused_f32(const float* scal4, const int32_t* rowptr,
                                       const float* w7, float b7, float* out, const uint8_t* tile_perm,
                                       desco_stream_t stream) {
   if (num_nodes == 0) return 0;
-  auto mis16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) != 0; };
-  auto mis8 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 7) != 0; };
   if (!scal4 || !rowptr || !g1 || !p || !z || !zp || !r || !t || !u || !tp || !d1 || !w1_planes ||
       !wp_planes || !w3_planes || !b3 || !w5_planes || !b5 || !w7 || !out || num_nodes < 0 ||
       num_q < 1 || num_q > 65535 || mis16(scal4) || mis16(w1_planes) || mis16(wp_planes) ||
@@ -653,22 +644,9 @@ extern "C" int desco_gossip_fused_f32(const float* scal4, const int32_t* rowptr,
     if (e != hipSuccess || !base) return fail((int)e, "desco_gossip_fused_f32: no work-queue symbol");
     a.queue = base + 2 * (seq.fetch_add(1) % GF_QSLOTS);
   }
-  static DeviceOnce attr_once;        // function attributes are per device
-  if (!attr_once.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gossip_fused_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)GOSSIP_LDS_BYTES);
-    if (e != hipSuccess) return fail((int)e, "desco_gossip_fused_f32: cannot size LDS");
-    attr_once.mark();
-  }
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
-  const int64_t nitems = bx * num_q;
-  const unsigned grid = (unsigned)(nitems < (int64_t)cus ? nitems : (int64_t)cus);
+  if (hipError_t e = size_dynamic_lds<gossip_fused_kernel>((int)GOSSIP_LDS_BYTES); e != hipSuccess)
+    return fail((int)e, "desco_gossip_fused_f32: cannot size LDS");
+  const unsigned grid = persistent_grid(bx * num_q);
   hipLaunchKernelGGL(gossip_fused_kernel, dim3(grid), dim3(GNT), GOSSIP_LDS_BYTES, (hipStream_t)stream,
                      a, bx);
   return launch_status("desco_gossip_fused_f32");

@@ -27,8 +27,6 @@ namespace desco {
 
 namespace {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
 constexpr int GL_ROWS = 64;                     // rows per workgroup tile
 constexpr int GL_AST = 136;                     // A image row stride in halves (128 + 8: rows 4 banks apart)
 constexpr int GL_APLANE = GL_ROWS * GL_AST;     // halves per plane
@@ -254,7 +252,6 @@ extern "C" int desco_gossip_layer_f16x3_f32(const float* h, const int32_t* rowpt
                                             const int16_t* p_planes, const float* p_scale,
                                             const int16_t* pn_planes, const float* pn_scale, float* acc, float* out,
                                             desco_stream_t stream) {
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (num_nodes < 0 || num_q < 1)
     return fail(DESCO_EINVAL, "desco_gossip_layer_f16x3_f32: bad argument (num_nodes >= 0, num_q >= 1)");
   if (num_nodes == 0) return 0;

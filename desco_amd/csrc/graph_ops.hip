@@ -651,8 +651,8 @@ extern "C" int desco_csr_gather_sum_f32(const float* x, int64_t ldx, const int32
                                         const int32_t* vcol, int64_t num_rows, int slots,
                                         float* out, desco_stream_t stream) {
   if (num_rows == 0) return 0;
-  if (!x || !vrowptr || !out || num_rows < 0 || ldx % 4 || (reinterpret_cast<uintptr_t>(x) & 15) ||
-      (reinterpret_cast<uintptr_t>(out) & 15) || !(slots == 1 || slots == 2 || slots == 4))
+  if (!x || !vrowptr || !out || num_rows < 0 || ldx % 4 || mis16(x) ||
+      mis16(out) || !(slots == 1 || slots == 2 || slots == 4))
     return fail(DESCO_EINVAL, "desco_csr_gather_sum_f32: bad argument");
   if (!vcol) return fail(DESCO_EINVAL, "desco_csr_gather_sum_f32: vcol must be readable at index 0");
   const int64_t blocks = (num_rows + 15) / 16;
@@ -675,9 +675,8 @@ extern "C" int desco_csr_gather_sum_add_f32(const float* x, int64_t ldx, const i
                                             int64_t ld_extra, float* out, int64_t ldo,
                                             desco_stream_t stream) {
   if (num_rows == 0) return 0;
-  auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
   if (!x || !rowptr || !col || !extra || !out || num_rows < 0 || ldx % 4 || ld_extra % 4 || ldo % 4 ||
-      !al16(x) || !al16(extra) || !al16(out))
+      mis16(x) || mis16(extra) || mis16(out))
     return fail(DESCO_EINVAL, "desco_csr_gather_sum_add_f32: bad argument");
   const int64_t blocks = (num_rows + 15) / 16;
   if (!grid_ok(blocks)) return fail(DESCO_EINVAL, "desco_csr_gather_sum_add_f32: too many rows");
@@ -692,11 +691,10 @@ extern "C" int desco_shmp_bwd_dx_f32(const float* d, int64_t ldd, const int32_t*
                                      const int32_t* seg_id, const float* dcanon, int64_t ld_canon,
                                      const float* relu_src, float mask_scale, float* out, desco_stream_t stream) {
   if (num_rows == 0) return 0;
-  auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
   if (!d || !t_rowptr || !t_col || !dpool || !seg_id || !out || num_rows < 0 || num_count < 0 ||
       num_count > num_rows || ldd % 4 || ld_pool % 4 ||
-      (dcanon && ld_canon % 4) || self_off_count % 4 || self_off_canon % 4 || !al16(d) || !al16(dpool) ||
-      !al16(out) || (dcanon && !al16(dcanon)) || (relu_src && !al16(relu_src)))
+      (dcanon && ld_canon % 4) || self_off_count % 4 || self_off_canon % 4 || mis16(d) || mis16(dpool) ||
+      mis16(out) || (dcanon && mis16(dcanon)) || (relu_src && mis16(relu_src)))
     return fail(DESCO_EINVAL, "desco_shmp_bwd_dx_f32: bad argument");
   const int64_t blocks = (num_rows + 15) / 16;
   if (!grid_ok(blocks)) return fail(DESCO_EINVAL, "desco_shmp_bwd_dx_f32: too many rows");
@@ -709,8 +707,7 @@ extern "C" int desco_shmp_bwd_dx_f32(const float* d, int64_t ldd, const int32_t*
 extern "C" int desco_add_rows_f32(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t num_rows,
                                   int ncols, desco_stream_t stream) {
   if (num_rows == 0) return 0;
-  auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
-  if (!dst || !src || num_rows < 0 || ncols <= 0 || ncols % 4 || ldd % 4 || lds % 4 || !al16(dst) || !al16(src))
+  if (!dst || !src || num_rows < 0 || ncols <= 0 || ncols % 4 || ldd % 4 || lds % 4 || mis16(dst) || mis16(src))
     return fail(DESCO_EINVAL, "desco_add_rows_f32: bad argument");
   const int chunks = ncols / 4;
   const int64_t blocks = (num_rows * chunks + 255) / 256;
@@ -727,9 +724,8 @@ extern "C" int desco_segment_sum_f32(const float* x, int64_t ldx, int ncols,
   if (num_seg == 0) return 0;
   if (!seg_ptr || !out || num_seg < 0 || ncols <= 0)
     return fail(DESCO_EINVAL, "desco_segment_sum_f32: bad argument");
-  auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
-  if (ncols == 64 && ldx % 4 == 0 && ldo % 4 == 0 && al16(x) && al16(out) &&
-      (!extra || (ld_extra % 4 == 0 && al16(extra)))) {
+  if (ncols == 64 && ldx % 4 == 0 && ldo % 4 == 0 && !mis16(x) && !mis16(out) &&
+      (!extra || (ld_extra % 4 == 0 && !mis16(extra)))) {
     const int64_t blocks64 = (num_seg + 15) / 16;
     if (!grid_ok(blocks64)) return fail(DESCO_EINVAL, "desco_segment_sum_f32: too many segments");
     hipLaunchKernelGGL(segment_sum64_kernel, dim3((unsigned)blocks64), dim3(256), 0,
@@ -748,9 +744,8 @@ extern "C" int desco_segment_sum_layers_f32(const float* x, int64_t ldx, int64_t
                                            const int32_t* seg_ptr, int64_t num_seg, const float* extra,
                                            int64_t ld_extra, float* out, int64_t ldo, desco_stream_t stream) {
   if (num_seg == 0 || num_layers == 0) return 0;
-  auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
   if (!x || !seg_ptr || !out || num_seg < 0 || num_layers < 0 || num_layers > 65535 || ldx % 4 || ldo % 4 ||
-      layer_stride % 4 || !al16(x) || !al16(out) || (extra && (ld_extra % 4 || !al16(extra))))
+      layer_stride % 4 || mis16(x) || mis16(out) || (extra && (ld_extra % 4 || mis16(extra))))
     return fail(DESCO_EINVAL, "desco_segment_sum_layers_f32: bad argument");
   const int64_t blocks64 = (num_seg + 15) / 16;
   if (!grid_ok(blocks64)) return fail(DESCO_EINVAL, "desco_segment_sum_layers_f32: too many segments");
@@ -764,11 +759,10 @@ extern "C" int desco_pool_reduce_f32(const float* part, const uint32_t* pool_bit
                                      const float* extra, int64_t ld_extra, float* out, int64_t ldo,
                                      int tile_rows, desco_stream_t stream) {
   if (num_seg == 0) return 0;
-  auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
   if (tile_rows != 16)
     return fail(DESCO_EINVAL, "desco_pool_reduce_f32: tile_rows must be desco_shmp_pool_tile_rows() (16)");
-  if (!part || !pool_bits || !pool_slot || !seg_ptr || !out || num_seg < 0 || ldo % 4 || !al16(part) ||
-      !al16(out) || (extra && (ld_extra % 4 || !al16(extra))))
+  if (!part || !pool_bits || !pool_slot || !seg_ptr || !out || num_seg < 0 || ldo % 4 || mis16(part) ||
+      mis16(out) || (extra && (ld_extra % 4 || mis16(extra))))
     return fail(DESCO_EINVAL, "desco_pool_reduce_f32: bad argument");
   const int64_t blocks = (num_seg + 15) / 16;
   if (!grid_ok(blocks)) return fail(DESCO_EINVAL, "desco_pool_reduce_f32: too many segments");
@@ -782,7 +776,6 @@ extern "C" int desco_pool_reduce_multi_f32(int num, const float* const* pool_par
                                            const float* const* extras, int64_t ld_extra, float* const* outs, int64_t ldo,
                                            int tile_rows, desco_stream_t stream) {
   if (num == 0 || num_seg == 0) return 0;
-  auto al16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
   if (num < 0 || num > 8 || !pool_parts || !outs || tile_rows != 16 || !pool_bits || !pool_slot ||
       !seg_ptr || num_seg < 0 || ldo % 4 || (extras && ld_extra % 4))
     return fail(DESCO_EINVAL, "desco_pool_reduce_multi_f32: bad argument (1..8 layers)");
@@ -792,7 +785,7 @@ extern "C" int desco_pool_reduce_multi_f32(int num, const float* const* pool_par
     pm.part[i] = pool_parts[j];
     pm.extra[i] = extras ? extras[j] : nullptr;
     pm.out[i] = outs[j];
-    if (!pm.part[i] || !pm.out[i] || !al16(pm.part[i]) || !al16(pm.out[i]) || (pm.extra[i] && !al16(pm.extra[i])))
+    if (!pm.part[i] || !pm.out[i] || mis16(pm.part[i]) || mis16(pm.out[i]) || (pm.extra[i] && mis16(pm.extra[i])))
       return fail(DESCO_EINVAL, "desco_pool_reduce_multi_f32: NULL or misaligned layer operand");
   }
   const int64_t blocks = (num_seg + 15) / 16;
@@ -808,7 +801,7 @@ extern "C" int desco_count_head_f32(const float* t, int64_t ldt, const float* qh
                                     int64_t num_b, int num_q, desco_stream_t stream) {
   if (num_b == 0 || num_q == 0) return 0;
   if (!t || !qh || !w2 || !out || num_b < 0 || num_q < 0 || num_q > HEAD_MAXQ || hid <= 0 ||
-      hid % 64 || hid > HEAD_MAXHID || ldt % 4 || (reinterpret_cast<uintptr_t>(t) & 15))
+      hid % 64 || hid > HEAD_MAXHID || ldt % 4 || mis16(t))
     return fail(DESCO_EINVAL, "desco_count_head_f32: bad argument (num_q <= 32, hid%64, hid <= 256)");
   int64_t blocks = (num_b + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -927,7 +920,6 @@ extern "C" int desco_degree_affine_pool_f32(const int32_t* vrowptr, int64_t num_
                                             int act, float slope, float* out, int64_t ldo, const uint32_t* pool_bits,
                                             const int32_t* pool_slot, float* pool_part, desco_stream_t stream) {
   if (num_rows == 0) return 0;
-  auto mis16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) != 0; };
   if (!vrowptr || !coef || !pool_bits || !pool_slot || !pool_part || num_rows < 0 || slots < 1 || slots > DA_MAXS ||
       (out && (ldo % 4 || mis16(out))) || mis16(coef) || mis16(pool_part))
     return fail(DESCO_EINVAL, "desco_degree_affine_pool_f32: bad argument (slots <= 4, 16-byte rows)");
@@ -947,7 +939,6 @@ extern "C" int desco_degree_affine_f32(const int32_t* vrowptr, int64_t row0, int
                                        const float* extra, int64_t ld_extra, float* out,
                                        int64_t ldo, float* row_absmax, desco_stream_t stream) {
   if (num_rows == 0) return 0;
-  auto mis16 = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) != 0; };
   if (!vrowptr || !coef || !out || row0 < 0 || num_rows < 0 || slots < 1 || slots > DA_MAXS ||
       ldo % 4 || mis16(out) || mis16(coef) || (extra && (ld_extra % 4 || mis16(extra))))
     return fail(DESCO_EINVAL, "desco_degree_affine_f32: bad argument (slots <= 4, 16-byte rows)");

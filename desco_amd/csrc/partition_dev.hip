@@ -363,14 +363,10 @@ static int part_dev_launch(bool fill, const PartDevArgs& a, int num_waves, hipSt
   if (lds > 160 * 1024)
     return fail(DESCO_EINVAL, "desco_partition_dev: largest graph does not fit the LDS workspace "
                               "(use desco_partition_build)");
-  static DeviceOnce attr_once;        // function attributes are per device
-  if (!attr_once.done()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(partition_dev_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(partition_dev_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_once.mark();
-  }
+  const hipError_t e = fill ? size_dynamic_lds<partition_dev_kernel<true>>(160 * 1024)
+                            : size_dynamic_lds<partition_dev_kernel<false>>(160 * 1024);
+  if (e != hipSuccess)
+    return fail((int)e, fill ? "desco_partition_dev_fill: cannot size LDS" : "desco_partition_dev_count: cannot size LDS");
   if (fill)
     hipLaunchKernelGGL(partition_dev_kernel<true>, dim3(blocks), dim3(256), lds, st, a);
   else

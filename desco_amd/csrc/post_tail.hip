@@ -29,8 +29,6 @@
 namespace desco {
 namespace tail {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -38,10 +36,7 @@ constexpr int D1 = 64, D2 = 256, D3 = 64;     // output widths of the three laye
 constexpr int ST64 = 72, ST256 = 264;         // LDS row strides in halves: 16-byte reads of 32 rows conflict-free
 constexpr int W1_H = 2 * D1 * ST64, W2_H = 2 * D2 * ST64, W3_H = 2 * D3 * ST256;
 constexpr int NWT = 8;                        // waves per workgroup: the count head (224 registers) ...
-#ifndef DESCO_TAIL_WAVES
-#define DESCO_TAIL_WAVES 12
-#endif
-constexpr int TNW = DESCO_TAIL_WAVES;         // ... and the post_mp tail (162 registers: three waves per SIMD)
+constexpr int TNW = 12;                       // ... and the post_mp tail (162 registers: three waves per SIMD)
 constexpr size_t TAIL_LDS = (size_t)(W1_H + W2_H + W3_H) * 2 + (size_t)(D1 + D2 + D3) * 4;
 static_assert(TAIL_LDS <= 160 * 1024, "post_mp tail: LDS budget exceeded");
 
@@ -345,10 +340,7 @@ __device__ __forceinline__ float raw_max(const float a, const float b) {
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-#ifndef DESCO_HEAD_RING
-#define DESCO_HEAD_RING 4      // (6 and 8 measured 3-5 % slower: more registers, nothing left to cover)
-#endif
-constexpr int HSTEPS = HQ * 4, HRING = DESCO_HEAD_RING;
+constexpr int HSTEPS = HQ * 4, HRING = 4;      // (a ring of 6 and 8 measured 3-5 % slower: more registers, nothing left to cover)
 template <int I>
 __device__ __forceinline__ void head_request(desco_f4& slot, const uint32_t qaddr) {
   constexpr int off = (I % HQ) * (HHID * 4) + (I / HQ) * 16;
@@ -368,19 +360,11 @@ __device__ __forceinline__ void head_steps(desco_f4 (&ring)[HRING], const uint32
     constexpr int j = I % HQ, v = I / HQ, younger = (HSTEPS - 1 - I) < (HRING - 1) ? (HSTEPS - 1 - I) : (HRING - 1);
     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[I % HRING]) : "n"(younger));
     const desco_f4 qv = ring[I % HRING];
-#if !defined(DESCO_HEAD_ADDFORM)
     // relu(t + q) = max(t, -q) + q on the NEGATED table (sum_c r[c] Qh[q, c] is a per-query constant, folded into SQ): four
-    // v_max_f32 + two v_pk_fma_f32 per quad instead of eight instructions (0.83 -> 0.70 ms per 1.2 M rows;
-    // -DDESCO_HEAD_ADDFORM keeps the add / relu / fma form: 2-4x smaller rounding error, both far inside the gates)
+    // v_max_f32 + two v_pk_fma_f32 per quad instead of eight instructions (0.83 -> 0.70 ms per 1.2 M rows; the add / relu /
+    // fma form it replaced had a 2-4x smaller rounding error, both far inside the gates)
     const desco_f2 z01 = {raw_max(t2[2 * v].x, qv.x), raw_max(t2[2 * v].y, qv.y)};
     const desco_f2 z23 = {raw_max(t2[2 * v + 1].x, qv.z), raw_max(t2[2 * v + 1].y, qv.w)};
-#else
-    desco_f2 z01 = t2[2 * v] + desco_f2{qv.x, qv.y}, z23 = t2[2 * v + 1] + desco_f2{qv.z, qv.w};
-    z01.x = fmaxf(z01.x, 0.f);
-    z01.y = fmaxf(z01.y, 0.f);
-    z23.x = fmaxf(z23.x, 0.f);
-    z23.y = fmaxf(z23.y, 0.f);
-#endif
     acc[j] = __builtin_elementwise_fma(z01, r2[2 * v], acc[j]);
     acc[j] = __builtin_elementwise_fma(z23, r2[2 * v + 1], acc[j]);
     if constexpr (I + HRING < HSTEPS) head_request<I + HRING>(ring[I % HRING], qaddr);
@@ -398,22 +382,14 @@ __global__ __launch_bounds__(NWT * 64) void count_head_emb_kernel(HeadArgs g) {
   fill_image<64, false>(Wt, g.wt, 2 * HHID, ST64, tid);
   for (int i = tid; i < HQ * HHID; i += NWT * 64) {
     const int q = i >> 8, c = i & 255;
-#if !defined(DESCO_HEAD_ADDFORM)
     QT[q * HHID + head_index(c)] = -g.qh[(int64_t)q * g.ldq + c];
-#else
-    QT[q * HHID + head_index(c)] = g.qh[(int64_t)q * g.ldq + c];
-#endif
   }
   for (int i = tid; i < HHID; i += NWT * 64) R[head_index(i)] = (1.f - g.slope) * g.w2[i];
   const float b2 = g.b2_dev ? *g.b2_dev : g.b2;
   if (tid < HQ) {
     float sdot = 0.f;
     for (int c = 0; c < HHID; ++c) sdot = fmaf(g.w2[c], g.qh[(int64_t)tid * g.ldq + c], sdot);
-#if !defined(DESCO_HEAD_ADDFORM)
     SQ[tid] = sdot + b2;            // slope (w2.Qh) + (1 - slope) (w2.Qh)
-#else
-    SQ[tid] = fmaf(g.slope, sdot, b2);
-#endif
   }
   const float iwt = g.st[1];
   __syncthreads();
@@ -529,26 +505,16 @@ extern "C" int desco_post_mp_tail_f16x3_f32(const float* x, int64_t ldx, int64_t
                                             const float* w3_scale, const float* b3, float* out, int64_t ldo,
                                             desco_stream_t stream) {
   if (m < 0 || !x || !w1_planes || !w1_scale || !w2_planes || !w2_scale || !w3_planes || !w3_scale || !out ||
-      ldx < 64 || ldx % 4 || ldo < 64 || ldo % 4 || ((uintptr_t)x & 15) || ((uintptr_t)out & 15) ||
-      ((uintptr_t)w1_planes & 7) || ((uintptr_t)w2_planes & 7) || ((uintptr_t)w3_planes & 7))
+      ldx < 64 || ldx % 4 || ldo < 64 || ldo % 4 || mis16(x) || mis16(out) ||
+      mis8(w1_planes) || mis8(w2_planes) || mis8(w3_planes))
     return fail(DESCO_EINVAL, "desco_post_mp_tail_f16x3_f32: bad argument");
   if (m == 0) return 0;
   tail::TailArgs g{x, ldx, m, reinterpret_cast<const short*>(w1_planes), reinterpret_cast<const short*>(w2_planes),
                    reinterpret_cast<const short*>(w3_planes), w1_scale, w2_scale, w3_scale, b1, b2, b3, out, ldo};
-  static DeviceOnce attr_once;
-  if (!attr_once.done()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tail::post_tail_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_once.mark();
-  }
+  if (hipError_t e = size_dynamic_lds<tail::post_tail_kernel>(160 * 1024); e != hipSuccess)
+    return fail((int)e, "desco_post_mp_tail_f16x3_f32: cannot size LDS");
   const int64_t tiles = (m + 31) / 32;
-  const int64_t want = (tiles + tail::TNW - 1) / tail::TNW;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  const unsigned grid = (unsigned)(want < cus ? want : cus);
+  const unsigned grid = persistent_grid((tiles + tail::TNW - 1) / tail::TNW);
   g.grid = grid;
   hipLaunchKernelGGL(tail::post_tail_kernel, dim3(grid), dim3(tail::TNW * 64), tail::TAIL_LDS, (hipStream_t)stream, g);
   return launch_status("desco_post_mp_tail_f16x3_f32");
@@ -559,27 +525,17 @@ extern "C" int desco_count_head_emb_f16x3_f32(const float* emb, int64_t lde, int
                                               const float* w2, float b2, const float* b2_dev, float slope,
                                               int exp2_minus_1, float* out, int64_t ldo, int num_q,
                                               desco_stream_t stream) {
-  if (m < 0 || !emb || !wt_planes || !wt_scale || !qh || !w2 || !out || lde < 64 || lde % 4 || ((uintptr_t)emb & 15) ||
-      ((uintptr_t)wt_planes & 7) || hid != tail::HHID || num_q != tail::HQ || ldq < hid || ldo < num_q ||
+  if (m < 0 || !emb || !wt_planes || !wt_scale || !qh || !w2 || !out || lde < 64 || lde % 4 || mis16(emb) ||
+      mis8(wt_planes) || hid != tail::HHID || num_q != tail::HQ || ldq < hid || ldo < num_q ||
       !(slope < 1.f))
     return fail(DESCO_EINVAL, "desco_count_head_emb_f16x3_f32: bad argument (hid must be 256, num_q 29)");
   if (m == 0) return 0;
   tail::HeadArgs g{emb, lde, m, reinterpret_cast<const short*>(wt_planes), wt_scale, qh, ldq, w2, b2, b2_dev, slope,
                    exp2_minus_1, out, ldo};
-  static DeviceOnce attr_once;
-  if (!attr_once.done()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tail::count_head_emb_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_once.mark();
-  }
+  if (hipError_t e = size_dynamic_lds<tail::count_head_emb_kernel>(160 * 1024); e != hipSuccess)
+    return fail((int)e, "desco_count_head_emb_f16x3_f32: cannot size LDS");
   const int64_t tiles = (m + 31) / 32;
-  const int64_t want = (tiles + tail::NWT - 1) / tail::NWT;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  const unsigned grid = (unsigned)(want < cus ? want : cus);
+  const unsigned grid = persistent_grid((tiles + tail::NWT - 1) / tail::NWT);
   g.grid = grid;
   hipLaunchKernelGGL(tail::count_head_emb_kernel, dim3(grid), dim3(tail::NWT * 64), tail::HEAD_LDS, (hipStream_t)stream, g);
   return launch_status("desco_count_head_emb_f16x3_f32");

@@ -2,6 +2,7 @@
 // bf16x6 and f16x3 split forms, 16-row wave tiles).
 #pragma once
 #include <stdint.h>
+#include "common_host.hpp"
 
 namespace desco {
 
@@ -49,7 +50,6 @@ struct ShmpArgs {
 // The argument checks both forms share: operands present and 16-byte aligned (float4 loads and stores), slot counts
 // within S <= MAXS, out / out2 not aliasing x.  Each form adds its own (slots_mfma bound, out, pooling, ...).
 inline bool shmp_args_ok(const ShmpArgs& g, const void* weights) {
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   return g.x && (g.vrowptr || g.S == 0) && weights && g.row0 >= 0 && g.num_rows >= 0 && g.sm >= 0 && g.st >= 0 &&
          g.st <= 2 && g.sm + g.st <= g.S && g.S <= MAXS && !(g.S == 0 && (g.sm || g.st)) && (g.st == 0 || g.ytab) &&
          g.ldx % 4 == 0 && (g.st == 0 || g.ldy % 4 == 0) && !mis16(g.x) && !mis16(weights) &&

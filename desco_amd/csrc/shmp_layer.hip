@@ -61,9 +61,6 @@ static_assert(A_FLOATS >= WR * AH, "the fp32 image must fit in the plane region"
 // absent sources of a batched gather step read this row instead of being predicated away
 __device__ __attribute__((aligned(16))) float shmp_zero_row[64] = {};
 
-
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-
 __device__ __forceinline__ void f4add(float4& a, const float4 b) {
   a.x += b.x;
   a.y += b.y;
@@ -71,46 +68,10 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
   a.w += b.w;
 }
 
-// ---- gather machinery (macros: every temporary is a named register) ----------------
-// They use the enclosing scope's rp, ec, ebase, grow0, nr, xb, yb, zrow, g, S, g8, l8 and the
-// registers lo*/hi* (sums), u*/w* (loads in flight), c*/n* (cursors).
-#define DESCO_CUR(it_, slot_)                              \
-  {                                                        \
-    const int v_ = ((it_) * 8 + g8) * S + (slot_);         \
-    c##it_ = rp[v_] - ebase;                               \
-    n##it_ = rp[v_ + 1] - ebase;                           \
-  }
-#define DESCO_CURS(slot_) DESCO_CUR(0, slot_) DESCO_CUR(1, slot_) DESCO_CUR(2, slot_) DESCO_CUR(3, slot_)
-// two sources of row it_ (staged ids only: e < WCAP), unconditional loads
-#define DESCO_ISSUE2(it_, base_, ld_)                                                 \
-  {                                                                                   \
-    const int m_ = n##it_ < WCAP ? n##it_ : WCAP;                                     \
-    const bool k0_ = c##it_ < m_, k1_ = c##it_ + 1 < m_;                              \
-    const int i0_ = ec[k0_ ? c##it_ : 0], i1_ = ec[k1_ ? c##it_ + 1 : 0];             \
-    const float* p0_ = k0_ ? (base_) + (int64_t)i0_ * (ld_) : zrow;                   \
-    const float* p1_ = k1_ ? (base_) + (int64_t)i1_ * (ld_) : zrow;                   \
-    u##it_##0 = *reinterpret_cast<const float4*>(p0_);                                \
-    u##it_##1 = *reinterpret_cast<const float4*>(p0_ + 32);                           \
-    w##it_##0 = *reinterpret_cast<const float4*>(p1_);                                \
-    w##it_##1 = *reinterpret_cast<const float4*>(p1_ + 32);                           \
-    c##it_ += (k0_ ? 1 : 0) + (k1_ ? 1 : 0);                                          \
-  }
-#define DESCO_CONSUME2(it_)                                                           \
-  {                                                                                   \
-    f4add(lo##it_, u##it_##0);                                                        \
-    f4add(hi##it_, u##it_##1);                                                        \
-    f4add(lo##it_, w##it_##0);                                                        \
-    f4add(hi##it_, w##it_##1);                                                        \
-  }
-#define DESCO_ZERO_SUMS()                                   \
-  {                                                         \
-    lo0 = make_float4(0.f, 0.f, 0.f, 0.f);                  \
-    lo1 = lo0; lo2 = lo0; lo3 = lo0;                        \
-    hi0 = lo0; hi1 = lo0; hi2 = lo0; hi3 = lo0;             \
-  }
-#define DESCO_ANY_STAGED()                                                                    \
-  __any((c0 < (n0 < WCAP ? n0 : WCAP)) | (c1 < (n1 < WCAP ? n1 : WCAP)) |                     \
-        (c2 < (n2 < WCAP ? n2 : WCAP)) | (c3 < (n3 < WCAP ? n3 : WCAP)))
+// ---- gather machinery: shmp_gather.hpp, over the rows it = 0..3 of a lane group; what differs from the 16-row
+//      kernel follows here ----------------------------------------------------------------------------------
+#define DESCO_ROWS(M, ...) M(0, ##__VA_ARGS__) M(1, ##__VA_ARGS__) M(2, ##__VA_ARGS__) M(3, ##__VA_ARGS__)
+#include "shmp_gather.hpp"
 // the row itself: rows beyond nr re-read the wave's last valid row (never stored)
 #define DESCO_ISSUE_SELF(it_)                                                                  \
   {                                                                                            \
@@ -119,13 +80,7 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
     u##it_##0 = *reinterpret_cast<const float4*>(p_);                                          \
     u##it_##1 = *reinterpret_cast<const float4*>(p_ + 32);                                     \
   }
-// table pseudo block: the first source of table slot 0 (-> u) and of table slot 1 (-> w) of row it_
-#define DESCO_TAB_CUR(it_)                                                                  \
-  const int v_ = ((it_) * 8 + g8) * S + g.sm;                                               \
-  const int ca_ = rp[v_] - ebase, na_ = rp[v_ + 1] - ebase;                                 \
-  const int nb_ = ST > 1 ? rp[v_ + 2] - ebase : na_;                                        \
-  const bool k0_ = ca_ < (na_ < WCAP ? na_ : WCAP);                                         \
-  const bool k1_ = ST > 1 && na_ < (nb_ < WCAP ? nb_ : WCAP);
+// first step of the table pseudo block (cursors: DESCO_TAB_CUR)
 #define DESCO_ISSUE_TAB(it_)                                                                \
   {                                                                                         \
     DESCO_TAB_CUR(it_)                                                                      \
@@ -154,86 +109,6 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
     d##it_ = na_ + (k1_ ? 1 : 0);                                                           \
     m##it_ = nb_;                                                                           \
   }
-// heavy rows (hub / canonical rows of dense neighborhoods, or ids beyond the staged WCAP): the
-// whole wave cooperates on one row at a time -- lane group k takes sources c+k, c+k+8, ... and
-// the 8 partial sums are folded with three xor-shuffles (lanes with equal l8 hold the same columns)
-#define DESCO_COOP(it_, base_, ld_)                                                       \
-  {                                                                                       \
-    unsigned long long m_ = __ballot(c##it_ < n##it_);                                    \
-    while (m_) {                                                                          \
-      const int sl_ = __builtin_ctzll(m_);                                                \
-      const int og_ = sl_ >> 3;                                                           \
-      const int cc_ = __shfl(c##it_, sl_, 64), nn_ = __shfl(n##it_, sl_, 64);             \
-      float4 p_ = make_float4(0.f, 0.f, 0.f, 0.f), q_ = p_;                               \
-      for (int e_ = cc_ + g8; e_ < nn_; e_ += 8) {                                        \
-        const int64_t j_ = e_ < WCAP ? ec[e_] : g.vcol[ebase + e_];                       \
-        const float* s_ = (base_) + j_ * (ld_);                                           \
-        const float4 v0_ = *reinterpret_cast<const float4*>(s_);                          \
-        const float4 v1_ = *reinterpret_cast<const float4*>(s_ + 32);                     \
-        f4add(p_, v0_);                                                                   \
-        f4add(q_, v1_);                                                                   \
-      }                                                                                   \
-      _Pragma("unroll") for (int o_ = 8; o_ < 64; o_ <<= 1) {                             \
-        p_.x += __shfl_xor(p_.x, o_, 64);                                                 \
-        p_.y += __shfl_xor(p_.y, o_, 64);                                                 \
-        p_.z += __shfl_xor(p_.z, o_, 64);                                                 \
-        p_.w += __shfl_xor(p_.w, o_, 64);                                                 \
-        q_.x += __shfl_xor(q_.x, o_, 64);                                                 \
-        q_.y += __shfl_xor(q_.y, o_, 64);                                                 \
-        q_.z += __shfl_xor(q_.z, o_, 64);                                                 \
-        q_.w += __shfl_xor(q_.w, o_, 64);                                                 \
-      }                                                                                   \
-      if (g8 == og_) {                                                                    \
-        f4add(lo##it_, p_);                                                               \
-        f4add(hi##it_, q_);                                                               \
-        c##it_ = n##it_;                                                                  \
-      }                                                                                   \
-      m_ &= ~(0xffULL << (og_ * 8));                                                      \
-    }                                                                                     \
-  }
-// finish a gathered block whose first step is already in flight: consume it, up to EXTRA_STEPS more
-// batched steps (two sources per row each: all four rows of a lane group advance together), then
-// the cooperative path for rows that are heavier still (one row at a time, the whole wave on it)
-#define DESCO_FINISH(base_, ld_)                                                           \
-  {                                                                                        \
-    DESCO_CONSUME2(0) DESCO_CONSUME2(1) DESCO_CONSUME2(2) DESCO_CONSUME2(3)                \
-    for (int st_ = 0; st_ < EXTRA_STEPS && DESCO_ANY_STAGED(); ++st_) {                    \
-      DESCO_ISSUE2(0, base_, ld_) DESCO_ISSUE2(1, base_, ld_)                              \
-      DESCO_ISSUE2(2, base_, ld_) DESCO_ISSUE2(3, base_, ld_)                              \
-      DESCO_CONSUME2(0) DESCO_CONSUME2(1) DESCO_CONSUME2(2) DESCO_CONSUME2(3)              \
-    }                                                                                      \
-    if (__any((c0 < n0) | (c1 < n1) | (c2 < n2) | (c3 < n3))) {                            \
-      DESCO_COOP(0, base_, ld_) DESCO_COOP(1, base_, ld_) DESCO_COOP(2, base_, ld_)        \
-      DESCO_COOP(3, base_, ld_)                                                            \
-    }                                                                                      \
-  }
-// first step of block b_ (cursors + loads); nothing waits on the loads here
-#define DESCO_ISSUE_BLOCK(b_)                                                              \
-  {                                                                                        \
-    if ((b_) < KB - 1) {                                                                   \
-      DESCO_CURS(b_)                                                                       \
-      DESCO_ISSUE2(0, xb, LDX) DESCO_ISSUE2(1, xb, LDX)                                \
-      DESCO_ISSUE2(2, xb, LDX) DESCO_ISSUE2(3, xb, LDX)                                \
-    } else if ((b_) == KB - 1) {                                                           \
-      DESCO_ISSUE_SELF(0) DESCO_ISSUE_SELF(1) DESCO_ISSUE_SELF(2) DESCO_ISSUE_SELF(3)      \
-    } else {                                                                               \
-      DESCO_ISSUE_TAB(0) DESCO_ISSUE_TAB(1) DESCO_ISSUE_TAB(2) DESCO_ISSUE_TAB(3)          \
-    }                                                                                      \
-  }
-// bit s of `live`: relation slot s (an MFMA slot) has at least one source among the wave's 32 rows
-#define DESCO_SLOT_LIVE(s_)                                                                \
-  (__any((rp[(0 * 8 + g8) * S + (s_) + 1] > rp[(0 * 8 + g8) * S + (s_)]) |                  \
-         (rp[(1 * 8 + g8) * S + (s_) + 1] > rp[(1 * 8 + g8) * S + (s_)]) |                  \
-         (rp[(2 * 8 + g8) * S + (s_) + 1] > rp[(2 * 8 + g8) * S + (s_)]) |                  \
-         (rp[(3 * 8 + g8) * S + (s_) + 1] > rp[(3 * 8 + g8) * S + (s_)]))                   \
-       ? 1 << (s_) : 0)
-#define DESCO_TILE_LIVE()                                        \
-  {                                                              \
-    live = 0;                                                    \
-    if (KB - 1 > 0) live |= DESCO_SLOT_LIVE(0);                  \
-    if (KB - 1 > 1) live |= DESCO_SLOT_LIVE(1);                  \
-    if (KB - 1 > 2) live |= DESCO_SLOT_LIVE(2);                  \
-  }
 // first step of the first LIVE block after block a_ (a_ = -1: of the tile); dead slots are left
 // out of the software pipeline altogether, so the block behind one is not issued late.  The slot
 // index is a wave-uniform runtime value here (one copy of the gather issue code per site).
@@ -246,10 +121,9 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
       if ((a_) + 1 < KB - 1 && ((live >> ((a_) + 1)) & 1)) nb_ = (a_) + 1;                  \
       if (nb_ < KB - 1) {                                                                  \
         DESCO_CURS(nb_)                                                                    \
-        DESCO_ISSUE2(0, xb, LDX) DESCO_ISSUE2(1, xb, LDX)                                  \
-        DESCO_ISSUE2(2, xb, LDX) DESCO_ISSUE2(3, xb, LDX)                                  \
+        DESCO_ROWS(DESCO_ISSUE2, xb, LDX)                                                  \
       } else {                                                                             \
-        DESCO_ISSUE_SELF(0) DESCO_ISSUE_SELF(1) DESCO_ISSUE_SELF(2) DESCO_ISSUE_SELF(3)    \
+        DESCO_ROWS(DESCO_ISSUE_SELF)                                                       \
       }                                                                                    \
     } else if ((a_) + 1 < NB) {                                                            \
       DESCO_ISSUE_BLOCK((a_) + 1)                                                          \
@@ -353,23 +227,9 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer_f32_kernel(ShmpArgs g) {
   const float* zrow = shmp_zero_row + 4 * l8;
   (void)yb;
 
-  // ---- this wave's first tile ---------------------------------------------------------------
-  // XCD-aware tile order: blocks b, b+8, b+16, ... share an XCD (round-robin dispatch) and its 4 MB L2,
-  // so a neighborhood's rows -- the sources of all its tiles -- should be gathered by ONE XCD.  Measured
-  // (profiles/r2_f_ab_xcd_order.log): +0.5 % on Syn_1827 / MSRC+IMDB shapes, 0 on COX2 shapes (the
-  // gathers are not what bounds the kernel); contiguous eighths per XCD were 8 % SLOWER on Syn shapes
-  // (the dataset is ordered by graph size: the XCD with the dense end finishes last).  Speed only: any
-  // block -> XCD placement gives the same result.
-  int64_t tile, tend = ntiles;
+  // ---- this wave's first tile (XCD-aware order: shmp_gather.hpp) --------------------------------
+  int64_t tile = xcd_first_tile(), tend = ntiles;
   int tstride = gridDim.x;
-  if ((gridDim.x & 7) == 0) {
-    // chunks of (grid / 8) consecutive tiles go round robin over the XCDs: XCD x works on the 32
-    // neighbouring tiles of chunk 8 j + x in sweep j (locality), heavy and light regions of the dataset
-    // are spread over all XCDs (balance)
-    tile = (int64_t)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  } else {
-    tile = blockIdx.x;
-  }
   int64_t w0 = tile * (NW * WR) + wave * WR;               // first row of this wave (relative)
   if (tile >= tend || w0 >= g.num_rows) return;            // no barrier below: idle waves may leave
   int nr = (int)((g.num_rows - w0) < WR ? (g.num_rows - w0) : WR);
@@ -640,57 +500,29 @@ __global__ __launch_bounds__(NW * 64) void linear64_kernel(Lin64Args g) {
 #undef DESCO_LIN_LOAD
 }
 
-#undef DESCO_CUR
-#undef DESCO_CURS
-#undef DESCO_ISSUE2
-#undef DESCO_CONSUME2
-#undef DESCO_ZERO_SUMS
-#undef DESCO_ANY_STAGED
-#undef DESCO_ISSUE_SELF
-#undef DESCO_TAB_CUR
-#undef DESCO_ISSUE_TAB
-#undef DESCO_CONSUME_TAB
-#undef DESCO_COOP
-#undef DESCO_FINISH
-#undef DESCO_ISSUE_BLOCK
-#undef DESCO_ISSUE_AFTER
-#undef DESCO_TILE_LIVE
-#undef DESCO_SLOT_LIVE
-#undef DESCO_PUT_F32
-#undef DESCO_PUT_X6
-#undef DESCO_MFMA_HALF_F32
-#undef DESCO_MFMA_HALF_X6
-#undef DESCO_TAB_HALF
-
 template <int KB, int ST, bool LD64>
-static void shmp_launch_one(const ShmpArgs& g, unsigned grid, hipStream_t st) {
+static hipError_t shmp_launch_one(const ShmpArgs& g, unsigned grid, hipStream_t st) {
   constexpr size_t shmem = sizeof(float) * ((size_t)KB * 64 * 64 + (size_t)NW * WAVE_LDS);
   static_assert(shmem <= 160 * 1024, "SHMP layer: LDS budget exceeded");
-  static DeviceOnce attr_once;        // function attributes are per device
-  if (!attr_once.done()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shmp_layer_f32_kernel<KB, ST, LD64>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_once.mark();
-  }
-  hipLaunchKernelGGL((shmp_layer_f32_kernel<KB, ST, LD64>), dim3(grid), dim3(NW * 64), shmem, st, g);
+  const hipError_t e = size_dynamic_lds<shmp_layer_f32_kernel<KB, ST, LD64>>(160 * 1024);
+  if (e == hipSuccess)
+    hipLaunchKernelGGL((shmp_layer_f32_kernel<KB, ST, LD64>), dim3(grid), dim3(NW * 64), shmem, st, g);
+  return e;
 }
 
 template <int KB>
-static void shmp_launch_st(const ShmpArgs& g, unsigned grid, hipStream_t st) {
+static hipError_t shmp_launch_st(const ShmpArgs& g, unsigned grid, hipStream_t st) {
   const bool ld64 = g.ldx == 64 && (g.st == 0 || g.ldy == 64 * g.st);
-#define DESCO_ONE(ST_)                                         \
-  if (ld64)                                                    \
-    shmp_launch_one<KB, ST_, true>(g, grid, st);               \
-  else                                                         \
-    shmp_launch_one<KB, ST_, false>(g, grid, st);
+#define DESCO_ONE(ST_) \
+  return ld64 ? shmp_launch_one<KB, ST_, true>(g, grid, st) : shmp_launch_one<KB, ST_, false>(g, grid, st);
   switch (g.st) {
-    case 0: DESCO_ONE(0) break;
-    case 1: DESCO_ONE(1) break;
+    case 0: DESCO_ONE(0)
+    case 1: DESCO_ONE(1)
     default:
       if constexpr (KB <= 3) {           // sm + st <= 4 slots: four weight blocks leave room for one table slot
         DESCO_ONE(2)
       }
-      break;
+      return hipSuccess;
   }
 #undef DESCO_ONE
 }
@@ -727,21 +559,16 @@ extern "C" int desco_shmp_layer_f32(const float* x, int64_t ldx, const int32_t* 
   g.act = DESCO_ACT_RELU;
   if (!shmp_args_ok(g, wt) || slots_mfma > 3 || !out)
     return fail(DESCO_EINVAL, "desco_shmp_layer_f32: bad argument (slots_mfma <= 3, slots_table <= 2)");
-  const int64_t ntiles = (num_rows + NW * WR - 1) / (NW * WR);
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
-  const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
+  const unsigned grid = persistent_grid((num_rows + NW * WR - 1) / (NW * WR));
   hipStream_t st = (hipStream_t)stream;
+  hipError_t e;
   switch (slots_mfma) {
-    case 0: shmp_launch_st<1>(g, grid, st); break;
-    case 1: shmp_launch_st<2>(g, grid, st); break;
-    case 2: shmp_launch_st<3>(g, grid, st); break;
-    default: shmp_launch_st<4>(g, grid, st); break;
+    case 0: e = shmp_launch_st<1>(g, grid, st); break;
+    case 1: e = shmp_launch_st<2>(g, grid, st); break;
+    case 2: e = shmp_launch_st<3>(g, grid, st); break;
+    default: e = shmp_launch_st<4>(g, grid, st); break;
   }
+  if (e != hipSuccess) return fail((int)e, "desco_shmp_layer_f32: cannot size LDS");
   return launch_status("desco_shmp_layer_f32");
 }
 
@@ -753,26 +580,13 @@ extern "C" int desco_linear64_bf16x6_f32(const float* x, int64_t ldx, const int1
                                          desco_stream_t stream) {
   using namespace desco;
   if (num_rows == 0 || num_blocks == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (!x || !w_planes || !out || num_rows < 0 || num_blocks < 0 || ldx % 4 || mis16(x) ||
       mis16(w_planes) || x == out || mis16(out) || ldo % 4)
     return fail(DESCO_EINVAL, "desco_linear64_bf16x6_f32: bad argument");
-  const int64_t ntiles = (num_rows + NW * WR - 1) / (NW * WR);
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
-  const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
-  static DeviceOnce attr_once;        // function attributes are per device
-  if (!attr_once.done()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(linear64_kernel<1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(linear64_kernel<2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_once.mark();
-  }
+  const unsigned grid = persistent_grid((num_rows + NW * WR - 1) / (NW * WR));
+  hipError_t e = size_dynamic_lds<linear64_kernel<1>>(160 * 1024);
+  if (e == hipSuccess) e = size_dynamic_lds<linear64_kernel<2>>(160 * 1024);
+  if (e != hipSuccess) return fail((int)e, "desco_linear64_bf16x6_f32: cannot size LDS");
   constexpr size_t wave_bytes = sizeof(float) * (size_t)NW * A_FLOATS;
   for (int j = 0; j < num_blocks;) {
     const int nj = num_blocks - j >= 2 ? 2 : 1;

@@ -41,14 +41,8 @@ constexpr int RPN = WR * MAXS + 2;
 //  is then summed two at a time instead of by the cooperative path's eight partial sums, and which rows of a tile lie
 //  beyond the WCAP staged ids depends on the tile, so the 2-rank-vs-1-rank deviation of the un-chunked pipeline rose
 //  from 5e-5 to 1.05e-4 of 1 + |count|, past its 1e-4 gate (tests/test_multirank_gpu.py))
-#ifndef SHMP16_EXTRA_STEPS
-#define SHMP16_EXTRA_STEPS 9
-#endif
-#ifndef SHMP16_WCAP
-#define SHMP16_WCAP 200
-#endif
-constexpr int EXTRA_STEPS = SHMP16_EXTRA_STEPS; // batched 2-source steps after the prefetched one (<= 20 sources per row)
-constexpr int WCAP = SHMP16_WCAP;     // source ids staged per wave and buffer (longer slices fall back to global)
+constexpr int EXTRA_STEPS = 9;  // batched 2-source steps after the prefetched one (<= 20 sources per row)
+constexpr int WCAP = 200;       // source ids staged per wave and buffer (longer slices fall back to global)
 constexpr int A_FLOATS = 3 * WR * APS / 2;               // A region per wave: max(16*36, 3*16*32/2) floats (bf16x6 form)
 constexpr int WAVE_LDS = A_FLOATS + 2 * RPN + 2 * WCAP;  // floats per wave
 static_assert(A_FLOATS >= WR * AH, "the fp32 image must fit in the plane region");
@@ -60,10 +54,7 @@ static_assert(A_FLOATS_F16 >= 2 * WR * APS / 2, "the fp16 planes must fit in the
 // absent sources of a batched gather step read this row instead of being predicated away
 __device__ __attribute__((aligned(16))) float shmp16_zero_row[64] = {};
 
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-
 __device__ __forceinline__ void f4add(float4& a, const float4 b) {
-#if !defined(SHMP16_F4ADD_PACKED)
   // four plain adds: left to itself hipcc pairs them into two v_pk_add_f32, which cost more issue time than the four
   // (tu_no_packed_f32_begin.hpp; the whole file without packed selection spills).  Same-box A/B
   // (profiles/r6_aq_ab_f4add_scalar.log): count-row launch 6.45 -> 6.32 ms on Syn_1827 shapes (many gather steps per
@@ -72,12 +63,6 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
   asm("v_add_f32 %0, %0, %1" : "+v"(a.y) : "v"(b.y));
   asm("v_add_f32 %0, %0, %1" : "+v"(a.z) : "v"(b.z));
   asm("v_add_f32 %0, %0, %1" : "+v"(a.w) : "v"(b.w));
-#else
-  a.x += b.x;
-  a.y += b.y;
-  a.z += b.z;
-  a.w += b.w;
-#endif
 }
 
 // 4 bytes per lane from global straight into LDS: lane i's dword lands at dst_[i] (dst_ wave-uniform).
@@ -86,47 +71,14 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
 #define DESCO_DMA4(src_, dst_)                                                                 \
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_),      \
                                    (__attribute__((address_space(3))) void*)(dst_), 4, 0, 0)
-// ---- gather machinery (macros: every temporary is a named register) ----------------
-// They use the enclosing scope's rp, ec, ebase, grow0, nr, xb, yb, zrow, g, S, g8, l8 and the
-// registers lo*/hi* (sums), u*/w* (loads in flight), c*/n* (cursors).
-#define DESCO_CUR(it_, slot_)                              \
-  {                                                        \
-    const int v_ = ((it_) * 8 + g8) * S + (slot_);         \
-    c##it_ = rp[v_] - ebase;                               \
-    n##it_ = rp[v_ + 1] - ebase;                           \
-  }
-#define DESCO_CURS(slot_) DESCO_CUR(0, slot_) DESCO_CUR(1, slot_)
-// two sources of row it_ (staged ids only: e < WCAP), unconditional loads
-#define DESCO_ISSUE2(it_, base_, ld_)                                                 \
-  {                                                                                   \
-    const int m_ = n##it_ < WCAP ? n##it_ : WCAP;                                     \
-    const bool k0_ = c##it_ < m_, k1_ = c##it_ + 1 < m_;                              \
-    const int i0_ = ec[k0_ ? c##it_ : 0], i1_ = ec[k1_ ? c##it_ + 1 : 0];             \
-    const float* p0_ = k0_ ? (base_) + (int64_t)i0_ * (ld_) : zrow;                   \
-    const float* p1_ = k1_ ? (base_) + (int64_t)i1_ * (ld_) : zrow;                   \
-    u##it_##0 = *reinterpret_cast<const float4*>(p0_);                                \
-    u##it_##1 = *reinterpret_cast<const float4*>(p0_ + 32);                           \
-    w##it_##0 = *reinterpret_cast<const float4*>(p1_);                                \
-    w##it_##1 = *reinterpret_cast<const float4*>(p1_ + 32);                           \
-    c##it_ += (k0_ ? 1 : 0) + (k1_ ? 1 : 0);                                          \
-  }
-#define DESCO_CONSUME2(it_)                                                           \
-  {                                                                                   \
-    f4add(lo##it_, u##it_##0);                                                        \
-    f4add(hi##it_, u##it_##1);                                                        \
-    f4add(lo##it_, w##it_##0);                                                        \
-    f4add(hi##it_, w##it_##1);                                                        \
-  }
-#define DESCO_ZERO_SUMS()                                   \
-  {                                                         \
-    lo0 = make_float4(0.f, 0.f, 0.f, 0.f);                  \
-    lo1 = lo0;                                              \
-    hi0 = lo0; hi1 = lo0;                                   \
-  }
-#define DESCO_ANY_STAGED()                                                                    \
-  __any((c0 < (n0 < WCAP ? n0 : WCAP)) | (c1 < (n1 < WCAP ? n1 : WCAP)))
+// ---- gather machinery: shmp_gather.hpp, over the rows it = 0, 1 of a lane group; what differs from the 32-row
+//      kernel follows here ----------------------------------------------------------------------------------
+#define DESCO_ROWS(M, ...) M(0, ##__VA_ARGS__) M(1, ##__VA_ARGS__)
+#include "shmp_gather.hpp"
 // the row itself: rows beyond nr re-read the wave's last valid row (never stored)
-// (round 6, SHMP16_SELF_EARLY: into registers of their own -- s -- at the tile top, next to the first relation step)
+// (into registers of their own -- s -- at the tile top, next to the first relation step: DESCO_ISSUE_AFTER.  Requesting
+//  them under the MFMAs of the last relation block, into u, was measured and lost; such a variant is a patched copy of
+//  this file under tools/debug, never a build switch here)
 #define DESCO_ISSUE_SELF(it_)                                                                  \
   {                                                                                            \
     const int r_ = (it_) * 8 + g8;                                                             \
@@ -149,21 +101,14 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
       }                                                                                        \
       a0_.x = fmaxf(a0_.x, 0.f); a0_.y = fmaxf(a0_.y, 0.f); a0_.z = fmaxf(a0_.z, 0.f); a0_.w = fmaxf(a0_.w, 0.f); \
       a1_.x = fmaxf(a1_.x, 0.f); a1_.y = fmaxf(a1_.y, 0.f); a1_.z = fmaxf(a1_.z, 0.f); a1_.w = fmaxf(a1_.w, 0.f); \
-      DESCO_SELF_REG(it_, 0) = a0_;                                                            \
-      DESCO_SELF_REG(it_, 1) = a1_;                                                            \
+      s##it_##0 = a0_;                                                                         \
+      s##it_##1 = a1_;                                                                         \
     } else {                                                                                   \
       const float* p_ = xsb + (grow0 + (r_ < nr ? r_ : nr - 1)) * LDXS;                      \
-      DESCO_SELF_REG(it_, 0) = *reinterpret_cast<const float4*>(p_);                           \
-      DESCO_SELF_REG(it_, 1) = *reinterpret_cast<const float4*>(p_ + 32);                      \
+      s##it_##0 = *reinterpret_cast<const float4*>(p_);                                        \
+      s##it_##1 = *reinterpret_cast<const float4*>(p_ + 32);                                   \
     }                                                                                          \
   }
-// table pseudo block: the first source of table slot 0 (-> u) and of table slot 1 (-> w) of row it_
-#define DESCO_TAB_CUR(it_)                                                                  \
-  const int v_ = ((it_) * 8 + g8) * S + g.sm;                                               \
-  const int ca_ = rp[v_] - ebase, na_ = rp[v_ + 1] - ebase;                                 \
-  const int nb_ = ST > 1 ? rp[v_ + 2] - ebase : na_;                                        \
-  const bool k0_ = ca_ < (na_ < WCAP ? na_ : WCAP);                                         \
-  const bool k1_ = ST > 1 && na_ < (nb_ < WCAP ? nb_ : WCAP);
 // (a table slot without a source among the tile's rows -- live bits 8, 9 -- is neither loaded nor added:
 // only the rows next to the canonical node have one, half of the Syn_1827 tiles have none at all)
 #define DESCO_ISSUE_TAB(it_)                                                                \
@@ -198,95 +143,20 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
     d##it_ = na_ + (k1_ ? 1 : 0);                                                           \
     m##it_ = nb_;                                                                           \
   }
-// heavy rows (hub / canonical rows of dense neighborhoods, or ids beyond the staged WCAP): the
-// whole wave cooperates on one row at a time -- lane group k takes sources c+k, c+k+8, ... and
-// the 8 partial sums are folded with three xor-shuffles (lanes with equal l8 hold the same columns)
-#define DESCO_COOP(it_, base_, ld_)                                                       \
-  {                                                                                       \
-    unsigned long long m_ = __ballot(c##it_ < n##it_);                                    \
-    while (m_) {                                                                          \
-      const int sl_ = __builtin_ctzll(m_);                                                \
-      const int og_ = sl_ >> 3;                                                           \
-      const int cc_ = __shfl(c##it_, sl_, 64), nn_ = __shfl(n##it_, sl_, 64);             \
-      float4 p_ = make_float4(0.f, 0.f, 0.f, 0.f), q_ = p_;                               \
-      for (int e_ = cc_ + g8; e_ < nn_; e_ += 8) {                                        \
-        const int64_t j_ = e_ < WCAP ? ec[e_] : g.vcol[ebase + e_];                       \
-        const float* s_ = (base_) + j_ * (ld_);                                           \
-        const float4 v0_ = *reinterpret_cast<const float4*>(s_);                          \
-        const float4 v1_ = *reinterpret_cast<const float4*>(s_ + 32);                     \
-        f4add(p_, v0_);                                                                   \
-        f4add(q_, v1_);                                                                   \
-      }                                                                                   \
-      _Pragma("unroll") for (int o_ = 8; o_ < 64; o_ <<= 1) {                             \
-        p_.x += __shfl_xor(p_.x, o_, 64);                                                 \
-        p_.y += __shfl_xor(p_.y, o_, 64);                                                 \
-        p_.z += __shfl_xor(p_.z, o_, 64);                                                 \
-        p_.w += __shfl_xor(p_.w, o_, 64);                                                 \
-        q_.x += __shfl_xor(q_.x, o_, 64);                                                 \
-        q_.y += __shfl_xor(q_.y, o_, 64);                                                 \
-        q_.z += __shfl_xor(q_.z, o_, 64);                                                 \
-        q_.w += __shfl_xor(q_.w, o_, 64);                                                 \
-      }                                                                                   \
-      if (g8 == og_) {                                                                    \
-        f4add(lo##it_, p_);                                                               \
-        f4add(hi##it_, q_);                                                               \
-        c##it_ = n##it_;                                                                  \
-      }                                                                                   \
-      m_ &= ~(0xffULL << (og_ * 8));                                                      \
-    }                                                                                     \
-  }
-// finish a gathered block whose first step is already in flight: consume it, up to EXTRA_STEPS more
-// batched steps (two sources per row each: all four rows of a lane group advance together), then
-// the cooperative path for rows that are heavier still (one row at a time, the whole wave on it)
-#define DESCO_FINISH(base_, ld_)                                                           \
-  {                                                                                        \
-    DESCO_CONSUME2(0) DESCO_CONSUME2(1)                                                    \
-    for (int st_ = 0; st_ < EXTRA_STEPS && DESCO_ANY_STAGED(); ++st_) {                    \
-      DESCO_ISSUE2(0, base_, ld_) DESCO_ISSUE2(1, base_, ld_)                              \
-      DESCO_CONSUME2(0) DESCO_CONSUME2(1)                                                  \
-    }                                                                                      \
-    if (__any((c0 < n0) | (c1 < n1))) {                                                    \
-      DESCO_COOP(0, base_, ld_) DESCO_COOP(1, base_, ld_)                                  \
-    }                                                                                      \
-  }
-// first step of block b_ (cursors + loads); nothing waits on the loads here
-#define DESCO_ISSUE_BLOCK(b_)                                                              \
-  {                                                                                        \
-    if ((b_) < KB - 1) {                                                                   \
-      DESCO_CURS(b_)                                                                       \
-      DESCO_ISSUE2(0, xb, LDX) DESCO_ISSUE2(1, xb, LDX)                                \
-    } else if ((b_) == KB - 1) {                                                           \
-      DESCO_ISSUE_SELF(0) DESCO_ISSUE_SELF(1)                                              \
-    } else {                                                                               \
-      DESCO_ISSUE_TAB(0) DESCO_ISSUE_TAB(1)                                                \
-    }                                                                                      \
-  }
-// bit s of `live`: relation slot s (an MFMA slot) has at least one source among the wave's 16 rows
-#define DESCO_SLOT_ANY(s_)                                                                 \
-  (__any((rp[(0 * 8 + g8) * S + (s_) + 1] > rp[(0 * 8 + g8) * S + (s_)]) |                  \
-         (rp[(1 * 8 + g8) * S + (s_) + 1] > rp[(1 * 8 + g8) * S + (s_)])) != 0)
-#define DESCO_SLOT_LIVE(s_) (DESCO_SLOT_ANY(s_) ? 1 << (s_) : 0)
-#define DESCO_TILE_LIVE()                                        \
+// the relation slots' live bits, and bits 8, 9: table slot 0, 1 has a source among the wave's 16 rows
+#define DESCO_TILE_LIVE_TAB()                                    \
   {                                                              \
-    live = 0;                                                    \
-    if (KB - 1 > 0) live |= DESCO_SLOT_LIVE(0);                  \
-    if (KB - 1 > 1) live |= DESCO_SLOT_LIVE(1);                  \
-    if (KB - 1 > 2) live |= DESCO_SLOT_LIVE(2);                  \
+    DESCO_TILE_LIVE()                                            \
     if (ST > 0) live |= DESCO_SLOT_ANY(g.sm) ? 0x100 : 0;        \
     if (ST > 1) live |= DESCO_SLOT_ANY(g.sm + 1) ? 0x200 : 0;    \
   }
 // first step of the first LIVE block after block a_ (a_ = -1: of the tile); dead slots are left
 // out of the software pipeline altogether, so the block behind one is not issued late.  The slot
 // index is a wave-uniform runtime value here (one copy of the gather issue code per site).
-#ifndef SHMP16_SELF_LATE
-#define SHMP16_SELF_EARLY 1
-#endif
-#ifdef SHMP16_SELF_EARLY
 // The rows themselves (the self block's operand) need no index: they are requested at the tile top, together with the
 // first step of the first live relation block, into registers of their own -- one exposed round trip per tile less
 // (the self rows used to be requested under the MFMAs of the last relation block, which are 200 cycles long); the table
 // step moves up with them: it goes out behind the LAST relation block instead of behind the self block.
-#define DESCO_SELF_REG(it_, h_) s##it_##h_
 #define DESCO_ISSUE_AFTER(a_)                                                              \
   {                                                                                        \
     if ((a_) < KB - 1) {                                                                   \
@@ -296,35 +166,15 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
       if ((a_) + 1 < KB - 1 && ((live >> ((a_) + 1)) & 1)) nb_ = (a_) + 1;                  \
       if (nb_ < KB - 1) {                                                                  \
         DESCO_CURS(nb_)                                                                    \
-        DESCO_ISSUE2(0, xb, LDX) DESCO_ISSUE2(1, xb, LDX)                                  \
+        DESCO_ROWS(DESCO_ISSUE2, xb, LDX)                                                  \
       } else if (ST > 0 && (live & 0x300)) {                                               \
-        DESCO_ISSUE_TAB(0) DESCO_ISSUE_TAB(1)                                              \
+        DESCO_ROWS(DESCO_ISSUE_TAB)                                                        \
       }                                                                                    \
       if ((a_) < 0) {                                                                      \
-        DESCO_ISSUE_SELF(0) DESCO_ISSUE_SELF(1)                                            \
+        DESCO_ROWS(DESCO_ISSUE_SELF)                                                       \
       }                                                                                    \
     }                                                                                      \
   }
-#else
-#define DESCO_SELF_REG(it_, h_) u##it_##h_
-#define DESCO_ISSUE_AFTER(a_)                                                              \
-  {                                                                                        \
-    if ((a_) < KB - 1) {                                                                   \
-      int nb_ = KB - 1;                                                                    \
-      if ((a_) + 3 < KB - 1 && ((live >> ((a_) + 3)) & 1)) nb_ = (a_) + 3;                  \
-      if ((a_) + 2 < KB - 1 && ((live >> ((a_) + 2)) & 1)) nb_ = (a_) + 2;                  \
-      if ((a_) + 1 < KB - 1 && ((live >> ((a_) + 1)) & 1)) nb_ = (a_) + 1;                  \
-      if (nb_ < KB - 1) {                                                                  \
-        DESCO_CURS(nb_)                                                                    \
-        DESCO_ISSUE2(0, xb, LDX) DESCO_ISSUE2(1, xb, LDX)                                  \
-      } else {                                                                             \
-        DESCO_ISSUE_SELF(0) DESCO_ISSUE_SELF(1)                                            \
-      }                                                                                    \
-    } else if ((a_) + 1 < NB && (live & 0x300)) {                                          \
-      DESCO_ISSUE_BLOCK((a_) + 1)                                                          \
-    }                                                                                      \
-  }
-#endif
 // write one fp32 half image (every lane writes: row = it*8 + g8, 4 floats at 4*l8)
 #define DESCO_PUT_F32(av_, it_)                         \
   {                                                     \
@@ -387,7 +237,6 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
 // fit under it.  The lane group that holds a row reduces the maximum of its 64 gathered sums (3 DPP steps over the
 // group's 8 lanes); the accumulators (C/D layout: lane quarter g holds rows 4 g + e) follow a change of scale by an
 // exact multiplication and leave the scales in the epilogue.
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 // (a chain: hipcc folds it into four v_max3_f32 with |.| source modifiers)
 #define DESCO_ABSMAX8(a_, b_)                                                                                   \
   fmaxf(fmaxf(fmaxf(fmaxf(fmaxf(fmaxf(fmaxf(fabsf(a_.x), fabsf(a_.y)), fabsf(a_.z)), fabsf(a_.w)), fabsf(b_.x)), \
@@ -557,23 +406,9 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
   const float* zrow = shmp16_zero_row + 4 * l8;
   (void)yb;
 
-  // ---- this wave's first tile ---------------------------------------------------------------
-  // XCD-aware tile order: blocks b, b+8, b+16, ... share an XCD (round-robin dispatch) and its 4 MB L2,
-  // so a neighborhood's rows -- the sources of all its tiles -- should be gathered by ONE XCD.  Measured
-  // (profiles/r2_f_ab_xcd_order.log): +0.5 % on Syn_1827 / MSRC+IMDB shapes, 0 on COX2 shapes (the
-  // gathers are not what bounds the kernel); contiguous eighths per XCD were 8 % SLOWER on Syn shapes
-  // (the dataset is ordered by graph size: the XCD with the dense end finishes last).  Speed only: any
-  // block -> XCD placement gives the same result.
-  int64_t tile, tend = ntiles;
+  // ---- this wave's first tile (XCD-aware order: shmp_gather.hpp) --------------------------------
+  int64_t tile = xcd_first_tile(), tend = ntiles;
   int tstride = gridDim.x;
-  if ((gridDim.x & 7) == 0) {
-    // chunks of (grid / 8) consecutive tiles go round robin over the XCDs: XCD x works on the 32
-    // neighbouring tiles of chunk 8 j + x in sweep j (locality), heavy and light regions of the dataset
-    // are spread over all XCDs (balance)
-    tile = (int64_t)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  } else {
-    tile = blockIdx.x;
-  }
   // A block's 16-row wave tiles are handed out IN ORDER from a counter in LDS (sub-tile i = wave tile
   // i % NW of the block's (i / NW)-th block tile): whatever the waves' speeds, the tiles in flight in a
   // block are consecutive -- a window of a few hundred rows that also holds most of their sources (a
@@ -619,16 +454,14 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
   float4 u00, u01, u10, u11;                               // in flight: first source (lo, hi) of row it
   float4 w00, w01, w10, w11;                               // in flight: second source
   w00 = w01 = w10 = w11 = make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef SHMP16_SELF_EARLY
   float4 s00, s01, s10, s11;                               // in flight: the rows themselves (requested at the tile top)
-#endif
   int c0 = 0, c1 = 0, n0 = 0, n1 = 0;                      // cursors [c, n) rel. to ebase
   // bit b: relation slot b has at least one source among this wave's 16 rows.  A slot that is empty
   // for the whole wave tile (triangle edges in molecule graphs, tride edges in clique unions) is an
   // all-zero K block: it is left out of the tile's block sequence (wave-uniform; it would add exact
   // zeros), and the first gather step of the block behind it is issued in its place
   int live = 0;
-  DESCO_TILE_LIVE()
+  DESCO_TILE_LIVE_TAB()
   DESCO_ISSUE_AFTER(-1)
 
   for (;;) {
@@ -684,7 +517,7 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
       if (b < KB - 1) {
         DESCO_FINISH(xb, LDX)
       } else if (b == KB - 1) {
-        lo0 = DESCO_SELF_REG(0, 0); hi0 = DESCO_SELF_REG(0, 1); lo1 = DESCO_SELF_REG(1, 0); hi1 = DESCO_SELF_REG(1, 1);
+        lo0 = s00; hi0 = s01; lo1 = s10; hi1 = s11;
       } else {
         // canonical->count relations have at most one source per row: one step covers both table
         // slots; anything beyond that (general inputs) takes the cooperative path
@@ -785,7 +618,7 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
       w0 = w0n;
       nr = nrn;
       grow0 = g.row0 + w0n;
-      DESCO_TILE_LIVE()
+      DESCO_TILE_LIVE_TAB()
       DESCO_ISSUE_AFTER(-1)
     }
 
@@ -905,90 +738,47 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
   }
 }
 
-
-#undef DESCO_DMA4
-#undef DESCO_NEXT_SUB
-#undef DESCO_SUB_ROWS
-#undef DESCO_CUR
-#undef DESCO_CURS
-#undef DESCO_ISSUE2
-#undef DESCO_CONSUME2
-#undef DESCO_ZERO_SUMS
-#undef DESCO_ANY_STAGED
-#undef DESCO_ISSUE_SELF
-#undef DESCO_SELF_REG
-#undef DESCO_TAB_CUR
-#undef DESCO_ISSUE_TAB
-#undef DESCO_CONSUME_TAB
-#undef DESCO_COOP
-#undef DESCO_FINISH
-#undef DESCO_ISSUE_BLOCK
-#undef DESCO_SLOT_ANY
-#undef DESCO_SLOT_LIVE
-#undef DESCO_TILE_LIVE
-#undef DESCO_ISSUE_AFTER
-#undef DESCO_PUT_F32
-#undef DESCO_PUT_X6
-#undef DESCO_M16
-#undef DESCO_MFMA_HALF_X6
-#undef DESCO_TAB_HALF
-#undef DESCO_TAB_HALF_F16
-#undef DESCO_MFMA_HALF_F16
-#undef DESCO_F16
-#undef DESCO_PUT_F16
-#undef DESCO_BLOCK_SCALES
-#undef DESCO_GROUP_MAX
-#undef DESCO_ABSMAX8
-
 template <int NW, int KB, int ST, bool LD64, bool POOL, bool F16, bool SELFDEG = false>
-static void shmp16_launch_one(const ShmpArgs& g, unsigned grid, hipStream_t st) {
+static hipError_t shmp16_launch_one(const ShmpArgs& g, unsigned grid, hipStream_t st) {
   constexpr int WST = KB * 64 + 16;
   constexpr size_t w_floats = (size_t)(F16 ? 2 : 3) * 64 * WST / 2;
   constexpr size_t shmem = sizeof(float) * (w_floats + (size_t)NW * (F16 ? WAVE_LDS_F16 : WAVE_LDS) + 64 + 4 +
                                            (SELFDEG ? (MAXS + 1) * 64 : 0));
   static_assert(shmem <= 160 * 1024, "SHMP layer (16-row tiles): LDS budget exceeded");
-  static DeviceOnce attr_once;        // function attributes are per device
-  if (!attr_once.done()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_once.mark();
-  }
-  hipLaunchKernelGGL((shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG>), dim3(grid), dim3(NW * 64), shmem, st, g,
-                     g.vrowptr, g.pool_bits, g.pool_slot);
+  const hipError_t e = size_dynamic_lds<shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG>>(160 * 1024);
+  if (e == hipSuccess)
+    hipLaunchKernelGGL((shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG>), dim3(grid), dim3(NW * 64), shmem, st, g,
+                       g.vrowptr, g.pool_bits, g.pool_slot);
+  return e;
 }
 
+// false: the shape is not built; otherwise e = the status of sizing the kernel's LDS (the launch follows on success)
 template <int NW, int KB, bool F16>
-static bool shmp16_launch_st(const ShmpArgs& g, unsigned grid, hipStream_t st) {
+static bool shmp16_launch_st(const ShmpArgs& g, unsigned grid, hipStream_t st, hipError_t& e) {
   const bool ld64 = g.ldx == 64 && (g.st == 0 || g.ldy == 64 * g.st) && (!g.out || g.ldo == 64);      // (xself has its own stride)
   if (g.pool_part) {
     if constexpr (KB == 3) {
       if (g.st != 2) return false;
       if (g.self_coef) {                 // the rows themselves recomputed from their slot degrees (fp16 form only)
         if constexpr (F16) {
-          if (ld64)
-            shmp16_launch_one<NW, 3, 2, true, true, true, true>(g, grid, st);
-          else
-            shmp16_launch_one<NW, 3, 2, false, true, true, true>(g, grid, st);
+          e = ld64 ? shmp16_launch_one<NW, 3, 2, true, true, true, true>(g, grid, st)
+                   : shmp16_launch_one<NW, 3, 2, false, true, true, true>(g, grid, st);
           return true;
         } else {
           return false;
         }
       }
-      if (ld64)
-        shmp16_launch_one<NW, 3, 2, true, true, F16>(g, grid, st);
-      else
-        shmp16_launch_one<NW, 3, 2, false, true, F16>(g, grid, st);
+      e = ld64 ? shmp16_launch_one<NW, 3, 2, true, true, F16>(g, grid, st)
+               : shmp16_launch_one<NW, 3, 2, false, true, F16>(g, grid, st);
       return true;
     } else {
       return false;
     }
   }
   if (g.self_coef) return false;          // (built for the pooled count-row launch only)
-#define DESCO_ONE(ST_)                                \
-  if (ld64)                                           \
-    shmp16_launch_one<NW, KB, ST_, true, false, F16>(g, grid, st);    \
-  else                                                \
-    shmp16_launch_one<NW, KB, ST_, false, false, F16>(g, grid, st);
+#define DESCO_ONE(ST_)                                                         \
+  e = ld64 ? shmp16_launch_one<NW, KB, ST_, true, false, F16>(g, grid, st)     \
+           : shmp16_launch_one<NW, KB, ST_, false, false, F16>(g, grid, st);
   switch (g.st) {
     case 0: DESCO_ONE(0) break;
     case 1: DESCO_ONE(1) break;
@@ -1000,13 +790,12 @@ static bool shmp16_launch_st(const ShmpArgs& g, unsigned grid, hipStream_t st) {
 }
 
 template <int NW, bool F16>
-static bool shmp16_launch_nw(const ShmpArgs& g, int cus, hipStream_t st) {
-  const int64_t ntiles = (g.num_rows + NW * WR - 1) / (NW * WR);
-  const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
+static bool shmp16_launch_nw(const ShmpArgs& g, hipStream_t st, hipError_t& e) {
+  const unsigned grid = persistent_grid((g.num_rows + NW * WR - 1) / (NW * WR));
   switch (g.sm) {
-    case 0: return shmp16_launch_st<NW, 1, F16>(g, grid, st);
-    case 1: return shmp16_launch_st<NW, 2, F16>(g, grid, st);
-    default: return shmp16_launch_st<NW, 3, F16>(g, grid, st);
+    case 0: return shmp16_launch_st<NW, 1, F16>(g, grid, st, e);
+    case 1: return shmp16_launch_st<NW, 2, F16>(g, grid, st, e);
+    default: return shmp16_launch_st<NW, 3, F16>(g, grid, st, e);
   }
 }
 
@@ -1019,7 +808,6 @@ static int shmp16_launch(const char* who, const float* x, int64_t ldx, const int
                          float* pool_part = nullptr, float* row_absmax = nullptr, const float* xself = nullptr,
                          int64_t ldxs = 0, const float* self_coef = nullptr) {
   if (num_rows == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   const bool pool = pool_part != nullptr;
   if (pool && (!pool_bits || !pool_slot || row0 % WR || mis16(pool_part) || out2 || slots_mfma != 2 || slots_table != 2))
     return fail(DESCO_EINVAL, "desco_shmp_layer_pool_bf16x6_f32: bad pooling argument (row0 % tile rows, no out2, "
@@ -1057,21 +845,17 @@ static int shmp16_launch(const char* who, const float* x, int64_t ldx, const int
   g.ldxs = ldxs;
   g.self_coef = self_coef;
   if (!shmp_args_ok(g, wt_planes) || slots_mfma > 2 || (!out && !pool && !out2))
-    return fail(DESCO_EINVAL, "desco_shmp_layer_bf16x6_f32: bad argument (slots_mfma <= 2, slots_table <= 2)");
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
+    return fail(DESCO_EINVAL, (std::string(who) + ": bad argument (slots_mfma <= 2, slots_table <= 2)").c_str());
   // bf16x6 form: 16 waves per block (12 measured 2-6 % slower there: profiles/r2_h_ab_tile_rows.log).  fp16 form: TWELVE,
   // three per SIMD -- a quarter fewer tiles in flight per XCD means a quarter less traffic between two references to a
   // source row, and with half the matrix work per tile the fourth wave per SIMD is not needed to hide latency: Syn_1827
   // shapes 3.68 -> 3.39 ms per count-row launch, MSRC-21 + IMDB 2.93 -> 2.74, COX2 1.325 -> 1.30; 8, 10 and 14 waves are
   // all slower (profiles/r4_m_ab_shmp_waves.log)
-  const bool built = w_scale ? shmp16_launch_nw<12, true>(g, cus, (hipStream_t)stream)     // fp16 three-product planes
-                             : shmp16_launch_nw<16, false>(g, cus, (hipStream_t)stream);
+  hipError_t e = hipSuccess;
+  const bool built = w_scale ? shmp16_launch_nw<12, true>(g, (hipStream_t)stream, e)     // fp16 three-product planes
+                             : shmp16_launch_nw<16, false>(g, (hipStream_t)stream, e);
   if (!built) return fail(DESCO_EINVAL, "desco_shmp_layer_bf16x6_f32: shape not built");
+  if (e != hipSuccess) return fail((int)e, (std::string(who) + ": cannot size LDS").c_str());
   return launch_status(who);
 }
 

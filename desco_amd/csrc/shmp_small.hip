@@ -517,17 +517,12 @@ extern "C" int desco_shmp_trunk_small_fwd_f32(const float* x0, const int32_t* vr
   using namespace desco;
   using namespace desco::small;
   if (num_rows == 0 || num_seg == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (!x0 || !vrowptr || !vcol || !wt || !bias || !seg_ptr || !xall || !pooled || num_rows < 0 || num_rows > NMAX ||
       num_layers < 1 || num_seg < 0 || ldp < 64 * (num_layers + 1) || ldp % 4 || mis16(x0) || mis16(wt) ||
       mis16(bias) || mis16(xall) || mis16(pooled))
     return fail(DESCO_EINVAL, "desco_shmp_trunk_small_fwd_f32: bad argument (at most 144 rows, 16-byte alignment)");
-  static DeviceOnce once;
-  if (!once.done()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shmp_small_fwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kShmem);
-    once.mark();
-  }
+  if (hipError_t e = size_dynamic_lds<shmp_small_fwd_kernel>((int)kShmem); e != hipSuccess)
+    return fail((int)e, "desco_shmp_trunk_small_fwd_f32: cannot size LDS");
   FwdArgs g{x0, vrowptr, vcol, num_rows, num_layers, wt, bias, seg_ptr, num_seg, xall, pooled, ldp};
   hipLaunchKernelGGL(shmp_small_fwd_kernel, dim3(1), dim3(NT), kShmem, (hipStream_t)stream, g);
   return launch_status("desco_shmp_trunk_small_fwd_f32");
@@ -541,17 +536,12 @@ extern "C" int desco_shmp_trunk_small_bwd_f32(const float* x0, const float* xall
   using namespace desco;
   using namespace desco::small;
   if (num_rows == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (!x0 || !xall || !vrowptr || !vcol || !t_rowptr || !t_col || !seg_id || !wt_t || !dpooled || !dwt || !dbias ||
       !dx0 || num_rows < 0 || num_rows > NMAX || num_layers < 1 || ldp < 64 * (num_layers + 1) || ldp % 4 ||
       mis16(x0) || mis16(xall) || mis16(wt_t) || mis16(dpooled) || mis16(dwt) || mis16(dx0))
     return fail(DESCO_EINVAL, "desco_shmp_trunk_small_bwd_f32: bad argument (at most 144 rows, 16-byte alignment)");
-  static DeviceOnce once;
-  if (!once.done()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shmp_small_bwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kShmem);
-    once.mark();
-  }
+  if (hipError_t e = size_dynamic_lds<shmp_small_bwd_kernel>((int)kShmem); e != hipSuccess)
+    return fail((int)e, "desco_shmp_trunk_small_bwd_f32: cannot size LDS");
   BwdArgs g{x0, xall, vrowptr, vcol, t_rowptr, t_col, seg_id, num_rows, num_layers, wt_t, dpooled, ldp, dwt, dbias, dx0};
   hipLaunchKernelGGL(shmp_small_bwd_kernel, dim3(1), dim3(NT), kShmem, (hipStream_t)stream, g);
   return launch_status("desco_shmp_trunk_small_bwd_f32");
@@ -566,7 +556,6 @@ extern "C" int desco_shmp_trunk_graphs_fwd_f32(const float* x0, const int32_t* v
   using namespace desco;
   using namespace desco::small;
   if (num_rows == 0 || num_seg == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   DropArgs da = DropArgs{nullptr, 0u, 0u, 1.f};
   if (drop) {
     if (!drop->key || drop->site + 2u * (unsigned)num_layers >= 256u || num_rows > ((int64_t)1 << 34))
@@ -591,7 +580,6 @@ extern "C" int desco_shmp_trunk_graphs_bwd_f32(const float* x0, const float* xal
   using namespace desco;
   using namespace desco::small;
   if (num_rows == 0 || num_seg == 0) return 0;
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (!x0 || !xall || !vrowptr || !vcol || !t_rowptr || !t_col || !seg_ptr || !wt || !dpooled || !dwt || !dbias || !dx0 ||
       !workspace || num_rows < 0 || num_seg < 0 || num_layers < 1 || ldp < 64 * (num_layers + 1) || ldp % 4 ||
       mis16(x0) || mis16(xall) || mis16(wt) || mis16(dpooled) || mis16(dwt) || mis16(dx0) || mis16(workspace))

@@ -21,8 +21,6 @@ namespace desco {
 
 namespace {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
 constexpr int SW_ROWS = 64;
 
 struct WideLayerArgs {
@@ -205,13 +203,9 @@ __global__ __launch_bounds__(256) void shmp_layer_wide_kernel(const WideLayerArg
 template <int WP, int S>
 int launch_layer_wide(const WideLayerArgs& g, hipStream_t stream) {
   const size_t lds = (size_t)2 * SW_ROWS * (WP + 8) * sizeof(short) + SW_ROWS * sizeof(float);
-  static DeviceOnce attr_once;
-  if (lds > 65536 && !attr_once.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(shmp_layer_wide_kernel<WP, S>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail((int)e, "desco_shmp_layer_wide_f16x3_f32: cannot size LDS");
-    attr_once.mark();
-  }
+  if (lds > 65536)
+    if (hipError_t e = size_dynamic_lds<shmp_layer_wide_kernel<WP, S>>((int)lds); e != hipSuccess)
+      return fail((int)e, "desco_shmp_layer_wide_f16x3_f32: cannot size LDS");
   const int64_t blocks = (g.num_rows + SW_ROWS - 1) / SW_ROWS;
   hipLaunchKernelGGL((shmp_layer_wide_kernel<WP, S>), dim3((unsigned)blocks), dim3(256), lds, stream, g);
   return launch_status("desco_shmp_layer_wide_f16x3_f32");
@@ -332,7 +326,6 @@ extern "C" int desco_shmp_layer_wide_f16x3_f32(const float* x, int64_t ldx, cons
                                                int slots, int width, const int16_t* w_planes, const float* w_scale,
                                                const float* bias, float* out, int64_t ldo, float* out2, int64_t ld2,
                                                desco_stream_t stream) {
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (row0 < 0 || num_rows < 0 || !(slots == 2 || slots == 4) || vslots < slots || vslots > 4 ||
       !(width == 64 || width == 128 || width == 192 || width == 256))
     return fail(DESCO_EINVAL, "desco_shmp_layer_wide_f16x3_f32: bad argument (row0, num_rows >= 0, slots in {2, 4}, "
@@ -362,7 +355,6 @@ extern "C" int desco_shmp_layer_wide_f16x3_f32(const float* x, int64_t ldx, cons
 extern "C" int desco_csr_gather_sum_wide_f32(const float* x, int64_t ldx, const int32_t* vrowptr, const int32_t* vcol,
                                              int64_t num_rows, int slots, int width, float* out, int64_t ldo,
                                              desco_stream_t stream) {
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (num_rows < 0 || !(slots == 1 || slots == 2 || slots == 4) || width <= 0 || width > 256 || width % 4)
     return fail(DESCO_EINVAL, "desco_csr_gather_sum_wide_f32: bad argument (num_rows >= 0, slots in {1, 2, 4}, "
                               "width % 4 == 0, width <= 256)");
@@ -383,7 +375,7 @@ extern "C" int desco_count_head_wide_f32(const float* t, int64_t ldt, const floa
                                          float* out, int64_t ldo, int64_t num_b, int num_q, desco_stream_t stream) {
   if (num_b == 0 || num_q == 0) return 0;
   if (!t || !qh || !w2 || !out || num_b < 0 || num_q < 0 || num_q > 32 || hid <= 0 || hid % 64 || hid > HW_MAXHID ||
-      ldt % 4 || ldt < hid || ldq < hid || ldo < num_q || (reinterpret_cast<uintptr_t>(t) & 15))
+      ldt % 4 || ldt < hid || ldq < hid || ldo < num_q || mis16(t))
     return fail(DESCO_EINVAL, "desco_count_head_wide_f32: bad argument (NULL pointer, num_q > 32, hid not a multiple of "
                               "64 up to 1024, t not 16-byte aligned, ldt % 4 != 0, ldt / ldq < hid or ldo < num_q)");
   int64_t blocks = (num_b + 255) / 256;

@@ -402,7 +402,6 @@ extern "C" size_t desco_gemm_tn_workspace(int64_t m, int k, int n, int* splits_o
 extern "C" int desco_gemm_tn_f32(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t m,
                                  int k, int n, float* out, int64_t ldo, int accumulate,
                                  float* workspace, desco_stream_t stream) {
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (!a || !b || !out || !workspace || m < 0 || k <= 0 || n <= 0 || k % TK || n % TN || lda % 4 ||
       ldb % 4 || mis16(a) || mis16(b))
     return fail(DESCO_EINVAL, "desco_gemm_tn_f32: bad argument (k%64, n%64, 16-byte alignment)");
@@ -438,7 +437,6 @@ extern "C" int desco_linear_bwd_w_f32(const float* a1, int64_t lda1, int k1, con
                                       int64_t lda2, int k2, const float* dz, int64_t lddz, int64_t m,
                                       int n, float* dwt, int64_t lddw, float* dbias, float* workspace,
                                       desco_stream_t stream) {
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   const int k = k1 + k2;
   if ((m > 0 && (!a1 || !dz)) || !dwt || !workspace || m < 0 || k1 <= 0 || k1 % TK || k2 < 0 || k2 % TK || n <= 0 ||
       n % TN || (k2 > 0 && ((m > 0 && !a2) || lda2 % 4 || mis16(a2))) || lda1 % 4 || lddz % 4 || mis16(a1) || mis16(dz))
@@ -470,7 +468,6 @@ extern "C" size_t desco_linear_bwd_w_multi_workspace(int num, const desco_bwd_w_
 
 extern "C" int desco_linear_bwd_w_multi_f32(int num, const desco_bwd_w_desc* d, float* workspace,
                                             desco_stream_t stream) {
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (num < 0 || num > kBwdWMulti || (num > 0 && (!d || !workspace)))
     return fail(DESCO_EINVAL, "desco_linear_bwd_w_multi_f32: 0..16 problems per call, workspace required");
   BwdWMulti q;
@@ -516,7 +513,7 @@ extern "C" int desco_colsum_f32(const float* x, int64_t ldx, int64_t m, int n, f
   if (splits < 1) splits = 1;
   const int64_t slab = (m + splits - 1) / splits;
   hipStream_t st = (hipStream_t)stream;
-  if (n % 4 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+  if (n % 4 == 0 && ldx % 4 == 0 && !mis16(x))
     hipLaunchKernelGGL(colsum_partial4_kernel, dim3((n + 63) / 64, (unsigned)splits), dim3(256), 0, st, x,
                        ldx, m, n, slab > 0 ? slab : 1, workspace);
   else
@@ -561,8 +558,7 @@ __global__ __launch_bounds__(256) void smallk_bwd_partial_kernel(const float* __
 
 extern "C" int desco_linear_smallk_bwd_f32(const float* feat, int64_t ldf, int k, const float* dout, int64_t ldd,
                                            int64_t m, float* dwb, float* workspace, desco_stream_t stream) {
-  if (!feat || !dout || !dwb || !workspace || m < 0 || k < 1 || k > 16 || ldd % 4 ||
-      (reinterpret_cast<uintptr_t>(dout) & 15))
+  if (!feat || !dout || !dwb || !workspace || m < 0 || k < 1 || k > 16 || ldd % 4 || mis16(dout))
     return fail(DESCO_EINVAL, "desco_linear_smallk_bwd_f32: bad argument (1 <= k <= 16, 64 output columns)");
   int64_t splits = (m + 255) / 256;
   if (splits > 512) splits = 512;
@@ -629,7 +625,6 @@ __global__ __launch_bounds__(256) void rowdot_bwd_kernel(const float* __restrict
 extern "C" int desco_rowdot_bwd_f32(const float* y, int64_t ldy, int n, const float* w, const float* dout,
                                     int64_t num_rows, float* dz, int64_t lddz, float* dwb, float* workspace,
                                     desco_stream_t stream) {
-  auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (!y || !w || !dout || !dz || !dwb || !workspace || num_rows < 0 || n < 16 || n > 1024 || n % 16 || 256 % (n / 4) ||
       ldy % 4 || lddz % 4 || mis16(y) || mis16(w) || mis16(dz) || mis16(workspace))
     return fail(DESCO_EINVAL, "desco_rowdot_bwd_f32: bad argument (n = 16, 32, 64, ..., 1024: at most 64 row groups per pass; 16-byte alignment)");

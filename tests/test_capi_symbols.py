@@ -261,3 +261,80 @@ def test_per_graph_trunk_entry_points_validate_their_arguments():
     rejects(name, bwd(dp=p + 4))
     rejects(name, bwd(nl=0))
     assert L.desco_shmp_trunk_graphs_max_rows() == 8
+
+
+def test_entry_points_refuse_misaligned_pointers():
+    """A float4-accessed operand that is 4 bytes off a 16-byte boundary comes back as DESCO_EINVAL naming the entry point,
+    before any HIP call.  Every other argument of each call is valid (fake aligned host pointers, never dereferenced),
+    so the misaligned pointer is what the call trips on."""
+    L = _lib.lib()
+    buf = np.zeros(64 * 1024, np.float32)
+    idx = np.zeros(64, np.int32)
+    p, q = buf.ctypes.data, idx.ctypes.data
+    assert p % 16 == 0
+    o, t, w = p + 65536, p + 131072, p + 196608            # distinct aligned operands: out, table / second input, weights
+
+    def rejects(name, rc):
+        assert rc == -1, name
+        assert name.encode() in L.desco_last_error(), (name, L.desco_last_error())
+        assert L.desco_rng_next(None, None, None) == -1          # (resets the message for the next case)
+
+    def layer_f32(x=p, ytab=t, out=o):
+        return L.desco_shmp_layer_f32(x, 64, q, q, 0, 8, 4, 2, 2, w, w, ytab, 128, 0, out, 64, None, 0, None)
+
+    def layer_f16(x=p, ytab=t, out=o, planes=w):
+        return L.desco_shmp_layer_f16x3_f32(x, 64, q, q, 0, 8, 4, 2, 2, planes, w, w, ytab, 128, 0, out, 64, None, 0,
+                                            None, None, 0, None)
+
+    def linear64(x=p, planes=w, out=o):
+        return L.desco_linear64_bf16x6_f32(x, 64, planes, 1, w, 0, 0.0, out, 64, 8, None)
+
+    def gemm_x6(a1=p, planes=w):
+        return L.desco_gemm_bf16x6_f32(a1, 64, 64, None, 0, 0, planes, 64, None, 1, None, 0, None, 0, 0.0, o, 64, 8, None)
+
+    def gemm_f16(a1=p, planes=w):
+        return L.desco_gemm_f16x3_f32(a1, 64, 64, None, 0, 0, planes, t, 64, None, 1, None, 0, None, 0, 0.0, o, 64, 8, t,
+                                      None)
+
+    def gemm_tn(a=p, b=t):
+        return L.desco_gemm_tn_f32(a, 64, b, 64, 8, 64, 64, o, 64, 0, w, None)
+
+    def gossip_layer(h=p, acc=t, out=o):
+        return L.desco_gossip_layer_f16x3_f32(h, q, q, 8, 2, w, w, w, w, w, w, w, None, None, acc, out, None)
+
+    parts = (ctypes.c_void_p * 2)(t, t + 4096)
+
+    def anchor_post(a=p, x0=w, pp=parts):
+        return L.desco_anchor_pool_post_f16x3_f32(a, 192, 192, w, w, w, 0, 0.0, w, 2, w, w, 0, 0.0, o, 64, 8, q, q, q, pp,
+                                                  x0, 16, None)
+
+    def gather_wide(x=p, out=o):
+        return L.desco_csr_gather_sum_wide_f32(x, 64, q, q, 8, 4, 64, out, 64, None)
+
+    def layer_wide(x=p, planes=w):
+        return L.desco_shmp_layer_wide_f16x3_f32(x, 64, q, q, 4, 0, 8, 4, 64, planes, w, w, o, 64, None, 0, None)
+
+    rejects("desco_shmp_layer_f32", layer_f32(x=p + 4))
+    rejects("desco_shmp_layer_f32", layer_f32(ytab=t + 4))
+    rejects("desco_shmp_layer_f32", layer_f32(out=o + 4))
+    rejects("desco_shmp_layer_f16x3_f32", layer_f16(x=p + 4))
+    rejects("desco_shmp_layer_f16x3_f32", layer_f16(planes=w + 4))
+    rejects("desco_shmp_layer_f16x3_f32", layer_f16(out=o + 4))
+    rejects("desco_linear64_bf16x6_f32", linear64(x=p + 4))
+    rejects("desco_linear64_bf16x6_f32", linear64(planes=w + 4))
+    rejects("desco_linear64_bf16x6_f32", linear64(out=o + 4))
+    rejects("desco_gemm_bf16x6_f32", gemm_x6(a1=p + 4))
+    rejects("desco_gemm_bf16x6_f32", gemm_x6(planes=w + 4))
+    rejects("desco_gemm_f16x3_f32", gemm_f16(a1=p + 4))
+    rejects("desco_gemm_f16x3_f32", gemm_f16(planes=w + 4))
+    rejects("desco_gemm_tn_f32", gemm_tn(a=p + 4))
+    rejects("desco_gemm_tn_f32", gemm_tn(b=t + 4))
+    rejects("desco_gossip_layer_f16x3_f32", gossip_layer(h=p + 4))
+    rejects("desco_gossip_layer_f16x3_f32", gossip_layer(acc=t + 4))
+    rejects("desco_anchor_pool_post_f16x3_f32", anchor_post(a=p + 4))
+    rejects("desco_anchor_pool_post_f16x3_f32", anchor_post(x0=w + 4))
+    rejects("desco_anchor_pool_post_f16x3_f32", anchor_post(pp=(ctypes.c_void_p * 2)(t, t + 4100)))
+    rejects("desco_csr_gather_sum_wide_f32", gather_wide(x=p + 4))
+    rejects("desco_csr_gather_sum_wide_f32", gather_wide(out=o + 4))
+    rejects("desco_shmp_layer_wide_f16x3_f32", layer_wide(x=p + 4))
+    rejects("desco_shmp_layer_wide_f16x3_f32", layer_wide(planes=w + 4))

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Build a variant of the library for same-box A/B runs (tools/debug/ab_libs.sh): tools/debug/ab_build.sh <name> <source.hip> [flags]
-# compiles ONE kernel source with extra flags (e.g. -DSHMP16_SELF_LATE) and links it with the other objects of the
+# compiles ONE kernel source -- a patched COPY of a production kernel kept under tools/debug: the production sources hold no
+# A/B switches, so <source.hip> is the variant, under the production file's name (its object replaces that one; -I. finds
+# the headers) -- with optional extra flags and links it with the other objects of the
 # current build into tools/debug/_ab/lib<name>.so.
 set -e
 NAME=$1; SRC=$2; shift 2
