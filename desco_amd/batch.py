@@ -285,6 +285,85 @@ class QueryBatch(_TrainIndexMixin):
         return self.graph_ptr
 
 
+def _graphset_device_csr(graphs: GraphSet, device: torch.device):
+    """(rowptr int64, col int32) of a GraphSet on ``device``, uploaded once per set and device: every GraphBatch over
+    a graph range of the set reads the same two tensors."""
+    cache = graphs.__dict__.setdefault("_device_csr", {})
+    if device not in cache:
+        cache[device] = (torch.from_numpy(graphs.rowptr).to(device), torch.from_numpy(graphs.col).to(device))
+    return cache[device]
+
+
+class GraphBatch(_TrainIndexMixin):
+    """Whole target graphs as one single-type ("union_node") block with 2 relation slots (union_triangle, union_tride):
+    the whole-graph twin of ``QueryBatch`` -- the same arrays -- for the model without canonical partition
+    (NeighborhoodCountingModel.to_hetero_wo_canonical; reference workload.py:800-833).  Graphs [g0, g1) of a
+    ``GraphSet``.  On a cuda device the typed CSR is built there from the set's device CSR (desco_graph_tconv_dev: the
+    large arrays never visit the host); on the CPU by the host routine (desco_graph_tconv) -- in either case when
+    ``vrowptr`` / ``vcol`` are first read.
+
+    ``node_feature``: None = ZeroNodeFeat; True = the set's ``node_feat`` rows (--use_node_feature); or a
+    [num_rows, input_dim] tensor.  ``y`` [G, Q]."""
+
+    slots = 2
+
+    def __init__(self, graphs: GraphSet, device, g0: int = 0, g1: Optional[int] = None, node_feature=None,
+                 y: Optional[torch.Tensor] = None, input_dim: int = 1):
+        g1 = graphs.num_graphs if g1 is None else g1
+        if not 0 <= g0 <= g1 <= graphs.num_graphs:
+            raise ValueError(f"GraphBatch: graph range [{g0}, {g1}) outside the set's {graphs.num_graphs} graphs")
+        self.graphs, self.g0, self.g1 = graphs, g0, g1
+        self.device = _norm_device(device)
+        device = self.device
+        n0, n1 = int(graphs.graph_ptr[g0]), int(graphs.graph_ptr[g1])
+        e0, e1 = int(graphs.rowptr[n0]), int(graphs.rowptr[n1])
+        self.num_graphs, self.num_rows = g1 - g0, n1 - n0
+        self.graph_ptr_host = graphs.graph_ptr[g0:g1 + 1] - n0
+        if 2 * self.num_rows + 1 >= 2 ** 31 or e1 - e0 >= 2 ** 31:
+            raise ValueError("graph batch too large for int32 row / edge offsets; split it")
+        self._nodes, self._edges = (n0, n1), (e0, e1)
+        self.graph_ptr = _i32(self.graph_ptr_host, device)
+        if node_feature is True:
+            if graphs.node_feat is None:
+                raise ValueError("node_feature=True needs a set with node features (GraphSet.node_feat)")
+            node_feature = torch.from_numpy(graphs.node_feat[n0:n1])
+        self.node_feature = None
+        self.input_dim = input_dim
+        if node_feature is not None:
+            nf = torch.as_tensor(node_feature, dtype=torch.float32)
+            if nf.dim() != 2 or nf.shape[0] != self.num_rows:
+                raise ValueError(f"GraphBatch: node_feature must be [{self.num_rows}, F], got {tuple(nf.shape)}")
+            self.node_feature = nf.to(device).contiguous()
+            self.input_dim = nf.shape[1]
+        self.y = None if y is None else y.to(device)
+
+    def __getattr__(self, name):
+        # vrowptr / vcol are built when first read: a batch handed out on the CPU by a dataset and moved to the GPU
+        # by the trainer (``to``) never runs the host routine, and its arrays are made where they are used
+        if name not in ("vrowptr", "vcol"):
+            raise AttributeError(name)
+        from . import ops
+        (n0, n1), (e0, e1) = self._nodes, self._edges
+        if self.device.type == "cuda":
+            rowptr, col = _graphset_device_csr(self.graphs, self.device)
+            self.vrowptr, self.vcol = ops.graph_tconv_dev(rowptr, col, n0, n1 - n0, e0, e1 - e0)
+        else:
+            vr, vc = ops.graph_tconv_host(self.graphs.rowptr, self.graphs.col, n0, n1 - n0)
+            self.vrowptr, self.vcol = torch.from_numpy(vr), torch.from_numpy(vc)
+        return self.__dict__[name]
+
+    def to(self, device):
+        if _norm_device(device) == self.device:
+            return self
+        return GraphBatch(self.graphs, device, self.g0, self.g1, self.node_feature, self.y, self.input_dim)
+
+    def _seg_ptr_host(self):
+        return self.graph_ptr_host
+
+    def _seg_ptr_device(self):
+        return self.graph_ptr
+
+
 class GossipBatch:
     """Whole target graphs for the gossip stage: symmetric CSR (ascending cols) + x [N,Q].
 

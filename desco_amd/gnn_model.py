@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .batch import GossipBatch, NeighborhoodBatch, QueryBatch
+from .batch import GossipBatch, GraphBatch, NeighborhoodBatch, QueryBatch
 
 H = 64
 # the fused gossip pass in the three-product fp16 form (csrc/gossip_f16.hip); False: the six-product bf16 kernel
@@ -363,8 +363,8 @@ class BaseGNN(nn.Module):
             if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
                 return gossip_forward_train(self, data, query_emb)
             return gossip_forward(self, data, query_emb)
-        if not isinstance(data, (NeighborhoodBatch, QueryBatch)):
-            raise TypeError("BaseGNN.forward expects a NeighborhoodBatch or QueryBatch")
+        if not isinstance(data, (NeighborhoodBatch, QueryBatch, GraphBatch)):
+            raise TypeError("BaseGNN.forward expects a NeighborhoodBatch, QueryBatch or GraphBatch")
         if self.gnn_core.node_types is None:
             raise NotImplementedError(
                 "homogeneous SAGE (ablation, hetero_graph=False) is out of the hot path; call "

@@ -169,13 +169,23 @@ class NeighborhoodCountingModel(_LightningLike):
             raise NotImplementedError("order-4 (union_1..11) SHMP is outside the hot path")
         return self.to_hetero_old(tconv_target=SHMP_target, tconv_query=SHMP_query)
 
+    def to_hetero_wo_canonical(self, tconv_target=False, tconv_query=False):     # :325-369
+        """The ablation without canonical partition: the target model reads WHOLE graphs (a ``GraphBatch``) and is of
+        the query model's shape -- one node type, the two relation slots, no anchor MLP (``anchor_mlp`` keeps its
+        parameters, as in the reference, and is never applied: BaseGNN.forward uses it on canonical rows only),
+        global_add_pool over all nodes of a graph, then post_mp."""
+        for gnn, tconv in ((self.emb_model, tconv_target), (self.emb_model_query, tconv_query)):
+            gnn.gnn_core.to_hetero(QUERY_NODE_TYPES, QUERY_EDGE_TYPES_TCONV if tconv else QUERY_EDGE_TYPES_UNION)
+        self.tconv_target, self.tconv_query = tconv_target, tconv_query
+        return self
+
     def on_load_checkpoint(self, checkpoint: Dict[str, Any]) -> None:   # :508-532
         a = checkpoint["hyper_parameters"]["args"]
         use_canonical = getattr(a, "use_canonical", True)
         if a.use_hetero and use_canonical:
             self.to_hetero_old(tconv_target=a.use_tconv, tconv_query=a.use_tconv)
         elif a.use_hetero:
-            raise NotImplementedError("to_hetero_wo_canonical (ablation) is outside the hot path")
+            self.to_hetero_wo_canonical(tconv_target=a.use_tconv, tconv_query=a.use_tconv)
 
     # ---- queries ----------------------------------------------------------------------------------
     def set_queries(self, query_ids, queries=None, transform=None, hetero=True, device=None):

@@ -858,6 +858,43 @@ def segment_ids(seg_ptr: torch.Tensor, num_rows: int) -> torch.Tensor:
     return out
 
 
+def graph_tconv_host(rowptr, col, node0: int, num_nodes: int, num_threads: int = 0):
+    """(vrowptr [2 num_nodes + 1], vcol [E]) int32 numpy: the 2-slot (union_triangle, union_tride) typed CSR of the
+    nodes [node0, node0 + num_nodes) of a graph set's CSR -- whole graphs --, re-based to the block, by the host
+    routine (desco_graph_tconv; host arrays, no GPU involved)."""
+    import numpy as np
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    if not (0 <= node0 and 0 <= num_nodes and node0 + num_nodes < len(rowptr)):
+        raise ValueError("graph_tconv_host: node range outside the CSR")
+    ne = int(rowptr[node0 + num_nodes] - rowptr[node0])
+    vrowptr, vcol = np.empty(2 * num_nodes + 1, dtype=np.int32), np.empty(ne, dtype=np.int32)
+    _lib.check(_lib.lib().desco_graph_tconv(rowptr.ctypes.data, col.ctypes.data, node0, num_nodes, vrowptr.ctypes.data,
+                                            vcol.ctypes.data, num_threads), "graph_tconv")
+    return vrowptr, vcol
+
+
+def graph_tconv_dev(rowptr: torch.Tensor, col: torch.Tensor, node0: int, num_nodes: int, edge0: int, num_edges: int):
+    """The same arrays on the device (desco_graph_tconv_dev: flag, scan, fill) from the set's device CSR (``rowptr``
+    int64, ``col`` int32); ``edge0`` = rowptr[node0] and ``num_edges`` are the caller's (it holds the host rowptr)."""
+    dev = rowptr.device
+    if not (0 <= node0 and 0 <= num_nodes and node0 + num_nodes < rowptr.numel() and 0 <= edge0 and 0 <= num_edges
+            and edge0 + num_edges <= col.numel()):
+        raise ValueError("graph_tconv_dev: node / edge range outside the CSR")
+    vrowptr = torch.empty(2 * num_nodes + 1, device=dev, dtype=torch.int32)
+    vcol = torch.empty(num_edges, device=dev, dtype=torch.int32)
+    L = _lib.lib()
+    ws = torch.empty((int(L.desco_graph_tconv_dev_workspace(num_edges)) + 7) // 8, device=dev, dtype=torch.int64)
+    with _Timed("graph_tconv_kernels", 0.0, 16.0 * num_edges + 16.0 * num_nodes, launches=3):
+        _lib.check(L.desco_graph_tconv_dev(_dev(rowptr, "rowptr", torch.int64),
+                                           _dev(col, "col", torch.int32) if num_edges else None, node0, num_nodes,
+                                           edge0, num_edges, _dev(vrowptr, "vrowptr", torch.int32),
+                                           _dev(vcol, "vcol", torch.int32) if num_edges else None,
+                                           _dev(ws, "workspace", torch.int64) if num_edges else None, _stream()),
+                   "graph_tconv_dev")
+    return vrowptr, vcol
+
+
 def partition_slice_dev(count_ptr: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, count_orig: torch.Tensor,
                         num_neigh: int, num_count: int, b0: int, b1: int, block_count: int, block_edges: int):
     """(count_ptr, count_orig, vrowptr, vcol) of neighborhoods [b0, b1) as a self-contained block, on the device

@@ -268,6 +268,7 @@ class Trainer:
         side = torch.cuda.Stream(self.device) if use_graphs else None
         for epoch in range(self.max_epochs):
             model.train()
+            step_losses = []     # (device scalar, graphs) of the plain eager steps: read once, at the epoch's end
             if use_graphs and multi:
                 self._ddp_epoch(model, opt, steps, buckets, ddp, side, capture=epoch >= 1)
             elif use_graphs:
@@ -285,12 +286,19 @@ class Trainer:
                     loss = model.training_step(batch, i)
                     AG.backward(loss)          # (loss.backward() seeded without torch's ones_like fill)
                     opt.step()
+                    step_losses.append((loss.detach(), batch.num_graphs))
             model.eval()
             val = self._mean_loss(model, datamodule.val_dataloader(), "validation_step")
             sched.step(val)
             if hasattr(opt, "sync_lr"):      # replayed steps read the rate from device memory (optim.Adam)
                 opt.sync_lr()
             self.history.append({"epoch": epoch, cfg["monitor"]: val, "lr": float(opt.param_groups[0]["lr"])})
+            if step_losses:
+                # the epoch's training loss (mean over its steps, weighted by their graphs; every step saw other
+                # weights): one read-back per epoch, none per step
+                w = torch.tensor([n for _, n in step_losses], dtype=torch.float64)
+                v = torch.stack([l.reshape(()) for l, _ in step_losses]).double().cpu()
+                self.history[-1]["train_loss"] = float((v * w).sum() / w.sum())
             if self._rank0() and self.verbose:
                 print(f"epoch {epoch}: {cfg['monitor']} = {val:.6g}  lr = {float(opt.param_groups[0]['lr']):.3g}",
                       flush=True)

@@ -16,7 +16,7 @@ from typing import Iterator, List, Optional
 import numpy as np
 import torch
 
-from .batch import GossipBatch, NeighborhoodBatch
+from .batch import GossipBatch, GraphBatch, NeighborhoodBatch
 from .graphs import GraphSet
 from .partition import NeighborhoodPartition, build_partition
 
@@ -166,6 +166,34 @@ class GossipDataset:
             yield self.batch(g0, min(g0 + batch_size, len(self)), device)
 
 
+class WoCanonicalDataset:
+    """One item per WHOLE target graph, for the model without canonical partition (workload.py:351-360, 800-833 of
+    the reference: a list of single-type hetero graphs with ``y`` [1, Q]).  Items batch into ``GraphBatch``es over
+    graph ranges of the one ``GraphSet``; ``y`` [G, Q] is what Workload.generate_wo_canonical_dataset stores."""
+
+    def __init__(self, dataset, y: Optional[torch.Tensor] = None, transform=None, node_feat: bool = False):
+        _check_transforms("WoCanonicalDataset", transform, None, None)
+        self.dataset = _as_graphset(dataset)
+        self.transform = transform
+        self.node_feat = bool(node_feat)
+        if self.node_feat and self.dataset.node_feat is None:
+            raise ValueError("node_feat=True needs a dataset with node features (GraphSet.node_feat)")
+        if y is not None and len(y) != self.dataset.num_graphs:
+            raise ValueError(f"y has {len(y)} rows for {self.dataset.num_graphs} graphs")
+        self.y = y
+
+    def __len__(self):
+        return self.dataset.num_graphs
+
+    def batch(self, g0: int, g1: int, device="cpu") -> GraphBatch:
+        return GraphBatch(self.dataset, device, g0, g1, node_feature=True if self.node_feat else None,
+                          y=None if self.y is None else self.y[g0:g1])
+
+    def batches(self, batch_size: int, device="cpu") -> Iterator[GraphBatch]:
+        for g0 in range(0, len(self), batch_size):
+            yield self.batch(g0, min(g0 + batch_size, len(self)), device)
+
+
 class Workload:
     """Owns the target dataset, ground truth and the two pipeline datasets (workload.py:363-747)."""
 
@@ -188,6 +216,8 @@ class Workload:
         self.canonical_count_truth = torch.tensor([[]])
         self.neighborhood_dataset: Optional[NeighborhoodDataset] = None
         self.gossip_dataset: Optional[GossipDataset] = None
+        self.graphlet_count_truth: Optional[torch.Tensor] = None
+        self.wo_canonical_dataset: Optional[WoCanonicalDataset] = None
 
     def generate_pipeline_datasets(self, depth_neigh, neighborhood_transform=None,
                                    gossip_transform=None, pre_transform=None, pre_filter=None,
@@ -242,6 +272,29 @@ class Workload:
             os.makedirs(os.path.dirname(path), exist_ok=True)
             torch.save(truth, path)
         return truth
+
+    # ---- the ablation without canonical partition (workload.py:771-833) ---------------------------
+    def canonical_to_graphlet_truth(self, canonical_count_truth: torch.Tensor) -> torch.Tensor:   # :791-798
+        """[G, Q] per-graph sums of the canonical counts [V, Q] (a node-level count summed over a graph's nodes is the
+        graph's count of the pattern)."""
+        t = torch.as_tensor(canonical_count_truth)
+        gid = torch.from_numpy(self.dataset.node_graph_ids())
+        out = torch.zeros((self.dataset.num_graphs, t.shape[1]), dtype=t.dtype)
+        out.index_add_(0, gid, t)
+        self.graphlet_count_truth = out
+        return out
+
+    def generate_wo_canonical_dataset(self, transform=None):                    # :800-833
+        """``self.wo_canonical_dataset``: the whole graphs with ``y = log2(graphlet_count_truth + 1)`` -- the reference
+        stores the LOGARITHM here (:829-831) and the model's losses take log2(y + 1) of it once more
+        (lightning_model.py:244-248); kept as it is, see DESIGN.md section 7.  ``transform``: ToTconvHetero or None (the
+        batch always carries both relation slots; a model without tconv ties them to one weight)."""
+        if getattr(self, "graphlet_count_truth", None) is None:
+            raise RuntimeError("call canonical_to_graphlet_truth() first (ablation_wo_canonical.py)")
+        y = torch.log2(self.graphlet_count_truth + 1).to(torch.float32)
+        self.wo_canonical_dataset = WoCanonicalDataset(self.dataset, y, transform=transform,
+                                                       node_feat=self.use_node_feat)
+        return self.wo_canonical_dataset
 
     # ---- stage glue --------------------------------------------------------------------------------
     def apply_neighborhood_count(self, count):                                    # :728-731

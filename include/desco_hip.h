@@ -161,6 +161,30 @@ int desco_pool_index_dev(const int32_t* count_ptr, int64_t num_neigh, int64_t nu
 int desco_neigh_rows_dev(const int64_t* neigh_index, int64_t num_neigh, const int64_t* graph_ptr, int64_t num_graphs,
                          int32_t* scatter_index, int32_t* neigh_graph_ptr, desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Typed CSR of WHOLE graphs: what the model without canonical partition (to_hetero_wo_canonical) reads of its target
+ * graphs -- one node type, the two relation slots of the query model (csrc/graph_tconv.cpp, csrc/graph_tconv_dev.hip).
+ * Input: the CSR of a graph set over global node ids, rowptr int64 / col int32 (symmetric, loop free, rows ascending),
+ * and a block of whole graphs in it, the nodes [node0, node0 + num_nodes) (graph_ptr[g0] .. graph_ptr[g1]; the graph
+ * boundaries inside the block play no part, an edge never leaves its graph).  Output, re-based to the block:
+ *   vrowptr[2 num_nodes + 1]: entry 2 v + t starts the sources of row v in slot t; slot 0 = "union_triangle" (source
+ *      and row share a neighbour), slot 1 = "union_tride" (they do not) -- ToTconvHetero, transforms.py:180-255
+ *   vcol[num_edges]: source rows (node id - node0), ascending inside each (row, slot)
+ * with num_edges = rowptr[node0 + num_nodes] - rowptr[node0] <= INT32_MAX.  A source outside the block counts as tride.
+ *
+ * desco_graph_tconv: HOST arrays, OpenMP over rows (num_threads 0 = the runtime's default).
+ * desco_graph_tconv_dev: DEVICE arrays; edge0 = rowptr[node0] and num_edges are passed by the caller (who allocated
+ *   vcol with them); workspace: desco_graph_tconv_dev_workspace(num_edges) bytes, 8-byte aligned (may be NULL without
+ *   edges).  Three launches on `stream` (flag, scan, fill), no allocation, no synchronisation, no atomics; the work of
+ *   a lane does not grow with the degree of a hub and nothing is sized by the largest graph.  Bit-identical to the
+ *   host routine.
+ * ------------------------------------------------------------------------------------------ */
+int desco_graph_tconv(const int64_t* rowptr, const int32_t* col, int64_t node0, int64_t num_nodes, int32_t* vrowptr,
+                      int32_t* vcol, int num_threads);
+size_t desco_graph_tconv_dev_workspace(int64_t num_edges);
+int desco_graph_tconv_dev(const int64_t* rowptr, const int32_t* col, int64_t node0, int64_t num_nodes, int64_t edge0,
+                          int64_t num_edges, int32_t* vrowptr, int32_t* vcol, void* workspace, desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
