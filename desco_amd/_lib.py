@@ -71,6 +71,7 @@ SIGNATURES = {
     "desco_device_count": (c_int, []),
     "desco_last_error": (c_char_p, []),
     "desco_partition_build": (c_int, [vp, i64, vp, vp, i32, i32, i32, POINTER(vp)]),
+    "desco_partition_build_mode": (c_int, [vp, i64, vp, vp, i32, i32, i32, i32, POINTER(vp)]),
     "desco_partition_sizes": (c_int, [vp, POINTER(i64), POINTER(i64), POINTER(i64), POINTER(i64)]),
     "desco_partition_export": (c_int, [vp, vp, vp, vp, vp, vp, vp]),
     "desco_partition_free": (None, [vp]),
@@ -141,6 +142,9 @@ SIGNATURES = {
     "desco_partition_dev_scan": (c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
     "desco_partition_dev_fill": (c_int, [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp,
                                          i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "desco_partition_dev_count_mode": (c_int, [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "desco_partition_dev_fill_mode": (c_int, [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp,
+                                              i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
     "desco_partition_dev_slice": (c_int, [vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
     "desco_partition_dev_degree_sort_workspace": (ctypes.c_size_t, [i64, i64]),
     "desco_partition_dev_degree_sort": (c_int, [vp, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp]),

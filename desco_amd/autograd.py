@@ -851,9 +851,9 @@ class FoldSpec:
 
         rows = []
         for l in range(L):
-            row = [add(core.updates[l][t].weight), add(core.updates[l][t].bias)]
-            row += [add(core.convs[l][k].lin.weight) for k in keys]
-            row += [add(core.convs[l][k].lin.bias) for k in uniq]
+            row = [add(core.update(l, t).weight), add(core.update(l, t).bias)]
+            row += [add(core.conv(l, k).lin.weight) for k in keys]
+            row += [add(core.conv(l, k).lin.bias) for k in uniq]
             rows.append(row)
         self.params = params
         self._core, self._t, self._keys, self._uniq = core, t, keys, uniq
@@ -877,9 +877,9 @@ class FoldSpec:
         core, t = self._core, self._t
         live = []
         for l in range(self.L):
-            live += [core.updates[l][t].weight, core.updates[l][t].bias]
-            live += [core.convs[l][k].lin.weight for k in self._keys]
-            live += [core.convs[l][k].lin.bias for k in self._uniq]
+            live += [core.update(l, t).weight, core.update(l, t).bias]
+            live += [core.conv(l, k).lin.weight for k in self._keys]
+            live += [core.conv(l, k).lin.bias for k in self._uniq]
         seen, uniq_live = set(), []
         for p in live:
             if id(p) not in seen:

@@ -71,7 +71,10 @@ class NeighborhoodBatch(_TrainIndexMixin):
     slots = 4
 
     def __init__(self, part: NeighborhoodPartition, device, node_feature: Optional[torch.Tensor] = None,
-                 y: Optional[torch.Tensor] = None, input_dim: int = 1):
+                 y: Optional[torch.Tensor] = None, input_dim: int = 1, anchor_flag: bool = False):
+        """``anchor_flag``: the batch of a homogeneous model (NeighborhoodDataset(hetero_graph=False)) -- ``node_feature``
+        [num_rows, 1] is 0 on the count rows and 1 on the canonical rows (get_neigh_canonical, data.py:369-371), made on
+        ``device`` (and made again there by ``to``: never uploaded)."""
         self.part = part
         self.device = _norm_device(device)
         device = self.device
@@ -88,11 +91,20 @@ class NeighborhoodBatch(_TrainIndexMixin):
         self.input_dim = input_dim if node_feature is None else node_feature.shape[1]
         # None == all-zero features (ZeroNodeFeat, workload.py:431-440): pre_mp output is its bias
         self.node_feature = None if node_feature is None else node_feature.to(device).float()
+        self.anchor_flag = bool(anchor_flag)
+        if self.anchor_flag:
+            if node_feature is not None:
+                raise ValueError("NeighborhoodBatch: anchor_flag makes node_feature itself; pass none")
+            self.input_dim = 1
+            self.node_feature = torch.zeros((self.num_rows, 1), device=device)
+            self.node_feature[self.num_count:] = 1.0
         self.y = None if y is None else y.to(device)
 
     def to(self, device):
         if _norm_device(device) == self.device:
             return self
+        if self.anchor_flag:
+            return NeighborhoodBatch(self.part, device, None, self.y, 1, anchor_flag=True)
         return NeighborhoodBatch(self.part, device, self.node_feature, self.y, self.input_dim)
 
     def _seg_ptr_host(self):

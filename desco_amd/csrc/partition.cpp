@@ -73,8 +73,11 @@ inline bool share_neighbor(const int32_t* ra, int da, const int32_t* rb, int db,
   return false;
 }
 
+// restricted = the homogeneous ablation's node set (k_neigh_canonical, data.py:341-350): `depth` BFS
+// rounds from v that only step onto ids <= v; no full-graph ball, connected as built.  Steps (4) on
+// are shared.
 void process_graph(int64_t base, int64_t n, const int64_t* rowptr, const int32_t* col, int depth,
-                   Scratch& s, GraphOut& o) {
+                   bool restricted, Scratch& s, GraphOut& o) {
   s.ensure((size_t)n);
   o.indicator.assign((size_t)n, 0);
   for (int64_t v = 0; v < n; ++v) {
@@ -85,42 +88,66 @@ void process_graph(int64_t base, int64_t n, const int64_t* rowptr, const int32_t
       s.stamp = 0;
     }
     const int32_t st = ++s.stamp;
-    // (1) BFS ball of radius `depth` in the FULL graph (data.py:329-338)
-    s.ball.clear();
-    s.frontier.clear();
-    s.frontier.push_back((int32_t)v);
-    s.mark_ball[v] = st;
-    s.ball.push_back((int32_t)v);
-    for (int l = 0; l < depth && !s.frontier.empty(); ++l) {
-      s.next.clear();
-      for (int32_t u : s.frontier) {
-        const int64_t gu = base + u;
-        for (int64_t e = rowptr[gu]; e < rowptr[gu + 1]; ++e) {
-          const int32_t w = (int32_t)(col[e] - base);
-          if (s.mark_ball[w] != st) {
-            s.mark_ball[w] = st;
-            s.next.push_back(w);
-            s.ball.push_back(w);
+    if (restricted) {
+      s.comp.clear();
+      s.comp.push_back((int32_t)v);
+      s.mark_comp[v] = st;
+      s.frontier.clear();
+      s.frontier.push_back((int32_t)v);
+      for (int l = 0; l < depth && !s.frontier.empty(); ++l) {
+        s.next.clear();
+        for (int32_t u : s.frontier) {
+          const int64_t gu = base + u;
+          for (int64_t e = rowptr[gu]; e < rowptr[gu + 1]; ++e) {
+            const int32_t w = (int32_t)(col[e] - base);
+            if (w > v) break;  // rows sorted ascending
+            if (s.mark_comp[w] != st) {
+              s.mark_comp[w] = st;
+              s.next.push_back(w);
+              s.comp.push_back(w);
+            }
           }
         }
+        s.frontier.swap(s.next);
       }
-      s.frontier.swap(s.next);
-    }
-    // (2) keep ids <= v, applied AFTER the BFS (data.py:385)
-    for (int32_t u : s.ball)
-      if (u <= v) s.mark_keep[u] = st;
-    // (3) connected component of v inside the induced subgraph (data.py:387-390)
-    s.comp.clear();
-    s.comp.push_back((int32_t)v);
-    s.mark_comp[v] = st;
-    for (size_t h = 0; h < s.comp.size(); ++h) {
-      const int64_t gu = base + s.comp[h];
-      for (int64_t e = rowptr[gu]; e < rowptr[gu + 1]; ++e) {
-        const int32_t w = (int32_t)(col[e] - base);
-        if (w > v) break;  // rows sorted ascending
-        if (s.mark_keep[w] == st && s.mark_comp[w] != st) {
-          s.mark_comp[w] = st;
-          s.comp.push_back(w);
+    } else {
+      // (1) BFS ball of radius `depth` in the FULL graph (data.py:329-338)
+      s.ball.clear();
+      s.frontier.clear();
+      s.frontier.push_back((int32_t)v);
+      s.mark_ball[v] = st;
+      s.ball.push_back((int32_t)v);
+      for (int l = 0; l < depth && !s.frontier.empty(); ++l) {
+        s.next.clear();
+        for (int32_t u : s.frontier) {
+          const int64_t gu = base + u;
+          for (int64_t e = rowptr[gu]; e < rowptr[gu + 1]; ++e) {
+            const int32_t w = (int32_t)(col[e] - base);
+            if (s.mark_ball[w] != st) {
+              s.mark_ball[w] = st;
+              s.next.push_back(w);
+              s.ball.push_back(w);
+            }
+          }
+        }
+        s.frontier.swap(s.next);
+      }
+      // (2) keep ids <= v, applied AFTER the BFS (data.py:385)
+      for (int32_t u : s.ball)
+        if (u <= v) s.mark_keep[u] = st;
+      // (3) connected component of v inside the induced subgraph (data.py:387-390)
+      s.comp.clear();
+      s.comp.push_back((int32_t)v);
+      s.mark_comp[v] = st;
+      for (size_t h = 0; h < s.comp.size(); ++h) {
+        const int64_t gu = base + s.comp[h];
+        for (int64_t e = rowptr[gu]; e < rowptr[gu + 1]; ++e) {
+          const int32_t w = (int32_t)(col[e] - base);
+          if (w > v) break;  // rows sorted ascending
+          if (s.mark_keep[w] == st && s.mark_comp[w] != st) {
+            s.mark_comp[w] = st;
+            s.comp.push_back(w);
+          }
         }
       }
     }
@@ -168,9 +195,15 @@ struct desco_partition {
   std::vector<int32_t> count_ptr, count_orig, vrowptr, vcol;
 };
 
-extern "C" int desco_partition_build(const int64_t* graph_ptr, int64_t num_graphs,
-                                     const int64_t* rowptr, const int32_t* col, int depth,
-                                     int quirk_batch, int num_threads, desco_partition** out) {
+extern "C" int desco_partition_build_mode(const int64_t* graph_ptr, int64_t num_graphs,
+                                          const int64_t* rowptr, const int32_t* col, int depth, int mode,
+                                          int quirk_batch, int num_threads, desco_partition** out) {
+  if (mode != DESCO_NEIGH_BALL && mode != DESCO_NEIGH_RESTRICTED)
+    return desco::fail(DESCO_EINVAL, "desco_partition_build_mode: unknown neighborhood mode");
+  if (mode == DESCO_NEIGH_RESTRICTED && quirk_batch != 0)
+    return desco::fail(DESCO_EINVAL, "desco_partition_build_mode: the remove_self_loops quirk emulation (quirk_batch) "
+                                     "is not offered for restricted neighborhoods; pass 0");
+  const bool restricted = mode == DESCO_NEIGH_RESTRICTED;
   if (!graph_ptr || !rowptr || (!col && rowptr[graph_ptr[num_graphs]] > 0) || !out || depth < 0 ||
       num_graphs < 0 || quirk_batch < 0)
     return desco::fail(DESCO_EINVAL, "desco_partition_build: bad argument");
@@ -193,7 +226,7 @@ extern "C" int desco_partition_build(const int64_t* graph_ptr, int64_t num_graph
           err = 1;
           continue;
         }
-        process_graph(base, n, rowptr, col, depth, s, gout[(size_t)g]);
+        process_graph(base, n, rowptr, col, depth, restricted, s, gout[(size_t)g]);
       }
     }
     if (err) return desco::fail(DESCO_EINVAL, "desco_partition_build: graph_ptr not monotone");
@@ -323,6 +356,13 @@ extern "C" int desco_partition_build(const int64_t* graph_ptr, int64_t num_graph
   } catch (const std::bad_alloc&) {
     return desco::fail(DESCO_ENOMEM, "desco_partition_build: out of memory");
   }
+}
+
+extern "C" int desco_partition_build(const int64_t* graph_ptr, int64_t num_graphs,
+                                     const int64_t* rowptr, const int32_t* col, int depth,
+                                     int quirk_batch, int num_threads, desco_partition** out) {
+  return desco_partition_build_mode(graph_ptr, num_graphs, rowptr, col, depth, DESCO_NEIGH_BALL, quirk_batch,
+                                    num_threads, out);
 }
 
 extern "C" int desco_partition_sizes(const desco_partition* p, int64_t* num_neigh,

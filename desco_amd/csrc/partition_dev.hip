@@ -20,6 +20,11 @@
 // bit, and the canonical node (the maximum id) is the last bit.  Output is bit-identical to the host
 // builder's (tests/test_partition_dev_gpu.py).  The PyG remove_self_loops quirk emulation
 // (quirk_batch) is only offered by the host builder.
+//
+// mode = DESCO_NEIGH_RESTRICTED (the *_mode entry points) is the homogeneous ablation's definition
+// (k_neigh_canonical, data.py:341-350): `depth` BFS rounds from v that only ever step onto ids <= v.
+// There is no full-graph ball -- step (1) and the ball test drop out, step (2) gets the depth limit --
+// and everything after the node set (edges, slots, rows, layout) is the same code.
 #include "common_device.hpp"
 
 namespace desco {
@@ -55,8 +60,9 @@ __device__ __forceinline__ bool bm_test(const uint32_t* bm, int i) { return (bm[
 
 // One BFS expansion sweep of the whole wave: for every node of `cur`, lanes stride over its
 // adjacency; newly marked nodes are appended to `nxt` (wave-aggregated).  COMP = false: ball of the
-// full graph; COMP = true: only neighbours <= v that are in the ball bitmap.
-template <bool COMP>
+// full graph; COMP = true: only neighbours <= v that are in the ball bitmap (BALL = false: any
+// neighbour <= v, the restricted definition).
+template <bool COMP, bool BALL = true>
 __device__ __forceinline__ int expand(const PartDevArgs& g, int64_t base, int v, const int* cur, int ncur,
                                       int* nxt, uint32_t* bm_mark, const uint32_t* bm_ball, int lane) {
   int nn = 0;
@@ -69,7 +75,7 @@ __device__ __forceinline__ int expand(const PartDevArgs& g, int64_t base, int v,
       int w = 0;
       if (e < e1) {
         w = g.col[e] - (int)base;
-        const bool ok = COMP ? (w <= v && bm_test(bm_ball, w)) : true;
+        const bool ok = COMP ? (w <= v && (!BALL || bm_test(bm_ball, w))) : true;
         if (ok) {
           const uint32_t bit = 1u << (w & 31);
           const uint32_t old = atomicOr(&bm_mark[w >> 5], bit);
@@ -103,7 +109,7 @@ __device__ __forceinline__ bool share_neighbor(const int32_t* ra, int da, const 
   return false;
 }
 
-template <bool FILL>
+template <bool FILL, bool RESTRICTED>
 __global__ __launch_bounds__(256) void partition_dev_kernel(PartDevArgs g) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -133,23 +139,26 @@ __global__ __launch_bounds__(256) void partition_dev_kernel(PartDevArgs g) {
       bm_comp[i] = 0u;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    // (1) BFS ball of radius depth in the FULL graph (data.py:329-338)
-    if (lane == 0) {
-      bm_ball[v >> 5] = 1u << (v & 31);
-      qa[0] = v;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     int* cur = qa;
     int* nxt = qb;
     int ncur = 1;
-    for (int l = 0; l < g.depth && ncur > 0; ++l) {
-      ncur = expand<false>(g, base, v, cur, ncur, nxt, bm_ball, bm_ball, lane);
-      int* t = cur;
-      cur = nxt;
-      nxt = t;
+    if (!RESTRICTED) {
+      // (1) BFS ball of radius depth in the FULL graph (data.py:329-338)
+      if (lane == 0) {
+        bm_ball[v >> 5] = 1u << (v & 31);
+        qa[0] = v;
+      }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      for (int l = 0; l < g.depth && ncur > 0; ++l) {
+        ncur = expand<false>(g, base, v, cur, ncur, nxt, bm_ball, bm_ball, lane);
+        int* t = cur;
+        cur = nxt;
+        nxt = t;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      }
     }
-    // (2)+(3) ids <= v (applied after the BFS, data.py:385) and the component of v (data.py:387-390)
+    // (2)+(3) ids <= v (applied after the BFS, data.py:385) and the component of v (data.py:387-390);
+    // RESTRICTED: `depth` rounds that only step onto ids <= v (data.py:341-350), connected as built
     if (lane == 0) {
       bm_comp[v >> 5] = 1u << (v & 31);
       qa[0] = v;
@@ -159,8 +168,8 @@ __global__ __launch_bounds__(256) void partition_dev_kernel(PartDevArgs g) {
     nxt = qb;
     ncur = 1;
     int nn = 1;
-    while (ncur > 0) {
-      ncur = expand<true>(g, base, v, cur, ncur, nxt, bm_comp, bm_ball, lane);
+    for (int l = 0; (!RESTRICTED || l < g.depth) && ncur > 0; ++l) {
+      ncur = expand<true, !RESTRICTED>(g, base, v, cur, ncur, nxt, bm_comp, bm_ball, lane);
       nn += ncur;
       int* t = cur;
       cur = nxt;
@@ -357,27 +366,32 @@ static int64_t part_ws_words(int n_max) {
   return 3 * nw + 2 * (int64_t)n_max + ((int64_t)n_max + 3) / 4 + 4;
 }
 
-static int part_dev_launch(bool fill, const PartDevArgs& a, int num_waves, hipStream_t st) {
+template <bool FILL, bool RESTRICTED>
+static int part_dev_launch_as(const PartDevArgs& a, unsigned blocks, size_t lds, hipStream_t st) {
+  const hipError_t e = size_dynamic_lds<partition_dev_kernel<FILL, RESTRICTED>>(160 * 1024);
+  if (e != hipSuccess)
+    return fail((int)e, FILL ? "desco_partition_dev_fill: cannot size LDS" : "desco_partition_dev_count: cannot size LDS");
+  hipLaunchKernelGGL((partition_dev_kernel<FILL, RESTRICTED>), dim3(blocks), dim3(256), lds, st, a);
+  return launch_status(FILL ? "desco_partition_dev_fill" : "desco_partition_dev_count");
+}
+
+static int part_dev_launch(bool fill, bool restricted, const PartDevArgs& a, int num_waves, hipStream_t st) {
   const unsigned blocks = (unsigned)((num_waves + 3) / 4);
   const size_t lds = (size_t)4 * a.ws_words * sizeof(uint32_t);
   if (lds > 160 * 1024)
     return fail(DESCO_EINVAL, "desco_partition_dev: largest graph does not fit the LDS workspace "
                               "(use desco_partition_build)");
-  const hipError_t e = fill ? size_dynamic_lds<partition_dev_kernel<true>>(160 * 1024)
-                            : size_dynamic_lds<partition_dev_kernel<false>>(160 * 1024);
-  if (e != hipSuccess)
-    return fail((int)e, fill ? "desco_partition_dev_fill: cannot size LDS" : "desco_partition_dev_count: cannot size LDS");
   if (fill)
-    hipLaunchKernelGGL(partition_dev_kernel<true>, dim3(blocks), dim3(256), lds, st, a);
-  else
-    hipLaunchKernelGGL(partition_dev_kernel<false>, dim3(blocks), dim3(256), lds, st, a);
-  return launch_status(fill ? "desco_partition_dev_fill" : "desco_partition_dev_count");
+    return restricted ? part_dev_launch_as<true, true>(a, blocks, lds, st) : part_dev_launch_as<true, false>(a, blocks, lds, st);
+  return restricted ? part_dev_launch_as<false, true>(a, blocks, lds, st) : part_dev_launch_as<false, false>(a, blocks, lds, st);
 }
 
-extern "C" int desco_partition_dev_count(const int64_t* graph_ptr, const int32_t* node_graph,
-                                         const int32_t* rowptr, const int32_t* col, int64_t num_nodes,
-                                         int depth, int n_max, int num_waves, int32_t* nsize, int32_t* ecnt_count, int32_t* ecnt_canon,
-                                         desco_stream_t stream) {
+extern "C" int desco_partition_dev_count_mode(const int64_t* graph_ptr, const int32_t* node_graph,
+                                              const int32_t* rowptr, const int32_t* col, int64_t num_nodes,
+                                              int depth, int mode, int n_max, int num_waves, int32_t* nsize,
+                                              int32_t* ecnt_count, int32_t* ecnt_canon, desco_stream_t stream) {
+  if (mode != DESCO_NEIGH_BALL && mode != DESCO_NEIGH_RESTRICTED)
+    return fail(DESCO_EINVAL, "desco_partition_dev_count_mode: unknown neighborhood mode");
   if (num_nodes == 0) return 0;
   if (!graph_ptr || !node_graph || !rowptr || !nsize || !ecnt_count || !ecnt_canon ||
       num_nodes < 0 || depth < 0 || n_max < 1 || num_waves < 4 || num_waves % 4)
@@ -394,7 +408,15 @@ extern "C" int desco_partition_dev_count(const int64_t* graph_ptr, const int32_t
   a.nsize = nsize;
   a.ecnt_count = ecnt_count;
   a.ecnt_canon = ecnt_canon;
-  return part_dev_launch(false, a, num_waves, (hipStream_t)stream);
+  return part_dev_launch(false, mode == DESCO_NEIGH_RESTRICTED, a, num_waves, (hipStream_t)stream);
+}
+
+extern "C" int desco_partition_dev_count(const int64_t* graph_ptr, const int32_t* node_graph,
+                                         const int32_t* rowptr, const int32_t* col, int64_t num_nodes,
+                                         int depth, int n_max, int num_waves, int32_t* nsize, int32_t* ecnt_count, int32_t* ecnt_canon,
+                                         desco_stream_t stream) {
+  return desco_partition_dev_count_mode(graph_ptr, node_graph, rowptr, col, num_nodes, depth, DESCO_NEIGH_BALL, n_max,
+                                        num_waves, nsize, ecnt_count, ecnt_canon, stream);
 }
 
 extern "C" int desco_partition_dev_scan(const int32_t* nsize, const int32_t* ecnt_count,
@@ -411,14 +433,16 @@ extern "C" int desco_partition_dev_scan(const int32_t* nsize, const int32_t* ecn
   return launch_status("desco_partition_dev_scan");
 }
 
-extern "C" int desco_partition_dev_fill(const int64_t* graph_ptr, const int32_t* node_graph,
-                                        const int32_t* rowptr, const int32_t* col, int64_t num_nodes,
-                                        int depth, int n_max, int num_waves, const int64_t* b_index, const int64_t* row_off,
-                                        const int64_t* eoff_count, const int64_t* eoff_canon,
-                                        int64_t num_neigh, int64_t num_count, int64_t edges_count,
-                                        int64_t edges_canon, int64_t* neigh_index, uint8_t* indicator,
-                                        int32_t* count_ptr, int32_t* count_orig, int32_t* vrowptr,
-                                        int32_t* vcol, desco_stream_t stream) {
+extern "C" int desco_partition_dev_fill_mode(const int64_t* graph_ptr, const int32_t* node_graph,
+                                             const int32_t* rowptr, const int32_t* col, int64_t num_nodes,
+                                             int depth, int mode, int n_max, int num_waves, const int64_t* b_index,
+                                             const int64_t* row_off, const int64_t* eoff_count,
+                                             const int64_t* eoff_canon, int64_t num_neigh, int64_t num_count,
+                                             int64_t edges_count, int64_t edges_canon, int64_t* neigh_index,
+                                             uint8_t* indicator, int32_t* count_ptr, int32_t* count_orig,
+                                             int32_t* vrowptr, int32_t* vcol, desco_stream_t stream) {
+  if (mode != DESCO_NEIGH_BALL && mode != DESCO_NEIGH_RESTRICTED)
+    return fail(DESCO_EINVAL, "desco_partition_dev_fill_mode: unknown neighborhood mode");
   if (num_nodes == 0) return 0;
   if (!graph_ptr || !node_graph || !rowptr || !b_index || !row_off || !eoff_count ||
       !eoff_canon || !indicator || !count_ptr || !vrowptr || num_nodes < 0 || depth < 0 || n_max < 1 ||
@@ -449,5 +473,19 @@ extern "C" int desco_partition_dev_fill(const int64_t* graph_ptr, const int32_t*
   a.vrowptr = vrowptr;
   a.vcol = vcol;
   a.Etotal = edges_count + edges_canon;
-  return part_dev_launch(true, a, num_waves, (hipStream_t)stream);
+  return part_dev_launch(true, mode == DESCO_NEIGH_RESTRICTED, a, num_waves, (hipStream_t)stream);
+}
+
+extern "C" int desco_partition_dev_fill(const int64_t* graph_ptr, const int32_t* node_graph,
+                                        const int32_t* rowptr, const int32_t* col, int64_t num_nodes,
+                                        int depth, int n_max, int num_waves, const int64_t* b_index, const int64_t* row_off,
+                                        const int64_t* eoff_count, const int64_t* eoff_canon,
+                                        int64_t num_neigh, int64_t num_count, int64_t edges_count,
+                                        int64_t edges_canon, int64_t* neigh_index, uint8_t* indicator,
+                                        int32_t* count_ptr, int32_t* count_orig, int32_t* vrowptr,
+                                        int32_t* vcol, desco_stream_t stream) {
+  return desco_partition_dev_fill_mode(graph_ptr, node_graph, rowptr, col, num_nodes, depth, DESCO_NEIGH_BALL, n_max,
+                                       num_waves, b_index, row_off, eoff_count, eoff_canon, num_neigh, num_count,
+                                       edges_count, edges_canon, neigh_index, indicator, count_ptr, count_orig,
+                                       vrowptr, vcol, stream);
 }

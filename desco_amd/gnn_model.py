@@ -74,6 +74,9 @@ QUERY_EDGE_TYPES_TCONV = [
     ("union_node", "union_tride", "union_node"),
 ]
 QUERY_EDGE_TYPES_UNION = [("union_node", "union", "union_node")]
+# a homogeneous core (use_hetero=False) serves every row type of the batches with its one set of weights
+HOMO_ROW_TYPES = ["count", "canonical", "union_node"]
+HOMO_KEY = "lin"
 
 
 # widths of the neighborhood / query models (--neigh_hidden_dim): H == 64 runs the fused kernels; any other width up to
@@ -222,6 +225,9 @@ class BaseGNNCore(nn.Module):
         self.post_input_dim = hidden_dim * args.layer_num + pre_dim_out          # :207
         self.node_types: Optional[List[str]] = None
         self.edge_types: Optional[List[Tuple[str, str, str]]] = None
+        # the row types a HOMOGENEOUS core packs operands for (row_types()); the owner narrows it to what its batches
+        # hold (NeighborhoodCountingModel: count + canonical for the target model, union_node for the query model)
+        self.homo_row_types: List[str] = list(HOMO_ROW_TYPES)
 
     def to_hetero(self, node_types: Sequence[str], edge_types: Sequence[Tuple[str, str, str]]):
         """pyg.nn.to_hetero(aggr="sum") equivalent for this module [EXT, SURVEY App. C]."""
@@ -241,8 +247,38 @@ class BaseGNNCore(nn.Module):
         self.node_types, self.edge_types = list(node_types), [tuple(e) for e in edge_types]
         return self
 
+    # ---- per-type / per-relation accessors ----------------------------------------------------------------------------
+    # What the weight packers read.  After ``to_hetero`` they index the per-type / per-relation ModuleDicts; a
+    # HOMOGENEOUS core (use_hetero=False, never converted: the reference's ablation_gnns.py model) has ONE pre_mp, one
+    # convs[l].lin and one updates[l], which every row type and relation slot reads -- so the same Parameter enters a
+    # fold several times and autograd sums its gradient over the uses.  (Aliasing the module inside ModuleDicts would
+    # duplicate the state-dict keys.)
+    def is_homogeneous(self) -> bool:
+        return self.node_types is None and not self.use_hetero and self.conv_type == "SAGE"
+
+    def row_types(self) -> List[str]:
+        """the row types a batch can hold: the model's node types, or ``homo_row_types`` for a homogeneous core"""
+        if self.node_types is not None:
+            return self.node_types
+        if not self.is_homogeneous():
+            raise NotImplementedError("the SAGE core has no node types yet: call to_hetero_old()/to_hetero() first "
+                                      "(main.py:221-224), or build the model with use_hetero=False (ablation_gnns.py)")
+        return self.homo_row_types
+
+    def pre_lin(self, t: str) -> nn.Linear:
+        return self.pre_mp[0] if self.node_types is None else self.pre_mp[0][t]
+
+    def conv(self, l: int, key: str) -> SAGEConv:
+        return self.convs[l] if self.node_types is None else self.convs[l][key]
+
+    def update(self, l: int, t: str) -> nn.Linear:
+        return self.updates[l] if self.node_types is None else self.updates[l][t]
+
     def slot_keys(self, dst_type: str) -> List[str]:
         """Module keys of the relation slots (triangle, tride) x (source types) feeding dst_type."""
+        if self.node_types is None:
+            self.row_types()                     # (raises unless homogeneous)
+            return [HOMO_KEY] * (4 if dst_type == "count" else 2)      # one relation: one weight, one bias
         keys = []
         srcs = [dst_type] if len(self.node_types) == 1 else ["count", "canonical"]
         for src in srcs:
@@ -289,8 +325,18 @@ class BaseGNNCore(nn.Module):
                     emb = torch.cat((emb, h), 1)                                                          # :275
                 return emb
             if self.node_types is None:
-                raise NotImplementedError("homogeneous SAGE (ablation) is out of the hot path; call to_hetero first")
-            xs = {t: ops.linear_smallk(x[t].float().contiguous(), ops.transposed(self.pre_mp[0][t].weight),
+                # homogeneous SAGE (ablation_gnns.py): ``x`` [N, input_dim], ``edge_index`` [2, E]; returns [N, 64 (L + 1)]
+                self.row_types()                                                                          # (raises unless homogeneous)
+                lin = self.pre_mp[0]
+                h = ops.linear_smallk(x.float().contiguous(), ops.transposed(lin.weight), lin.bias)       # :231
+                emb = h
+                for l in range(self.layer_num):
+                    x_neigh = self.convs[l](h, edge_index)                                                # :262
+                    up = self.updates[l]
+                    h = self._relu_dropout(ops.gemm(x_neigh, ops.transposed(up.weight), up.bias, a2=h.contiguous()), l)
+                    emb = torch.cat((emb, h), 1)                                                          # :275
+                return emb
+            xs ={t: ops.linear_smallk(x[t].float().contiguous(), ops.transposed(self.pre_mp[0][t].weight),
                                        self.pre_mp[0][t].bias) for t in self.node_types}
             emb = dict(xs)
             for l in range(self.layer_num):
@@ -365,10 +411,12 @@ class BaseGNN(nn.Module):
             return gossip_forward(self, data, query_emb)
         if not isinstance(data, (NeighborhoodBatch, QueryBatch, GraphBatch)):
             raise TypeError("BaseGNN.forward expects a NeighborhoodBatch, QueryBatch or GraphBatch")
-        if self.gnn_core.node_types is None:
-            raise NotImplementedError(
-                "homogeneous SAGE (ablation, hetero_graph=False) is out of the hot path; call "
-                "to_hetero_old()/to_hetero() first (main.py:221-224)")
+        # a homogeneous model (use_hetero=False: ablation_gnns.py) runs the same fused path on its one set of weights
+        # (BaseGNNCore accessors); a hetero model that has not been converted yet is refused here
+        self.gnn_core.row_types()
+        if self.gnn_core.is_homogeneous() and isinstance(data, NeighborhoodBatch) and data.node_feature is None:
+            raise ValueError("a homogeneous model marks the anchor by node_feature (1 on canonical rows, 0 elsewhere): "
+                             "this NeighborhoodBatch carries none (NeighborhoodDataset(hetero_graph=False) builds it)")
         if self.is_wide():
             # (the padded channels are exactly zero: callers see the true width)
             return self.forward_padded(data, drop_key)[:, :self.output_dim]
@@ -410,18 +458,18 @@ def pack_shmp(gnn: BaseGNN, bf16_planes: bool = True) -> dict:
     """bf16_planes: also emit the pre-split weight planes of the bf16x6 GEMMs (inference only)."""
     core = gnn.gnn_core
     pk = {"pre": {}, "layers": []}
-    for t in core.node_types:
-        pk["pre"][t] = _lin_t(core.pre_mp[0][t])
+    for t in core.row_types():
+        pk["pre"][t] = _lin_t(core.pre_lin(t))
     # Folding (U_n W_s)^T for every (layer, destination type, slot) and U_n sum_s b_s + c for every
     # (layer, type): two batched matmuls instead of ~100 tiny ones (the training step re-folds the
     # weights every step; per-product launches made it host-bound).  Differentiable.
     items, un_items, bias_items, un_rows = [], [], [], []
     for l in range(core.layer_num):
-        for t in core.node_types:
-            Un = core.updates[l][t].weight[:, :H]
+        for t in core.row_types():
+            Un = core.update(l, t).weight[:, :H]
             bsum, seen = 0, set()
             for key in core.slot_keys(t):
-                conv = core.convs[l][key]
+                conv = core.conv(l, key)
                 items.append(conv.lin.weight)
                 un_items.append(Un)
                 if key not in seen:      # one bias per edge TYPE (use_tconv=False ties two slots)
@@ -434,8 +482,8 @@ def pack_shmp(gnn: BaseGNN, bf16_planes: bool = True) -> dict:
     it = ib = 0
     for l in range(core.layer_num):
         per_type = {}
-        for t in core.node_types:
-            U, c = core.updates[l][t].weight, core.updates[l][t].bias
+        for t in core.row_types():
+            U, c = core.update(l, t).weight, core.update(l, t).bias
             Ux = U[:, H:]
             nslots = len(core.slot_keys(t))
             blocks = [folded[it + k] for k in range(nslots)]
@@ -748,14 +796,14 @@ def pack_shmp_stacked(gnn: BaseGNN) -> dict:
     core = gnn.gnn_core
     L = core.layer_num
     out = {}
-    for t in core.node_types:
+    for t in core.row_types():
         keys = core.slot_keys(t)
         uniq = list(dict.fromkeys(keys))                 # one bias per edge TYPE (use_tconv=False ties two slots)
-        U = torch.stack([core.updates[l][t].weight for l in range(L)])                   # [L, 64, 128]
-        c = torch.stack([core.updates[l][t].bias for l in range(L)])                     # [L, 64]
+        U = torch.stack([core.update(l, t).weight for l in range(L)])                    # [L, 64, 128]
+        c = torch.stack([core.update(l, t).bias for l in range(L)])                      # [L, 64]
         Un, Ux = U[:, :, :H], U[:, :, H:]
-        W = torch.stack([core.convs[l][k].lin.weight for l in range(L) for k in keys]).view(L, len(keys), H, H)
-        bs = torch.stack([core.convs[l][k].lin.bias for l in range(L) for k in uniq]).view(L, len(uniq), H).sum(1)
+        W = torch.stack([core.conv(l, k).lin.weight for l in range(L) for k in keys]).view(L, len(keys), H, H)
+        bs = torch.stack([core.conv(l, k).lin.bias for l in range(L) for k in uniq]).view(L, len(uniq), H).sum(1)
         folded = torch.matmul(Un.unsqueeze(1), W).transpose(-1, -2)                       # (U_n W_s)^T
         Wt = torch.cat([folded, Ux.transpose(-1, -2).unsqueeze(1)], dim=1).reshape(L, (len(keys) + 1) * H, H)
         fb = _mv(Un, bs) + c
@@ -818,7 +866,7 @@ def shmp_forward_train(gnn: BaseGNN, batch, drop_key: Optional[torch.Tensor] = N
     # stacked form.  Everything between the parameters and that node is this library's kernels too (round 5): the
     # folding reads the parameters through an address table (autograd.FoldShmp), the K-major copies of pre_mp /
     # anchor_mlp / post_mp are one copy2d launch (autograd.TransposedMany), pre_mp writes one buffer (PreLinear).
-    lins = [core.pre_mp[0][t] for t, *_ in groups] + ([gnn.anchor_mlp[0]] if has_anchor else []) + \
+    lins = [core.pre_lin(t) for t, *_ in groups] + ([gnn.anchor_mlp[0]] if has_anchor else []) + \
            [gnn.post_mp[i] for i in (0, 3, 5, 7)]
     wts = AG.TransposedMany.apply(*[m.weight for m in lins])
     ng = len(groups)
@@ -874,25 +922,25 @@ def pack_shmp_wide(gnn: BaseGNN, planes: bool = True) -> dict:
     wp = padded_width(h)
     L = core.layer_num
     pk = {"h": h, "wp": wp, "pre": {}, "layers": []}
-    for t in core.node_types:
-        lin = core.pre_mp[0][t]
+    for t in core.row_types():
+        lin = core.pre_lin(t)
         pk["pre"][t] = (_pad_to(lin.weight.t(), lin.in_features, wp).contiguous(), _pad_to(lin.bias, wp).contiguous())
     for l in range(L):
         per_type = {}
-        for t in core.node_types:
-            U, c = core.updates[l][t].weight, core.updates[l][t].bias
+        for t in core.row_types():
+            U, c = core.update(l, t).weight, core.update(l, t).bias
             Un, Ux = U[:, :h], U[:, h:]
             keys = core.slot_keys(t)
-            blocks = [(Un @ core.convs[l][k].lin.weight).t() for k in keys]                 # (U_n W_s)^T
+            blocks = [(Un @ core.conv(l, k).lin.weight).t() for k in keys]                  # (U_n W_s)^T
             blocks.append(Ux.t())
-            bsum = sum(core.convs[l][k].lin.bias for k in dict.fromkeys(keys))                # one bias per edge TYPE
+            bsum = sum(core.conv(l, k).lin.bias for k in dict.fromkeys(keys))                 # one bias per edge TYPE
             wt = _pad_blocks(torch.cat(blocks, 0), h, wp, len(blocks), 1).contiguous()      # [(S+1) wp, wp]
             e = {"wt": wt, "b": _pad_to(_mv(Un, bsum) + c, wp).contiguous(), "slots": len(keys)}
             if planes:
                 e["w16"] = ops.split_f16_planes(wt.t())
             per_type[t] = e
         pk["layers"].append(per_type)
-    if core.node_types != QUERY_NODE_TYPES:
+    if core.row_types() != QUERY_NODE_TYPES:
         aw = gnn.anchor_mlp[0]
         pk["anchor"] = (_pad_blocks(aw.weight.t(), h, wp, L + 1, L + 1).contiguous(),
                         torch.nn.functional.pad(aw.bias.view(L + 1, h), (0, wp - h)).reshape(-1).contiguous())

@@ -151,6 +151,10 @@ class NeighborhoodCountingModel(_LightningLike):
                                  emb_channels=hidden_dim, **kwargs)
         self.emb_model_query = BaseGNN(input_dim, hidden_dim, hidden_dim, args,
                                        emb_channels=hidden_dim, **kwargs)
+        # (homogeneous models, use_hetero=False: the row types each model's batches hold -- BaseGNNCore.row_types)
+        self.emb_model.gnn_core.homo_row_types = (list(TARGET_NODE_TYPES) if getattr(args, "use_canonical", True)
+                                                  else list(QUERY_NODE_TYPES))
+        self.emb_model_query.gnn_core.homo_row_types = list(QUERY_NODE_TYPES)
         self.count_model = nn.Sequential(nn.Linear(2 * hidden_dim, 4 * args.hidden_dim),
                                          nn.LeakyReLU(), nn.Linear(4 * args.hidden_dim, 1))
         self._qemb_cache = None
@@ -196,7 +200,8 @@ class NeighborhoodCountingModel(_LightningLike):
             warnings.warn("neighborhood diameter {:d} is too small for the queries, the minimum is "
                           "{:d}".format(self.depth, min_len_neighbor))
         self.queries_flat = flat
-        self.query_feat = query_node_features(queries_nx, self.input_dim)
+        # hetero=False (a homogeneous query model): all-zero features, whatever the graphs carry (lightning_model.py:72-79)
+        self.query_feat = query_node_features(queries_nx, self.input_dim) if hetero else None
         self.query_loader = QueryBatch(flat, device or self.device, self.input_dim, self.query_feat)
         self._qemb_cache = None
 

@@ -47,18 +47,19 @@ class NeighborhoodPartition:
     ``num_count``, ``num_rows`` and ``num_edges`` never download anything."""
 
     def __init__(self, neigh_index, indicator, count_ptr, count_orig, vrowptr, vcol, depth: int = 4,
-                 quirk_batch: int = 0):
+                 quirk_batch: int = 0, restricted: bool = False):
         self._host = {"neigh_index": neigh_index, "indicator": indicator, "count_ptr": count_ptr,
                       "count_orig": count_orig, "vrowptr": vrowptr, "vcol": vcol}
         self.depth = depth
         self.quirk_batch = quirk_batch
+        self.restricted = bool(restricted)
         self.device_arrays = None
         self._sizes = None
         self.downloads = {f: 0 for f in _ARRAY_FIELDS}
 
     @classmethod
     def from_device_arrays(cls, device_arrays: dict, num_neigh: int, num_count: int, num_edges: int, depth: int = 4,
-                           quirk_batch: int = 0) -> "NeighborhoodPartition":
+                           quirk_batch: int = 0, restricted: bool = False) -> "NeighborhoodPartition":
         """A device-resident partition: ``device_arrays`` holds ``device`` and one tensor per field (``indicator`` as
         uint8); the three sizes are what the builder read back."""
         missing = [f for f in ("device",) + _ARRAY_FIELDS if f not in device_arrays]
@@ -66,7 +67,7 @@ class NeighborhoodPartition:
             raise ValueError(f"from_device_arrays: missing {missing}")
         self = cls.__new__(cls)
         self._host = {}
-        self.depth, self.quirk_batch = depth, quirk_batch
+        self.depth, self.quirk_batch, self.restricted = depth, quirk_batch, bool(restricted)
         self.device_arrays = device_arrays
         self._sizes = (int(num_neigh), int(num_count), int(num_edges))
         self.downloads = {f: 0 for f in _ARRAY_FIELDS}
@@ -85,6 +86,7 @@ class NeighborhoodPartition:
     def __repr__(self):
         return (f"NeighborhoodPartition(num_neigh={self.num_neigh}, num_count={self.num_count}, "
                 f"num_edges={self.num_edges}, depth={self.depth}, quirk_batch={self.quirk_batch}, "
+                f"restricted={self.restricted}, "
                 f"device={'no' if self.device_arrays is None else self.device_arrays['device']})")
 
     @property
@@ -122,7 +124,7 @@ class NeighborhoodPartition:
             neigh_index=self.neigh_index[b0:b1], indicator=self.indicator,
             count_ptr=(self.count_ptr[b0:b1 + 1] - c0).astype(np.int32),
             count_orig=self.count_orig[c0:c1], vrowptr=vr.astype(np.int32),
-            vcol=col.astype(np.int32), depth=self.depth, quirk_batch=self.quirk_batch)
+            vcol=col.astype(np.int32), depth=self.depth, quirk_batch=self.quirk_batch, restricted=self.restricted)
 
     def select(self, idx) -> "NeighborhoodPartition":
         """The neighborhoods ``idx`` (ascending indices, any subset) as a self-contained block: what
@@ -148,7 +150,7 @@ class NeighborhoodPartition:
         return NeighborhoodPartition(
             neigh_index=self.neigh_index[idx], indicator=self.indicator, count_ptr=cp2.astype(np.int32),
             count_orig=self.count_orig[rows_old], vrowptr=vr2.astype(np.int32), vcol=col_new.astype(np.int32),
-            depth=self.depth, quirk_batch=self.quirk_batch)
+            depth=self.depth, quirk_batch=self.quirk_batch, restricted=self.restricted)
 
     def degree_sorted(self, num_threads: int = 0) -> "NeighborhoodPartition":
         """The same block with the count rows of every neighborhood re-ordered by decreasing / increasing (by the parity
@@ -173,7 +175,7 @@ class NeighborhoodPartition:
             vr2.ctypes.data, vc2.ctypes.data, nkey.ctypes.data, num_threads), "desco_partition_degree_sort")
         return NeighborhoodPartition(
             neigh_index=self.neigh_index, indicator=self.indicator, count_ptr=self.count_ptr, count_orig=co2,
-            vrowptr=vr2, vcol=vc2, depth=self.depth, quirk_batch=self.quirk_batch)
+            vrowptr=vr2, vcol=vc2, depth=self.depth, quirk_batch=self.quirk_batch, restricted=self.restricted)
 
     # ---- device-resident twins (csrc/batch_dev.hip) ------------------------------------------
     def _device_arrays(self, what: str) -> dict:
@@ -208,7 +210,7 @@ class NeighborhoodPartition:
         out = NeighborhoodPartition.from_device_arrays(
             {"device": da["device"], "count_ptr": cp2, "vrowptr": vr2, "vcol": vc2, "count_orig": co2,
              "neigh_index": da["neigh_index"][b0:b1], "indicator": da["indicator"]},
-            b1 - b0, nc, ne, self.depth, self.quirk_batch)
+            b1 - b0, nc, ne, self.depth, self.quirk_batch, self.restricted)
         if "indicator" in self._host:
             out._host["indicator"] = self._host["indicator"]
         return out
@@ -225,7 +227,8 @@ class NeighborhoodPartition:
                                                       B, Nc, E, da["neigh_index"].contiguous(), num_blocks)
         out = NeighborhoodPartition.from_device_arrays(
             {"device": da["device"], "count_ptr": da["count_ptr"], "vrowptr": vr2, "vcol": vc2, "count_orig": co2,
-             "neigh_index": da["neigh_index"], "indicator": da["indicator"]}, B, Nc, E, self.depth, self.quirk_batch)
+             "neigh_index": da["neigh_index"], "indicator": da["indicator"]}, B, Nc, E, self.depth, self.quirk_batch,
+            self.restricted)
         for f in ("count_ptr", "neigh_index", "indicator"):      # host views already downloaded stay shared
             if f in self._host:
                 out._host[f] = self._host[f]
@@ -266,14 +269,23 @@ for _f in _ARRAY_FIELDS:
 del _f
 
 
+NEIGH_BALL, NEIGH_RESTRICTED = 0, 1          # DESCO_NEIGH_* of include/desco_hip.h
+
+
 def build_partition(graphs: GraphSet, depth: int = 4, quirk_batch: int = 0,
-                    num_threads: int = 0) -> NeighborhoodPartition:
+                    num_threads: int = 0, restricted: bool = False) -> NeighborhoodPartition:
+    """``restricted=True`` builds the homogeneous ablation's neighborhoods (``depth`` BFS rounds that only step onto ids
+    <= v: the reference's k_neigh_canonical) in place of the ball / id filter / component of get_neigh_hetero; the
+    remove_self_loops quirk emulation is not offered with it."""
+    if restricted and quirk_batch:
+        raise ValueError("build_partition: quirk_batch is not offered with restricted=True; pass 0")
     L = _lib.lib()
     handle = ctypes.c_void_p()
     gp, rp, col = graphs.graph_ptr, graphs.rowptr, graphs.col
-    _lib.check(L.desco_partition_build(gp.ctypes.data, graphs.num_graphs, rp.ctypes.data,
-                                       col.ctypes.data, depth, quirk_batch, num_threads,
-                                       ctypes.byref(handle)), "desco_partition_build")
+    _lib.check(L.desco_partition_build_mode(gp.ctypes.data, graphs.num_graphs, rp.ctypes.data,
+                                            col.ctypes.data, depth, NEIGH_RESTRICTED if restricted else NEIGH_BALL,
+                                            quirk_batch, num_threads, ctypes.byref(handle)),
+               "desco_partition_build_mode")
     try:
         B, Nc, E, Nt = (ctypes.c_int64() for _ in range(4))
         _lib.check(L.desco_partition_sizes(handle, ctypes.byref(B), ctypes.byref(Nc),
@@ -291,12 +303,12 @@ def build_partition(graphs: GraphSet, depth: int = 4, quirk_batch: int = 0,
     finally:
         L.desco_partition_free(handle)
     return NeighborhoodPartition(neigh_index, indicator.astype(bool), count_ptr, count_orig,
-                                 vrowptr, vcol, depth, quirk_batch)
+                                 vrowptr, vcol, depth, quirk_batch, restricted)
 
 
 def build_partition_device(graphs: GraphSet, depth: int = 4, device="cuda",
-                           num_waves: int = 0) -> NeighborhoodPartition:
-    """Same result as ``build_partition`` (quirk_batch = 0), computed on the GPU by
+                           num_waves: int = 0, restricted: bool = False) -> NeighborhoodPartition:
+    """Same result as ``build_partition`` (quirk_batch = 0; either neighborhood definition), computed on the GPU by
     desco_partition_dev_* (csrc/partition_dev.hip).  The flat CSR is produced in
     device memory and stays there: the returned object keeps all six arrays in ``device_arrays`` (so that
     ``NeighborhoodBatch`` does not upload them again) and downloads a host view of a field only when it is read.  Graphs too large for the per-wave LDS
@@ -322,9 +334,10 @@ def build_partition_device(graphs: GraphSet, depth: int = 4, device="cuda",
     i32 = dict(device=dev, dtype=torch.int32)
     i64 = dict(device=dev, dtype=torch.int64)
     nsize, ecc, eck = (torch.empty(V, **i32) for _ in range(3))
-    _lib.check(L.desco_partition_dev_count(gp.data_ptr(), node_graph.data_ptr(), rowptr.data_ptr(),
-                                           col.data_ptr(), V, depth, n_max, num_waves,
-                                           nsize.data_ptr(), ecc.data_ptr(), eck.data_ptr(), st),
+    mode = NEIGH_RESTRICTED if restricted else NEIGH_BALL
+    _lib.check(L.desco_partition_dev_count_mode(gp.data_ptr(), node_graph.data_ptr(), rowptr.data_ptr(),
+                                                col.data_ptr(), V, depth, mode, n_max, num_waves,
+                                                nsize.data_ptr(), ecc.data_ptr(), eck.data_ptr(), st),
                "desco_partition_dev_count")
     b_index, row_off, eoc, eok = (torch.empty(V, **i64) for _ in range(4))
     totals = torch.zeros(4, **i64)
@@ -339,13 +352,13 @@ def build_partition_device(graphs: GraphSet, depth: int = 4, device="cuda",
     count_orig = torch.empty(Nc, **i32)
     vrowptr = torch.empty(4 * (Nc + B) + 1, **i32)
     vcol = torch.empty(Ec + Ek, **i32)
-    _lib.check(L.desco_partition_dev_fill(gp.data_ptr(), node_graph.data_ptr(), rowptr.data_ptr(),
-                                          col.data_ptr(), V, depth, n_max, num_waves,
-                                          b_index.data_ptr(), row_off.data_ptr(), eoc.data_ptr(),
-                                          eok.data_ptr(), B, Nc, Ec, Ek, neigh_index.data_ptr(),
-                                          indicator.data_ptr(), count_ptr.data_ptr(),
-                                          count_orig.data_ptr(), vrowptr.data_ptr(), vcol.data_ptr(), st),
+    _lib.check(L.desco_partition_dev_fill_mode(gp.data_ptr(), node_graph.data_ptr(), rowptr.data_ptr(),
+                                               col.data_ptr(), V, depth, mode, n_max, num_waves,
+                                               b_index.data_ptr(), row_off.data_ptr(), eoc.data_ptr(),
+                                               eok.data_ptr(), B, Nc, Ec, Ek, neigh_index.data_ptr(),
+                                               indicator.data_ptr(), count_ptr.data_ptr(),
+                                               count_orig.data_ptr(), vrowptr.data_ptr(), vcol.data_ptr(), st),
                "desco_partition_dev_fill")
     return NeighborhoodPartition.from_device_arrays(
         {"device": dev, "count_ptr": count_ptr, "vrowptr": vrowptr, "vcol": vcol, "neigh_index": neigh_index,
-         "indicator": indicator, "count_orig": count_orig, "graph_ptr": gp}, B, Nc, Ec + Ek, depth, 0)
+         "indicator": indicator, "count_orig": count_orig, "graph_ptr": gp}, B, Nc, Ec + Ek, depth, 0, restricted)

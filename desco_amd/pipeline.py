@@ -67,12 +67,24 @@ class InferencePipeline:
         Costs one launch set per chunk instead of one per 48 M-row block: off by default."""
         from . import distributed as D
         self.nm, self.gm = neigh_model, gossip_model
+        # a homogeneous neighborhood model (args.use_hetero False: ablation_gnns.py) reads the restricted neighborhoods,
+        # with the anchor flag as node_feature; it has no gossip stage (gossip_model None, run(gossip=False)) -- one GPU
+        core = getattr(getattr(neigh_model, "emb_model", None), "gnn_core", None)
+        self.restricted = bool(core is not None and core.is_homogeneous())
+        if self.restricted and quirk_batch:
+            raise NotImplementedError("a homogeneous model reads the restricted neighborhoods, for which the "
+                                      "remove_self_loops quirk emulation (quirk_batch) is not offered; pass 0")
+        if partition is not None and bool(getattr(partition, "restricted", False)) != self.restricted:
+            raise ValueError(f"the given partition was built with restricted={partition.restricted}, the model needs "
+                             f"restricted={self.restricted}")
         # rank / world taken from the process group: every rank builds its pipeline, and rank 0 decides the cuts for all
         agree = rank is None and world is None
         self.rank = D.rank() if rank is None else int(rank)
         self.world = D.world_size() if world is None else int(world)
         if not 0 <= self.rank < self.world:
             raise ValueError(f"rank {self.rank} outside world of {self.world}")
+        if self.restricted and (self.world > 1 or chunks is not None):
+            raise NotImplementedError("a homogeneous model (use_hetero=False) runs on one GPU, without chunks")
         self.num_graphs_total = graphs.num_graphs
         self.graph_range = (0, graphs.num_graphs)
         self.chunks = None if chunks is None else int(chunks)
@@ -106,7 +118,7 @@ class InferencePipeline:
             self.partition_backend = "none"
             self.partition = NeighborhoodPartition(
                 np.zeros((0, 2), np.int64), np.zeros(0, bool), np.zeros(1, np.int32), np.zeros(0, np.int32),
-                np.zeros(1, np.int32), np.zeros(0, np.int32), depth, 0)
+                np.zeros(1, np.int32), np.zeros(0, np.int32), depth, 0, self.restricted)
             self.neigh_batches, self.gossip_batches, self.num_queries = [], [], None
             return
         # canonical partition: built on the GPU (csrc/partition_dev.hip) unless the PyG quirk
@@ -117,13 +129,13 @@ class InferencePipeline:
             partition = None
             if partition_backend == "device" and quirk_batch == 0:
                 try:
-                    partition = build_partition_device(graphs, depth, device)
+                    partition = build_partition_device(graphs, depth, device, restricted=self.restricted)
                     self.partition_backend = "device"
                 except RuntimeError as e:
                     if "does not fit the LDS workspace" not in str(e):
                         raise
             if partition is None:
-                partition = build_partition(graphs, depth, quirk_batch, num_threads)
+                partition = build_partition(graphs, depth, quirk_batch, num_threads, restricted=self.restricted)
                 self.partition_backend = "host"
         self.partition = partition
         part = self.partition
@@ -161,7 +173,7 @@ class InferencePipeline:
             self.scatter_index = torch.from_numpy(rows.astype(np.int32)).to(device)
             # neighborhoods are ordered by graph: segment pointer for aggregate_neighborhood_count
             self.neigh_graph_ptr = torch.from_numpy(ngp.astype(np.int32)).to(device)
-        self.neigh_batches = [NeighborhoodBatch(blk, device) for blk in blocks]
+        self.neigh_batches = [NeighborhoodBatch(blk, device, anchor_flag=self.restricted) for blk in blocks]
         for b in self.neigh_batches:
             b.device_prologue = self.device_prologue
         self.node_graph_ptr = torch.from_numpy(graphs.graph_ptr.astype(np.int32)).to(device)
@@ -285,6 +297,8 @@ class InferencePipeline:
         out["graph_neigh_count"] = ops.segment_sum(neigh_count, self.neigh_graph_ptr, G)   # :400-404
         if not gossip:
             return out
+        if gm is None:
+            raise ValueError("InferencePipeline.run(gossip=True) needs a gossip model; this pipeline was built with None")
         # workload.py:107-112: x = zeros; x[indicator] = count.  The rows outside the indicator are never written, so
         # the zeros of the first pass stay; the indicator rows are overwritten by every pass.
         x = bufs["x"]

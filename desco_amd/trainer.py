@@ -247,6 +247,11 @@ class Trainer:
             # (the wide path's training step -- --neigh_hidden_dim != 64 -- is not validated under capture)
             raise NotImplementedError("--graph_capture supports --neigh_hidden_dim 64 only; train a model of another "
                                       "width without it")
+        if use_graphs and any(getattr(m, "is_homogeneous", lambda: False)() for m in model.modules()):
+            # (the homogeneous model's step -- shared parameters entering the folds several times -- is not validated
+            #  under capture)
+            raise NotImplementedError("--graph_capture does not support a homogeneous model (use_hetero=False, "
+                                      "ablation_gnns.py); train it without graph capture")
         # shuffle=False (main.py:195): the batch stream is the same every epoch, so the device-resident
         # batches (and their backward indices) are built once.  Data parallel: optimisation step k
         # consumes the `world` consecutive batches [k*world, (k+1)*world), one per rank, weighted by

@@ -18,7 +18,7 @@ import torch
 
 from .batch import GossipBatch, GraphBatch, NeighborhoodBatch
 from .graphs import GraphSet
-from .partition import NeighborhoodPartition, build_partition
+from .partition import NeighborhoodPartition, build_partition, build_partition_device
 
 
 def _as_graphset(dataset) -> GraphSet:
@@ -41,14 +41,35 @@ def _check_transforms(who, transform, pre_transform, pre_filter):
         raise NotImplementedError(f"{who}: pre_transform / pre_filter callables are not supported (no PyG data list)")
 
 
+def _build_restricted(graphs: GraphSet, depth: int, num_threads: int):
+    """The restricted partition (hetero_graph=False): on the GPU when there is one, by the host builder when there is
+    none or a graph exceeds the device builder's per-wave LDS workspace (InferencePipeline's rule)."""
+    if torch.cuda.is_available() and graphs.num_graphs:
+        try:
+            return build_partition_device(graphs, depth, "cuda", restricted=True), "device"
+        except RuntimeError as e:
+            if "does not fit the LDS workspace" not in str(e):
+                raise
+    return build_partition(graphs, depth, 0, num_threads, restricted=True), "host"
+
+
 class NeighborhoodDataset:
-    """One canonical neighborhood per node with >= 1 edge in it (workload.py:153-324)."""
+    """One canonical neighborhood per node with >= 1 edge in it (workload.py:153-324).  ``hetero_graph=False`` (the
+    ablation without heterogeneous message passing, ablation_gnns.py): the neighborhoods of get_neigh_canonical -- the
+    restricted partition -- with the anchor marked by ``node_feature`` (1 on the canonical row) instead of a node type;
+    the arrays and the batches keep their layout."""
 
     def __init__(self, depth_neigh, root, dataset=None, nx_targets=None, transform=None,
                  pre_transform=None, pre_filter=None, hetero_graph=True, node_feat=False,
                  node_feat_key="feat", quirk_batch: int = 0, num_threads: int = 0):
-        if not hetero_graph:
-            raise NotImplementedError("hetero_graph=False (ablation) is outside the hot path")
+        self.hetero_graph = bool(hetero_graph)
+        if not hetero_graph and node_feat:
+            raise NotImplementedError(
+                "hetero_graph=False together with --use_node_feature (node_feat=True) is not supported: column 0 of "
+                "node_feature is the anchor flag of the homogeneous model")
+        if not hetero_graph and quirk_batch:
+            raise NotImplementedError("hetero_graph=False: the remove_self_loops quirk emulation (quirk_batch) is not "
+                                      "offered for the restricted neighborhoods; pass 0")
         if dataset is None and nx_targets is None:
             raise AttributeError("must create Neighborhood dataset with a dataset")
         _check_transforms("NeighborhoodDataset", transform, pre_transform, pre_filter)
@@ -71,9 +92,14 @@ class NeighborhoodDataset:
             z = cached
             self.partition = NeighborhoodPartition(
                 np.load(paths[1]), np.load(paths[2]), z["count_ptr"], z["count_orig"],
-                z["vrowptr"], z["vcol"], depth_neigh, int(z["quirk_batch"]))
+                z["vrowptr"], z["vcol"], depth_neigh, int(z["quirk_batch"]), restricted=not hetero_graph)
+            self.partition_backend = "cache"
         else:
-            self.partition = build_partition(self.dataset, depth_neigh, quirk_batch, num_threads)
+            if hetero_graph:
+                self.partition, self.partition_backend = build_partition(self.dataset, depth_neigh, quirk_batch,
+                                                                         num_threads), "host"
+            else:
+                self.partition, self.partition_backend = _build_restricted(self.dataset, depth_neigh, num_threads)
             if paths:
                 os.makedirs(pdir, exist_ok=True)
                 p = self.partition
@@ -86,7 +112,7 @@ class NeighborhoodDataset:
 
     @property
     def processed_file_names(self) -> List[str]:
-        d = str(self.depth_neigh)
+        d = str(self.depth_neigh) + ("" if self.hetero_graph else "_homo")       # workload.py:200
         return ["neighs_csr_depth_" + d + ".npz", "neighs_index_depth_" + d + ".npy",
                 "neighs_indicator_depth_" + d + ".npy"]
 
@@ -103,7 +129,8 @@ class NeighborhoodDataset:
             nf = self.dataset.node_feat
             canon = self.dataset.graph_ptr[part.neigh_index[:, 0]] + part.neigh_index[:, 1]
             feat = torch.from_numpy(np.concatenate([nf[part.count_orig], nf[canon]]))
-        return NeighborhoodBatch(part, device, node_feature=feat, y=y)
+        # hetero_graph=False: the anchor flag as node_feature, made where the batch lives
+        return NeighborhoodBatch(part, device, node_feature=feat, y=y, anchor_flag=not self.hetero_graph)
 
     def batches(self, batch_size: int, device="cpu") -> Iterator[NeighborhoodBatch]:
         for b0 in range(0, len(self), batch_size):
@@ -203,6 +230,10 @@ class Workload:
         self.root = root
         self.hetero_graph = hetero_graph
         self.use_node_feat = node_feat_len != -1                                   # workload.py:383
+        if not hetero_graph and self.use_node_feat:
+            raise NotImplementedError(
+                "Workload(hetero_graph=False) together with --use_node_feature (node_feat_len != -1) is not supported: "
+                "column 0 of node_feature is the anchor flag of the homogeneous model")
         if self.use_node_feat:
             nf = self.dataset.node_feat
             if nf is None or nf.shape[1] != node_feat_len:

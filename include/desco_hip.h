@@ -79,6 +79,19 @@ int desco_partition_export(const desco_partition* p, int64_t* neigh_index, uint8
                            int32_t* vcol);
 void desco_partition_free(desco_partition* p);
 
+/* The neighborhood definition (`mode` of the *_mode entry points; the entry points without it build DESCO_NEIGH_BALL):
+ *   DESCO_NEIGH_BALL        BFS ball of radius depth in the full graph, ids <= v, component of v (get_neigh_hetero,
+ *                           data.py:375-396)
+ *   DESCO_NEIGH_RESTRICTED  depth BFS rounds from v that only step onto ids <= v (k_neigh_canonical / get_neigh_canonical,
+ *                           data.py:341-372: the homogeneous ablation); a subset of the former, connected as built.
+ * Edges, slots, row order and the output layout are the same in both.  quirk_batch must be 0 with
+ * DESCO_NEIGH_RESTRICTED (DESCO_EINVAL otherwise). */
+#define DESCO_NEIGH_BALL 0
+#define DESCO_NEIGH_RESTRICTED 1
+int desco_partition_build_mode(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                               const int32_t* col, int depth, int mode, int quirk_batch, int num_threads,
+                               desco_partition** out);
+
 /* Optional re-ordering of a block's count rows (host arrays, same layout in and out): inside every neighborhood the
  * count rows are sorted by their number of count -> count sources (the neighborhood's heavier relation slot first,
  * descending when neigh_key[b] is even, ascending when odd -- pass the canonical node's id inside its graph so that the
@@ -119,6 +132,19 @@ int desco_partition_dev_fill(const int64_t* graph_ptr, const int32_t* node_graph
                              int64_t* neigh_index, uint8_t* indicator, int32_t* count_ptr,
                              int32_t* count_orig, int32_t* vrowptr, int32_t* vcol,
                              desco_stream_t stream);
+/* the same two passes with the neighborhood definition as an argument (DESCO_NEIGH_*); the scan is shared */
+int desco_partition_dev_count_mode(const int64_t* graph_ptr, const int32_t* node_graph,
+                                   const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int depth,
+                                   int mode, int n_max, int num_waves, int32_t* nsize, int32_t* ecnt_count,
+                                   int32_t* ecnt_canon, desco_stream_t stream);
+int desco_partition_dev_fill_mode(const int64_t* graph_ptr, const int32_t* node_graph,
+                                  const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int depth,
+                                  int mode, int n_max, int num_waves, const int64_t* b_index,
+                                  const int64_t* row_off, const int64_t* eoff_count, const int64_t* eoff_canon,
+                                  int64_t num_neigh, int64_t num_count, int64_t edges_count,
+                                  int64_t edges_canon, int64_t* neigh_index, uint8_t* indicator,
+                                  int32_t* count_ptr, int32_t* count_orig, int32_t* vrowptr, int32_t* vcol,
+                                  desco_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * DEVICE: from the device partition to the arrays a batch's kernels read (csrc/batch_dev.hip).  Integer kernels that
