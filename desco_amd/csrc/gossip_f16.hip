@@ -35,6 +35,9 @@
 //     MFMA triple.  Packed fp32 selection is back on and the end-of-block accumulator drain is gone: the wrong-result
 //     mode of round 4 was one operand selection of the packed instructions (OP_SEL on src1/src2), which this source
 //     does not produce and tools/check_isa.py refuses in the linked library (profiles/r5_a_gossip_f16_hazard.md).
+//   * The epilogue constants travel in the ring's ordered LDS stream, requested one to two pair steps ahead and waited
+//     for with counted waits: no `lgkmcnt(0)` and no compiler-issued LDS access between the first and the last MFMA of a
+//     query (the comment above GF16_REQ; tools/isa_waits.py, tests/test_gossip_isa_waits.py).
 #include "tu_no_packed_f32_begin.hpp"
 #include "common_device.hpp"
 
@@ -139,49 +142,99 @@ __device__ __forceinline__ float absmax16(const f32x4 a, const f32x4 b, const f3
 // traffic.  The stream is the same for every query and node, so the ring runs on across block
 // boundaries, epilogues, queries and work units (round 4 requested each fragment one step ahead and waited out the LDS
 // latency in front of every MFMA triple: hipcc sinks a plain C++ LDS read to just above its use).
+// The epilogue constants (u, d1, tp, zp_q, b3, b5, w7) travel in the SAME stream: a lane needs quad i = features
+// 16 i + 4 q .. + 3 of a 64-float row, four ds_read_b128 from ONE base register per region (cstq = cst + 4 q,
+// zpq = zpw + 4 q; row and quad in the immediate offset) into CA / CB, issued in front of the REQ of pair steps 1 and 2
+// of the block whose epilogue uses them and waited for behind the block (GF16_CWAIT): twelve and six MFMAs ahead.
+// (As plain C++ reads they were 44 ds_read_b128 from 29 hoisted address registers, each followed within three
+// instructions by an `s_waitcnt lgkmcnt(0)` that also drained the ring: SQ_WAIT_ANY 29 % of the wave cycles, 14 % now,
+// profiles/gossip_const_ahead_ab.md.)  r / t are the same for every query and are read once per wave; zp_q is stored to
+// the wave's own row and read back by the same ordered stream.
 // The reads and the waits are inline asm so that their ISSUE POINTS are fixed: volatile asm statements keep their program
 // order (also against the compiler's own LDS accesses), the fragments are outputs of the read and in/outputs of the wait,
-// so the MFMAs that use them come after it.  The counted wait is safe whatever else the compiler puts in between: LDS
-// operations of a wave return in order, a fragment read is complete once at most as many LGKM operations are outstanding
-// as were issued after it, and lgkmcnt(4) -- the four reads of the one younger pair step -- is at most that number.
+// so the MFMAs that use them come after it.  The MFMAs themselves are builtins, which the scheduler moves freely between
+// asm statements (it used to put the waits of two pair steps back to back, in front of both steps' MFMAs, so that the
+// second wait met reads issued just before it): two operand ties fix them.  The last read of REQ(d + 2) carries the B
+// operand of pair step d as an untouched in/output, so the six MFMAs of pair step d come AFTER the requests issued in
+// it; WAIT(d + 1) and CWAIT carry the two accumulators of the pair step before them in the same way, so those MFMAs come
+// BEFORE the next wait.  Neither asm reads or writes the tied registers.
+// The counted wait is safe whatever else the compiler puts in between: LDS operations of a wave return in order, so a
+// read is complete once at most as many LGKM operations are outstanding as were issued after it.  All LDS operations
+// between the first and the last MFMA of a query are this file's asm, so that number is known: WAIT(d) follows REQ(d + 1)
+// and the constant reads of pair step d - 1 (lgkmcnt(4) or (8)), CWAIT follows the REQs of pair steps 2 and 3 of its
+// block (lgkmcnt(8)).  Two things this rests on are checked on the compiled kernel by tests/test_gossip_isa_waits.py
+// (tools/isa_waits.py): the query chain holds no compiler-issued LDS access, and no SCALAR MEMORY LOAD -- those return
+// out of order and share the counter, a counted wait could not tell them from the reads (every kernel argument the loop
+// uses is in registers before it).
 // Hazards the compiler does not see (its hazard recogniser and waitcnt insertion do not look inside the asm):
-//   * RAW on a fragment: covered by GF16_WAIT's counted wait (above).
+//   * RAW on a fragment or a constant: covered by the counted waits (above).
 //   * WAW against an MFMA result: excluded by construction -- the only MFMA destinations are the accumulators acc0..acc3,
-//     which are live across every REQ / WAIT of a block, and a ring slot is a live asm OUTPUT from its REQ to its last
-//     MFMA: two simultaneously live values never share a register.
+//     which are live across every REQ / WAIT of a block, and a ring slot or constant quad is a live asm OUTPUT from its
+//     read to its last use: two simultaneously live values never share a register.
 //   * WAR against an MFMA that still reads the slot (a slot re-requested while the MFMAs of its previous contents are in
 //     flight): slot d % 3 is re-requested by REQ(d + 3), which is issued in front of the MFMAs of pair step d + 1 -- the
 //     six MFMAs of pair step d have all been ISSUED by then, an MFMA reads its A / B operands in its first passes, and
 //     the read's data returns an LDS round trip (> 64 cycles, > the 16 cycles of one 16x16x32 MFMA) later.
+//   * WAR on a constant quad (CA / CB re-requested for the next epilogue, or zp_q's row overwritten by the next query's
+//     store): the quads are asm outputs, so a request whose predecessor is still live gets other registers, and where
+//     the registers are reused the previous epilogue's VALU instructions come earlier in program order and a VALU reads
+//     its operands at issue; the store follows the previous query's reads of the row in the same in-order queue.
 //   tests/test_model_gpu.py holds this to bit-identical repeats on molecule, Syn_1827, MSRC-21 + IMDB and hub / ragged
-//   shapes (200 / 100 launches each).
+//   shapes (200 / 100 launches each), tests/test_gossip_const_ahead_gpu.py on the shapes where a constant has the least
+//   time to arrive.
 struct WFrag { f16x8 h0, l0, h1, l1; };          // tiles 2 p (0) and 2 p + 1 (1)
 #define GF16_RD_(dst_, base_, off_) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst_) : "v"(base_), "n"(off_));
-#define GF16_REQ(d_)                                                                                    \
+// ... with x_ tied through (see above)
+#define GF16_RDX_(dst_, base_, off_, x_)                                                                \
+  asm volatile("ds_read_b128 %0, %2 offset:%3" : "=v"(dst_), "+v"(x_) : "v"(base_), "n"(off_));
+#define GF16_REQX(d_, x_)                                                                               \
   {                                                                                                     \
     constexpr int dd_ = (d_) % 36, byte_ = (dd_ / 4) * (WBLK * 2) + ((dd_ % 4) / 2) * (2 * 16 * 64 * 2); \
     const uint32_t b_ = (dd_ % 2 ? wa1 : wa0) + (uint32_t)(byte_ & ~0xffff);                            \
     GF16_RD_(WF[(d_) % 3].h0, b_, byte_ & 0xffff)                                                       \
     GF16_RD_(WF[(d_) % 3].l0, b_, (byte_ & 0xffff) + WPL * 2)                                           \
     GF16_RD_(WF[(d_) % 3].h1, b_, (byte_ & 0xffff) + 16 * 64 * 2)                                       \
-    GF16_RD_(WF[(d_) % 3].l1, b_, (byte_ & 0xffff) + 16 * 64 * 2 + WPL * 2)                             \
+    GF16_RDX_(WF[(d_) % 3].l1, b_, (byte_ & 0xffff) + 16 * 64 * 2 + WPL * 2, x_)                        \
   }
-#define GF16_WAIT(d_)                                                                                   \
-  asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(WF[(d_) % 3].h0), "+v"(WF[(d_) % 3].l0), "+v"(WF[(d_) % 3].h1), \
-               "+v"(WF[(d_) % 3].l1));
-// pair step d_: (accA_, accB_) += W[tiles 2p, 2p+1][k step] X^T, three products each, smallest first, chains interleaved
-#define GF16_PAIR(d_, accA_, accB_, xh_, xl_)                                                           \
+#define GF16_REQ(d_) { uint32_t x_ = 0; GF16_REQX(d_, x_) }
+// the accumulators a wait is tied to (operands of the wait's asm)
+#define GF16_AFTER(a_, b_) , "+v"(a_), "+v"(b_)
+#define GF16_WAIT(d_, n_, ...)                                                                          \
+  asm volatile("s_waitcnt lgkmcnt(" #n_ ")" : "+v"(WF[(d_) % 3].h0), "+v"(WF[(d_) % 3].l0), "+v"(WF[(d_) % 3].h1), \
+               "+v"(WF[(d_) % 3].l1) __VA_ARGS__);
+#define GF16_CRD4(dst_, base_, off_)                                                                    \
+  GF16_RD_(dst_[0], base_, off_) GF16_RD_(dst_[1], base_, (off_) + 64)                                  \
+  GF16_RD_(dst_[2], base_, (off_) + 128) GF16_RD_(dst_[3], base_, (off_) + 192)
+#define GF16_CWAIT2(n_)                                                                                 \
+  asm volatile("s_waitcnt lgkmcnt(" #n_ ")" : "+v"(CA[0]), "+v"(CA[1]), "+v"(CA[2]), "+v"(CA[3]), "+v"(CB[0]), \
+               "+v"(CB[1]), "+v"(CB[2]), "+v"(CB[3]) GF16_AFTER(acc2, acc3));
+#define GF16_CWAIT1(n_)                                                                                 \
+  asm volatile("s_waitcnt lgkmcnt(" #n_ ")" : "+v"(CB[0]), "+v"(CB[1]), "+v"(CB[2]), "+v"(CB[3]) GF16_AFTER(acc2, acc3));
+// pair step d_: (accA_, accB_) += W[tiles 2p, 2p+1][k step] X^T, three products each, smallest first, chains interleaved.
+// n_ = 4 + the constant reads of pair step d_ - 1; crd_ = this pair step's constant reads (may be empty); the variadic
+// tail = GF16_AFTER(the accumulators of pair step d_ - 1), empty behind a CWAIT or where the query chain starts.
+#define GF16_PAIR(d_, accA_, accB_, xh_, xl_, n_, crd_, ...)                                            \
   {                                                                                                     \
-    GF16_WAIT(d_)                                                                                       \
-    GF16_REQ((d_) + 2)                                                                                  \
+    GF16_WAIT(d_, n_, __VA_ARGS__)                                                                      \
+    crd_                                                                                                \
+    GF16_REQX((d_) + 2, xh_)                                                                            \
     GF16_MFMA(WF[(d_) % 3].l0, xh_, accA_) GF16_MFMA(WF[(d_) % 3].l1, xh_, accB_)                       \
     GF16_MFMA(WF[(d_) % 3].h0, xl_, accA_) GF16_MFMA(WF[(d_) % 3].h1, xl_, accB_)                       \
     GF16_MFMA(WF[(d_) % 3].h0, xh_, accA_) GF16_MFMA(WF[(d_) % 3].h1, xh_, accB_)                       \
   }
-// the 24 MFMAs of weight block b_ on this wave's 16 nodes: acc_i += W[16 i .. +15][:] X^T
-#define GF16_BLOCK(b_, X_)                                                                              \
-  GF16_PAIR(4 * (b_) + 0, acc0, acc1, X_.h0, X_.l0) GF16_PAIR(4 * (b_) + 1, acc0, acc1, X_.h1, X_.l1)   \
-  GF16_PAIR(4 * (b_) + 2, acc2, acc3, X_.h0, X_.l0) GF16_PAIR(4 * (b_) + 3, acc2, acc3, X_.h1, X_.l1)
+// The 24 MFMAs of weight block b_ on this wave's 16 nodes: acc_i += W[16 i .. +15][:] X^T.  n2_ / n3_ = the counts of
+// the waits of pair steps 2 / 3, c1_ / c2_ = the constant reads of pair steps 1 / 2, after0_ = what the block's first
+// wait is tied to (the variadic tail: GF16_AFTER(..) or nothing).
+#define GF16_BLOCK_(b_, X_, n2_, n3_, c1_, c2_, ...)                                                    \
+  GF16_PAIR(4 * (b_) + 0, acc0, acc1, X_.h0, X_.l0, 4, , __VA_ARGS__)                                   \
+  GF16_PAIR(4 * (b_) + 1, acc0, acc1, X_.h1, X_.l1, 4, c1_, GF16_AFTER(acc0, acc1))                     \
+  GF16_PAIR(4 * (b_) + 2, acc2, acc3, X_.h0, X_.l0, n2_, c2_, GF16_AFTER(acc0, acc1))                   \
+  GF16_PAIR(4 * (b_) + 3, acc2, acc3, X_.h1, X_.l1, n3_, , GF16_AFTER(acc2, acc3))
+#define GF16_BLOCK(b_, X_, ...) GF16_BLOCK_(b_, X_, 4, 4, , , __VA_ARGS__)
+// ... with the eight constant quads of its epilogue requested in pair steps 1 and 2, in front of GF16_CWAIT2(8)
+#define GF16_BLOCK_C2(b_, X_, c1_, c2_, ...) GF16_BLOCK_(b_, X_, 8, 8, c1_, c2_, __VA_ARGS__)
+// ... with four quads requested in pair step 2, in front of GF16_CWAIT1(8)
+#define GF16_BLOCK_C1(b_, X_, c2_, ...) GF16_BLOCK_(b_, X_, 4, 8, , c2_, __VA_ARGS__)
 #define GF16_ZERO() { acc0 = acc1 = acc2 = acc3 = f32x4{0.f, 0.f, 0.f, 0.f}; }
 #define GF16_SCALE(f_) { acc0 *= (f_); acc1 *= (f_); acc2 *= (f_); acc3 *= (f_); }
 
@@ -224,14 +277,25 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
   // LDS byte addresses of this lane's fragment chunk of k step 0 / 1 in weight block 0, tile 0, hi plane
   const uint32_t wa0 = (uint32_t)(uintptr_t)(WB + wrow * 64 + (((0 + q4) ^ wswz) << 3));
   const uint32_t wa1 = (uint32_t)(uintptr_t)(WB + wrow * 64 + (((4 + q4) ^ wswz) << 3));
+  // ... and of this lane's constant quads: cst + 4 q4 (rows u, d1, tp, b3, b5, w7 by offset), zpw + 4 q4, and the
+  // standard-order r / t quads at cst + 768 + 8 q4
+  const uint32_t cstq = (uint32_t)(uintptr_t)(cst + 4 * q4);
+  const uint32_t zpq = (uint32_t)(uintptr_t)(zpw + 4 * q4);
+  const uint32_t zpl = (uint32_t)(uintptr_t)(zpw + lane);
+  const uint32_t rtq = (uint32_t)(uintptr_t)(cst + 768 + 8 * q4);
   WFrag WF[3];
+  f32x4 CA[4], CB[4];                                  // the constant quads in flight (GF16_CRD4 / GF16_CWAIT)
+  // r and t are the same for every query: read once, in front of the ring's head start, kept in registers
+  f32x4 r0, r1, r2, r3, t0, t1, t2, t3;
+  GF16_RD_(r0, rtq, 0) GF16_RD_(r1, rtq, 16) GF16_RD_(r2, rtq, 128) GF16_RD_(r3, rtq, 144)
+  GF16_RD_(t0, rtq, 256) GF16_RD_(t1, rtq, 272) GF16_RD_(t2, rtq, 384) GF16_RD_(t3, rtq, 400)
   GF16_REQ(0) GF16_REQ(1)                              // the ring's head start: pair steps 0 and 1 of the first query
+  asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));
 
   const int QC = (Q + WQ - 1) / WQ;
   const int64_t nunits = num_groups * QC;
   const unsigned long long nwaves = (unsigned long long)g.grid_blocks * 8;      // (= gridDim.x; passed, not queried)
   int64_t unit = (int64_t)__builtin_amdgcn_workgroup_id_x() * 8 + wave;
-  const int fq = 4 * q4;
   // this lane's 16 features of the standard-order operands (hh, h1): 8 q4 .. +7 and 32 + 8 q4 .. +7
   const int fa = 8 * q4, fb = 32 + 8 * q4;
 #define GW_V4(p_) (*reinterpret_cast<const f32x4*>(p_))
@@ -295,7 +359,8 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
     GW_PREFETCH(qa)
 
     for (int q = qa; q < qb; ++q) {
-      zpw[lane] = nzp;
+      // zp_q: one float per lane into this wave's row, read back as quads in block 3 (same wave, same in-order queue)
+      asm volatile("ds_write_b32 %0, %1" : : "v"(zpl), "v"(nzp));
       const float gq = ngq;
       const float4 si = nsi;                           // (a0, b0, a1, x)
       f32x4 acc0, acc1, acc2, acc3;
@@ -305,10 +370,6 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
         // ---- neighbour sum and own h1 in the B layout of the first GEMM ----------------------------------------------
         const f32x4 p0 = np0, p1 = np1, p2 = np2, p3 = np3, z0 = nz0, z1 = nz1, z2 = nz2, z3 = nz3;
         const float4 c0 = nr0, c1 = nr1, c2 = nr2, c3 = nr3;
-        const f32x4 r0 = GW_V4(cst + 768 + fa), r1 = GW_V4(cst + 768 + fa + 4), r2 = GW_V4(cst + 768 + fb),
-                    r3 = GW_V4(cst + 768 + fb + 4);
-        const f32x4 t0 = GW_V4(cst + 832 + fa), t1 = GW_V4(cst + 832 + fa + 4), t2 = GW_V4(cst + 832 + fb),
-                    t3 = GW_V4(cst + 832 + fb + 4);
         const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
         f32x4 h0 = zero4, h1 = zero4, h2 = zero4, h3 = zero4;
 // (three dependent FMAs per feature, z first: as a sum of products hipcc emits mul + 2 fma + add)
@@ -358,13 +419,12 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
       float s_c;
       // ---- blocks 0, 1: h2 = relu([hh|h1] W1 + a1*u + d1) ------------------------------------------------------------
       GF16_ZERO()
-      GF16_BLOCK(0, XH)
-      GF16_BLOCK(1, X1)
+      GF16_BLOCK(0, XH, )
+      GF16_BLOCK_C2(1, X1, GF16_CRD4(CA, cstq, 0), GF16_CRD4(CB, cstq, 64 * 4), GF16_AFTER(acc2, acc3))    // u, d1
+      GF16_CWAIT2(8)
       {
         const float f = pow2_inverse(s_a) * winv1;
-        const float* u_ = cst + fq;
-        const float* d_ = cst + 64 + fq;
-#define GW_EPI1(a_, i_) a_ = __builtin_elementwise_max(fma4(f, a_, fma4(si.z, GW_V4(u_ + 16 * (i_)), GW_V4(d_ + 16 * (i_)))), f32x4{0.f, 0.f, 0.f, 0.f});
+#define GW_EPI1(a_, i_) a_ = __builtin_elementwise_max(fma4(f, a_, fma4(si.z, CA[i_], CB[i_])), f32x4{0.f, 0.f, 0.f, 0.f});
         GW_EPI1(acc0, 0) GW_EPI1(acc1, 1) GW_EPI1(acc2, 2) GW_EPI1(acc3, 3)
 #undef GW_EPI1
         s_c = f16_scale_for(quarters_max(absmax16(acc0, acc1, acc2, acc3)));
@@ -372,19 +432,18 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
       }
       // ---- blocks 2, 3: y1 = leaky([h1|h2] Wp + x*tp + zp_q, 0.1) ------------------------------------------------------
       GF16_ZERO()
-      GF16_BLOCK(2, X1)
+      GF16_BLOCK(2, X1, )
       {
         const float rs = s_c * pow2_inverse(s_a);
         GF16_SCALE(rs)
       }
-      GF16_BLOCK(3, XC)
+      GF16_BLOCK_C2(3, XC, GF16_CRD4(CA, cstq, 128 * 4), GF16_CRD4(CB, zpq, 0), GF16_AFTER(acc2, acc3))    // tp, zp_q
+      GF16_CWAIT2(8)
       {
         const float f = pow2_inverse(s_c) * winvp;
-        const float* t_ = cst + 128 + fq;
-        const float* z_ = zpw + fq;
 #define GW_EPI2(a_, i_)                                                                                       \
   {                                                                                                           \
-    const f32x4 v_ = fma4(f, a_, fma4(si.w, GW_V4(t_ + 16 * (i_)), GW_V4(z_ + 16 * (i_))));                    \
+    const f32x4 v_ = fma4(f, a_, fma4(si.w, CA[i_], CB[i_]));                                                 \
     a_ = __builtin_elementwise_max(v_, v_ * 0.1f);                                                            \
   }
         GW_EPI2(acc0, 0) GW_EPI2(acc1, 1) GW_EPI2(acc2, 2) GW_EPI2(acc3, 3)
@@ -394,11 +453,11 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
       }
       // ---- block 4: y2 = relu(y1 W3 + b3) ----------------------------------------------------------------------------
       GF16_ZERO()
-      GF16_BLOCK(4, XC)
+      GF16_BLOCK_C1(4, XC, GF16_CRD4(CB, cstq, 192 * 4), )                           // b3
+      GF16_CWAIT1(8)
       {
         const float f = pow2_inverse(s_c) * winv3;
-        const float* b_ = cst + 192 + fq;
-#define GW_EPI3(a_, i_) a_ = __builtin_elementwise_max(fma4(f, a_, GW_V4(b_ + 16 * (i_))), f32x4{0.f, 0.f, 0.f, 0.f});
+#define GW_EPI3(a_, i_) a_ = __builtin_elementwise_max(fma4(f, a_, CB[i_]), f32x4{0.f, 0.f, 0.f, 0.f});
         GW_EPI3(acc0, 0) GW_EPI3(acc1, 1) GW_EPI3(acc2, 2) GW_EPI3(acc3, 3)
 #undef GW_EPI3
         s_c = f16_scale_for(quarters_max(absmax16(acc0, acc1, acc2, acc3)));
@@ -408,12 +467,11 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
       f32x4 hp = {0.f, 0.f, 0.f, 0.f};                 // four running sums per lane, folded once after the last block
       const float fh = pow2_inverse(s_c) * winv5;
 #define GW_HEAD1(a_, cg_, i_)                                                                                 \
-  hp = __builtin_elementwise_fma(__builtin_elementwise_max(fma4(fh, a_, GW_V4(cst + 256 + 64 * (cg_) + 16 * (i_) + fq)), \
-                                                           f32x4{0.f, 0.f, 0.f, 0.f}),                        \
-                                 GW_V4(cst + 512 + 64 * (cg_) + 16 * (i_) + fq), hp);
+  hp = __builtin_elementwise_fma(__builtin_elementwise_max(fma4(fh, a_, CA[i_]), f32x4{0.f, 0.f, 0.f, 0.f}), CB[i_], hp);
 #define GW_HEAD(cg_)                                                                                         \
   GF16_ZERO()                                                                                                \
-  GF16_BLOCK(5 + (cg_), XC)                                                                    \
+  GF16_BLOCK_C2(5 + (cg_), XC, GF16_CRD4(CA, cstq, (256 + 64 * (cg_)) * 4), GF16_CRD4(CB, cstq, (512 + 64 * (cg_)) * 4), ) /* b5, w7 */ \
+  GF16_CWAIT2(8)                                                                                             \
   GW_HEAD1(acc0, cg_, 0) GW_HEAD1(acc1, cg_, 1) GW_HEAD1(acc2, cg_, 2) GW_HEAD1(acc3, cg_, 3)
       GW_HEAD(0) GW_HEAD(1) GW_HEAD(2) GW_HEAD(3)
 #undef GW_HEAD
