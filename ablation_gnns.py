@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """The ablation WITHOUT heterogeneous message passing on the MI355X-native path, with the reference driver's CLI and flow
-(ablation_gnns.py of the reference).  One plain SAGE model -- one pre_mp, one convs[l].lin and one updates[l] for every
-node and every edge, the anchor marked by node_feature = 1 instead of a node type -- over the canonical neighborhoods of
+(ablation_gnns.py of the reference).  One plain SAGE (or GIN / GCN) model -- one pre_mp and one set of layer weights
+for every node and every edge, the anchor marked by node_feature = 1 instead of a node type -- over the neighborhoods of
 get_neigh_canonical (the restricted partition), and no gossip stage:
 
     ground truth (canonical counts) -> Workload(hetero_graph=False) (restricted neighborhoods, built on the GPU, with
     the 0/1 anchor feature) -> NeighborhoodCountingModel(use_hetero=False) (train / load, test, predict)
     -> per-graph sums -> config_<dataset>.txt + norm-MSE / MAE grouped by query size
 
-``use_hetero=False``, ``use_tconv=False``, ``conv_type="SAGE"`` are forced and the gossip stage is off, whatever the
-command line says (reference :559-566).  Flags: desco_amd/config.py.
+``use_hetero=False`` and ``use_tconv=False`` are forced and the gossip stage is off, whatever the command line says
+(reference :559-566).  ``--neigh_conv_type`` chooses the layer: SAGE (the default, the reference driver's only one), or
+the plain baselines GIN and GCN on the fused plain-layer kernel; anything else is refused.  Flags:
+desco_amd/config.py.
 """
 from __future__ import annotations
 
@@ -31,6 +33,11 @@ from desco_amd.trainer import ModelCheckpoint, Trainer
 from desco_amd.workload import Workload
 
 
+# the layer types of the homogeneous model (the reference driver hard-codes SAGE under a comment about "limited
+# implemented scenarios"; its model classes take all three)
+ABLATION_CONV_TYPES = ("SAGE", "GIN", "GCN")
+
+
 def build_workload(name, query_ids, nx_queries, depth, num_cpu, root="data"):
     """Target graphs, canonical ground truth (loaded or computed; it does not depend on the neighborhood definition),
     the restricted neighborhoods with their anchor feature"""
@@ -48,6 +55,15 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, neig
          nx_queries=None, atlas_query_ids=None, output_dir="results/raw", data_root="data"):
     if nx_queries is None and atlas_query_ids is None:
         raise ValueError("nx_queries and atlas_query_ids cannot be both None")
+    conv = getattr(args_neighborhood, "conv_type", "SAGE")
+    if conv not in ABLATION_CONV_TYPES:
+        raise NotImplementedError(f"--neigh_conv_type {conv}: ablation_gnns.py runs {', '.join(ABLATION_CONV_TYPES)} "
+                                  "(GAT and PNACONV are not on the hot path)")
+    if conv != "SAGE":
+        gpus = args_opt.gpu if isinstance(args_opt.gpu, list) else [args_opt.gpu]
+        if getattr(args_neighborhood, "use_node_feature", False) or len(gpus) > 1:
+            raise NotImplementedError(f"--neigh_conv_type {conv} runs on one GPU and without --use_node_feature (column 0 "
+                                      "of node_feature is the anchor flag of the homogeneous model)")
     if getattr(args_neighborhood, "use_node_feature", False):
         raise NotImplementedError("ablation_gnns.py (hetero_graph=False) together with --use_node_feature is not "
                                   "supported: column 0 of node_feature is the anchor flag of the homogeneous model")
@@ -151,7 +167,7 @@ if __name__ == "__main__":
     # the ablation's model (reference :559-566)
     args_neighborhood.use_hetero = False
     args_neighborhood.use_tconv = False
-    args_neighborhood.conv_type = "SAGE"
+    # (--neigh_conv_type is honoured: SAGE by default, GIN or GCN for the plain baselines; main() refuses anything else)
     args_opt.test_gossip = False
     args_opt.train_gossip = False
     output_dir = args_opt.output_dir or os.path.join(

@@ -161,6 +161,8 @@ SIGNATURES = {
     "desco_shmp_layer_wide_f16x3_f32": (c_int, [vp, i64, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp, vp, i64, vp, i64,
                                                 vp]),
     "desco_csr_gather_sum_wide_f32": (c_int, [vp, i64, vp, vp, i64, i32, i32, vp, i64, vp]),
+    "desco_plain_layer_f16x3_f32": (c_int, [vp, i64, vp, vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp,
+                                            i64, i64, vp]),
     "desco_count_head_wide_f32": (c_int, [vp, i64, vp, i64, i32, vp, f32, vp, f32, i32, vp, i64, i64, i32, vp]),
     "desco_gossip_f16_stream": (c_int, [vp, vp, vp, vp, vp, vp]),
     "desco_gossip_fused_f16x3_f32": (c_int, [vp, vp, vp, i64, i32] + [vp] * 14 + [f32, vp, vp, vp, vp]),

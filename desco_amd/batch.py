@@ -65,6 +65,16 @@ class _TrainIndexMixin:
         return self._train_index
 
 
+    def plain_csr(self):
+        """(rowptr [num_rows + 1], col): the PLAIN CSR of the block -- one entry per row, the union of the row's relation
+        slots, which is all its neighbours (a homogeneous model reads it: plain_forward).  A strided read of the
+        virtual-row pointer, made once per batch.  The blocks are symmetric, so this is also its own transposed index."""
+        c = self.__dict__.get("_plain_csr")
+        if c is None:
+            c = self.__dict__["_plain_csr"] = (self.vrowptr[::self.slots].contiguous(), self.vcol)
+        return c
+
+
 class NeighborhoodBatch(_TrainIndexMixin):
     """B canonical neighborhoods: N_c count rows followed by B canonical rows, 4-slot CSR."""
 

@@ -134,6 +134,79 @@ class SAGEConv(nn.Module):
         return "{}({}, {})".format(self.__class__.__name__, self.in_channels, self.out_channels)
 
 
+# plain layer types of a homogeneous core (--neigh_conv_type GIN / GCN, ablation_gnns.py)
+PLAIN_CONV_TYPES = ("GIN", "GCN")
+
+
+def _plain_aggregate(x: torch.Tensor, edge_index, n_dst: int) -> torch.Tensor:
+    """agg[i] = sum of x[src] over the edges into i (PyG ``propagate`` with aggr="add"; no self loops are added or
+    removed) for x of a width % 4 == 0 up to MAX_HIDDEN, on desco_csr_gather_sum_wide_f32"""
+    if edge_index is None:
+        edge_index = torch.zeros((2, 0), dtype=torch.long, device=x.device)
+    dst, order = torch.sort(edge_index[1], stable=True)
+    col = edge_index[0][order].to(torch.int32)
+    rowptr = torch.zeros(n_dst + 1, dtype=torch.int64, device=x.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n_dst), 0)
+    return ops.csr_gather_sum_wide(x.float().contiguous(), rowptr.to(torch.int32), col, n_dst, 1)
+
+
+class GINConv(nn.Module):
+    """The reference's GINConv (gnn_model.py:422-446): sum aggregation and nothing else -- the ``nn`` handed to it is
+    never stored, the (1 + eps) x term is commented out there.  Holds NO parameters (no ``convs.l.*`` keys)."""
+
+    def __init__(self, in_channels, out_channels, aggr="add", **kwargs):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+
+    def forward(self, x, edge_index, size=None):
+        return _plain_aggregate(x, edge_index, x.shape[0] if size is None else size[1])
+
+    def __repr__(self):
+        return "{}({}, {})".format(self.__class__.__name__, self.in_channels, self.out_channels)
+
+
+class GINEps(nn.Module):
+    """The reference's TrivalParam (gnn_model.py:449-460): the BUFFER ``eps`` of shape [1] (key ``eps.l.eps``)"""
+
+    def __init__(self, n=0.0):
+        super().__init__()
+        self.n = n
+        self.register_buffer("eps", torch.tensor([float(n)]))
+
+    def forward(self) -> torch.Tensor:
+        return self.eps
+
+    def reset_parameters(self):
+        self.eps.data.fill_(self.n)
+
+
+class GCNConv(nn.Module):
+    """pyg_nn.GCNConv(i, h, normalize=False) of PyG 2.2.0, restated (PyG-only semantics, unpinned: DESIGN.md 2):
+    ``lin`` = Linear without bias (glorot), ``bias`` [h] (zeros); out = (sum of x_j over the row's neighbours) lin^T +
+    bias -- with normalize=False neither self loops nor a normalisation are added."""
+
+    def __init__(self, in_channels, out_channels, aggr="add", **kwargs):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.lin = nn.Linear(in_channels, out_channels, bias=False)
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.xavier_uniform_(self.lin.weight)          # torch_geometric.nn.inits.glorot
+        nn.init.zeros_(self.bias)
+
+    def forward(self, x, edge_index, size=None):
+        wp = padded_width(self.in_channels)
+        agg = _plain_aggregate(torch.nn.functional.pad(x.float(), (0, wp - x.shape[1])), edge_index,
+                               x.shape[0] if size is None else size[1])
+        return ops.gemm(agg, _pad_to(self.lin.weight.t(), wp, padded_width(self.out_channels)).contiguous(),
+                        _pad_to(self.bias, padded_width(self.out_channels)).contiguous())[:, :self.out_channels]
+
+    def __repr__(self):
+        return "{}({}, {})".format(self.__class__.__name__, self.in_channels, self.out_channels)
+
+
 class GossipConv(nn.Module):
     """Direction-gated message passing conditioned on the query embedding (gnn_model.py:280-359).
     Holds ``lin_com``, ``lin_update``, ``lin_gate``; executed by ``gossip_forward``."""
@@ -209,6 +282,8 @@ class BaseGNNCore(nn.Module):
             pre_dim_out += kwargs["emb_channels"]
         self.convs = nn.ModuleList()
         self.updates = nn.ModuleList()
+        if args.conv_type == "GIN":
+            self.eps = nn.ModuleList()                                              # :141-143
         for l in range(args.layer_num):
             hidden_input_dim = hidden_dim
             if l == 0 and self.input_pattern_emb:
@@ -219,9 +294,26 @@ class BaseGNNCore(nn.Module):
             elif args.conv_type == "SAGE":
                 self.convs.append(SAGEConv(hidden_input_dim, hidden_dim, aggr="add"))     # :187
                 self.updates.append(nn.Linear(2 * hidden_dim, hidden_dim))                # :190
+            elif args.conv_type in PLAIN_CONV_TYPES:
+                if args.use_hetero:
+                    raise NotImplementedError(
+                        f"--neigh_conv_type {args.conv_type} runs as a homogeneous model only (use_hetero=False: "
+                        "ablation_gnns.py --neigh_conv_type " + args.conv_type + "); the heterogeneous (to_hetero) form "
+                        "of a GIN / GCN core is not on the hot path")
+                if self.input_pattern_emb:
+                    raise NotImplementedError(f"--neigh_conv_type {args.conv_type}: no query embedding as input feature")
+                if args.conv_type == "GIN":
+                    self.convs.append(GINConv(hidden_input_dim, hidden_dim, aggr="add"))           # :186-187 (no parameters)
+                    self.updates.append(nn.Sequential(nn.Linear(hidden_dim, hidden_dim), nn.ReLU(),
+                                                      nn.Linear(hidden_dim, hidden_dim)))          # :191-198
+                    self.eps.append(GINEps(0.0))                                                   # :199
+                else:
+                    self.convs.append(GCNConv(hidden_input_dim, hidden_dim, aggr="add"))           # :200-201
             else:
                 raise NotImplementedError(
-                    f"conv_type {args.conv_type!r}: only SAGE (SHMP) and GOSSIP are on the hot path")
+                    f"--neigh_conv_type {args.conv_type}: only SAGE (SHMP; homogeneous in ablation_gnns.py), GIN and GCN "
+                    "(homogeneous, ablation_gnns.py) and --gossip_conv_type GOSSIP are on the hot path; GAT and PNACONV "
+                    "are not")
         self.post_input_dim = hidden_dim * args.layer_num + pre_dim_out          # :207
         self.node_types: Optional[List[str]] = None
         self.edge_types: Optional[List[Tuple[str, str, str]]] = None
@@ -231,6 +323,9 @@ class BaseGNNCore(nn.Module):
 
     def to_hetero(self, node_types: Sequence[str], edge_types: Sequence[Tuple[str, str, str]]):
         """pyg.nn.to_hetero(aggr="sum") equivalent for this module [EXT, SURVEY App. C]."""
+        if self.conv_type in PLAIN_CONV_TYPES:
+            raise NotImplementedError(f"--neigh_conv_type {self.conv_type}: to_hetero of a GIN / GCN core is not on the "
+                                      "hot path; these cores run homogeneous (use_hetero=False, ablation_gnns.py)")
         if self.conv_type != "SAGE":
             raise NotImplementedError("to_hetero is only defined for the SAGE (SHMP) core")
         if self.node_types is not None:
@@ -254,7 +349,11 @@ class BaseGNNCore(nn.Module):
     # fold several times and autograd sums its gradient over the uses.  (Aliasing the module inside ModuleDicts would
     # duplicate the state-dict keys.)
     def is_homogeneous(self) -> bool:
-        return self.node_types is None and not self.use_hetero and self.conv_type == "SAGE"
+        return self.node_types is None and not self.use_hetero and (self.conv_type == "SAGE" or self.is_plain())
+
+    def is_plain(self) -> bool:
+        """a GIN or GCN core: homogeneous, run by the plain-layer kernel at every width (plain_forward)"""
+        return self.conv_type in PLAIN_CONV_TYPES
 
     def row_types(self) -> List[str]:
         """the row types a batch can hold: the model's node types, or ``homo_row_types`` for a homogeneous core"""
@@ -327,6 +426,8 @@ class BaseGNNCore(nn.Module):
             if self.node_types is None:
                 # homogeneous SAGE (ablation_gnns.py): ``x`` [N, input_dim], ``edge_index`` [2, E]; returns [N, 64 (L + 1)]
                 self.row_types()                                                                          # (raises unless homogeneous)
+                if self.is_plain():
+                    return self._forward_plain(x, edge_index)
                 lin = self.pre_mp[0]
                 h = ops.linear_smallk(x.float().contiguous(), ops.transposed(lin.weight), lin.bias)       # :231
                 emb = h
@@ -355,6 +456,32 @@ class BaseGNNCore(nn.Module):
                 xs = new
                 emb = {t: torch.cat((emb[t], xs[t]), dim=1) for t in self.node_types}
             return emb
+
+    def _forward_plain(self, x, edge_index):
+        """the GIN / GCN branches of ``forward`` (gnn_model.py:262-270), op by op on rows zero-padded to the padded
+        width: GIN  x = relu(updates[l](agg + (1 + eps_l x)))  -- the parentheses as the reference writes them;
+        GCN  x = relu(convs[l](x)).  Returns [N, hidden (L + 1)]."""
+        hd, wp = self.hidden_dim, padded_width(self.hidden_dim)
+        lin = self.pre_mp[0]
+        h = ops.linear_smallk(x.float().contiguous(), _pad_to(lin.weight.t(), lin.in_features, wp).contiguous(),
+                              _pad_to(lin.bias, wp).contiguous())                                         # :231
+        live = torch.zeros(wp, device=h.device)
+        live[:hd] = 1.0                                          # the constant 1 reaches the true channels only
+        emb = [h]
+        for l in range(self.layer_num):
+            agg = _plain_aggregate(h, edge_index, h.shape[0])                                             # :262
+            if self.conv_type == "GIN":
+                u = self.updates[l]
+                z = agg + (live + self.eps[l]() * h)                                                      # :266
+                t = ops.gemm(z.contiguous(), _pad_to(u[0].weight.t(), wp, wp).contiguous(), _pad_to(u[0].bias, wp).contiguous(),
+                             act=ops.ACT_RELU)
+                h = ops.gemm(t, _pad_to(u[2].weight.t(), wp, wp).contiguous(), _pad_to(u[2].bias, wp).contiguous())
+            else:
+                c = self.convs[l]
+                h = ops.gemm(agg, _pad_to(c.lin.weight.t(), wp, wp).contiguous(), _pad_to(c.bias, wp).contiguous())  # :268-270
+            h = self._relu_dropout(h, l)                                                                  # :273-274
+            emb.append(h)
+        return torch.cat([e[:, :hd] for e in emb], 1)                                                     # :275
 
     def _relu_dropout(self, h, layer, node_type=None):
         """relu (gnn_model.py:273) and, in training mode with dropout > 0, F.dropout (:274) as this library's
@@ -390,7 +517,8 @@ class BaseGNN(nn.Module):
 
     # -- weight folding ---------------------------------------------------------------------------
     def _param_version(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+        # (buffers too: GIN's eps enters the packed operands and the cached query embeddings)
+        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
 
     def packed(self):
         """Kernel operands folded from the parameters; cached until a parameter changes."""
@@ -398,7 +526,8 @@ class BaseGNN(nn.Module):
         if self._pack_cache is None or self._pack_cache[0] != ver:
             with torch.no_grad():
                 pk = pack_gossip(self) if self.conv_type == "GOSSIP" else \
-                    (pack_shmp_wide(self) if self.is_wide() else pack_shmp(self))
+                    (pack_plain(self) if self.gnn_core.is_plain() else
+                     (pack_shmp_wide(self) if self.is_wide() else pack_shmp(self)))
             self._pack_cache = (ver, pk)
         return self._pack_cache[1]
 
@@ -425,12 +554,16 @@ class BaseGNN(nn.Module):
         return shmp_forward(self, data)
 
     def is_wide(self) -> bool:
-        """True for a SAGE model of another width than 64: it runs the wide path (shmp_forward_wide)"""
-        return self.conv_type != "GOSSIP" and self.gnn_core.hidden_dim != H
+        """True for a SAGE model of another width than 64 (it runs the wide path, shmp_forward_wide) and for a plain GIN /
+        GCN model of ANY width (plain_forward): both work on operands zero-padded to padded_width(hidden_dim)"""
+        return self.conv_type != "GOSSIP" and (self.gnn_core.hidden_dim != H or self.gnn_core.is_plain())
 
     def forward_padded(self, data, drop_key=None) -> torch.Tensor:
         """wide path: the graph embeddings [B, padded_width(output_dim)] (zero beyond output_dim)"""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if self.gnn_core.is_plain():
+            return plain_forward_train(self, data, drop_key) if train else plain_forward(self, data)
+        if train:
             return shmp_forward_train_wide(self, data, drop_key)
         return shmp_forward_wide(self, data)
 
@@ -940,6 +1073,13 @@ def pack_shmp_wide(gnn: BaseGNN, planes: bool = True) -> dict:
                 e["w16"] = ops.split_f16_planes(wt.t())
             per_type[t] = e
         pk["layers"].append(per_type)
+    return _pack_wide_tail(gnn, pk, planes)
+
+
+def _pack_wide_tail(gnn: BaseGNN, pk: dict, planes: bool) -> dict:
+    """the anchor MLP and post_mp operands of the padded-operand paths (pack_shmp_wide, pack_plain), padded block by block"""
+    core = gnn.gnn_core
+    h, wp, L = pk["h"], pk["wp"], core.layer_num
     if core.row_types() != QUERY_NODE_TYPES:
         aw = gnn.anchor_mlp[0]
         pk["anchor"] = (_pad_blocks(aw.weight.t(), h, wp, L + 1, L + 1).contiguous(),
@@ -1063,6 +1203,162 @@ def shmp_forward_train_wide(gnn: BaseGNN, batch, drop_key: Optional[torch.Tensor
             e = pk["layers"][l][t]
             parts.append(AG.Linear.apply(agg[r0:r1, :su * wp], X[-1][r0:r1], e["wt"], e["b"], ops.ACT_RELU, 0.0))
         xl = torch.cat(parts, 0)
+        if p_layer > 0.0:                                                              # gnn_model.py:274
+            xl = xl * ops.dropout_mask(ops.DropSite(drop_key, wide_layer_drop_site(l), p_layer), N, wp)
+        X.append(xl)
+    if nb:
+        canon = torch.cat([xl[Nc:] for xl in X], dim=1)
+        aw, ab = pk["anchor"]
+        anch = AG.Linear.apply(canon, None, aw, ab, ops.ACT_LEAKY, 0.1)
+        pooled = torch.cat([AG.SegmentSumWide.apply(xl[:Nc], seg_ptr, ti["seg_id"], ti["ident_ptr"],
+                                                    anch[:, l * wp:(l + 1) * wp].contiguous())
+                            for l, xl in enumerate(X)], dim=1)
+    else:
+        pooled = torch.cat([AG.SegmentSumWide.apply(xl, seg_ptr, ti["seg_id"], ti["ident_ptr"], None) for xl in X], dim=1)
+    (w0, b0), (w3, b3), (w5, b5), (w7, b7) = pk["post"]
+    h = AG.Linear.apply(pooled, None, w0, b0, ops.ACT_NONE, 0.0)
+    if p_post > 0.0:                                                                   # post_mp.1 (gnn_model.py:46)
+        h = h * ops.dropout_mask(ops.DropSite(drop_key, POST_DROP_SITE, p_post), h.shape[0], h.shape[1])
+    h = F.leaky_relu(h, 0.1)
+    h = AG.Linear.apply(h, None, w3, b3, ops.ACT_RELU, 0.0)
+    h = AG.Linear.apply(h, None, w5, b5, ops.ACT_RELU, 0.0)
+    return AG.Linear.apply(h, None, w7, b7, ops.ACT_NONE, 0.0)
+
+
+# -------------------------------------------------------------------------------------------------
+# plain GIN / GCN neighborhood / query models (--neigh_conv_type GIN / GCN, homogeneous)
+# -------------------------------------------------------------------------------------------------
+# a plain layer as ONE fused launch (desco_plain_layer_f16x3_f32: gather, the eps x term, one or two products, relu);
+# False: the un-fused composition (desco_csr_gather_sum_wide_f32 with slots = 1, the eps x term, gemm_f16x3 once or
+# twice), for A/B runs and as the fused kernel's cross-check
+PLAIN_FUSED = os.environ.get("DESCO_PLAIN_FUSED", "1") != "0"
+
+
+def pack_plain(gnn: BaseGNN, planes: bool = True) -> dict:
+    """The operands of a plain GIN / GCN model, zero-padded to wp = padded_width(h) like pack_shmp_wide's (K-major
+    [in, out] matrices; ``planes``: also the fp16 planes of the f16x3 kernels).  Per layer ``wt1``, ``b1`` and, for GIN,
+    ``wt2``, ``b2``, ``eps`` (the buffer itself, read on the device).  GIN's constant 1 -- the reference's
+    ``x_neigh + (1 + eps x)`` -- is folded into the first bias over the TRUE width, b1' = b1 + W1 1, so that the padded
+    channels stay exactly 0.  Differentiable (training)."""
+    core = gnn.gnn_core
+    h = core.hidden_dim
+    wp = padded_width(h)
+    lin = core.pre_mp[0]
+    pre = (_pad_to(lin.weight.t(), lin.in_features, wp).contiguous(), _pad_to(lin.bias, wp).contiguous())
+    pk = {"h": h, "wp": wp, "pre": {t: pre for t in core.row_types()}, "layers": []}
+    for l in range(core.layer_num):
+        if core.conv_type == "GIN":
+            u = core.updates[l]
+            W1, W2 = u[0].weight, u[2].weight
+            e = {"wt1": _pad_to(W1.t(), wp, wp).contiguous(), "b1": _pad_to(u[0].bias + W1.sum(1), wp).contiguous(),
+                 "wt2": _pad_to(W2.t(), wp, wp).contiguous(), "b2": _pad_to(u[2].bias, wp).contiguous(),
+                 "eps": core.eps[l].eps}
+        else:
+            c = core.convs[l]
+            e = {"wt1": _pad_to(c.lin.weight.t(), wp, wp).contiguous(), "b1": _pad_to(c.bias, wp).contiguous()}
+        if planes:
+            e["w1_16"] = ops.split_f16_planes(e["wt1"].t())
+            if "wt2" in e:
+                e["w2_16"] = ops.split_f16_planes(e["wt2"].t())
+        pk["layers"].append(e)
+    return _pack_wide_tail(gnn, pk, planes)
+
+
+def _plain_tail(pk, batch, X, canon, Nc, seg_ptr, B):
+    """the wide path's tail: anchor on the f16x3 GEMM, pooling with the anchor block as ``extra``, fp32 post_mp"""
+    wp = pk["wp"]
+    dev = X[0].device
+    pooled = torch.empty((B, len(X) * wp), device=dev)
+    anch = None if canon is None else ops.gemm_f16x3(canon, pk["anchor16"], pk["anchor"][1], act=ops.ACT_LEAKY, slope=0.1)
+    for l, xl in enumerate(X):                                                         # :88-89, :107
+        ops.segment_sum(xl[:Nc], seg_ptr, B, extra=None if anch is None else anch[:, l * wp:(l + 1) * wp],
+                        out=pooled[:, l * wp:(l + 1) * wp])
+    (w0, b0), (w3, b3), (w5, b5), (w7, b7) = pk["post"]                                # :44-53
+    h = ops.gemm(pooled, w0, b0, act=ops.ACT_LEAKY, slope=0.1)
+    h = ops.gemm(h, w3, b3, act=ops.ACT_RELU)
+    h = ops.gemm(h, w5, b5, act=ops.ACT_RELU)
+    return ops.gemm(h, w7, b7)
+
+
+def plain_forward(gnn: BaseGNN, batch) -> torch.Tensor:
+    """Inference of a plain GIN / GCN model (BaseGNN.forward with use_hetero False, gnn_model.py:58-109, :262-270) on the
+    operands of pack_plain -> graph embeddings [B, padded_width(output_dim)]: one linear_smallk for pre_mp over all
+    rows, ONE desco_plain_layer_f16x3_f32 launch per layer over all N rows of the batch's plain CSR (it also writes the
+    canonical rows into their column block of the anchor operand), then shmp_forward_wide's tail."""
+    pk = gnn.packed()
+    core = gnn.gnn_core
+    wp = pk["wp"]
+    dev = batch.vrowptr.device
+    N, B, L = batch.num_rows, batch.num_graphs, core.layer_num
+    Nc, groups, seg_ptr = _wide_groups(batch)
+    nb = isinstance(batch, NeighborhoodBatch)
+    rowptr, col = batch.plain_csr()
+    feat = batch.node_feature
+    if feat is None:
+        feat = _wide_zero_feat(gnn, batch, N, dev)
+    x = torch.empty((N, wp), device=dev)
+    ops.linear_smallk(feat, *pk["pre"][groups[0][0]], out=x)                           # :231
+    canon = torch.empty((B, (L + 1) * wp), device=dev) if nb else None             # emb["canonical"]
+    anchored = nb and N > Nc
+    if anchored:
+        ops.copy2d_multi([(x[Nc:], canon[:, :wp])])
+    X = [x]
+    for l in range(L):
+        e = pk["layers"][l]
+        xn = torch.empty((N, wp), device=dev)
+        cblock = canon[:, (l + 1) * wp:(l + 2) * wp] if anchored else None
+        if PLAIN_FUSED:
+            ops.plain_layer(X[-1], rowptr, col, 0, N, e["w1_16"], e["b1"], e.get("w2_16"), e.get("b2"),
+                            self_scale=e.get("eps"), out=xn, out2=cblock, out2_row0=Nc)            # :262-273
+        else:
+            z = ops.csr_gather_sum_wide(X[-1], rowptr, col, N, 1)
+            if "eps" in e:
+                z = z + e["eps"] * X[-1]
+            if "w2_16" in e:
+                t = ops.gemm_f16x3(z, e["w1_16"], e["b1"], act=ops.ACT_RELU)
+                ops.gemm_f16x3(t, e["w2_16"], e["b2"], act=ops.ACT_RELU, out=xn)
+            else:
+                ops.gemm_f16x3(z, e["w1_16"], e["b1"], act=ops.ACT_RELU, out=xn)
+            if anchored:
+                ops.copy2d_multi([(xn[Nc:], cblock)])
+        X.append(xn)
+    return _plain_tail(pk, batch, X, canon if nb else None, Nc, seg_ptr, B)
+
+
+def plain_forward_train(gnn: BaseGNN, batch, drop_key: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable twin of ``plain_forward`` -> [B, padded_width(output_dim)]: the per-op autograd composition of
+    shmp_forward_train_wide (SmallKLinear, GatherSumWide with slots = 1, Linear, SegmentSumWide) on operands padded with
+    differentiable torch ops, so that the gradients reach the true-width parameters only; ``eps`` is a buffer and gets
+    none.  The batch CSR is symmetric, so the transposed index of the plain CSR is the plain CSR itself.  Dropout: the
+    counter-based factors at sites wide_layer_drop_site(l) and POST_DROP_SITE of ``drop_key``."""
+    from . import autograd as AG
+    import torch.nn.functional as F
+    core = gnn.gnn_core
+    dev = batch.vrowptr.device
+    N, L = batch.num_rows, core.layer_num
+    Nc, groups, seg_ptr = _wide_groups(batch)
+    nb = isinstance(batch, NeighborhoodBatch)
+    p_layer = float(core.dropout or 0.0) if gnn.training else 0.0
+    p_post = float(gnn.post_mp[1].p or 0.0) if gnn.training else 0.0
+    if (p_layer > 0.0 or p_post > 0.0) and drop_key is None:
+        drop_key = ops.rng_next(dev)
+    pk = pack_plain(gnn, planes=False)
+    wp = pk["wp"]
+    feat = batch.node_feature
+    if feat is None:
+        feat = _wide_zero_feat(gnn, batch, N, dev)
+    ti = batch.train_index()
+    rowptr, col = batch.plain_csr()
+    X = [AG.SmallKLinear.apply(feat, *pk["pre"][groups[0][0]])]
+    for l in range(L):
+        e = pk["layers"][l]
+        z = AG.GatherSumWide.apply(X[-1], rowptr, col, rowptr, col, N, 1)
+        if "eps" in e:
+            z = z + e["eps"] * X[-1]
+            t = AG.Linear.apply(z, None, e["wt1"], e["b1"], ops.ACT_RELU, 0.0)
+            xl = AG.Linear.apply(t, None, e["wt2"], e["b2"], ops.ACT_RELU, 0.0)
+        else:
+            xl = AG.Linear.apply(z, None, e["wt1"], e["b1"], ops.ACT_RELU, 0.0)
         if p_layer > 0.0:                                                              # gnn_model.py:274
             xl = xl * ops.dropout_mask(ops.DropSite(drop_key, wide_layer_drop_site(l), p_layer), N, wp)
         X.append(xl)

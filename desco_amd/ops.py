@@ -1848,6 +1848,38 @@ def shmp_layer_wide(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, 
             op, ldo, o2, ld2, _stream()), "shmp_layer_wide")
 
 
+def plain_layer(x: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, row0: int, num_rows: int, w1: "F16Planes",
+                b1: torch.Tensor, w2: Optional["F16Planes"] = None, b2: Optional[torch.Tensor] = None,
+                self_scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                out2: Optional[torch.Tensor] = None, out2_row0: int = 0) -> None:
+    """One plain GIN / GCN layer (desco_plain_layer_f16x3_f32) for rows [row0, row0 + num_rows) of width Wp = x.shape[1]:
+    z = sum over the row of the plain CSR (``rowptr`` has one entry per row) of x[col[e]] + self_scale x[r];
+    h = z W1 + b1; with ``w2``: h = relu(h) W2 + b2; y = relu(h).  ``w1`` / ``w2`` = split_f16_planes(W.T) [2, Wp, Wp];
+    ``self_scale``: a one-element device tensor (GIN's eps buffer) or None.  Writes rows row0.. of ``out`` and / or, for
+    rows r >= out2_row0, row r - out2_row0 of ``out2`` (a view with unit inner stride, e.g. a column block)."""
+    width = x.shape[1]
+    assert isinstance(w1, F16Planes) and tuple(w1.shape) == (2, width, width)
+    mats = 1 if w2 is None else 2
+    if mats == 2:
+        assert isinstance(w2, F16Planes) and tuple(w2.shape) == (2, width, width) and b2 is not None
+    xp, ldx = _rows(x, "x")
+    op, ldo = (None, 0) if out is None else _rows(out, "out")
+    o2, ld2 = (None, 0) if out2 is None else _rows(out2, "out2")
+    if out2 is not None:
+        assert out2.shape[0] >= row0 + num_rows - out2_row0
+    nb = 4.0 * width * (num_rows * (2 + (out is not None) + (out2 is not None))) + 4.0 * (num_rows + 1)
+    with _Timed("plain_layer_kernel", 2.0 * num_rows * mats * width * width, nb):
+        if col.numel() == 0:        # (read only below an edge: any int32 device pointer, no fill launched)
+            col = rowptr
+        _lib.check(_lib.lib().desco_plain_layer_f16x3_f32(
+            xp, ldx, _dev(rowptr, "rowptr", torch.int32), _dev(col, "col", torch.int32),
+            None if self_scale is None else _dev(self_scale, "self_scale"), int(row0), int(num_rows), width, mats,
+            _dev(w1.planes, "w1", torch.int16), _dev(w1.scale, "w1_scale"), _dev(b1.contiguous(), "b1"),
+            None if w2 is None else _dev(w2.planes, "w2", torch.int16), None if w2 is None else _dev(w2.scale, "w2_scale"),
+            None if w2 is None else _dev(b2.contiguous(), "b2"), op, ldo, o2, ld2, int(out2_row0), _stream()),
+            "plain_layer")
+
+
 def count_head_wide(t: torch.Tensor, qh: torch.Tensor, w2: torch.Tensor, b2, slope: float,
                     exp2_minus_1: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``count_head`` for hidden widths up to 1024 (desco_count_head_wide_f32; hid % 64 == 0, <= 32 queries).

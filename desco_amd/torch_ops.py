@@ -52,6 +52,10 @@ SCHEMAS = {
     "shmp_layer_fused_f16x3": "(Tensor x, Tensor vrowptr, Tensor vcol, int row0, int num_rows, int slots_stored, "
                               "int slots_mfma, Tensor planes, Tensor scale, Tensor bias, Tensor? ytab, int ytab_row0, "
                               "Tensor(a!) out) -> Tensor(a!)",
+    # one plain GIN / GCN layer (csrc/plain_layer.hip): planes2 / scale2 / bias2 given = the two-Linear (GIN) form
+    "plain_layer_f16x3": "(Tensor x, Tensor rowptr, Tensor col, int row0, int num_rows, Tensor planes1, Tensor scale1, "
+                         "Tensor bias1, Tensor? planes2, Tensor? scale2, Tensor? bias2, Tensor? self_scale, "
+                         "Tensor(a!) out) -> Tensor(a!)",
     "gossip_f16_stream": "(Tensor[] planes, Tensor[] scales) -> Tensor[]",
     "gossip_fused_f16x3": "(Tensor scal4, Tensor rowptr, Tensor col, int num_nodes, int num_q, Tensor[] operands, "
                           "float b7, Tensor(a!) queue, Tensor? tile_perm) -> Tensor",
@@ -137,5 +141,12 @@ _CUDA.impl("split_f16_planes", _split_f16_planes)
 _CUDA.impl("gemm_f16x3", lambda a1, planes, scale, bias, a2, act, slope:
            ops.gemm_f16x3(a1, ops.F16Planes(planes, scale), bias, a2=a2, act=act, slope=slope))
 _CUDA.impl("shmp_layer_fused_f16x3", _shmp_layer_fused_f16x3)
+def _plain_layer_f16x3(x, rowptr, col, row0, num_rows, planes1, scale1, bias1, planes2, scale2, bias2, self_scale, out):
+    ops.plain_layer(x, rowptr, col, row0, num_rows, ops.F16Planes(planes1, scale1), bias1,
+                    None if planes2 is None else ops.F16Planes(planes2, scale2), bias2, self_scale=self_scale, out=out)
+    return out
+
+
+_CUDA.impl("plain_layer_f16x3", _plain_layer_f16x3)
 _CUDA.impl("gossip_f16_stream", _gossip_f16_stream)
 _CUDA.impl("gossip_fused_f16x3", _gossip_fused_f16x3)

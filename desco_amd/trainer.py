@@ -243,6 +243,12 @@ class Trainer:
         # (dropout does not stand in the way of replay: the masks are functions of a (seed, step) pair in device memory
         #  that a captured launch advances -- ops.rng_next -- so every replay draws the next mask)
         use_graphs = self.graph_capture and self.device.type == "cuda"
+        plain = next((m.conv_type for m in model.modules() if getattr(m, "is_plain", lambda: False)()), None)
+        if plain is not None and (use_graphs or world > 1 or multi):
+            # (a plain GIN / GCN model's step -- the per-op composition, gnn_model.plain_forward_train -- is validated
+            #  neither under capture nor data parallel)
+            raise NotImplementedError(f"--neigh_conv_type {plain} trains on one GPU without --graph_capture "
+                                      "(ablation_gnns.py); got " + ("graph capture" if use_graphs else "more than one rank"))
         if use_graphs and any(getattr(m, "is_wide", lambda: False)() for m in model.modules()):
             # (the wide path's training step -- --neigh_hidden_dim != 64 -- is not validated under capture)
             raise NotImplementedError("--graph_capture supports --neigh_hidden_dim 64 only; train a model of another "

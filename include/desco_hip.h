@@ -821,6 +821,24 @@ int desco_shmp_layer_wide_f16x3_f32(const float* x, int64_t ldx, const int32_t* 
 int desco_csr_gather_sum_wide_f32(const float* x, int64_t ldx, const int32_t* vrowptr, const int32_t* vcol,
                                   int64_t num_rows, int slots, int width, float* out, int64_t ldo, desco_stream_t stream);
 
+/* One layer of a plain (homogeneous) GIN or GCN neighborhood model, fused (--neigh_conv_type GIN / GCN,
+ * csrc/plain_layer.hip), on operands zero-padded to width = 64 ceil(H / 64) in {64, 128, 192, 256}: for rows r in
+ * [row0, row0 + num_rows) of a PLAIN CSR (rowptr indexed by r, col = rows of x),
+ *   z[r] = sum_{e in [rowptr[r], rowptr[r + 1])} x[col[e]]  (fp32, CSR order)  + s x[r]     (s = *self_scale; 0 if NULL)
+ *   h    = z W1 + b1;      num_mats == 2:  h = relu(h) W2 + b2;      y[r] = relu(h)
+ * W1, W2 [width, width] are passed as planes [2][width][width] / scale = desco_split_f16x2_f32 of their transposes
+ * (w2_planes, w2_scale, b2 are read for num_mats == 2 only).  Both products run in the three-product f16x3 form with
+ * one power-of-two scale per row and product; relu(h) stays in the workgroup.  y[r] goes to out[r * ldo] (may be NULL)
+ * and, for r >= out2_row0, to out2[(r - out2_row0) * ld2] (may be NULL), at least one of them.  x and the planes
+ * 16-byte aligned, ldx % 4 == 0; out / out2 must not be x.  A row whose relu(h) is all zero gives relu(b2) exactly.
+ * Results are bit-reproducible and depend neither on the tiling nor on row0.  self_scale is read on the device (no
+ * host synchronisation).  Capturable. */
+int desco_plain_layer_f16x3_f32(const float* x, int64_t ldx, const int32_t* rowptr, const int32_t* col,
+                                const float* self_scale, int64_t row0, int64_t num_rows, int width, int num_mats,
+                                const int16_t* w1_planes, const float* w1_scale, const float* b1,
+                                const int16_t* w2_planes, const float* w2_scale, const float* b2, float* out,
+                                int64_t ldo, float* out2, int64_t ld2, int64_t out2_row0, desco_stream_t stream);
+
 /* desco_count_head_f32 (same arguments and results, exp2_minus_1 and b2_dev included) for hid % 64 == 0, hid <= 1024;
  * num_q <= 32; t 16-byte aligned, ldt % 4 == 0, ldt and ldq >= hid, ldo >= num_q. */
 int desco_count_head_wide_f32(const float* t, int64_t ldt, const float* qh, int64_t ldq, int hid, const float* w2,
