@@ -424,6 +424,8 @@ class GossipTrunk(torch.autograd.Function):
     (csrc/common_device.hpp); no mask tensor exists.  The step's key is drawn here (ops.rng_next: capturable)."""
 
     SITE_H1, SITE_H2, SITE_POST = 0, 1, 2
+    # the order of save_for_backward (tests read the activations by name)
+    SAVED = ("rowptr", "col", "C6", "C3", "C2", "g1c", "w3", "w5", "wt1", "wtp", "w7", "h1", "hh", "h2", "y", "y3", "y5", "key")
 
     @staticmethod
     def layer_site(l: int) -> int:
@@ -567,6 +569,8 @@ class GossipTrunkDeep(torch.autograd.Function):
     wt_l [128,64], V_l [Q,3,64].  Returns pred [R] = x + post_mp.7(...)."""
 
     layer_site = staticmethod(GossipTrunk.layer_site)
+    # the order of save_for_backward: these, then h_1 .. h_L, hh_1 .. hh_{L-1}, g_1 .. g_{L-1}, wt_1 .. wt_{L-1}
+    SAVED_HEAD = ("rowptr", "col", "C6", "C3", "C2", "w3", "w5", "wtp", "w7", "y", "y3", "y5", "key")
 
     @staticmethod
     def _sites(key, drop, L):

@@ -222,7 +222,9 @@ def check_grads(gm, grads, sd, what):
 
 # (L = 1 at model seed 0 puts an activation of this batch within fp32 rounding of a ReLU / LeakyReLU kink: every layer-0
 #  gradient then differs from the oracle's by the same 1e-3 .. 8e-3 whether or not the dropout path runs at p = 0, and
-#  by 5e-7 with dropout 0.3 on the same weights; seed 2 is a point where the gradient is defined to fp32 accuracy)
+#  by 5e-7 with dropout 0.3 on the same weights; seed 2 is a point where the gradient is defined to fp32 accuracy.
+#  tests/test_gossip_trunk_kernels_gpu.py holds the same nodes per element with relu' pinned to their own activations,
+#  where no kink can hide or fake an error.)
 @pytest.mark.parametrize("L,seed", [(1, 2), (3, 0)])
 def test_deep_gossip_training_vs_oracle(train_setup, L, seed):
     gs, x, y, qemb = train_setup
