@@ -95,6 +95,13 @@ SIGNATURES = {
     "desco_canonical_counts_match_labelled": (c_int, [vp, i64, vp, vp, vp, vp, i64, i32, i32, vp]),
     "desco_canonical_counts_match_labelled_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64,
                                                           i32, i64, i64, vp, vp]),
+    "desco_canonical_counts_match_mode": (c_int, [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "desco_canonical_counts_match_mode_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, i32, i32,
+                                                      i64, i64, vp, vp]),
+    "desco_canonical_counts_match_labelled_mode": (c_int, [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "desco_canonical_counts_match_labelled_mode_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp,
+                                                               i64, i32, i32, i64, i64, vp, vp]),
+    "desco_canonical_noninduced_transform_dev": (c_int, [vp, i64, vp, i64, i32, i32, i32, vp, i64, vp]),
     "desco_linear_smallk_f32": (c_int, [vp, i64, i32, vp, vp, vp, i64, i64, i32, vp]),
     "desco_csr_gather_sum_f32": (c_int, [vp, i64, vp, vp, i64, i32, vp, vp]),
     "desco_gemm_f32": (c_int, [vp, i64, i32, vp, i64, i32, vp, i32, vp, i32, vp, i32, vp, i32, f32,

@@ -175,6 +175,36 @@ __global__ __launch_bounds__(GT_THREADS) void gt_count_kernel(GtArgs a) {
   }
 }
 
+// NON-INDUCED counts of small queries from the census of ALL connected k-node classes (the enumerator above visits
+// every connected k-subset once, so the census costs what one induced column costs):
+//   out[v][q] (+)= sum_c counts[v][c] * m[c][q],   m[c][q] = occurrences of query q in class c (exact, int64).
+// One thread per out element; m (at most 32 x 64 int64 = 16 KB) sits in LDS, the C counts of a row are read by the Q
+// threads of that row from the same addresses.  Integer arithmetic modulo 2^64, as numpy's int64 product.
+constexpr int GT_TR_MAXC = 32, GT_TR_MAXQ = 64;
+
+struct GtTransformArgs {
+  const unsigned long long* counts;  // [N][ldc]
+  const unsigned long long* m;       // [C][Q]
+  unsigned long long* out;           // [N][ldo]
+  int64_t ldc, ldo, total;           // total = N * Q
+  int C, Q, accumulate;
+};
+
+__global__ __launch_bounds__(GT_THREADS) void gt_transform_kernel(GtTransformArgs a) {
+  __shared__ unsigned long long m_s[GT_TR_MAXC * GT_TR_MAXQ];
+  for (int i = threadIdx.x; i < a.C * a.Q; i += GT_THREADS) m_s[i] = a.m[i];
+  __syncthreads();                                 // (the only barrier: every thread reaches it)
+  const int64_t idx = (int64_t)blockIdx.x * GT_THREADS + threadIdx.x;
+  if (idx >= a.total) return;
+  const int64_t row = idx / a.Q;
+  const int q = (int)(idx - row * a.Q);
+  const unsigned long long* cnt = a.counts + row * a.ldc;
+  unsigned long long* dst = a.out + row * a.ldo + q;
+  unsigned long long sum = a.accumulate ? *dst : 0ull;
+  for (int c = 0; c < a.C; ++c) sum += cnt[c] * m_s[c * a.Q + q];
+  *dst = sum;
+}
+
 }  // namespace desco
 
 using namespace desco;
@@ -285,4 +315,21 @@ extern "C" int desco_canonical_counts_dev(const int64_t* graph_ptr, int64_t num_
            cls, kmax, num_queries, num_nodes, num_entries, reinterpret_cast<unsigned long long*>(out)};
   hipLaunchKernelGGL(gt_count_kernel, dim3((unsigned)wblocks), dim3(GT_THREADS), 0, s, a);
   return launch_status("desco_canonical_counts_dev");
+}
+
+extern "C" int desco_canonical_noninduced_transform_dev(const int64_t* counts, int64_t ldc, const int64_t* m,
+                                                        int64_t num_nodes, int num_classes, int num_queries,
+                                                        int accumulate, int64_t* out, int64_t ldo,
+                                                        desco_stream_t stream) {
+  if (num_nodes == 0 || num_queries == 0) return 0;
+  if (!counts || !m || !out || num_nodes < 0 || num_classes < 1 || num_classes > GT_TR_MAXC || num_queries < 0 ||
+      num_queries > GT_TR_MAXQ || ldc < num_classes || ldo < num_queries || (accumulate != 0 && accumulate != 1))
+    return fail(DESCO_EINVAL,
+                "desco_canonical_noninduced_transform_dev: bad argument (1..32 classes, at most 64 queries)");
+  const int64_t total = num_nodes * num_queries, blocks = (total + GT_THREADS - 1) / GT_THREADS;
+  if (blocks > INT32_MAX) return fail(DESCO_EINVAL, "desco_canonical_noninduced_transform_dev: too many rows");
+  GtTransformArgs a{reinterpret_cast<const unsigned long long*>(counts), reinterpret_cast<const unsigned long long*>(m),
+                    reinterpret_cast<unsigned long long*>(out), ldc, ldo, total, num_classes, num_queries, accumulate};
+  hipLaunchKernelGGL(gt_transform_kernel, dim3((unsigned)blocks), dim3(GT_THREADS), 0, (hipStream_t)stream, a);
+  return launch_status("desco_canonical_noninduced_transform_dev");
 }

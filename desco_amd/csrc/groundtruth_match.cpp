@@ -29,6 +29,16 @@
 // isomorphism CLASSES (numbered by first query; the caller expands out[:, class_of_query]), its records carry the
 // label of every position and are sorted by (label of position 0, label of position 1) with a bucket table behind
 // them (groundtruth_match.hpp): a root and its first neighbour select the one bucket whose records can match.
+//
+// NON-INDUCED mode (desco_canonical_counts_match_mode, desco_canonical_counts_match_labelled_mode with induced = 0):
+//
+//   count[v][q] = #{ injective f : {f(a), f(b)} in E(G) for every {a, b} in E(q), max(im f) = v } / |Aut(q)|
+//
+// i.e. occurrences of q as a not necessarily induced subgraph (monomorphisms), rooted at the largest image.  The plan
+// is the same, byte for byte: anchors, matching order and order constraints depend on Aut(q) alone, and Aut(q) acts
+// freely on monomorphisms by pre-composition exactly as on induced embeddings, so the argument above holds word for
+// word with "isomorphisms q -> G[S]" replaced by "the |Aut(q)| monomorphisms with one image (node AND edge set)".  Only
+// the reading of rec[GTM_ADJ] differs: a set bit still means "adjacent", a clear bit means nothing.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -335,7 +345,8 @@ int build_plan_labelled(const char* who, const int32_t* q_nodes, const int32_t* 
 }
 
 // One graph's matcher state.  LAB: the labelled matcher, which tests a candidate's label before its adjacency bits.
-template <bool LAB>
+// IND: induced matching (a clear GTM_ADJ bit means NOT adjacent); else a clear bit asks nothing.
+template <bool LAB, bool IND>
 struct Matcher {
   int64_t base;
   const int64_t* rowptr;
@@ -356,7 +367,8 @@ struct Matcher {
                    gt = (uint32_t)rec[GTM_GT + level];
     for (int j = 0; j < level; ++j) {
       const int w = img[j];
-      if (u == w || adj(u, w) != (want >> j & 1)) return false;
+      if (u == w) return false;
+      if (IND ? adj(u, w) != (want >> j & 1) : (want >> j & 1) && !adj(u, w)) return false;
       if ((lt >> j & 1) && !(u < w)) return false;
       if ((gt >> j & 1) && !(u > w)) return false;
     }
@@ -507,12 +519,15 @@ int desco::match_plan_labelled_check(const char* who, const int32_t* plan, int64
   return 0;
 }
 
-extern "C" int desco_canonical_counts_match(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
-                                            const int32_t* col, const int32_t* plan, int64_t plan_entries,
-                                            int num_queries, int num_threads, int64_t* out) {
+namespace {
+
+template <bool IND>
+int counts_match(const std::string& who, const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                 const int32_t* col, const int32_t* plan, int64_t plan_entries, int num_queries, int num_threads,
+                 int64_t* out) {
   if (!graph_ptr || !rowptr || !out || num_graphs < 0 || num_queries < 0)
-    return fail(DESCO_EINVAL, "desco_canonical_counts_match: bad argument");
-  if (const int rc = match_plan_check("desco_canonical_counts_match", plan, plan_entries, num_queries)) return rc;
+    return fail(DESCO_EINVAL, (who + ": bad argument").c_str());
+  if (const int rc = match_plan_check(who.c_str(), plan, plan_entries, num_queries)) return rc;
   try {
     const int64_t total = graph_ptr[num_graphs];
     std::memset(out, 0, sizeof(int64_t) * (size_t)total * (size_t)num_queries);
@@ -542,7 +557,7 @@ extern "C" int desco_canonical_counts_match(const int64_t* graph_ptr, int64_t nu
           const int w = (int)(col[e] - base);
           bits[(size_t)u * words + (w >> 6)] |= (uint64_t)1 << (w & 63);
         }
-      Matcher<false> m;
+      Matcher<false, IND> m;
       m.base = base;
       m.rowptr = rowptr;
       m.col = col;
@@ -561,21 +576,20 @@ extern "C" int desco_canonical_counts_match(const int64_t* graph_ptr, int64_t nu
         }
       }
     }
-    if (oom) return fail(DESCO_ENOMEM, "desco_canonical_counts_match: out of memory");
+    if (oom) return fail(DESCO_ENOMEM, (who + ": out of memory").c_str());
     return 0;
   } catch (const std::bad_alloc&) {
-    return fail(DESCO_ENOMEM, "desco_canonical_counts_match: out of memory");
+    return fail(DESCO_ENOMEM, (who + ": out of memory").c_str());
   }
 }
 
-extern "C" int desco_canonical_counts_match_labelled(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
-                                                     const int32_t* col, const int32_t* labels, const int32_t* plan,
-                                                     int64_t plan_entries, int num_classes, int num_threads,
-                                                     int64_t* out) {
-  const char* who = "desco_canonical_counts_match_labelled";
+template <bool IND>
+int counts_match_labelled(const std::string& who, const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                          const int32_t* col, const int32_t* labels, const int32_t* plan, int64_t plan_entries,
+                          int num_classes, int num_threads, int64_t* out) {
   if (!graph_ptr || !rowptr || !out || num_graphs < 0 || num_classes < 0 || (graph_ptr[num_graphs] > 0 && !labels))
-    return fail(DESCO_EINVAL, "desco_canonical_counts_match_labelled: bad argument");
-  if (const int rc = match_plan_labelled_check(who, plan, plan_entries, num_classes)) return rc;
+    return fail(DESCO_EINVAL, (who + ": bad argument").c_str());
+  if (const int rc = match_plan_labelled_check(who.c_str(), plan, plan_entries, num_classes)) return rc;
   try {
     const int64_t total = graph_ptr[num_graphs];
     std::memset(out, 0, sizeof(int64_t) * (size_t)total * (size_t)num_classes);
@@ -605,7 +619,7 @@ extern "C" int desco_canonical_counts_match_labelled(const int64_t* graph_ptr, i
           const int w = (int)(col[e] - base);
           bits[(size_t)u * words + (w >> 6)] |= (uint64_t)1 << (w & 63);
         }
-      Matcher<true> m;
+      Matcher<true, IND> m;
       m.base = base;
       m.rowptr = rowptr;
       m.col = col;
@@ -626,9 +640,51 @@ extern "C" int desco_canonical_counts_match_labelled(const int64_t* graph_ptr, i
         }
       }
     }
-    if (oom) return fail(DESCO_ENOMEM, "desco_canonical_counts_match_labelled: out of memory");
+    if (oom) return fail(DESCO_ENOMEM, (who + ": out of memory").c_str());
     return 0;
   } catch (const std::bad_alloc&) {
-    return fail(DESCO_ENOMEM, "desco_canonical_counts_match_labelled: out of memory");
+    return fail(DESCO_ENOMEM, (who + ": out of memory").c_str());
   }
+}
+
+}  // namespace
+
+extern "C" int desco_canonical_counts_match(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                            const int32_t* col, const int32_t* plan, int64_t plan_entries,
+                                            int num_queries, int num_threads, int64_t* out) {
+  return counts_match<true>("desco_canonical_counts_match", graph_ptr, num_graphs, rowptr, col, plan, plan_entries,
+                            num_queries, num_threads, out);
+}
+
+extern "C" int desco_canonical_counts_match_mode(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                                 const int32_t* col, const int32_t* plan, int64_t plan_entries,
+                                                 int num_queries, int induced, int num_threads, int64_t* out) {
+  const char* who = "desco_canonical_counts_match_mode";
+  if (induced != 0 && induced != 1) return fail(DESCO_EINVAL, "desco_canonical_counts_match_mode: induced must be 0 or 1");
+  return induced ? counts_match<true>(who, graph_ptr, num_graphs, rowptr, col, plan, plan_entries, num_queries,
+                                      num_threads, out)
+                 : counts_match<false>(who, graph_ptr, num_graphs, rowptr, col, plan, plan_entries, num_queries,
+                                       num_threads, out);
+}
+
+extern "C" int desco_canonical_counts_match_labelled(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                                     const int32_t* col, const int32_t* labels, const int32_t* plan,
+                                                     int64_t plan_entries, int num_classes, int num_threads,
+                                                     int64_t* out) {
+  return counts_match_labelled<true>("desco_canonical_counts_match_labelled", graph_ptr, num_graphs, rowptr, col,
+                                     labels, plan, plan_entries, num_classes, num_threads, out);
+}
+
+extern "C" int desco_canonical_counts_match_labelled_mode(const int64_t* graph_ptr, int64_t num_graphs,
+                                                          const int64_t* rowptr, const int32_t* col,
+                                                          const int32_t* labels, const int32_t* plan,
+                                                          int64_t plan_entries, int num_classes, int induced,
+                                                          int num_threads, int64_t* out) {
+  const char* who = "desco_canonical_counts_match_labelled_mode";
+  if (induced != 0 && induced != 1)
+    return fail(DESCO_EINVAL, "desco_canonical_counts_match_labelled_mode: induced must be 0 or 1");
+  return induced ? counts_match_labelled<true>(who, graph_ptr, num_graphs, rowptr, col, labels, plan, plan_entries,
+                                               num_classes, num_threads, out)
+                 : counts_match_labelled<false>(who, graph_ptr, num_graphs, rowptr, col, labels, plan, plan_entries,
+                                                num_classes, num_threads, out);
 }

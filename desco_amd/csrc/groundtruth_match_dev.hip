@@ -30,6 +30,12 @@
 // of the entry is found by the whole wave too (64 probes per step).  Every surviving item has positions 0 and 1
 // matched; the label of a later position's candidate (one 4-byte load; the wanted label sits in LDS with the rest
 // of the record) is tested before the bitset loop.
+//
+// NON-INDUCED mode (desco_canonical_counts_match_mode_dev, desco_canonical_counts_match_labelled_mode_dev with
+// induced = 0; two more instantiations of the kernel template, the two above compile to what they were): count[v][q] =
+// the occurrences of q as a not necessarily induced subgraph whose largest node is v, i.e. the injective edge-preserving
+// maps with maximum image v divided by |Aut(q)|.  Same plans, same items, same slices: a set adjacency-mask bit still
+// asks for an edge, a clear bit asks nothing (groundtruth_match.cpp has the argument).
 #include <type_traits>
 
 #include "common_device.hpp"
@@ -58,6 +64,10 @@ struct GtmLabArgs : GtmArgs {          // num_anchors = the largest bucket: item
   const int32_t* buckets;              // the plan's bucket table (device)
   int num_buckets;
 };
+
+// the same arguments for the non-induced instantiations (the type selects the mode at compile time)
+struct GtmMonoArgs : GtmArgs {};
+struct GtmLabMonoArgs : GtmLabArgs {};
 
 __device__ __forceinline__ int64_t gtm_row_of_entry(const int64_t* __restrict__ rowptr, int64_t n, int64_t e) {
   int64_t lo = 0, hi = n;            // last row with rowptr[row] <= e
@@ -91,8 +101,8 @@ struct GtmCtx {
   const int* qlab;                   // this wave's per-position labels (LDS)
 };
 
-// does u fit position `level`, given the images of the positions before it?
-template <bool LAB>
+// does u fit position `level`, given the images of the positions before it?  IND: a clear mask bit means NOT adjacent
+template <bool LAB, bool IND>
 __device__ __forceinline__ bool gtm_fits(const GtmCtx& c, int level, int u) {
   if constexpr (LAB) {
     if (c.lab[u] != c.qlab[level]) return false;
@@ -102,7 +112,11 @@ __device__ __forceinline__ bool gtm_fits(const GtmCtx& c, int level, int u) {
   for (int j = 0; j < level; ++j) {
     const int w = c.img[j * GTM_THREADS];
     const unsigned a = (unsigned)(row[w >> 6] >> (w & 63)) & 1u;
-    if (u == w || a != ((want >> j) & 1u)) return false;
+    if constexpr (IND) {
+      if (u == w || a != ((want >> j) & 1u)) return false;
+    } else {
+      if (u == w || (((want >> j) & 1u) & ~a)) return false;
+    }
     if (((order >> j) & 1u) && !(u < w)) return false;
     if (((order >> (16 + j)) & 1u) && !(u > w)) return false;
   }
@@ -111,7 +125,8 @@ __device__ __forceinline__ bool gtm_fits(const GtmCtx& c, int level, int u) {
 
 template <class Args>
 __global__ __launch_bounds__(GTM_THREADS) void gtm_count_kernel(Args a) {
-  constexpr bool LAB = std::is_same<Args, GtmLabArgs>::value;
+  constexpr bool LAB = std::is_base_of<GtmLabArgs, Args>::value;
+  constexpr bool IND = !std::is_same<Args, GtmMonoArgs>::value && !std::is_same<Args, GtmLabMonoArgs>::value;
   constexpr int HEAD = LAB ? GTML_HEAD : GTM_HEAD, REC = LAB ? GTML_REC : GTM_REC;
   __shared__ int img_s[GTM_KMAX * GTM_THREADS];
   __shared__ long long cur_s[GTM_KMAX * GTM_THREADS];
@@ -186,7 +201,7 @@ __global__ __launch_bounds__(GTM_THREADS) void gtm_count_kernel(Args a) {
     for (int64_t e2 = r0 + lane; e2 < r1; e2 += 64) {
       const int u2 = (int)(a.col[e2] - base);
       if (u2 >= c.lv) break;                       // rows ascend
-      if (!gtm_fits<LAB>(c, 2, u2)) continue;
+      if (!gtm_fits<LAB, IND>(c, 2, u2)) continue;
       if (k == 3) {
         ++found;
         continue;
@@ -204,7 +219,7 @@ __global__ __launch_bounds__(GTM_THREADS) void gtm_count_kernel(Args a) {
           continue;
         }
         cur[level * GTM_THREADS] = ec + 1;
-        if (!gtm_fits<LAB>(c, level, u)) continue;
+        if (!gtm_fits<LAB, IND>(c, level, u)) continue;
         if (level + 1 == k) {
           ++found;
         } else {
@@ -224,24 +239,26 @@ __global__ __launch_bounds__(GTM_THREADS) void gtm_count_kernel(Args a) {
 
 using namespace desco;
 
-extern "C" int desco_canonical_counts_match_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
-                                                const int64_t* rowptr, int64_t num_entries, const int32_t* col,
-                                                const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
-                                                int64_t num_words, const int32_t* plan_host, const int32_t* plan_dev,
-                                                int64_t plan_entries, int num_queries, int64_t entry_begin,
-                                                int64_t entry_end, int64_t* out, desco_stream_t stream) {
-  const char* who = "desco_canonical_counts_match_dev";
+namespace {
+
+template <class Args>
+int gtm_launch(const std::string& name, const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+               const int64_t* rowptr, int64_t num_entries, const int32_t* col, const int32_t* node_graph,
+               const int64_t* bit_off, uint64_t* bits, int64_t num_words, const int32_t* plan_host,
+               const int32_t* plan_dev, int64_t plan_entries, int num_queries, int64_t entry_begin, int64_t entry_end,
+               int64_t* out, desco_stream_t stream) {
+  const char* who = name.c_str();
   if (num_nodes == 0 || num_queries == 0) return 0;
   if (!graph_ptr || !rowptr || !node_graph || !bit_off || !bits || !plan_dev || !out || num_graphs < 0 ||
       num_nodes < 0 || num_entries < 0 || num_words < 0 || num_queries < 0 || (num_entries > 0 && !col) ||
       entry_begin < 0 || entry_end < entry_begin || entry_end > num_entries)
-    return fail(DESCO_EINVAL, "desco_canonical_counts_match_dev: bad argument");
+    return fail(DESCO_EINVAL, (name + ": bad argument").c_str());
   if (const int rc = match_plan_check(who, plan_host, plan_entries, num_queries)) return rc;
   const int num_anchors = plan_host[1];
   hipStream_t s = (hipStream_t)stream;
   if (entry_begin == 0) {                          // the first slice: zero the counts, build the bitset rows
     if (hipMemsetAsync(out, 0, (size_t)num_nodes * num_queries * 8, s) != hipSuccess)
-      return launch_status("desco_canonical_counts_match_dev: memset");
+      return launch_status((name + ": memset").c_str());
     if (const int rc = gt_build_bitsets(graph_ptr, rowptr, col, node_graph, bit_off, bits, num_words, num_nodes,
                                         num_entries, stream, who))
       return rc;
@@ -250,12 +267,83 @@ extern "C" int desco_canonical_counts_match_dev(const int64_t* graph_ptr, int64_
   if (items == 0) return 0;
   const int64_t blocks = (items + GTM_WAVES - 1) / GTM_WAVES;
   if (blocks > INT32_MAX)
-    return fail(DESCO_EINVAL, "desco_canonical_counts_match_dev: slice too large (entries x anchors / 4 > 2^31 - 1)");
-  GtmArgs a{graph_ptr, rowptr, col, node_graph, bit_off, reinterpret_cast<const unsigned long long*>(bits),
-            plan_dev, num_anchors, num_queries, num_nodes, entry_begin, items,
-            reinterpret_cast<unsigned long long*>(out)};
-  hipLaunchKernelGGL(gtm_count_kernel<GtmArgs>, dim3((unsigned)blocks), dim3(GTM_THREADS), 0, s, a);
+    return fail(DESCO_EINVAL, (name + ": slice too large (entries x anchors / 4 > 2^31 - 1)").c_str());
+  Args a;
+  static_cast<GtmArgs&>(a) = GtmArgs{graph_ptr, rowptr, col, node_graph, bit_off,
+                                     reinterpret_cast<const unsigned long long*>(bits), plan_dev, num_anchors,
+                                     num_queries, num_nodes, entry_begin, items,
+                                     reinterpret_cast<unsigned long long*>(out)};
+  hipLaunchKernelGGL(gtm_count_kernel<Args>, dim3((unsigned)blocks), dim3(GTM_THREADS), 0, s, a);
   return launch_status(who);
+}
+
+template <class Args>
+int gtm_launch_labelled(const std::string& name, const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                        const int64_t* rowptr, int64_t num_entries, const int32_t* col, const int32_t* node_graph,
+                        const int64_t* bit_off, uint64_t* bits, int64_t num_words, const int32_t* labels,
+                        const int32_t* plan_host, const int32_t* plan_dev, int64_t plan_entries, int num_classes,
+                        int64_t entry_begin, int64_t entry_end, int64_t* out, desco_stream_t stream) {
+  const char* who = name.c_str();
+  if (num_nodes == 0 || num_classes == 0) return 0;
+  if (!graph_ptr || !rowptr || !node_graph || !bit_off || !bits || !labels || !plan_dev || !out || num_graphs < 0 ||
+      num_nodes < 0 || num_entries < 0 || num_words < 0 || num_classes < 0 || (num_entries > 0 && !col) ||
+      entry_begin < 0 || entry_end < entry_begin || entry_end > num_entries)
+    return fail(DESCO_EINVAL, (name + ": bad argument").c_str());
+  if (const int rc = match_plan_labelled_check(who, plan_host, plan_entries, num_classes)) return rc;
+  const int num_recs = plan_host[1], num_buckets = plan_host[2], largest = plan_host[3];
+  hipStream_t s = (hipStream_t)stream;
+  if (entry_begin == 0) {                          // the first slice: zero the counts, build the bitset rows
+    if (hipMemsetAsync(out, 0, (size_t)num_nodes * num_classes * 8, s) != hipSuccess)
+      return launch_status((name + ": memset").c_str());
+    if (const int rc = gt_build_bitsets(graph_ptr, rowptr, col, node_graph, bit_off, bits, num_words, num_nodes,
+                                        num_entries, stream, who))
+      return rc;
+  }
+  const int64_t items = (entry_end - entry_begin) * largest;     // (entry, j-th record of the entry's bucket)
+  if (items == 0) return 0;
+  const int64_t blocks = (items + GTM_WAVES - 1) / GTM_WAVES;
+  if (blocks > INT32_MAX)
+    return fail(DESCO_EINVAL, (name + ": slice too large (entries x largest bucket / 4 > 2^31 - 1)").c_str());
+  Args a;
+  static_cast<GtmArgs&>(a) = GtmArgs{graph_ptr, rowptr, col, node_graph, bit_off,
+                                     reinterpret_cast<const unsigned long long*>(bits), plan_dev, largest, num_classes,
+                                     num_nodes, entry_begin, items, reinterpret_cast<unsigned long long*>(out)};
+  a.labels = labels;
+  a.buckets = plan_dev + GTML_HEAD + (int64_t)num_recs * GTML_REC;
+  a.num_buckets = num_buckets;
+  hipLaunchKernelGGL(gtm_count_kernel<Args>, dim3((unsigned)blocks), dim3(GTM_THREADS), 0, s, a);
+  return launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int desco_canonical_counts_match_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                                const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                                const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                                int64_t num_words, const int32_t* plan_host, const int32_t* plan_dev,
+                                                int64_t plan_entries, int num_queries, int64_t entry_begin,
+                                                int64_t entry_end, int64_t* out, desco_stream_t stream) {
+  return gtm_launch<GtmArgs>("desco_canonical_counts_match_dev", graph_ptr, num_graphs, num_nodes, rowptr, num_entries,
+                             col, node_graph, bit_off, bits, num_words, plan_host, plan_dev, plan_entries, num_queries,
+                             entry_begin, entry_end, out, stream);
+}
+
+extern "C" int desco_canonical_counts_match_mode_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                                     const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                                     const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                                     int64_t num_words, const int32_t* plan_host,
+                                                     const int32_t* plan_dev, int64_t plan_entries, int num_queries,
+                                                     int induced, int64_t entry_begin, int64_t entry_end, int64_t* out,
+                                                     desco_stream_t stream) {
+  const char* who = "desco_canonical_counts_match_mode_dev";
+  if (induced != 0 && induced != 1)
+    return fail(DESCO_EINVAL, "desco_canonical_counts_match_mode_dev: induced must be 0 or 1");
+  return induced ? gtm_launch<GtmArgs>(who, graph_ptr, num_graphs, num_nodes, rowptr, num_entries, col, node_graph,
+                                       bit_off, bits, num_words, plan_host, plan_dev, plan_entries, num_queries,
+                                       entry_begin, entry_end, out, stream)
+                 : gtm_launch<GtmMonoArgs>(who, graph_ptr, num_graphs, num_nodes, rowptr, num_entries, col, node_graph,
+                                           bit_off, bits, num_words, plan_host, plan_dev, plan_entries, num_queries,
+                                           entry_begin, entry_end, out, stream);
 }
 
 extern "C" int desco_canonical_counts_match_labelled_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
@@ -265,35 +353,25 @@ extern "C" int desco_canonical_counts_match_labelled_dev(const int64_t* graph_pt
                                                          const int32_t* plan_host, const int32_t* plan_dev,
                                                          int64_t plan_entries, int num_classes, int64_t entry_begin,
                                                          int64_t entry_end, int64_t* out, desco_stream_t stream) {
-  const char* who = "desco_canonical_counts_match_labelled_dev";
-  if (num_nodes == 0 || num_classes == 0) return 0;
-  if (!graph_ptr || !rowptr || !node_graph || !bit_off || !bits || !labels || !plan_dev || !out || num_graphs < 0 ||
-      num_nodes < 0 || num_entries < 0 || num_words < 0 || num_classes < 0 || (num_entries > 0 && !col) ||
-      entry_begin < 0 || entry_end < entry_begin || entry_end > num_entries)
-    return fail(DESCO_EINVAL, "desco_canonical_counts_match_labelled_dev: bad argument");
-  if (const int rc = match_plan_labelled_check(who, plan_host, plan_entries, num_classes)) return rc;
-  const int num_recs = plan_host[1], num_buckets = plan_host[2], largest = plan_host[3];
-  hipStream_t s = (hipStream_t)stream;
-  if (entry_begin == 0) {                          // the first slice: zero the counts, build the bitset rows
-    if (hipMemsetAsync(out, 0, (size_t)num_nodes * num_classes * 8, s) != hipSuccess)
-      return launch_status("desco_canonical_counts_match_labelled_dev: memset");
-    if (const int rc = gt_build_bitsets(graph_ptr, rowptr, col, node_graph, bit_off, bits, num_words, num_nodes,
-                                        num_entries, stream, who))
-      return rc;
-  }
-  const int64_t items = (entry_end - entry_begin) * largest;     // (entry, j-th record of the entry's bucket)
-  if (items == 0) return 0;
-  const int64_t blocks = (items + GTM_WAVES - 1) / GTM_WAVES;
-  if (blocks > INT32_MAX)
-    return fail(DESCO_EINVAL,
-                "desco_canonical_counts_match_labelled_dev: slice too large (entries x largest bucket / 4 > 2^31 - 1)");
-  GtmLabArgs a;
-  static_cast<GtmArgs&>(a) = GtmArgs{graph_ptr, rowptr, col, node_graph, bit_off,
-                                     reinterpret_cast<const unsigned long long*>(bits), plan_dev, largest, num_classes,
-                                     num_nodes, entry_begin, items, reinterpret_cast<unsigned long long*>(out)};
-  a.labels = labels;
-  a.buckets = plan_dev + GTML_HEAD + (int64_t)num_recs * GTML_REC;
-  a.num_buckets = num_buckets;
-  hipLaunchKernelGGL(gtm_count_kernel<GtmLabArgs>, dim3((unsigned)blocks), dim3(GTM_THREADS), 0, s, a);
-  return launch_status(who);
+  return gtm_launch_labelled<GtmLabArgs>("desco_canonical_counts_match_labelled_dev", graph_ptr, num_graphs, num_nodes,
+                                         rowptr, num_entries, col, node_graph, bit_off, bits, num_words, labels,
+                                         plan_host, plan_dev, plan_entries, num_classes, entry_begin, entry_end, out,
+                                         stream);
+}
+
+extern "C" int desco_canonical_counts_match_labelled_mode_dev(
+    const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes, const int64_t* rowptr, int64_t num_entries,
+    const int32_t* col, const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits, int64_t num_words,
+    const int32_t* labels, const int32_t* plan_host, const int32_t* plan_dev, int64_t plan_entries, int num_classes,
+    int induced, int64_t entry_begin, int64_t entry_end, int64_t* out, desco_stream_t stream) {
+  const char* who = "desco_canonical_counts_match_labelled_mode_dev";
+  if (induced != 0 && induced != 1)
+    return fail(DESCO_EINVAL, "desco_canonical_counts_match_labelled_mode_dev: induced must be 0 or 1");
+  return induced ? gtm_launch_labelled<GtmLabArgs>(who, graph_ptr, num_graphs, num_nodes, rowptr, num_entries, col,
+                                                   node_graph, bit_off, bits, num_words, labels, plan_host, plan_dev,
+                                                   plan_entries, num_classes, entry_begin, entry_end, out, stream)
+                 : gtm_launch_labelled<GtmLabMonoArgs>(who, graph_ptr, num_graphs, num_nodes, rowptr, num_entries, col,
+                                                       node_graph, bit_off, bits, num_words, labels, plan_host,
+                                                       plan_dev, plan_entries, num_classes, entry_begin, entry_end, out,
+                                                       stream);
 }

@@ -3,6 +3,7 @@ process pool, workload.py:551-726)."""
 from __future__ import annotations
 
 import ctypes
+import functools
 from typing import Sequence
 
 import numpy as np
@@ -41,10 +42,15 @@ def _device_eligible(graphs: GraphSet, q_nodes: np.ndarray) -> bool:
     return int((n * ((n + 63) // 64)).sum()) <= _DEVICE_BITSET_LIMIT_WORDS
 
 
-def canonical_counts_device(graphs: GraphSet, queries: Sequence, device="cuda") -> torch.Tensor:
+def canonical_counts_device(graphs: GraphSet, queries: Sequence, device="cuda", induced: bool = True) -> torch.Tensor:
     """The counts of ``canonical_counts`` computed on the MI355X (csrc/groundtruth_dev.hip):
     queries of 2..5 nodes, at most 32, pairwise non-isomorphic.  Returns a [num_nodes, num_queries]
-    int64 tensor on ``device``."""
+    int64 tensor on ``device``.
+    ``induced=False``: the non-induced counts (see ``canonical_counts``) of queries of 2..5 nodes, any number of them,
+    duplicates included: the census of all connected classes of the queries' sizes by the same kernel, then the exact
+    int64 transform on the device (``desco_canonical_noninduced_transform_dev``), without a round trip."""
+    if not induced:
+        return _noninduced_device(graphs, _flatten_queries(queries)[0], torch.device(device))
     _, q_nodes, q_edge_ptr, q_edges = _flatten_queries(queries)
     L = _lib.lib()
     table = np.empty(1098, dtype=np.int16)
@@ -76,25 +82,39 @@ def canonical_counts_device(graphs: GraphSet, queries: Sequence, device="cuda") 
 
 
 def canonical_counts(graphs: GraphSet, queries: Sequence, num_threads: int = 0,
-                     backend: str = "auto") -> torch.Tensor:
+                     backend: str = "auto", induced: bool = True, method: str = "auto") -> torch.Tensor:
     """[num_nodes, num_queries] float tensor of canonical counts (the reference stores doubles).
     ``queries``: networkx graphs or (n, edges) pairs, connected, 2..16 nodes.
     ``backend``: "host" (OpenMP), "device" (HIP kernels), "auto", or "vf2" (the reference's procedure in Python:
     the yardstick of the tests and the way out for queries above 16 nodes).
     Columns of queries with at most 6 nodes go to the ESU enumerators -- "auto": the device when a GPU is present
     and the queries fit its path (2..5 nodes, <= 32, distinct classes), else the host.  Columns of larger queries
-    go to the matcher (``canonical_counts_match``) with the same ``backend``; the results are joined in query order."""
+    go to the matcher (``canonical_counts_match``) with the same ``backend``; the results are joined in query order.
+    ``induced=False``: NON-INDUCED counts, count[v][q] = #{injective f : f maps every edge of q onto an edge of G,
+    max(im f) = v} / |Aut(q)| -- occurrences that need only CONTAIN the query's edges (P3 in a triangle: 3, all at the
+    largest node).  Columns of at most 6 nodes come from the census of all connected classes of that size, run where
+    induced columns of that size run, and the exact int64 transform ``noninduced_matrix``; larger ones from the
+    matcher's non-induced mode; "vf2" is ``subgraph_monomorphisms_iter`` keyed and divided the same way.
+    ``method``: "auto" (the routing above) or "matcher" (every size to the matcher, to compare the two native routes)."""
+    if method not in ("auto", "matcher"):
+        raise ValueError(f"unknown method {method!r}")
     if backend == "vf2":
-        return _canonical_counts_vf2(graphs, queries)
+        return _canonical_counts_vf2(graphs, queries, induced)
+    if not induced and backend not in ("auto", "host", "device"):
+        raise ValueError(f"unknown backend {backend!r}")
     flat, q_nodes, q_edge_ptr, q_edges = _flatten_queries(queries)
+    if method == "matcher":
+        return canonical_counts_match(graphs, flat, backend, num_threads, induced=induced)
     large = [i for i, k in enumerate(q_nodes) if k > 6]
     if large:
         small = [i for i, k in enumerate(q_nodes) if k <= 6]
         out = torch.zeros((graphs.num_nodes, len(flat)), dtype=torch.double)
-        out[:, large] = canonical_counts_match(graphs, [flat[i] for i in large], backend, num_threads)
+        out[:, large] = canonical_counts_match(graphs, [flat[i] for i in large], backend, num_threads, induced=induced)
         if small:
-            out[:, small] = canonical_counts(graphs, [flat[i] for i in small], num_threads, backend)
+            out[:, small] = canonical_counts(graphs, [flat[i] for i in small], num_threads, backend, induced)
         return out
+    if not induced:
+        return _noninduced_small(graphs, flat, backend, num_threads)
     if backend == "device" or (backend == "auto" and _device_eligible(graphs, q_nodes)):
         try:
             return canonical_counts_device(graphs, queries).cpu().double()
@@ -109,6 +129,147 @@ def canonical_counts(graphs: GraphSet, queries: Sequence, num_threads: int = 0,
                                         q_edges.ctypes.data if len(q_edges) else None, len(flat),
                                         num_threads, out.ctypes.data), "desco_canonical_counts")
     return torch.from_numpy(out).double()
+
+
+# ---- non-induced counts of small queries: census of all classes + an exact transform ---------------------------------
+@functools.lru_cache(maxsize=None)
+def census_classes(k: int):
+    """All connected k-node graphs, k = 2..6, as a tuple of (k, edges) in graph-atlas order: 1, 2, 6, 21 and 112."""
+    if k == 2:
+        return ((2, ((0, 1),)),)
+    if not 3 <= k <= 6:
+        raise ValueError("census classes exist for 2..6 nodes")
+    from .data import gen_query_ids, graph_atlas_plus
+    return tuple((k, tuple(tuple(e) for e in graph_atlas_plus(i).edges())) for i in gen_query_ids([k]))
+
+
+_occurrence_rows = {}               # (k, sorted edges) -> int64 [number of classes]: computed once per process
+
+
+def _noninduced_rows(flat) -> np.ndarray:
+    """int64 [len(flat), number of k-node classes], rows M_k[q][:] of queries ``flat`` that all have k nodes (2..6):
+    the occurrences of q in every class representative, by the host matcher's non-induced mode."""
+    k = int(flat[0][0])
+    classes = census_classes(k)
+    keys = [(k, tuple(sorted((min(a, b), max(a, b)) for a, b in edges))) for _, edges in flat]
+    todo = sorted({key for key in keys if key not in _occurrence_rows})
+    if todo:
+        reps = GraphSet.from_edge_lists([(n, list(e)) for n, e in classes])
+        counts = _match_host_int64(reps, [(n, list(e)) for n, e in todo], False, 1)
+        per_class = counts.reshape(len(classes), k, len(todo)).sum(axis=1)
+        for j, key in enumerate(todo):
+            _occurrence_rows[key] = np.ascontiguousarray(per_class[:, j])
+    return np.stack([_occurrence_rows[key] for key in keys])
+
+
+def noninduced_matrix(k: int) -> np.ndarray:
+    """M_k, int64 [C, C] over ``census_classes(k)``: M_k[q][c] = the occurrences of class q in class c as a not
+    necessarily induced subgraph.  noninduced[v][q] = sum_c M_k[q][c] * induced[v][c]: a k-subset whose induced
+    subgraph is c holds M_k[q][c] occurrences of q, and ESU visits every connected k-subset once."""
+    return _noninduced_rows([(n, list(e)) for n, e in census_classes(k)])
+
+
+def _census_plan(flat):
+    """Checks the queries (the matcher's plan refuses what is not connected, loop-free, of 2..16 nodes) and returns
+    [(classes, query indices, M rows)] per census call: the sizes 2..5 together (30 classes at most), size 6 apart."""
+    match_plan(flat)
+    groups = []
+    for sizes in ((2, 3, 4, 5), (6,)):
+        classes, idx, blocks = [], [], []
+        for k in sizes:
+            mine = [i for i, (n, _) in enumerate(flat) if n == k]
+            if mine:
+                blocks.append((len(classes), mine, _noninduced_rows([flat[i] for i in mine])))
+                classes += [(n, list(e)) for n, e in census_classes(k)]
+                idx += mine
+        if idx:
+            m = np.zeros((len(classes), len(idx)), dtype=np.int64)          # [C, Q]: zero across sizes
+            col = 0
+            for c0, mine, rows in blocks:
+                m[c0:c0 + rows.shape[1], col:col + len(mine)] = rows.T
+                col += len(mine)
+            groups.append((classes, idx, m))
+    return groups
+
+
+def _transform_device(census: torch.Tensor, m: np.ndarray, out: torch.Tensor, accumulate: bool):
+    """out[:, :] (+)= census @ m on the device, int64: census [N, C <= 32], m [C, Q], out [N, Q]; Q in chunks of 64."""
+    L = _lib.lib()
+    dev = census.device
+    N, C = census.shape
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for q0 in range(0, m.shape[1], 64):
+            q1 = min(q0 + 64, m.shape[1])
+            m_d = torch.from_numpy(np.ascontiguousarray(m[:, q0:q1])).to(dev)
+            _lib.check(L.desco_canonical_noninduced_transform_dev(
+                census.data_ptr(), census.stride(0), m_d.data_ptr(), N, C, q1 - q0, int(accumulate),
+                out.data_ptr() + 8 * q0, out.stride(0), stream), "desco_canonical_noninduced_transform_dev")
+            torch.cuda.current_stream(dev).synchronize()        # m_d is released when this iteration ends
+
+
+def noninduced_transform_device(census: torch.Tensor, m, accumulate_into=None) -> torch.Tensor:
+    """``census`` [N, C] int64 on the GPU times ``m`` [C, Q] int64 (numpy or tensor), modulo 2^64, by the HIP kernel of
+    ``canonical_counts_device(induced=False)``: C of 1..32, any Q.  Returns the [N, Q] int64 tensor on the census's
+    device; with ``accumulate_into`` (such a tensor) the product is added to it."""
+    if not census.is_cuda:
+        raise RuntimeError("noninduced_transform_device: no CPU fallback (the host route uses numpy int64)")
+    m = np.ascontiguousarray(m.cpu().numpy() if isinstance(m, torch.Tensor) else m, dtype=np.int64)
+    census = census.contiguous()
+    if census.dtype != torch.int64 or census.dim() != 2 or m.ndim != 2 or m.shape[0] != census.shape[1]:
+        raise ValueError("noninduced_transform_device: census [N, C] int64 and m [C, Q] int64")
+    out = accumulate_into if accumulate_into is not None else \
+        torch.empty((census.shape[0], m.shape[1]), dtype=torch.int64, device=census.device)
+    if out.shape != (census.shape[0], m.shape[1]) or out.dtype != torch.int64 or out.stride(1) != 1:
+        raise ValueError("noninduced_transform_device: accumulate_into must be [N, Q] int64 with unit column stride")
+    if census.shape[0] and m.shape[1]:
+        _transform_device(census, m, out, accumulate_into is not None)
+    return out
+
+
+def _noninduced_device(graphs: GraphSet, flat, dev) -> torch.Tensor:
+    """[num_nodes, len(flat)] int64 on ``dev``: device census of the classes, 32 per call, and the transform kernel."""
+    out = torch.zeros((graphs.num_nodes, len(flat)), dtype=torch.int64, device=dev)
+    if not flat:
+        return out
+    groups = _census_plan(flat)
+    if max(n for n, _ in flat) > 5:
+        raise RuntimeError("canonical_counts_device: the device path takes queries of 2..5 nodes")
+    if graphs.num_nodes == 0:
+        return out
+    for classes, idx, m in groups:
+        part = torch.zeros((graphs.num_nodes, len(idx)), dtype=torch.int64, device=dev)
+        for c0 in range(0, len(classes), 32):
+            census = canonical_counts_device(graphs, classes[c0:c0 + 32], dev)
+            _transform_device(census, m[c0:c0 + 32], part, c0 > 0)
+        out[:, torch.tensor(idx, device=dev)] = part
+    return out
+
+
+def _noninduced_small(graphs: GraphSet, flat, backend: str, num_threads: int) -> torch.Tensor:
+    """Non-induced counts of queries of at most 6 nodes as a [num_nodes, len(flat)] double tensor on the CPU.  The census
+    of a size goes where induced columns of that size go: the device when ``backend`` says so or "auto" finds the
+    classes eligible (2..5 nodes, a GPU, bitsets within the limit), else the host enumerator and numpy int64."""
+    out = np.zeros((graphs.num_nodes, len(flat)), dtype=np.int64)
+    for classes, idx, m in _census_plan(flat):
+        sizes = np.array([n for n, _ in classes], dtype=np.int32)
+        if backend == "device" or (backend == "auto" and _device_eligible(graphs, sizes[:32])):
+            out[:, idx] = _noninduced_device(graphs, [flat[i] for i in idx], torch.device("cuda")).cpu().numpy()
+        else:
+            out[:, idx] = _induced_host_int64(graphs, classes, num_threads) @ m
+    return torch.from_numpy(out).double()
+
+
+def _induced_host_int64(graphs: GraphSet, flat, num_threads: int) -> np.ndarray:
+    """The host ESU enumerator (desco_canonical_counts) on queries of 2..6 nodes: int64 [num_nodes, len(flat)]."""
+    _, q_nodes, q_edge_ptr, q_edges = _flatten_queries(flat)
+    out = np.zeros((graphs.num_nodes, len(flat)), dtype=np.int64)
+    _lib.check(_lib.lib().desco_canonical_counts(graphs.graph_ptr.ctypes.data, graphs.num_graphs,
+                                                 graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
+                                                 q_nodes.ctypes.data, q_edge_ptr.ctypes.data,
+                                                 q_edges.ctypes.data if len(q_edges) else None, len(flat),
+                                                 num_threads, out.ctypes.data), "desco_canonical_counts")
+    return out
 
 
 # ---- large queries: the pattern-guided matcher ------------------------------------------------------------------------
@@ -140,11 +301,12 @@ def _bitset_words(graphs: GraphSet) -> np.ndarray:
 
 
 def canonical_counts_match_device(graphs: GraphSet, queries: Sequence, device="cuda",
-                                  slice_entries=None) -> torch.Tensor:
+                                  slice_entries=None, induced: bool = True) -> torch.Tensor:
     """The counts of ``canonical_counts_match`` computed on the MI355X (csrc/groundtruth_match_dev.hip).  Returns a
     [num_nodes, num_queries] int64 tensor on ``device``.  The CSR entries are cut into slices of ``slice_entries``
     (default: ``_MATCH_SLICE_WAVES`` waves per launch), one launch each, and the stream is synchronised and the
-    status checked after every slice; the slicing does not change the result."""
+    status checked after every slice; the slicing does not change the result.  ``induced=False``: the non-induced counts
+    of ``canonical_counts`` by the kernel's non-induced instantiation (same plan, same slices)."""
     plan = match_plan(queries)
     Q, A = int(plan[0]), int(plan[1])
     dev = torch.device(device)
@@ -170,11 +332,16 @@ def canonical_counts_match_device(graphs: GraphSet, queries: Sequence, device="c
         e0 = 0
         while True:
             e1 = min(e0 + slice_entries, E)
-            _lib.check(L.desco_canonical_counts_match_dev(
-                graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), E, col.data_ptr() if col.numel() else None,
-                node_graph.data_ptr(), bit_off_d.data_ptr(), bits.data_ptr(), int(bit_off[-1]), plan.ctypes.data,
-                plan_d.data_ptr(), len(plan), Q, e0, e1, out.data_ptr(), stream.cuda_stream),
-                "desco_canonical_counts_match_dev")
+            head = (graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), E, col.data_ptr() if col.numel() else None,
+                    node_graph.data_ptr(), bit_off_d.data_ptr(), bits.data_ptr(), int(bit_off[-1]), plan.ctypes.data,
+                    plan_d.data_ptr(), len(plan), Q)
+            if induced:
+                _lib.check(L.desco_canonical_counts_match_dev(*head, e0, e1, out.data_ptr(), stream.cuda_stream),
+                           "desco_canonical_counts_match_dev")
+            else:
+                _lib.check(L.desco_canonical_counts_match_mode_dev(*head, 0, e0, e1, out.data_ptr(),
+                                                                   stream.cuda_stream),
+                           "desco_canonical_counts_match_mode_dev")
             stream.synchronize()                # a fault of this slice surfaces here, before the next is enqueued
             e0 = e1
             if e0 >= E:
@@ -182,15 +349,32 @@ def canonical_counts_match_device(graphs: GraphSet, queries: Sequence, device="c
     return out
 
 
+def _match_host_int64(graphs: GraphSet, queries: Sequence, induced: bool, num_threads: int) -> np.ndarray:
+    """The host matcher: int64 [num_nodes, num_queries]."""
+    plan = match_plan(queries)
+    out = np.zeros((graphs.num_nodes, int(plan[0])), dtype=np.int64)
+    head = (graphs.graph_ptr.ctypes.data, graphs.num_graphs, graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
+            plan.ctypes.data, len(plan), int(plan[0]))
+    L = _lib.lib()
+    if induced:
+        _lib.check(L.desco_canonical_counts_match(*head, num_threads, out.ctypes.data), "desco_canonical_counts_match")
+    else:
+        _lib.check(L.desco_canonical_counts_match_mode(*head, 0, num_threads, out.ctypes.data),
+                   "desco_canonical_counts_match_mode")
+    return out
+
+
 def canonical_counts_match(graphs: GraphSet, queries: Sequence, backend: str = "auto",
-                           num_threads: int = 0, slice_entries=None) -> torch.Tensor:
+                           num_threads: int = 0, slice_entries=None, induced: bool = True) -> torch.Tensor:
     """Canonical counts by the pattern-guided induced-subgraph matcher: [num_nodes, num_queries] double tensor on the
     CPU, count[v][q] = #{S : max(S) = v, G[S] isomorphic to q} as ``canonical_counts``.  Its work follows the query
     instead of the number of connected k-subsets, so it takes queries of 2..16 nodes (small ones too, to be checked
     against ESU), any number of them, isomorphic duplicates included.
     ``backend``: "host" (OpenMP over graphs, ``num_threads`` threads), "device" (HIP kernel, ``slice_entries`` as in
     ``canonical_counts_match_device``) or "auto": the device when a GPU is present and the adjacency bitsets fit
-    ``_DEVICE_BITSET_LIMIT_WORDS``, else the host.  ``last_match_backend`` names the one that served the call."""
+    ``_DEVICE_BITSET_LIMIT_WORDS``, else the host.  ``last_match_backend`` names the one that served the call.
+    ``induced=False``: the non-induced counts of ``canonical_counts`` -- the same plan, a candidate only has to be
+    adjacent to the images the record's mask names."""
     global last_match_backend
     if backend not in ("host", "device", "auto"):
         raise ValueError(f"unknown backend {backend!r}")
@@ -199,19 +383,16 @@ def canonical_counts_match(graphs: GraphSet, queries: Sequence, backend: str = "
         backend = "device" if torch.cuda.is_available() and fits else "host"
     last_match_backend = backend
     if backend == "device":
-        return canonical_counts_match_device(graphs, queries, slice_entries=slice_entries).cpu().double()
-    plan = match_plan(queries)
-    out = np.zeros((graphs.num_nodes, int(plan[0])), dtype=np.int64)
-    _lib.check(_lib.lib().desco_canonical_counts_match(
-        graphs.graph_ptr.ctypes.data, graphs.num_graphs, graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
-        plan.ctypes.data, len(plan), int(plan[0]), num_threads, out.ctypes.data), "desco_canonical_counts_match")
-    return torch.from_numpy(out).double()
+        return canonical_counts_match_device(graphs, queries, slice_entries=slice_entries,
+                                             induced=induced).cpu().double()
+    return torch.from_numpy(_match_host_int64(graphs, queries, induced, num_threads)).double()
 
 
-def _canonical_counts_vf2(graphs: GraphSet, queries: Sequence) -> torch.Tensor:
+def _canonical_counts_vf2(graphs: GraphSet, queries: Sequence, induced: bool = True) -> torch.Tensor:
     """The reference's own procedure for unlabelled queries: networkx VF2, one match per isomorphism keyed by
     ``max(vmap.keys())`` (workload.py:327-348), divided by the query's automorphism count (data.py:61-67).  Any query
-    size; minutes where the native paths take milliseconds."""
+    size; minutes where the native paths take milliseconds.  ``induced=False``: one match per MONOMORPHISM
+    (``subgraph_monomorphisms_iter``), keyed and divided the same way."""
     import networkx as nx
     flat, _, _, _ = _flatten_queries(queries)
     GM = nx.algorithms.isomorphism.GraphMatcher
@@ -229,7 +410,8 @@ def _canonical_counts_vf2(graphs: GraphSet, queries: Sequence) -> torch.Tensor:
         sym = sum(1 for _ in GM(q, q).subgraph_isomorphisms_iter())
         for g, t in enumerate(targets):
             base = int(graphs.graph_ptr[g])
-            for vmap in GM(t, q).subgraph_isomorphisms_iter():
+            gm = GM(t, q)
+            for vmap in (gm.subgraph_isomorphisms_iter() if induced else gm.subgraph_monomorphisms_iter()):
                 out[base + max(vmap.keys()), qi] += 1
         out[:, qi] /= sym
     return out
@@ -413,7 +595,7 @@ def canonical_counts_labelled_device(graphs: GraphSet, queries: Sequence, node_f
 
 
 def canonical_counts_labelled(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat",
-                              backend: str = "auto", num_threads: int = 0) -> torch.Tensor:
+                              backend: str = "auto", num_threads: int = 0, induced: bool = True) -> torch.Tensor:
     """Canonical counts of LABELLED queries (--use_node_feature): [num_nodes, num_queries] double tensor on the CPU,
     count[v][q] = #{S : max(S) = v, G[S] connected, G[S] with its node labels isomorphic to labelled query q} --
     the reference's VF2 with ``node_match`` on the feature (workload.py:327-348) divided by the labelled symmetry
@@ -428,14 +610,28 @@ def canonical_counts_labelled(graphs: GraphSet, queries: Sequence, node_feat_key
     ``last_labelled_backend`` names the one that served the call.
     Columns of queries with 7..16 nodes go to the labelled matcher (``canonical_counts_match_labelled``) with the same
     ``backend`` and the results are joined in query order; a call made only of such queries sets
-    ``last_labelled_backend`` to the matcher's backend.  Above 16 nodes "auto" uses VF2 and "host" / "device" raise."""
+    ``last_labelled_backend`` to the matcher's backend.  Above 16 nodes "auto" uses VF2 and "host" / "device" raise.
+    ``induced=False``: NON-INDUCED labelled counts (label-preserving monomorphisms with the largest image v, divided by
+    the label-preserving automorphisms).  There is no labelled census: every size 2..16 goes to the labelled matcher."""
     global last_labelled_backend
     if backend not in ("vf2", "host", "device", "auto"):
         raise ValueError(f"unknown backend {backend!r}")
     if backend == "vf2":
         last_labelled_backend = "vf2"
-        return _canonical_counts_labelled_vf2(graphs, queries, node_feat_key)
+        return _canonical_counts_labelled_vf2(graphs, queries, node_feat_key, induced)
     lab = _Labelled(graphs, queries, node_feat_key)
+    if not induced:
+        if lab.nan or lab.kmax > 16:
+            if backend == "auto":
+                last_labelled_backend = "vf2"
+                return _canonical_counts_labelled_vf2(graphs, queries, node_feat_key, False)
+            if lab.nan:
+                raise RuntimeError(f"canonical_counts_labelled: {backend} path: " + lab.host_limit())
+            raise RuntimeError(f"canonical_counts_labelled: {backend} path: the native paths take labelled queries "
+                               "of 2..16 nodes (backend=\"vf2\" takes larger ones)")
+        out = canonical_counts_match_labelled(graphs, queries, node_feat_key, backend, num_threads, induced=False)
+        last_labelled_backend = last_labelled_match_backend
+        return out
     large = [i for i, k in enumerate(lab.q_nodes) if k > 6]
     if large and not (backend == "auto" and (lab.nan or lab.kmax > 16)):
         # columns above 6 nodes go to the labelled matcher with the same backend, the others where they always went
@@ -535,7 +731,7 @@ def labelled_match_waves(graphs: GraphSet, lab_or_labels, plan: np.ndarray):
     return launched, live
 
 
-def _labelled_match_device(graphs: GraphSet, lab: _Labelled, dev, slice_entries=None):
+def _labelled_match_device(graphs: GraphSet, lab: _Labelled, dev, slice_entries=None, induced: bool = True):
     """([num_nodes, num_classes] int64 counts on ``dev``, class_of_query)"""
     plan, coq = _match_plan_labelled(lab)
     C, largest = int(plan[0]), int(plan[3])
@@ -562,11 +758,17 @@ def _labelled_match_device(graphs: GraphSet, lab: _Labelled, dev, slice_entries=
         e0 = 0
         while True:
             e1 = min(e0 + slice_entries, E)
-            _lib.check(L.desco_canonical_counts_match_labelled_dev(
-                graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), E, col.data_ptr() if col.numel() else None,
-                node_graph.data_ptr(), bit_off_d.data_ptr(), bits.data_ptr(), int(bit_off[-1]), labels.data_ptr(),
-                plan.ctypes.data, plan_d.data_ptr(), len(plan), C, e0, e1, out.data_ptr(), stream.cuda_stream),
-                "desco_canonical_counts_match_labelled_dev")
+            head = (graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), E, col.data_ptr() if col.numel() else None,
+                    node_graph.data_ptr(), bit_off_d.data_ptr(), bits.data_ptr(), int(bit_off[-1]), labels.data_ptr(),
+                    plan.ctypes.data, plan_d.data_ptr(), len(plan), C)
+            if induced:
+                _lib.check(L.desco_canonical_counts_match_labelled_dev(*head, e0, e1, out.data_ptr(),
+                                                                       stream.cuda_stream),
+                           "desco_canonical_counts_match_labelled_dev")
+            else:
+                _lib.check(L.desco_canonical_counts_match_labelled_mode_dev(*head, 0, e0, e1, out.data_ptr(),
+                                                                            stream.cuda_stream),
+                           "desco_canonical_counts_match_labelled_mode_dev")
             stream.synchronize()                # a fault of this slice surfaces here, before the next is enqueued
             e0 = e1
             if e0 >= E:
@@ -580,27 +782,30 @@ def _require_no_nan(lab: _Labelled, who: str):
 
 
 def canonical_counts_match_labelled_device(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat",
-                                           device="cuda", slice_entries=None) -> torch.Tensor:
+                                           device="cuda", slice_entries=None, induced: bool = True) -> torch.Tensor:
     """The counts of ``canonical_counts_match_labelled`` computed on the MI355X (csrc/groundtruth_match_dev.hip, the
     labelled instantiation).  Returns a [num_nodes, num_queries] int64 tensor on ``device``.  Each labelled class is
     matched once and its column copied to every query of the class.  The CSR entries are cut into slices of
     ``slice_entries`` (default: ``_MATCH_SLICE_WAVES`` waves per launch, a wave being one (entry, record slot of the
-    largest label bucket) pair), one launch each, synchronised and checked; the slicing does not change the result."""
+    largest label bucket) pair), one launch each, synchronised and checked; the slicing does not change the result.
+    ``induced=False``: the non-induced labelled counts (the kernel's fourth instantiation; same plan, same slices)."""
     lab = _Labelled(graphs, queries, node_feat_key)
     _require_no_nan(lab, "canonical_counts_match_labelled_device")
     dev = torch.device(device)
-    out, coq = _labelled_match_device(graphs, lab, dev, slice_entries)
+    out, coq = _labelled_match_device(graphs, lab, dev, slice_entries, induced)
     return out.index_select(1, torch.from_numpy(coq).long().to(dev))
 
 
 def canonical_counts_match_labelled(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat",
-                                    backend: str = "auto", num_threads: int = 0, slice_entries=None) -> torch.Tensor:
+                                    backend: str = "auto", num_threads: int = 0, slice_entries=None,
+                                    induced: bool = True) -> torch.Tensor:
     """Labelled canonical counts (as ``canonical_counts_labelled``) by the pattern-guided matcher: [num_nodes,
     num_queries] double tensor on the CPU.  Labelled queries of 2..16 nodes (small ones too, to be checked against the
     labelled ESU path), any number of them, any number of distinct labels; isomorphic labelled copies are matched once.
     ``backend``: "host" (OpenMP over graphs, ``num_threads`` threads), "device" (HIP kernel) or "auto": the device when
     a GPU is present and the adjacency bitsets fit ``_DEVICE_BITSET_LIMIT_WORDS``, else the host.
-    ``last_labelled_match_backend`` names the one that served the call.  Features with NaN are refused (VF2 only)."""
+    ``last_labelled_match_backend`` names the one that served the call.  Features with NaN are refused (VF2 only).
+    ``induced=False``: label-preserving monomorphisms instead of induced embeddings, as ``canonical_counts_labelled``."""
     global last_labelled_match_backend
     if backend not in ("host", "device", "auto"):
         raise ValueError(f"unknown backend {backend!r}")
@@ -614,7 +819,7 @@ def canonical_counts_match_labelled(graphs: GraphSet, queries: Sequence, node_fe
         # expanded to query columns and converted on the device, in row chunks within the labelled paths' byte budget
         # (int64 + double copy of a chunk), each copied straight into its rows of the result
         dev = torch.device("cuda")
-        out, coq = _labelled_match_device(graphs, lab, dev, slice_entries)
+        out, coq = _labelled_match_device(graphs, lab, dev, slice_entries, induced)
         coq_d = torch.from_numpy(coq).long().to(dev)
         res = torch.empty((graphs.num_nodes, lab.num_queries), dtype=torch.double)
         rows = max(_DEVICE_LABEL_CHUNK_BYTES // (16 * max(lab.num_queries, 1)), 1)
@@ -623,14 +828,19 @@ def canonical_counts_match_labelled(graphs: GraphSet, queries: Sequence, node_fe
         return res
     plan, coq = _match_plan_labelled(lab)
     out = np.zeros((graphs.num_nodes, int(plan[0])), dtype=np.int64)
-    _lib.check(_lib.lib().desco_canonical_counts_match_labelled(
-        graphs.graph_ptr.ctypes.data, graphs.num_graphs, graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
-        lab.node_labels.ctypes.data, plan.ctypes.data, len(plan), int(plan[0]), num_threads, out.ctypes.data),
-        "desco_canonical_counts_match_labelled")
+    head = (graphs.graph_ptr.ctypes.data, graphs.num_graphs, graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
+            lab.node_labels.ctypes.data, plan.ctypes.data, len(plan), int(plan[0]))
+    if induced:
+        _lib.check(_lib.lib().desco_canonical_counts_match_labelled(*head, num_threads, out.ctypes.data),
+                   "desco_canonical_counts_match_labelled")
+    else:
+        _lib.check(_lib.lib().desco_canonical_counts_match_labelled_mode(*head, 0, num_threads, out.ctypes.data),
+                   "desco_canonical_counts_match_labelled_mode")
     return torch.from_numpy(out)[:, torch.from_numpy(coq).long()].double()
 
 
-def _canonical_counts_labelled_vf2(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat") -> torch.Tensor:
+def _canonical_counts_labelled_vf2(graphs: GraphSet, queries: Sequence, node_feat_key: str = "feat",
+                                   induced: bool = True) -> torch.Tensor:
     """The reference's own procedure: networkx VF2 with ``node_match`` on the feature (workload.py:327-348)
     divided by the labelled symmetry factor (data.py:61-68).  One matcher per (query, graph) in Python: the
     reference every native path is tested against, and the path for features that contain NaN."""
@@ -657,7 +867,7 @@ def _canonical_counts_labelled_vf2(graphs: GraphSet, queries: Sequence, node_fea
         for g, t in enumerate(targets):
             base = int(graphs.graph_ptr[g])
             gm = nx.algorithms.isomorphism.GraphMatcher(t, qq, node_match=match)
-            for vmap in gm.subgraph_isomorphisms_iter():
+            for vmap in (gm.subgraph_isomorphisms_iter() if induced else gm.subgraph_monomorphisms_iter()):
                 out[base + max(vmap.keys()), qi] += 1
         out[:, qi] /= sym
     return out

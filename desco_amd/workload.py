@@ -268,23 +268,28 @@ class Workload:
             self.gossip_dataset.apply_truth_from_dataset(self.canonical_count_truth)
 
     # ---- ground truth ----------------------------------------------------------------------------
-    def _truth_path(self, query_ids, queries=None):
+    def _truth_path(self, query_ids, queries=None, induced=True):
+        """The reference's file name (:485-493); non-induced truth (``induced=False``) lives beside it under the same
+        name with a ``_noninduced`` suffix, so that neither can be taken for the other."""
         import networkx as nx
         from .data import graph_atlas_plus
         qs = queries if queries is not None else [graph_atlas_plus(q) for q in query_ids]
-        name = "query_num_{:d}_query_len_sum_{:d}.pt".format(len(qs), sum(len(q) for q in qs))  # :485-493
+        name = "query_num_{:d}_query_len_sum_{:d}{}.pt".format(len(qs), sum(len(q) for q in qs),
+                                                               "" if induced else "_noninduced")
         return os.path.join(self.root, "CanonicalCountTruth", name)
 
-    def exist_groundtruth(self, query_ids, queries=None) -> bool:                 # :512-549
-        return os.path.exists(self._truth_path(query_ids, queries))
+    def exist_groundtruth(self, query_ids, queries=None, induced=True) -> bool:   # :512-549
+        return os.path.exists(self._truth_path(query_ids, queries, induced))
 
-    def load_groundtruth(self, query_ids, queries=None) -> torch.Tensor:         # :473-510
-        self.canonical_count_truth = torch.load(self._truth_path(query_ids, queries))
+    def load_groundtruth(self, query_ids, queries=None, induced=True) -> torch.Tensor:         # :473-510
+        self.canonical_count_truth = torch.load(self._truth_path(query_ids, queries, induced))
         self.query_ids = query_ids
         return self.canonical_count_truth
 
     def compute_groundtruth(self, query_ids=None, queries=None, num_workers=-1,
-                            save_to_file=True) -> torch.Tensor:                   # :551-726
+                            save_to_file=True, induced=True) -> torch.Tensor:     # :551-726
+        """``induced=False``: non-induced counts (occurrences that only have to contain the query's edges,
+        ``groundtruth.canonical_counts``); the models regress whichever [N, Q] tensor this returns."""
         from .groundtruth import canonical_counts, canonical_counts_labelled
         from .data import add_node_feat_to_networkx, graph_atlas_plus
         qs = queries if queries is not None else [graph_atlas_plus(q) for q in query_ids]
@@ -293,13 +298,13 @@ class Workload:
             qs = [g for q in qs for g in add_node_feat_to_networkx(q, eye, self.node_feat_key)]
         if self.use_node_feat:
             truth = canonical_counts_labelled(self.dataset, qs, self.node_feat_key, backend="auto",
-                                              num_threads=max(num_workers, 0))
+                                              num_threads=max(num_workers, 0), induced=induced)
         else:
-            truth = canonical_counts(self.dataset, qs, num_threads=max(num_workers, 0))
+            truth = canonical_counts(self.dataset, qs, num_threads=max(num_workers, 0), induced=induced)
         self.canonical_count_truth = truth
         self.query_ids = query_ids
         if save_to_file and self.root:
-            path = self._truth_path(query_ids, queries)
+            path = self._truth_path(query_ids, queries, induced)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             torch.save(truth, path)
         return truth

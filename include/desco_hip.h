@@ -363,6 +363,45 @@ int desco_canonical_counts_match_labelled_dev(const int64_t* graph_ptr, int64_t 
                                               int64_t entry_begin, int64_t entry_end, int64_t* out,
                                               desco_stream_t stream);
 
+/* NON-INDUCED counts (occurrences as a not necessarily induced subgraph; monomorphisms):
+ *   out[v][q] = #{ injective f : {f(a), f(b)} in E(G) for every {a, b} in E(q), max(im f) = v } / |Aut(q)|,
+ * int64, bit-exact.  Two occurrences on the same node set with different edge sets are two occurrences: P3 in a triangle
+ * counts 3, all at the triangle's largest node.  The four entries below are the four matchers above with one more
+ * argument, `induced`: 1 = the induced counts of the entry without `_mode`, 0 = the definition above; anything else is
+ * DESCO_EINVAL.  The PLANS are the same bytes in both modes (anchors, order and order constraints depend on Aut(q)
+ * alone, and Aut(q) acts freely on monomorphisms as it does on induced embeddings: one map per occurrence, divisor 1);
+ * with induced = 0 a set bit of rec[36 + i] still asks for an edge and a clear bit asks nothing.  Everything else --
+ * labels, the u < v root rule, slices, zeroing, atomics -- is as documented for the entry without `_mode`. */
+int desco_canonical_counts_match_mode(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                      const int32_t* col, const int32_t* plan, int64_t plan_entries, int num_queries,
+                                      int induced, int num_threads, int64_t* out);
+int desco_canonical_counts_match_mode_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                          const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                          const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                          int64_t num_words, const int32_t* plan_host, const int32_t* plan_dev,
+                                          int64_t plan_entries, int num_queries, int induced, int64_t entry_begin,
+                                          int64_t entry_end, int64_t* out, desco_stream_t stream);
+int desco_canonical_counts_match_labelled_mode(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                               const int32_t* col, const int32_t* labels, const int32_t* plan,
+                                               int64_t plan_entries, int num_classes, int induced, int num_threads,
+                                               int64_t* out);
+int desco_canonical_counts_match_labelled_mode_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                                   const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                                   const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                                   int64_t num_words, const int32_t* labels, const int32_t* plan_host,
+                                                   const int32_t* plan_dev, int64_t plan_entries, int num_classes,
+                                                   int induced, int64_t entry_begin, int64_t entry_end, int64_t* out,
+                                                   desco_stream_t stream);
+/* DEVICE: non-induced counts of SMALL queries from a census.  The ESU enumerators visit every connected k-subset once,
+ * so with counts[v][c] = the induced count of EVERY connected k-node class c (desco_canonical_counts_dev on the class
+ * representatives) the non-induced counts are  out[v][q] = sum_c counts[v][c] * m[c][q],  m[c][q] = the occurrences of q
+ * in c (0 when their sizes differ).  counts: int64 [N][ldc], m: int64 [num_classes][num_queries] (device), out: int64
+ * [N][ldo]; num_classes 1..32, num_queries <= 64; accumulate = 1 adds to out (a census cut into chunks of 32 classes),
+ * 0 overwrites it.  Integer arithmetic modulo 2^64.  Enqueues on `stream`, does not allocate or synchronise. */
+int desco_canonical_noninduced_transform_dev(const int64_t* counts, int64_t ldc, const int64_t* m, int64_t num_nodes,
+                                             int num_classes, int num_queries, int accumulate, int64_t* out,
+                                             int64_t ldo, desco_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * DEVICE kernels
  * ------------------------------------------------------------------------------------------ */

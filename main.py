@@ -28,14 +28,15 @@ from desco_amd.transforms import ToTconvHetero
 from desco_amd.workload import Workload
 
 
-def build_workload(name, query_ids, nx_queries, depth, transform, num_cpu, root="data", node_feat_len=-1):
+def build_workload(name, query_ids, nx_queries, depth, transform, num_cpu, root="data", node_feat_len=-1,
+                   induced=True):
     w = Workload(load_data(name, root_folder=root), os.path.join(root, name), hetero_graph=True,
                  node_feat_len=node_feat_len)
-    if w.exist_groundtruth(query_ids=query_ids, queries=nx_queries):
-        w.canonical_count_truth = w.load_groundtruth(query_ids=query_ids, queries=nx_queries)
+    if w.exist_groundtruth(query_ids=query_ids, queries=nx_queries, induced=induced):
+        w.canonical_count_truth = w.load_groundtruth(query_ids=query_ids, queries=nx_queries, induced=induced)
     else:
         w.canonical_count_truth = w.compute_groundtruth(query_ids=query_ids, queries=nx_queries,
-                                                        num_workers=num_cpu, save_to_file=True)
+                                                        num_workers=num_cpu, save_to_file=True, induced=induced)
     w.generate_pipeline_datasets(depth_neigh=depth, neighborhood_transform=transform)
     return w
 
@@ -60,6 +61,7 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
     transform = ToTconvHetero() if args_neighborhood.use_tconv else None
     assert args_neighborhood.use_hetero if args_neighborhood.use_tconv else True
     depth, ncpu = args_neighborhood.depth, args_opt.num_cpu
+    induced = not getattr(args_opt, "noninduced", False)          # --noninduced: all three splits regress that truth
 
     devices = args_opt.gpu if isinstance(args_opt.gpu, list) else [args_opt.gpu]
     # len(devices) > 1: one process per GPU (started by __main__ below or by torch.distributed.run);
@@ -80,11 +82,11 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
         tw = vw = None
         if train_neighborhood or train_gossip:
             tw = build_workload(args_opt.train_dataset, query_ids, nx_queries, depth, transform, ncpu, data_root,
-                                node_feat_len)
+                                node_feat_len, induced)
             vw = build_workload(args_opt.valid_dataset, query_ids, nx_queries, depth, transform, ncpu, data_root,
-                                node_feat_len)
+                                node_feat_len, induced)
         return tw, vw, build_workload(args_opt.test_dataset, query_ids, nx_queries, depth, transform, ncpu,
-                                      data_root, node_feat_len)
+                                      data_root, node_feat_len, induced)
 
     # rank 0 computes the ground truth / partitions and writes the on-disk caches; the others read
     # them.  They wait on the process group's store, not in a collective: a cold-cache build may
@@ -228,7 +230,9 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
     return report
 
 
-if __name__ == "__main__":
+def parse_args(argv=None):
+    """(args, args_neighborhood, args_gossip, args_opt) of a command line: the reference's flag groups plus this
+    build's own flags, which travel on ``args_opt``."""
     parser = argparse.ArgumentParser(description="DeSCo argument parser (MI355X-native path)")
     parse_optimizer(parser)
     parse_neighborhood(parser)
@@ -240,7 +244,19 @@ if __name__ == "__main__":
                         help="replay each neighborhood training batch's step from a hipGraph after epoch 0")
     parser.add_argument("--seed", type=int, default=None,
                         help="seed of the model initialisation and the batch order (the reference seeds neither: runs differ)")
-    args = parser.parse_args()
+    parser.add_argument("--noninduced", action="store_true",
+                        help="train and test on NON-INDUCED ground truth: occurrences that only have to contain the "
+                             "query's edges (cached beside the induced truth with a _noninduced suffix)")
+    args = parser.parse_args(argv)
+    args_neighborhood, args_gossip, args_opt = split_namespaces(args)
+    args_opt.precision = args.precision          # this build's flags (not in the reference's groups)
+    args_opt.graph_capture = args.graph_capture
+    args_opt.noninduced = args.noninduced
+    return args, args_neighborhood, args_gossip, args_opt
+
+
+if __name__ == "__main__":
+    args, args_neighborhood, args_gossip, args_opt = parse_args()
     gpus = args.gpu if isinstance(args.gpu, list) else [args.gpu]
     if len(gpus) > 1 and "WORLD_SIZE" not in os.environ:
         # --gpu 0 1 ..: start one process per GPU (what Lightning's "ddp" strategy does for
@@ -256,9 +272,6 @@ if __name__ == "__main__":
         _random.seed(args.seed)
         _np.random.seed(args.seed)
         _torch.manual_seed(args.seed)
-    args_neighborhood, args_gossip, args_opt = split_namespaces(args)
-    args_opt.precision = args.precision          # this build's flags (not in the reference's groups)
-    args_opt.graph_capture = args.graph_capture
     assert args_neighborhood.use_hetero
     query_ids = gen_query_ids(query_size=[3, 4, 5])
     output_dir = args_opt.output_dir or os.path.join(
