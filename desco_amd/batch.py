@@ -203,9 +203,13 @@ class NeighborhoodBatch(_TrainIndexMixin):
         relation slots 0 and 1 (count rows) replaced by their table rows, so that the second layer's launches gather
         from T (desco_shmp_layer_pool_table_f16x3_f32, which recomputes the launch's own rows from their degrees).  None when the batch has more than ``max_rows`` distinct tuples
         (the table must stay cache-resident to pay)."""
+        return self._table_indices(max_rows)[0]
+
+    def _table_indices(self, max_rows: int = 1 << 16):
+        """(degree_table_index, canonical_table_index): built together, once per batch"""
         if "_degree_table" in self.__dict__:
             return self.__dict__["_degree_table"]
-        res = None
+        res = ctab = None
         S, nc, n = self.slots, self.num_count, self.num_rows
         if S == 4 and nc > 0:
             vr = self.vrowptr.to(torch.int64)
@@ -226,8 +230,66 @@ class NeighborhoodBatch(_TrainIndexMixin):
                         row_id = inv.to(torch.int32)
                         vcol_t = torch.where(low, inv[col.clamp(max=nc - 1)], col).to(torch.int32)
                         res = (uptr.to(torch.int32).contiguous(), row_id.contiguous(), vcol_t.contiguous())
-        self.__dict__["_degree_table"] = res
-        return res
+                        ctab = self._canonical_table(deg[nc:], low, col, vcol_t, max_rows)
+        self.__dict__["_degree_table"] = (res, ctab)
+        return res, ctab
+
+    def _canonical_table(self, dq, low, col, vcol_t, max_rows):
+        """``canonical_table_index`` from the intermediates of ``degree_table_index``: ``dq`` [B, S] the canonical rows'
+        slot degrees, ``low`` / ``col`` per CSR entry (slot < 2; source id), ``vcol_t`` the count-slot remap"""
+        nc, n, S = self.num_count, self.num_rows, self.slots
+        if n <= nc:
+            return None
+        m = int(dq.max().item()) + 1
+        if m ** S >= 2 ** 62:
+            return None
+        key = dq[:, 0]
+        for s in range(1, S):
+            key = key * m + dq[:, s]
+        uniq, inv = torch.unique(key, return_inverse=True)
+        if uniq.numel() > max_rows or not bool(((col >= nc) | low).all()):
+            return None
+        ut = torch.stack([(uniq // (m ** (S - 1 - s))) % m for s in range(S)], dim=1)
+        uptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=ut.device), ut.reshape(-1).cumsum(0)])
+        vcol_tc = torch.where(low, vcol_t.to(torch.int64), inv[(col - nc).clamp(min=0)]).to(torch.int32)
+        return (uptr.to(torch.int32).contiguous(), inv.to(torch.int32).contiguous(), vcol_tc.contiguous())
+
+    def canonical_table_index(self):
+        """``degree_table_index`` once more for the CANONICAL rows (built with it, once per batch): ``(uptr_c, canon_id,
+        vcol_tc)`` or None.  Under ZeroNodeFeat the first-layer canonical rows are a function of their slot degrees too, so
+        the second layer's canonical->count table product has one distinct row per distinct tuple -- a dozen on molecule
+        shapes: ``uptr_c`` [U_c S + 1] is the row-pointer array of the U_c distinct tuples (input of
+        desco_degree_affine_f32), ``canon_id`` [B] each canonical row's tuple, and ``vcol_tc`` = ``vcol_t`` with the sources
+        of the two TABLE slots (canonical rows) replaced by their tuple ids as well, so that the second layer's count
+        launch reads ``ytab`` [U_c, .] with ``ytab_row0 = 0``.  None when ``degree_table_index`` is None or the canonical
+        rows have too many distinct tuples."""
+        return self._table_indices()[1]
+
+    @property
+    def table_empty(self) -> int:
+        """Which of the count rows' two TABLE slots -- the canonical->count relations: CSR slot 2 (triangle, table slot 0) and
+        CSR slot 3 (tride, table slot 1) -- have no entry in the whole block: bit t set = table slot t is empty.  Molecule
+        graphs have no triangles (1); the count launches then need no table columns for that relation
+        (gnn_model.TABLE_NARROW).  Two reductions over the count rows' pointers on the device and one read-back, cached;
+        the host-prologue path reads its numpy arrays."""
+        v = self.__dict__.get("_table_empty")
+        if v is None:
+            S, nc = self.slots, self.num_count
+            if nc == 0:
+                tot = (0, 0)
+            elif self._pool_on_device():
+                vr = self.vrowptr
+                tot = torch.stack([(vr[s + 1:S * nc + 1:S] - vr[s:S * nc:S]).sum() for s in (S - 2, S - 1)]).tolist()
+            else:
+                vr = np.asarray(self.part.vrowptr).astype(np.int64)
+                tot = [int((vr[s + 1:S * nc + 1:S] - vr[s:S * nc:S]).sum()) for s in (S - 2, S - 1)]
+            v = self.__dict__["_table_empty"] = (1 if tot[0] == 0 else 0) | (2 if tot[1] == 0 else 0)
+        return v
+
+    @property
+    def table1_empty(self) -> bool:
+        """table slot 1 (CSR slot 3) has no entry in the block"""
+        return bool(self.table_empty & 2)
 
     # PyG-style views -----------------------------------------------------------------------
     @property

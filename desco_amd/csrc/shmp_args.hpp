@@ -15,6 +15,11 @@ struct ShmpArgs {
   const int32_t* vcol;
   int64_t row0, num_rows;
   int S, sm, st;
+  // (16-row form, NARROW instantiations only: st = 2, ytab = the [n, 64] block of ONE table slot at column 0, ldy = 64)  bit t:
+  // the caller asserts that table slot t (CSR slot sm + t) has no entry in the whole block -- molecule graphs have no
+  // triangles, so the canonical->count triangle relation (table slot 0) is empty; that slot is neither tested for nor read
+  // (desco_shmp_layer_narrow_f16x3_f32).  Sits in what was padding: the other members keep their offsets.
+  int tab_empty;
   const float* wt;          // f32 mode: [(sm+1)*64][64]
   const short* wplanes;     // x6 mode: [3][64 n][(sm+1)*64 k] bf16 planes (hi, mid, lo); f16x3 mode: [2][64 n][..] fp16 (hi, lo)
   const float* wscale;      // f16x3 mode: device {scale, 1/scale} of the weight planes (desco_split_f16x2_f32); else null

@@ -111,6 +111,7 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
   }
 // (a table slot without a source among the tile's rows -- live bits 8, 9 -- is neither loaded nor added:
 // only the rows next to the canonical node have one, half of the Syn_1827 tiles have none at all)
+// (NARROW instantiations: the table is [n, 64], the block of the ONE table slot that has entries, at column 0 -- Y1O = 0)
 #define DESCO_ISSUE_TAB(it_)                                                                \
   {                                                                                         \
     DESCO_TAB_CUR(it_)                                                                      \
@@ -121,7 +122,7 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
       u##it_##1 = *reinterpret_cast<const float4*>(p0_ + 32);                               \
     }                                                                                       \
     if (ST > 1 && (live & 0x200)) {                                                         \
-      const float* p1_ = k1_ ? yb + 64 + (int64_t)i1_ * LDY : zrow;                         \
+      const float* p1_ = k1_ ? yb + Y1O + (int64_t)i1_ * LDY : zrow;                        \
       w##it_##0 = *reinterpret_cast<const float4*>(p1_);                                    \
       w##it_##1 = *reinterpret_cast<const float4*>(p1_ + 32);                               \
     }                                                                                       \
@@ -147,8 +148,9 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
 #define DESCO_TILE_LIVE_TAB()                                    \
   {                                                              \
     DESCO_TILE_LIVE()                                            \
-    if (ST > 0) live |= DESCO_SLOT_ANY(g.sm) ? 0x100 : 0;        \
-    if (ST > 1) live |= DESCO_SLOT_ANY(g.sm + 1) ? 0x200 : 0;    \
+    if (ST > 0 && !(tem & 1)) live |= DESCO_SLOT_ANY(g.sm) ? 0x100 : 0;     \
+    if (ST > 1 && !(tem & 2)) live |= DESCO_SLOT_ANY(g.sm + 1) ? 0x200 : 0; \
+    /* (tem is the constant 0 outside the NARROW instantiations) */         \
   }
 // first step of the first LIVE block after block a_ (a_ = -1: of the tile); dead slots are left
 // out of the software pipeline altogether, so the block behind one is not issued late.  The slot
@@ -341,8 +343,11 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
 // LD64: x and out rows are 64 floats and ytab rows 64*ST floats apart (the product path's layouts):
 // source-row addresses then need a shift instead of a 64-bit multiply per gathered row, and the stores
 // of a tile are one address with immediate offsets
+// NARROW (its own instantiations of the LD64, ST = 2, fp16 forms; every other instantiation is compiled exactly as without
+// it): one of the two table slots is asserted empty for the whole block (g.tab_empty) and ytab is the [n, 64] block of the
+// other one -- row stride 64 and column offset 0 at compile time, the empty slot's live bit never set
 // POOL: fused pooling epilogue (instantiated for the count-row launches only)
-template <int NW, int KB, int ST, bool LD64, bool POOL, bool F16, bool SELFDEG = false>
+template <int NW, int KB, int ST, bool LD64, bool POOL, bool F16, bool SELFDEG = false, bool NARROW = false>
 __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const int32_t* __restrict__ rowptr_s,
                                                               const uint32_t* __restrict__ pool_bits_s,
                                                               const int32_t* __restrict__ pool_slot_s) {
@@ -397,7 +402,13 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
   const int nslot = WR * S + 1;                            // <= 65: at most 2 per lane
   const int64_t ntiles = (g.num_rows + NW * WR - 1) / (NW * WR);
   constexpr int NB = KB + (ST > 0 ? 1 : 0);                // K blocks incl. the table pseudo block
-  const int64_t LDX = LD64 ? 64 : g.ldx, LDY = LD64 ? 64 * (ST > 0 ? ST : 1) : g.ldy;
+  static_assert(!NARROW || (LD64 && ST == 2), "the narrow table is built for the LD64 two-slot forms");
+  // NARROW: bit t = table slot t is asserted empty for the whole block -- its live bit is never set (no test, no load, no
+  // cooperative pass)
+  const int tem = NARROW ? g.tab_empty : 0;
+  constexpr int Y1O = NARROW ? 0 : 64;                         // column of table slot 1's block
+  (void)tem;
+  const int64_t LDX = LD64 ? 64 : g.ldx, LDY = LD64 ? (NARROW ? 64 : 64 * (ST > 0 ? ST : 1)) : g.ldy;
   const int64_t LDO = LD64 ? 64 : g.ldo;
   const float* xb = g.x + 4 * l8;
   const float* xsb = g.xself ? g.xself + 4 * l8 : xb;      // the launch's own rows (self block): x, or another tensor
@@ -523,13 +534,13 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
         // slots; anything beyond that (general inputs) takes the cooperative path
         int d0, d1, m0, m1;
         DESCO_CONSUME_TAB(0) DESCO_CONSUME_TAB(1)
-        if (__any((c0 < n0) | (c1 < n1))) {
+        if (!(tem & 1) && __any((c0 < n0) | (c1 < n1))) {
           DESCO_COOP(0, yb, LDY) DESCO_COOP(1, yb, LDY)
         }
-        if (ST > 1 && __any((d0 < m0) | (d1 < m1))) {
+        if (ST > 1 && !(tem & 2) && __any((d0 < m0) | (d1 < m1))) {
           c0 = d0; c1 = d1;
           n0 = m0; n1 = m1;
-          DESCO_COOP(0, yb + 64, LDY) DESCO_COOP(1, yb + 64, LDY)
+          DESCO_COOP(0, yb + Y1O, LDY) DESCO_COOP(1, yb + Y1O, LDY)
         }
       }
       // (round 6: issuing them one block earlier, behind the gather of the last live relation block, measured 1-2 % SLOWER on
@@ -738,16 +749,16 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
   }
 }
 
-template <int NW, int KB, int ST, bool LD64, bool POOL, bool F16, bool SELFDEG = false>
+template <int NW, int KB, int ST, bool LD64, bool POOL, bool F16, bool SELFDEG = false, bool NARROW = false>
 static hipError_t shmp16_launch_one(const ShmpArgs& g, unsigned grid, hipStream_t st) {
   constexpr int WST = KB * 64 + 16;
   constexpr size_t w_floats = (size_t)(F16 ? 2 : 3) * 64 * WST / 2;
   constexpr size_t shmem = sizeof(float) * (w_floats + (size_t)NW * (F16 ? WAVE_LDS_F16 : WAVE_LDS) + 64 + 4 +
                                            (SELFDEG ? (MAXS + 1) * 64 : 0));
   static_assert(shmem <= 160 * 1024, "SHMP layer (16-row tiles): LDS budget exceeded");
-  const hipError_t e = size_dynamic_lds<shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG>>(160 * 1024);
+  const hipError_t e = size_dynamic_lds<shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG, NARROW>>(160 * 1024);
   if (e == hipSuccess)
-    hipLaunchKernelGGL((shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG>), dim3(grid), dim3(NW * 64), shmem, st, g,
+    hipLaunchKernelGGL((shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG, NARROW>), dim3(grid), dim3(NW * 64), shmem, st, g,
                        g.vrowptr, g.pool_bits, g.pool_slot);
   return e;
 }
@@ -756,6 +767,26 @@ static hipError_t shmp16_launch_one(const ShmpArgs& g, unsigned grid, hipStream_
 template <int NW, int KB, bool F16>
 static bool shmp16_launch_st(const ShmpArgs& g, unsigned grid, hipStream_t st, hipError_t& e) {
   const bool ld64 = g.ldx == 64 && (g.st == 0 || g.ldy == 64 * g.st) && (!g.out || g.ldo == 64);      // (xself has its own stride)
+  if (g.st == 2 && g.ldy < 128) {
+    // the narrow table [n, 64] (shmp16_launch has checked tab_empty): its own instantiations, fp16 LD64 forms only
+    if constexpr (F16) {
+      if (!(g.ldx == 64 && g.ldy == 64 && (!g.out || g.ldo == 64))) return false;
+      if (g.pool_part) {
+        if constexpr (KB == 3) {
+          e = g.self_coef ? shmp16_launch_one<NW, 3, 2, true, true, true, true, true>(g, grid, st)
+                          : shmp16_launch_one<NW, 3, 2, true, true, true, false, true>(g, grid, st);
+          return true;
+        } else {
+          return false;
+        }
+      }
+      if (g.self_coef) return false;
+      e = shmp16_launch_one<NW, KB, 2, true, false, true, false, true>(g, grid, st);
+      return true;
+    } else {
+      return false;
+    }
+  }
   if (g.pool_part) {
     if constexpr (KB == 3) {
       if (g.st != 2) return false;
@@ -806,8 +837,15 @@ static int shmp16_launch(const char* who, const float* x, int64_t ldx, const int
                          int64_t ytab_row0, float* out, int64_t ldo, float* out2, int64_t ldo2, desco_stream_t stream,
                          const uint32_t* pool_bits = nullptr, const int32_t* pool_slot = nullptr,
                          float* pool_part = nullptr, float* row_absmax = nullptr, const float* xself = nullptr,
-                         int64_t ldxs = 0, const float* self_coef = nullptr) {
+                         int64_t ldxs = 0, const float* self_coef = nullptr, int tab_empty = 0) {
   if (num_rows == 0) return 0;
+  if (tab_empty < 0 || tab_empty > 3 || (tab_empty && slots_table != 2))
+    return fail(DESCO_EINVAL, (std::string(who) + ": table_slots_empty is a mask of the two table slots (slots_table == 2)").c_str());
+  // a table narrower than its slots: legal only as the [n, 64] block of ONE slot of a launch whose other table slot is
+  // asserted empty (the kernel then never addresses a second block)
+  if (ytab && slots_table >= 1 && ldy < 64 * slots_table && !(slots_table == 2 && tab_empty && ldy >= 64))
+    return fail(DESCO_EINVAL, (std::string(who) + ": ldy < 64 * slots_table (a narrow table [n, 64] with slots_table == 2 "
+                                                  "needs a table slot asserted empty: table_slots_empty)").c_str());
   const bool pool = pool_part != nullptr;
   if (pool && (!pool_bits || !pool_slot || row0 % WR || mis16(pool_part) || out2 || slots_mfma != 2 || slots_table != 2))
     return fail(DESCO_EINVAL, "desco_shmp_layer_pool_bf16x6_f32: bad pooling argument (row0 % tile rows, no out2, "
@@ -844,6 +882,7 @@ static int shmp16_launch(const char* who, const float* x, int64_t ldx, const int
   g.xself = xself;
   g.ldxs = ldxs;
   g.self_coef = self_coef;
+  g.tab_empty = (ytab && slots_table == 2 && ldy < 128) ? tab_empty : 0;   // (a wide table needs no assertion: parent's path)
   if (!shmp_args_ok(g, wt_planes) || slots_mfma > 2 || (!out && !pool && !out2))
     return fail(DESCO_EINVAL, (std::string(who) + ": bad argument (slots_mfma <= 2, slots_table <= 2)").c_str());
   // bf16x6 form: 16 waves per block (12 measured 2-6 % slower there: profiles/r2_h_ab_tile_rows.log).  fp16 form: TWELVE,
@@ -932,6 +971,26 @@ extern "C" int desco_shmp_layer_pool_table_f16x3_f32(const float* x, int64_t ldx
   return desco::shmp16_launch("desco_shmp_layer_pool_table_f16x3_f32", x, ldx, vrowptr, vcol, row0, num_rows,
                               slots_stored, slots_mfma, slots_table, wt_planes, w_scale, bias, ytab, ldy, ytab_row0, out,
                               ldo, nullptr, 0, stream, pool_bits, pool_slot, pool_part, nullptr, nullptr, 0, self_coef);
+}
+
+// The f16x3 layer in any of its forms -- plain (pool_part null), pooled, pooled with recomputed own rows (self_coef) --
+// for a block ONE OF WHOSE TABLE SLOTS is asserted empty (table_slots_empty: bit t = table slot t): ytab may then be the other
+// slot's block alone, [n, 64] with ldy = 64, and the same kernel instantiations run on it.
+extern "C" int desco_shmp_layer_narrow_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
+                                                 const int32_t* vcol, int64_t row0, int64_t num_rows,
+                                                 int slots_stored, int slots_mfma, int slots_table,
+                                                 const int16_t* wt_planes, const float* w_scale, const float* bias,
+                                                 const float* ytab, int64_t ldy, int64_t ytab_row0,
+                                                 float* out, int64_t ldo, float* out2, int64_t ldo2,
+                                                 float* row_absmax, const float* xself, int64_t ldxs,
+                                                 const uint32_t* pool_bits, const int32_t* pool_slot,
+                                                 float* pool_part, const float* self_coef, int table_slots_empty,
+                                                 desco_stream_t stream) {
+  if (!w_scale) return desco::fail(DESCO_EINVAL, "desco_shmp_layer_narrow_f16x3_f32: w_scale is null");
+  return desco::shmp16_launch("desco_shmp_layer_narrow_f16x3_f32", x, ldx, vrowptr, vcol, row0, num_rows, slots_stored,
+                              slots_mfma, slots_table, wt_planes, w_scale, bias, ytab, ldy, ytab_row0, out, ldo, out2,
+                              ldo2, stream, pool_bits, pool_slot, pool_part, row_absmax, xself, ldxs, self_coef,
+                              table_slots_empty);
 }
 
 extern "C" int desco_shmp_pool_tile_rows(void) { return desco::WR; }

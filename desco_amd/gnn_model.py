@@ -736,6 +736,22 @@ def _anchor_const_input(pk, gnn, canon, row_bound=None):
 # materialised tensor
 FIRST_LAYER_TABLE = os.environ.get("DESCO_FIRST_LAYER_TABLE", "1") != "0"
 
+# a block without an entry in one of the two table slots (molecule graphs: table slot 0, the canonical->count TRIANGLE
+# relation) gets no table columns for it -- the canonical->count product writes [B, 64] instead of [B, 128], the count launches
+# read the narrow table (desco_shmp_layer_narrow_f16x3_f32, NeighborhoodBatch.table_empty) -- and the second layer's product runs on the DISTINCT
+# first-layer canonical rows only (NeighborhoodBatch.canonical_table_index); bit-identical, DESIGN.md 4.1
+TABLE_NARROW = os.environ.get("DESCO_TABLE_NARROW", "1") != "0"
+
+
+def _layer2_table(canon_uptr: torch.Tensor, S: int, coef: torch.Tensor, planes: torch.Tensor) -> torch.Tensor:
+    """the second layer's canonical->count table on the U_c distinct first-layer canonical rows: the closed-form first layer on
+    the distinct degree tuples (``canon_uptr`` of canonical_table_index, ``coef`` the canonical rows' coefficients), then the
+    row-wise table product -- row u equals the full product's row of every canonical row with tuple u, bit for bit"""
+    rows = torch.empty(((canon_uptr.numel() - 1) // S, H), device=canon_uptr.device)
+    ops.degree_affine(canon_uptr, 0, rows.shape[0], S, coef, ops.ACT_RELU, 0.0, rows)
+    return ops.linear64(rows, planes)
+
+
 # the pooled embeddings [B, 64 (L + 1)] are never written: post_mp.0 forms its operand's chunks from the anchor rows and
 # the fused pooling's partial sums in its load phase (desco_pool_post_bf16x6_f32; neighborhoods of at most 33 count rows)
 POOL_POST_FUSED = os.environ.get("DESCO_POOL_POST_FUSED", "1") != "0"
@@ -781,6 +797,10 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
     if (FIRST_LAYER_TABLE and pool1 and canon_once and L >= 2 and "wt_tab" in pk["layers"][1]["count"]
             and isinstance(pk["layers"][1]["count"].get("wt_mfma_x6"), ops.F16Planes)):
         tab1 = batch.degree_table_index()
+    # no table columns for an empty table slot 1; then also layer 2's table from the distinct canonical degree tuples
+    temp = batch.table_empty if (TABLE_NARROW and nb and f16 and Nc > 0) else 0      # (bit t: table slot t is empty)
+    tblock = 1 if temp == 1 else 0                                                  # the 64-row block of wt_tab_l64 still needed
+    ctab = batch.canonical_table_index() if (temp and tab1 is not None) else None
     pool_parts = {}
     if fpool:
         pbits, pslot, nslots = batch.pool_index()
@@ -845,16 +865,28 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
             e = pk["layers"][l][t]
             if "wt_tab" in e:
                 crows = canon[:, l * H:(l + 1) * H] if canon_once else X[-1][Nc:]     # canonical rows of X_l
-                ytab = (ops.linear64(crows, e["wt_tab_l64"]) if GEMM_BF16X6 else
-                        ops.gemm(crows, e["wt_tab"]))                     # canonical rows x [W2|W3]
+                tem = temp if isinstance(e.get("wt_mfma_x6"), ops.F16Planes) else 0
+                y_row0, vcol_c = Nc, vcol_l
+                if tem and l == 1 and ctab is not None:
+                    # (the canonical rows of X_1 are a function of their degree tuple: U_c table rows, ids remapped)
+                    ytab = _layer2_table(ctab[0], S, _first_layer_coef(pk, "canonical", 2, S, x0, src_of_slot, dev),
+                                         e["wt_tab_l64"][tblock:tblock + 1])
+                    # (ctab[2] is tab1[2] with the TABLE slots' sources remapped as well; the canonical launch of this layer
+                    #  reads slots 0 and 1 only and keeps tab1[2])
+                    vcol_c, y_row0 = ctab[2], 0
+                elif tem:
+                    ytab = ops.linear64(crows, e["wt_tab_l64"][tblock:tblock + 1])   # canonical rows x W2 or W3: [B, 64]
+                else:
+                    ytab = (ops.linear64(crows, e["wt_tab_l64"]) if GEMM_BF16X6 else
+                            ops.gemm(crows, e["wt_tab"]))                 # canonical rows x [W2|W3]
                 pool = None
                 if fpool and "wt_mfma_x6" in e:
                     pool_parts[l + 1] = torch.empty((nslots, H), device=dev)
                     pool = (pbits, pslot, pool_parts[l + 1])
-                ops.shmp_layer(x_src, batch.vrowptr, vcol_l, r0, r1 - r0, S, 2,
+                ops.shmp_layer(x_src, batch.vrowptr, vcol_c, r0, r1 - r0, S, 2,
                                e.get("wt_mfma_x6", e["wt_mfma"]) if SHMP_BF16X6 else e["wt_mfma"],
                                e["b"], None if (pool is not None and last) else xn, ytab=ytab,
-                               ytab_row0=Nc, pool=pool, self_coef=coef_l)
+                               ytab_row0=y_row0, pool=pool, self_coef=coef_l, table_empty=tem)
             else:
                 canonical, w16 = t == "canonical", isinstance(e.get("wt_x6"), ops.F16Planes)
                 once = canon_once and canonical and w16

@@ -418,7 +418,8 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
                bias: torch.Tensor, out: Optional[torch.Tensor], ytab: Optional[torch.Tensor] = None,
                ytab_row0: int = 0, out2: Optional[torch.Tensor] = None,
                pool: Optional[tuple] = None, row_absmax: Optional[torch.Tensor] = None,
-               xself: Optional[torch.Tensor] = None, self_coef: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+               xself: Optional[torch.Tensor] = None, self_coef: Optional[torch.Tensor] = None,
+               table_empty: int = 0) -> Optional[torch.Tensor]:
     """Fused gather + folded Linear + relu for rows [row0, row0+num_rows) (see desco_hip.h).
     ``xself`` [num_rows, >= 64] (f16x3 form): the launch's own rows (self block) read from this view -- row i of the launch
     at xself[i - row0] -- instead of from ``x``; ``out`` may then be None when ``out2`` is given.
@@ -429,6 +430,8 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
     ``self_coef`` [slots_stored + 1, 64] (pooled f16x3 launch): the launch's own rows are recomputed from their slot
     degrees, relu(coef[S] + sum_s d_s coef[s]), instead of read (desco_shmp_layer_pool_table_f16x3_f32: ``x`` is then a
     table of the layer input's distinct rows and ``vcol`` addresses its rows).
+    ``table_empty`` (f16x3 form, two table slots): bit t set = the caller asserts that table slot t has no entry in the
+    block; ``ytab`` may then be the other slot's block alone, [n_src, 64] (desco_shmp_layer_narrow_f16x3_f32: same kernel).
     ``pool`` = (pool_bits, pool_slot, pool_part): also leave the per-(tile, segment) partial sums of
     the produced rows in ``pool_part`` (fused global_add_pool, finished by ``pool_reduce``); ``out``
     may then be None (rows not stored)."""
@@ -436,7 +439,9 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
     x6 = f16 or wt.dtype == torch.int16
     if pool is not None:
         return _shmp_layer_pool(x, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma, wt, bias, out,
-                                ytab, ytab_row0, pool, xself, self_coef)
+                                ytab, ytab_row0, pool, xself, self_coef, table_empty)
+    if table_empty and not f16:
+        raise ValueError("shmp_layer: table_empty is implemented by the f16x3 form only")
     if self_coef is not None:
         raise ValueError("shmp_layer: self_coef is implemented by the pooled f16x3 launch only")
     if f16:
@@ -456,7 +461,7 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
         xsp -= 4 * ldxs * row0                       # the entry point indexes it by the global row id
     st, yp, ldy = 0, None, 0
     if ytab is not None:
-        st = ytab.shape[1] // 64
+        st = 2 if table_empty else ytab.shape[1] // 64
         yp, ldy = _rows(ytab, "ytab")
     o2p, ldo2 = (None, 0) if out2 is None else _rows(out2, "out2")
     L = _lib.lib()
@@ -471,7 +476,11 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
         tail = (_dev(bias.contiguous(), "bias"), yp, ldy, ytab_row0, op, ldo, o2p, ldo2, _stream())
         if row_absmax is not None and not f16:
             raise ValueError("shmp_layer: row_absmax is an output of the f16x3 form only")
-        if f16:
+        if f16 and table_empty:
+            rc = L.desco_shmp_layer_narrow_f16x3_f32(*head, _dev(wt.planes, "wt", torch.int16), _dev(wt.scale, "w_scale"),
+                                                     *tail[:-1], _opt(row_absmax, "row_absmax"), xsp, ldxs, None, None,
+                                                     None, None, int(table_empty), tail[-1])
+        elif f16:
             rc = L.desco_shmp_layer_f16x3_f32(*head, _dev(wt.planes, "wt", torch.int16), _dev(wt.scale, "w_scale"),
                                               *tail[:-1], _opt(row_absmax, "row_absmax"), xsp, ldxs, tail[-1])
         else:
@@ -482,15 +491,17 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
 
 
 def _shmp_layer_pool(x, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma, wt, bias, out, ytab,
-                     ytab_row0, pool, xself=None, self_coef=None):
+                     ytab_row0, pool, xself=None, self_coef=None, table_empty=0):
     bits, slot, part = pool
     f16 = isinstance(wt, F16Planes)
+    if table_empty and not f16:
+        raise ValueError("shmp_layer(pool=...): table_empty is implemented by the f16x3 form only")
     if xself is not None or (self_coef is not None and not f16):
         raise ValueError("shmp_layer(pool=...): no xself; self_coef with the f16x3 form only")
     assert ytab is not None and (f16 or (wt.dtype == torch.int16 and wt.is_contiguous()))
     xp, ldx = _rows(x, "x")
     op, ldo = (None, 0) if out is None else _rows(out, "out")
-    st = ytab.shape[1] // 64
+    st = 2 if table_empty else ytab.shape[1] // 64
     yp, ldy = _rows(ytab, "ytab")
     L = _lib.lib()
     fl = 2.0 * num_rows * (slots_mfma + 1) * 64 * 64
@@ -508,6 +519,11 @@ def _shmp_layer_pool(x, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma,
                 _dev(slot, "pool_slot", torch.int32), _dev(part, "pool_part"), _stream())
         if self_coef is not None:
             assert tuple(self_coef.shape) == (slots_stored + 1, 64) and self_coef.is_contiguous()
+        if table_empty:
+            rc = L.desco_shmp_layer_narrow_f16x3_f32(*head, _dev(wt.planes, "wt", torch.int16), _dev(wt.scale, "w_scale"),
+                                                     *tail[:6], None, 0, None, None, 0, *tail[6:9],
+                                                     _opt(self_coef, "self_coef"), int(table_empty), tail[-1])
+        elif self_coef is not None:
             rc = L.desco_shmp_layer_pool_table_f16x3_f32(*head, _dev(wt.planes, "wt", torch.int16),
                                                          _dev(wt.scale, "w_scale"), *tail[:-1],
                                                          _dev(self_coef, "self_coef"), tail[-1])

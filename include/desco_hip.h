@@ -617,6 +617,28 @@ int desco_shmp_layer_pool_table_f16x3_f32(const float* x, int64_t ldx, const int
                                           const int32_t* pool_slot, float* pool_part, const float* self_coef,
                                           desco_stream_t stream);
 
+/* The f16x3 layer for a block ONE OF WHOSE TWO TABLE SLOTS has no entry at all.  Molecule graphs have no triangles: the
+ * canonical->count triangle relation -- CSR slot 2 (slot = 2 (source is canonical) + tride), table slot 0 -- is empty in the
+ * whole block.  One entry point for the three forms above: plain (pool_part NULL; out2, row_absmax, xself as in
+ * desco_shmp_layer_f16x3_f32), pooled (pool_bits / pool_slot / pool_part) and pooled with the own rows recomputed (self_coef).
+ * table_slots_empty: bit t set = the caller ASSERTS that table slot t (CSR slot slots_mfma + t) is empty; slots_table must be
+ * 2.  The kernel then neither tests for nor reads that slot's 64-column block of ytab, and ytab may be the NARROW table of the
+ * OTHER slot alone, [n, 64] with ldy = 64, its block at column 0 (the same kernel family: shmp_layer16_kernel<.., ST = 2, ..> with a
+ * compile-time 64 in instantiations of their own, NARROW; the wide table's kernels are compiled as before) -- the table product
+ * then writes half the bytes.  The narrow table needs ldx = 64, ldy = 64 and, with out, ldo = 64 (other strides: DESCO_EINVAL,
+ * shape not built).  Entries of a slot asserted empty, should the assertion be false, are ignored, never read out of bounds.
+ * With a wide table (ldy >= 128) the mask is not needed and not used: the launch is the respective entry point's above.
+ * ldy < 64 * slots_table without a slot asserted empty is refused with DESCO_EINVAL (as it is by those).  Results are
+ * bit-identical to the launch on the [n, 128] table. */
+int desco_shmp_layer_narrow_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr, const int32_t* vcol,
+                                      int64_t row0, int64_t num_rows, int slots_stored, int slots_mfma,
+                                      int slots_table, const int16_t* wt_planes, const float* w_scale,
+                                      const float* bias, const float* ytab, int64_t ldy, int64_t ytab_row0,
+                                      float* out, int64_t ldo, float* out2, int64_t ldo2, float* row_absmax,
+                                      const float* xself, int64_t ldxs, const uint32_t* pool_bits,
+                                      const int32_t* pool_slot, float* pool_part, const float* self_coef,
+                                      int table_slots_empty, desco_stream_t stream);
+
 int desco_pool_reduce_f32(const float* pool_part, const uint32_t* pool_bits, const int32_t* pool_slot,
                           const int32_t* seg_ptr, int64_t num_seg, const float* extra,
                           int64_t ld_extra, float* out, int64_t ldo, int tile_rows,
