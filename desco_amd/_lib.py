@@ -129,6 +129,8 @@ SIGNATURES = {
     "desco_shmp_pool_tile_rows": (c_int, []),
     "desco_degree_affine_f32": (c_int, [vp, i64, i64, i32, vp, i32, f32, vp, i64, vp, i64, vp, vp]),
     "desco_degree_affine_pool_f32": (c_int, [vp, i64, i32, vp, i32, f32, vp, i64, vp, vp, vp, vp]),
+    "desco_table_rows_pool_f32": (c_int, [vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
+    "desco_index_range_check_i32": (c_int, [vp, i64, i64, vp, vp]),
     "desco_gemm_bf16x6_f32": (c_int, [vp, i64, i32, vp, i64, i32, vp, i32, vp, i32, vp, i32, vp, i32, f32,
                                       vp, i64, i64, vp]),
     "desco_gemm_bf16_f32": (c_int, [vp, i64, i32, vp, i64, i32, vp, i32, vp, i32, vp, i32, vp, i32, f32,

@@ -265,6 +265,91 @@ class NeighborhoodBatch(_TrainIndexMixin):
         rows have too many distinct tuples."""
         return self._table_indices()[1]
 
+    # eligibility bounds of layer2_table_index: a 16-row tile of rows of total degree <= 8 stages all its source ids (the
+    # layer kernel's gather order is then a function of the row alone); a [16384, 64] fp32 table is 4 MiB, one XCD's L2
+    LAYER2_MAX_DEGREE = 8
+    LAYER2_MAX_CLASSES = 1 << 14
+    LAYER2_MIN_ROWS_PER_CLASS = 8
+
+    def layer2_table_index(self):
+        """The count rows' classes under the SECOND layer (built once per batch, on the batch's device): ``(cls, rep_uptr,
+        rep_vcol, vcol_2)`` or None.  With the first layer a table of degree tuples (``degree_table_index``,
+        ``canonical_table_index``), the second layer's count row i is a function of its four slot degrees and of its remapped
+        CSR segment ``vcol_tc`` -- table ids, the same in whichever neighborhood the row sits -- so rows that agree in both get
+        bit-equal X_2 rows: ``cls`` [num_count] int32 is each count row's class (exact: iterated pair refinement, one sorted
+        ``torch.unique`` per segment position, no hashing), ``rep_uptr`` [U_2 S + 1] / ``rep_vcol`` the compact 4-slot CSR of one
+        representative per class (its lowest row; the segment copied from ``vcol_tc``), on which the layer runs, and ``vcol_2``
+        = ``vcol`` with the sources of slots 0 and 1 replaced by their class.  None unless the block has an empty table slot
+        (``table_empty``) and both first-layer tables, no count row has more than 8 sources (tested before any sort), U_2 <=
+        16384 and 8 U_2 <= num_count (the LAYER2_* bounds above; the last one is about profit only, and tests on small
+        blocks lower it on their batch object)."""
+        if "_layer2_table" in self.__dict__:
+            return self.__dict__["_layer2_table"]
+        self.__dict__["_layer2_table"] = res = self._build_layer2_table()
+        return res
+
+    def _build_layer2_table(self):
+        S, nc, n = self.slots, self.num_count, self.num_rows
+        if nc == 0 or not self.table_empty:                     # (the narrow-table case only: a table slot without entries)
+            return None
+        vr = self.vrowptr.to(torch.int64)
+        start = vr[0:S * nc:S]
+        tdeg = vr[S:S * nc + 1:S] - start                       # total degree of every count row
+        dmax = int(tdeg.max().item())
+        if dmax > self.LAYER2_MAX_DEGREE:                       # (dense graphs leave here, before any sort)
+            return None
+        tab1, ctab = self._table_indices()
+        if tab1 is None or ctab is None:
+            return None
+        umax = min(self.LAYER2_MAX_CLASSES, nc // self.LAYER2_MIN_ROWS_PER_CLASS)
+        vcol_tc = ctab[2].to(torch.int64)
+        ne = vcol_tc.numel()
+        # pair refinement: rows of one class after step j agree in their degree tuple and in segment entries 0 .. j (the slot
+        # boundaries inside the segment follow from the degree tuple); an entry past the row's end counts as -1
+        key = tab1[1].to(torch.int64)
+        nkey = tab1[0].numel() // S
+        width = (int(vcol_tc.max().item()) + 2) if ne else 1
+        for j in range(dmax):
+            if nkey > umax:
+                return None
+            ent = torch.where(tdeg > j, vcol_tc[(start + j).clamp(max=max(ne - 1, 0))] + 1, torch.zeros_like(tdeg))
+            assert nkey * width < 2 ** 62
+            uniq, key = torch.unique(key * width + ent, return_inverse=True)
+            nkey = uniq.numel()
+        if nkey > umax:
+            return None
+        dev = vr.device
+        # the lowest row of every class: the first of its run in a STABLE sort by class (an atomic-min scatter of millions of
+        # rows onto a thousand addresses takes ten times as long)
+        order = torch.argsort(key, stable=True)
+        size = torch.bincount(key, minlength=nkey)
+        rep = order[torch.cumsum(size, 0) - size]
+        deg = (vr[1:S * nc + 1] - vr[:S * nc]).view(nc, S)
+        rep_uptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), deg[rep].reshape(-1).cumsum(0)])
+        pos = torch.arange(max(dmax, 1), device=dev)
+        idx = start[rep][:, None] + pos[None, :]
+        rep_vcol = vcol_tc[idx.clamp(max=max(ne - 1, 0))][pos[None, :] < tdeg[rep][:, None]] if ne else vcol_tc
+        cls = key.to(torch.int32).contiguous()
+        dall = vr[1:] - vr[:-1]
+        low = (torch.repeat_interleave(torch.arange(n * S, device=dev), dall) % S) < 2
+        col = self.vcol.to(torch.int64)
+        vcol_2 = torch.where(low, key[col.clamp(max=nc - 1)], col).to(torch.int32)
+        return (cls, rep_uptr.to(torch.int32).contiguous(), rep_vcol.to(torch.int32).contiguous(), vcol_2.contiguous())
+
+    def layer2_rep_pool_index(self):
+        """the fused-pooling index of ONE segment over the U_2 representatives (the pooled layer launch that computes their
+        rows wants one; its partial rows are discarded): (pool_bits, pool_slot, a [slots, 64] buffer for them), cached"""
+        idx = self.__dict__.get("_layer2_rep_pool")
+        if idx is None:
+            u2 = (self.layer2_table_index()[1].numel() - 1) // self.slots
+            nt = (u2 + 15) // 16
+            dev = self.vrowptr.device
+            bits = torch.zeros(nt, dtype=torch.int32, device=dev)
+            bits[nt - 1] = 1 << ((u2 - 1) % 16)
+            idx = self.__dict__["_layer2_rep_pool"] = (bits, torch.arange(nt, dtype=torch.int32, device=dev),
+                                                       torch.empty((nt, 64), device=dev))
+        return idx
+
     @property
     def table_empty(self) -> int:
         """Which of the count rows' two TABLE slots -- the canonical->count relations: CSR slot 2 (triangle, table slot 0) and

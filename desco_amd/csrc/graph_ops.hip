@@ -934,6 +934,102 @@ extern "C" int desco_degree_affine_pool_f32(const int32_t* vrowptr, int64_t num_
   return launch_status("desco_degree_affine_pool_f32");
 }
 
+// A layer whose rows exist as a table of their DISTINCT rows (gnn_model.SECOND_LAYER_TABLE: the second layer of a
+// molecule batch has about a thousand of them for millions of count rows): row i = table[cls[i]].  The same wave tiles as
+// degree_affine_pool_kernel -- one wave per 16-row tile, one lane per column, no LDS -- with the row a 256-byte read of the
+// (L2-resident) table instead of an affine map: lane l < 16 holds the class of tile row l, a row's class reaches the vector
+// unit as a wave-uniform operand (v_readlane), the tile's 16 reads go out together, and the running sum down the rows
+// leaves the partial rows the layer kernel's pooled launch on the same rows would (same order: bit-identical).
+namespace desco {
+__global__ __launch_bounds__(256) void table_rows_pool_kernel(const float* __restrict__ table, int64_t ldt,
+                                                              int num_table, const int32_t* __restrict__ cls,
+                                                              int64_t num_rows, float* __restrict__ out, int64_t ldo,
+                                                              const uint32_t* __restrict__ pool_bits,
+                                                              const int32_t* __restrict__ pool_slot,
+                                                              float* __restrict__ pool_part) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t ntiles = (num_rows + 15) / 16;
+  const float* tb = table + lane;
+  for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < ntiles; t += (int64_t)gridDim.x * 4) {
+    const int64_t ri = t * 16 + (lane & 15);
+    // (rows past the end repeat the last row's class: read, never stored or summed; a class outside the table -- the
+    //  caller's error, desco_index_range_check_i32 finds it -- reads the nearest table row, never out of bounds)
+    int c = cls[ri < num_rows ? ri : num_rows - 1];
+    c = c < 0 ? 0 : (c < num_table ? c : num_table - 1);
+    const uint32_t E = __builtin_amdgcn_readfirstlane(pool_bits[t]);
+    int slot = __builtin_amdgcn_readfirstlane(pool_slot[t]);
+    const int nr = (int)((num_rows - t * 16) < 16 ? (num_rows - t * 16) : 16);
+    float v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = tb[(int64_t)__builtin_amdgcn_readlane(c, r) * ldt];
+    float* o = out ? out + t * 16 * ldo + lane : nullptr;
+    float* pp = pool_part + lane;
+    float run = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (r < nr) {                                        // (wave-uniform)
+        if (o) o[r * ldo] = v[r];
+        run += v[r];
+        if ((E >> r) & 1u) {                               // row r ends its segment (wave-uniform)
+          pp[(int64_t)slot * 64] = run;
+          ++slot;
+          run = 0.f;
+        }
+      }
+    }
+    if (nr > 0 && !((E >> (nr - 1)) & 1u)) pp[(int64_t)slot * 64] = run;
+  }
+}
+
+// bad[0] |= 1 when an index lies outside [0, bound)
+__global__ __launch_bounds__(256) void index_range_check_kernel(const int32_t* __restrict__ idx, int64_t n, int64_t bound,
+                                                                int32_t* __restrict__ bad) {
+  bool b = false;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int32_t v = idx[i];
+    b |= v < 0 || v >= bound;
+  }
+  if (b) atomicOr(bad, 1);
+}
+}  // namespace desco
+
+extern "C" int desco_table_rows_pool_f32(const float* table, int64_t ldt, int64_t num_table, const int32_t* cls,
+                                         int64_t num_rows, float* out, int64_t ldo, const uint32_t* pool_bits,
+                                         const int32_t* pool_slot, float* pool_part, desco_stream_t stream) {
+  if (num_rows == 0) return 0;
+  if (!table || !cls || !pool_bits || !pool_slot || !pool_part || num_rows < 0 || num_table < 1 ||
+      num_table > INT32_MAX || ldt < 64 || ldt % 4 || mis16(table) || (out && (ldo < 64 || ldo % 4 || mis16(out))) ||
+      mis16(pool_part) || table == out)
+    return fail(DESCO_EINVAL, "desco_table_rows_pool_f32: bad argument (table, cls and the pooling index present, "
+                              "a table of 1 .. 2^31 - 1 rows, 16-byte rows of at least 64 floats, out != table)");
+  int64_t blocks = ((num_rows + 15) / 16 + 3) / 4;         // four wave tiles per block
+  if (blocks > 8 * 256) blocks = 8 * 256;
+  hipLaunchKernelGGL(table_rows_pool_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, ldt,
+                     (int)num_table, cls, num_rows, out, ldo, pool_bits, pool_slot, pool_part);
+  return launch_status("desco_table_rows_pool_f32");
+}
+
+extern "C" int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch,
+                                           desco_stream_t stream) {
+  if (n == 0) return 0;
+  if (!idx || !scratch || n < 0 || bound < 0)
+    return fail(DESCO_EINVAL, "desco_index_range_check_i32: bad argument");
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 8 * 256) blocks = 8 * 256;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t bad = 0;
+  if (hipMemsetAsync(scratch, 0, sizeof(int32_t), st) != hipSuccess)
+    return fail(DESCO_EINVAL, "desco_index_range_check_i32: scratch is not a device word");
+  hipLaunchKernelGGL(index_range_check_kernel, dim3((unsigned)blocks), dim3(256), 0, st, idx, n, bound, scratch);
+  const int rc = launch_status("desco_index_range_check_i32");
+  if (rc) return rc;
+  const hipError_t e = hipMemcpyAsync(&bad, scratch, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(st) : e;
+  if (e2 != hipSuccess) return fail((int)e2, "desco_index_range_check_i32: read-back failed");
+  if (bad) return fail(DESCO_EINVAL, "desco_index_range_check_i32: an index lies outside the table");
+  return 0;
+}
+
 extern "C" int desco_degree_affine_f32(const int32_t* vrowptr, int64_t row0, int64_t num_rows,
                                        int slots, const float* coef, int act, float slope,
                                        const float* extra, int64_t ld_extra, float* out,

@@ -742,6 +742,12 @@ FIRST_LAYER_TABLE = os.environ.get("DESCO_FIRST_LAYER_TABLE", "1") != "0"
 # first-layer canonical rows only (NeighborhoodBatch.canonical_table_index); bit-identical, DESIGN.md 4.1
 TABLE_NARROW = os.environ.get("DESCO_TABLE_NARROW", "1") != "0"
 
+# with both first-layer tables the SECOND layer's count rows are a function of their slot degrees and their remapped CSR
+# segment: a molecule batch has about a thousand distinct ones for millions of rows (NeighborhoodBatch.layer2_table_index).
+# The layer's count launch then runs on one representative per class, and desco_table_rows_pool_f32 writes the rows and their
+# pooled partial sums from that table; bit-identical (the layer kernel's arithmetic is row-local), DESIGN.md 4.1
+SECOND_LAYER_TABLE = os.environ.get("DESCO_SECOND_LAYER_TABLE", "1") != "0"
+
 
 def _layer2_table(canon_uptr: torch.Tensor, S: int, coef: torch.Tensor, planes: torch.Tensor) -> torch.Tensor:
     """the second layer's canonical->count table on the U_c distinct first-layer canonical rows: the closed-form first layer on
@@ -801,6 +807,8 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
     temp = batch.table_empty if (TABLE_NARROW and nb and f16 and Nc > 0) else 0      # (bit t: table slot t is empty)
     tblock = 1 if temp == 1 else 0                                                  # the 64-row block of wt_tab_l64 still needed
     ctab = batch.canonical_table_index() if (temp and tab1 is not None) else None
+    # ... and the second layer's count launch on the distinct rows of its OUTPUT (None: the batch is not eligible)
+    tab2 = batch.layer2_table_index() if (SECOND_LAYER_TABLE and ctab is not None and fpool and L >= 2) else None
     pool_parts = {}
     if fpool:
         pbits, pslot, nslots = batch.pool_index()
@@ -883,6 +891,16 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                 if fpool and "wt_mfma_x6" in e:
                     pool_parts[l + 1] = torch.empty((nslots, H), device=dev)
                     pool = (pbits, pslot, pool_parts[l + 1])
+                if l == 1 and tab2 is not None and tem and pool is not None:
+                    # the launch on the U_2 representatives' compact CSR (its pooled partials -- one segment -- are not used),
+                    # then every count row and the neighborhoods' partial sums from the table of their rows
+                    cls2, rep_uptr, rep_vcol, _ = tab2
+                    table2 = torch.empty(((rep_uptr.numel() - 1) // S, H), device=dev)
+                    ops.shmp_layer(x_src, rep_uptr, rep_vcol, 0, table2.shape[0], S, 2, e["wt_mfma_x6"], e["b"], table2,
+                                   ytab=ytab, ytab_row0=y_row0, pool=batch.layer2_rep_pool_index(),
+                                   self_coef=coef_l, table_empty=tem)
+                    ops.table_rows_pool(table2, cls2, r1 - r0, None if last else xn, pool)
+                    continue
                 ops.shmp_layer(x_src, batch.vrowptr, vcol_c, r0, r1 - r0, S, 2,
                                e.get("wt_mfma_x6", e["wt_mfma"]) if SHMP_BF16X6 else e["wt_mfma"],
                                e["b"], None if (pool is not None and last) else xn, ytab=ytab,

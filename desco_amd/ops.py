@@ -746,6 +746,31 @@ def degree_affine_pool(vrowptr: torch.Tensor, num_rows: int, slots: int, coef: t
             _stream()), "degree_affine_pool")
 
 
+def table_rows_pool(table: torch.Tensor, cls: torch.Tensor, num_rows: int, out: Optional[torch.Tensor],
+                    pool: tuple) -> None:
+    """rows [0, num_rows) of a layer computed on its distinct rows only: out[i] = table[cls[i]], with the rows' segment sums
+    fused in as in ``degree_affine_pool`` (desco_table_rows_pool_f32); ``out`` may be None (partials only)."""
+    bits, slot, part = pool
+    tp, ldt = _rows(table, "table")
+    assert cls.is_contiguous() and cls.numel() >= num_rows and table.shape[1] >= 64
+    op, ldo = (None, 64) if out is None else _rows(out, "out")
+    with _Timed("table_rows_pool_kernel", 0.0, (0.0 if out is None else 256.0) * num_rows + 4.0 * num_rows):
+        _lib.check(_lib.lib().desco_table_rows_pool_f32(
+            tp, ldt, table.shape[0], _dev(cls, "cls", torch.int32), num_rows, op, ldo,
+            _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32), _dev(part, "pool_part"),
+            _stream()), "table_rows_pool")
+
+
+def index_range_check(idx: torch.Tensor, bound: int) -> None:
+    """raise unless every entry of the int32 device index lies in [0, bound) (desco_index_range_check_i32; synchronises:
+    once per index, never in the pass)"""
+    assert idx.is_contiguous()
+    scratch = torch.empty(1, dtype=torch.int32, device=idx.device)
+    _lib.check(_lib.lib().desco_index_range_check_i32(_dev(idx, "idx", torch.int32), idx.numel(), bound,
+                                                      _dev(scratch, "scratch", torch.int32), _stream()),
+               "index_range_check")
+
+
 def gemm_split(a1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
                a2: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: float = 0.0,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:

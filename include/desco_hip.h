@@ -722,6 +722,19 @@ int desco_degree_affine_pool_f32(const int32_t* vrowptr, int64_t num_rows, int s
 /* row_absmax (optional, [num_rows]): row_absmax[i - row0] = max_c |out[i, c]| is WRITTEN -- the start of the per-row
  * bound desco_gemm_f16x3_f32 takes when these rows are the first column block of its operand. */
 
+/* The count rows of a layer that was computed on its DISTINCT rows only (host side: NeighborhoodBatch.layer2_table_index,
+ * gnn_model.SECOND_LAYER_TABLE): rows [0, num_rows) are out[i, 0:64] = table[cls[i], 0:64] (table [num_table, >= 64], row
+ * stride ldt; cls [num_rows] in [0, num_table)), with their global_add_pool fused in exactly as in
+ * desco_degree_affine_pool_f32: the same 16-row tiles, pool_bits / pool_slot index and partial rows -- bit for bit what the
+ * layer kernel's pooled launch leaves for the same rows.  out may be NULL (partials only).  A class outside the table reads
+ * the nearest table row (never out of bounds); desco_index_range_check_i32 is the check, made once per index. */
+int desco_table_rows_pool_f32(const float* table, int64_t ldt, int64_t num_table, const int32_t* cls, int64_t num_rows,
+                              float* out, int64_t ldo, const uint32_t* pool_bits, const int32_t* pool_slot,
+                              float* pool_part, desco_stream_t stream);
+/* DESCO_EINVAL when one of idx[0 .. n) (device) lies outside [0, bound); scratch: one device word.  Synchronises the
+ * stream: for indices built once per batch, not for the pass. */
+int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch, desco_stream_t stream);
+
 /* Indices of the backward pass, built on the device (replaces the per-batch host transposes):
  *  desco_vcsr_transpose_sym: the transposed index of a SYMMETRIC virtual-row CSR (every edge
  *    dst<-src has its mirror src<-dst; true for canonical-partition blocks, query graphs and the
