@@ -270,6 +270,11 @@ class NeighborhoodBatch(_TrainIndexMixin):
     LAYER2_MAX_DEGREE = 8
     LAYER2_MAX_CLASSES = 1 << 14
     LAYER2_MIN_ROWS_PER_CLASS = 8
+    # ... and of gnn_model.SECOND_LAYER_GATHER (the third layer gathering from that table, X_2's count rows never written): what
+    # it saves is the store and the read-back of X_2, which reach HBM only where the tensor outgrows the 256 MB memory-side
+    # cache -- below 2^18 count rows (64 MiB) the pass measures the same either way (real-size COX2, 130 022 rows: replayed pass
+    # 0.760 against 0.762 ms), and the rows stay where a caller can look at them.  About profit only, like the bound above
+    LAYER2_GATHER_MIN_ROWS = 1 << 18
 
     def layer2_table_index(self):
         """The count rows' classes under the SECOND layer (built once per batch, on the batch's device): ``(cls, rep_uptr,
@@ -286,6 +291,11 @@ class NeighborhoodBatch(_TrainIndexMixin):
         if "_layer2_table" in self.__dict__:
             return self.__dict__["_layer2_table"]
         self.__dict__["_layer2_table"] = res = self._build_layer2_table()
+        if res is not None and res[0].is_cuda:
+            from . import ops
+            # the classes address the table of the representatives' rows in two kernels (desco_table_rows_pool_f32 and the
+            # third layer's gather, desco_shmp_layer_selfidx_f16x3_f32): checked once per batch, here where they are built
+            ops.index_range_check(res[0], (res[1].numel() - 1) // self.slots)
         return res
 
     def _build_layer2_table(self):

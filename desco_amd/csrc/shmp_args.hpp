@@ -50,6 +50,11 @@ struct ShmpArgs {
   // (desco_degree_affine_f32's arithmetic, bit for bit).  With x = a table of the distinct rows of that layer's output and
   // column ids that address the table, X_1 [N, 64] need not exist (gnn_model.FIRST_LAYER_TABLE).
   const float* self_coef;
+  // ... or read from the SAME table as the sources: with self_idx the launch's own row i is x + self_idx[i] * ldx (i = the
+  // global row index that addresses vrowptr) -- x is a table of the distinct rows of the layer's input, vcol holds table
+  // ids, and the input rows [N, 64] need not exist (desco_shmp_layer_selfidx_f16x3_f32; the pooled narrow fp16 form, with
+  // neither xself nor self_coef).  Last member: the others keep their offsets.
+  const int32_t* self_idx;
 };
 
 // The argument checks both forms share: operands present and 16-byte aligned (float4 loads and stores), slot counts

@@ -103,6 +103,11 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
       a1_.x = fmaxf(a1_.x, 0.f); a1_.y = fmaxf(a1_.y, 0.f); a1_.z = fmaxf(a1_.z, 0.f); a1_.w = fmaxf(a1_.w, 0.f); \
       s##it_##0 = a0_;                                                                         \
       s##it_##1 = a1_;                                                                         \
+    } else if constexpr (SELFIDX) {                                                            \
+      /* the row = a row of the table x, at the tile's staged class id (LDS: sent with the tile's row pointers) */ \
+      const float* p_ = xb + (int64_t)si[r_ < nr ? r_ : nr - 1] * LDX;                         \
+      s##it_##0 = *reinterpret_cast<const float4*>(p_);                                        \
+      s##it_##1 = *reinterpret_cast<const float4*>(p_ + 32);                                   \
     } else {                                                                                   \
       const float* p_ = xsb + (grow0 + (r_ < nr ? r_ : nr - 1)) * LDXS;                      \
       s##it_##0 = *reinterpret_cast<const float4*>(p_);                                        \
@@ -347,7 +352,10 @@ __device__ __forceinline__ void f4add(float4& a, const float4 b) {
 // it): one of the two table slots is asserted empty for the whole block (g.tab_empty) and ytab is the [n, 64] block of the
 // other one -- row stride 64 and column offset 0 at compile time, the empty slot's live bit never set
 // POOL: fused pooling epilogue (instantiated for the count-row launches only)
-template <int NW, int KB, int ST, bool LD64, bool POOL, bool F16, bool SELFDEG = false, bool NARROW = false>
+// SELFIDX (its own instantiation, the pooled NARROW fp16 form; every other one is compiled exactly as without it): the launch's
+// own row i is x[self_idx[i]] -- x is a table of distinct rows that the sources AND the rows themselves address (shmp_args.hpp)
+template <int NW, int KB, int ST, bool LD64, bool POOL, bool F16, bool SELFDEG = false, bool NARROW = false,
+          bool SELFIDX = false>
 __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const int32_t* __restrict__ rowptr_s,
                                                               const uint32_t* __restrict__ pool_bits_s,
                                                               const int32_t* __restrict__ pool_slot_s) {
@@ -359,7 +367,8 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
   constexpr int WPL = 64 * WST;                            // shorts per weight plane
   constexpr int NP = F16 ? 2 : 3;                          // operand planes (fp16 hi / lo; bf16 hi / mid / lo)
   constexpr int W_FLOATS = NP * WPL / 2;
-  constexpr int WAVE_LDS_ = F16 ? WAVE_LDS_F16 : WAVE_LDS;
+  static_assert(!SELFIDX || (F16 && LD64 && NARROW && POOL && !SELFDEG), "SELFIDX is built for the pooled narrow fp16 form");
+  constexpr int WAVE_LDS_ = (F16 ? WAVE_LDS_F16 : WAVE_LDS) + (SELFIDX ? 2 * WR : 0);
   constexpr int A_FLOATS_ = F16 ? A_FLOATS_F16 : A_FLOATS;
   short* Wp = reinterpret_cast<short*>(lds);               // [NP][64 n][WST]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -371,6 +380,9 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
   int* ec = ecb;
   float* rs = reinterpret_cast<float*>(ecb + 2 * WCAP);    // F16: [16] row scales of the block being staged
   (void)rs;
+  int* sib = reinterpret_cast<int*>(rs + WR);              // SELFIDX: 2 x [16] ids of the tile's own rows (current / next tile)
+  int* si = sib;
+  (void)si;
   float* biasL = lds + W_FLOATS + NW * WAVE_LDS_;          // [64] bias (zeros without one), block-shared
   int* next_sub = reinterpret_cast<int*>(biasL + 64);      // the block's tile hand-out counter
   // SELFDEG (its own instantiation: the launch's own rows recomputed from their slot degrees, see shmp_args.hpp): the
@@ -455,6 +467,10 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
     const int eb = __builtin_amdgcn_readfirstlane(rp[0]);
     const int ecnt = __builtin_amdgcn_readfirstlane(rp[WR * S]) - eb;
     for (int i = lane; i < ecnt && i < WCAP; i += 64) ec[i] = g.vcol[eb + i];
+    // (SELFIDX launches always come here: the entry point requires two table slots, so S >= 2 -- a form without a CSR
+    //  would have to load these ids outside this branch)
+    if constexpr (SELFIDX)
+      if (lane < WR) si[lane] = g.self_idx[grow0 + (lane < nr ? lane : nr - 1)];
   } else if (lane == 0) {
     rp[0] = 0;
     rpb[RPN] = 0;
@@ -558,6 +574,9 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
 #pragma unroll
         for (int k_ = 0; k_ < (WCAP + 63) / 64; ++k_)
           if (lane + 64 * k_ < ne) DESCO_DMA4(ids + 64 * k_, ecn + 64 * k_);
+        // ... and the ids of its own rows (16 dwords; rows beyond the tile's last repeat it)
+        if constexpr (SELFIDX)
+          if (lane < WR) DESCO_DMA4(g.self_idx + (g.row0 + w0n) + (lane < nrn ? lane : nrn - 1), sib + (cur ^ 1) * WR);
       }
       // ---- the two 32-column halves of block b; the first gather step of block b+1 goes out
       //      under this block's MFMAs (after the low halves have left their registers)
@@ -624,6 +643,7 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
       ec = ecn;
       cur ^= 1;
       rp = rpn;
+      si = sib + cur * WR;
       ebase = ebn_cur;
       sub_n1 = DESCO_NEXT_SUB();
       w0 = w0n;
@@ -749,17 +769,18 @@ __global__ __launch_bounds__(NW * 64) void shmp_layer16_kernel(ShmpArgs g, const
   }
 }
 
-template <int NW, int KB, int ST, bool LD64, bool POOL, bool F16, bool SELFDEG = false, bool NARROW = false>
+template <int NW, int KB, int ST, bool LD64, bool POOL, bool F16, bool SELFDEG = false, bool NARROW = false,
+          bool SELFIDX = false>
 static hipError_t shmp16_launch_one(const ShmpArgs& g, unsigned grid, hipStream_t st) {
   constexpr int WST = KB * 64 + 16;
   constexpr size_t w_floats = (size_t)(F16 ? 2 : 3) * 64 * WST / 2;
-  constexpr size_t shmem = sizeof(float) * (w_floats + (size_t)NW * (F16 ? WAVE_LDS_F16 : WAVE_LDS) + 64 + 4 +
-                                           (SELFDEG ? (MAXS + 1) * 64 : 0));
+  constexpr size_t shmem = sizeof(float) * (w_floats + (size_t)NW * ((F16 ? WAVE_LDS_F16 : WAVE_LDS) + (SELFIDX ? 2 * WR : 0)) +
+                                           64 + 4 + (SELFDEG ? (MAXS + 1) * 64 : 0));
   static_assert(shmem <= 160 * 1024, "SHMP layer (16-row tiles): LDS budget exceeded");
-  const hipError_t e = size_dynamic_lds<shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG, NARROW>>(160 * 1024);
+  const hipError_t e = size_dynamic_lds<shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG, NARROW, SELFIDX>>(160 * 1024);
   if (e == hipSuccess)
-    hipLaunchKernelGGL((shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG, NARROW>), dim3(grid), dim3(NW * 64), shmem, st, g,
-                       g.vrowptr, g.pool_bits, g.pool_slot);
+    hipLaunchKernelGGL((shmp_layer16_kernel<NW, KB, ST, LD64, POOL, F16, SELFDEG, NARROW, SELFIDX>), dim3(grid), dim3(NW * 64), shmem,
+                       st, g, g.vrowptr, g.pool_bits, g.pool_slot);
   return e;
 }
 
@@ -773,20 +794,22 @@ static bool shmp16_launch_st(const ShmpArgs& g, unsigned grid, hipStream_t st, h
       if (!(g.ldx == 64 && g.ldy == 64 && (!g.out || g.ldo == 64))) return false;
       if (g.pool_part) {
         if constexpr (KB == 3) {
-          e = g.self_coef ? shmp16_launch_one<NW, 3, 2, true, true, true, true, true>(g, grid, st)
-                          : shmp16_launch_one<NW, 3, 2, true, true, true, false, true>(g, grid, st);
+          e = g.self_idx    ? shmp16_launch_one<NW, 3, 2, true, true, true, false, true, true>(g, grid, st)
+              : g.self_coef ? shmp16_launch_one<NW, 3, 2, true, true, true, true, true>(g, grid, st)
+                            : shmp16_launch_one<NW, 3, 2, true, true, true, false, true>(g, grid, st);
           return true;
         } else {
           return false;
         }
       }
-      if (g.self_coef) return false;
+      if (g.self_coef || g.self_idx) return false;
       e = shmp16_launch_one<NW, KB, 2, true, false, true, false, true>(g, grid, st);
       return true;
     } else {
       return false;
     }
   }
+  if (g.self_idx) return false;           // (built for the pooled narrow fp16 launch only)
   if (g.pool_part) {
     if constexpr (KB == 3) {
       if (g.st != 2) return false;
@@ -837,7 +860,8 @@ static int shmp16_launch(const char* who, const float* x, int64_t ldx, const int
                          int64_t ytab_row0, float* out, int64_t ldo, float* out2, int64_t ldo2, desco_stream_t stream,
                          const uint32_t* pool_bits = nullptr, const int32_t* pool_slot = nullptr,
                          float* pool_part = nullptr, float* row_absmax = nullptr, const float* xself = nullptr,
-                         int64_t ldxs = 0, const float* self_coef = nullptr, int tab_empty = 0) {
+                         int64_t ldxs = 0, const float* self_coef = nullptr, int tab_empty = 0,
+                         const int32_t* self_idx = nullptr) {
   if (num_rows == 0) return 0;
   if (tab_empty < 0 || tab_empty > 3 || (tab_empty && slots_table != 2))
     return fail(DESCO_EINVAL, (std::string(who) + ": table_slots_empty is a mask of the two table slots (slots_table == 2)").c_str());
@@ -882,6 +906,7 @@ static int shmp16_launch(const char* who, const float* x, int64_t ldx, const int
   g.xself = xself;
   g.ldxs = ldxs;
   g.self_coef = self_coef;
+  g.self_idx = self_idx;
   g.tab_empty = (ytab && slots_table == 2 && ldy < 128) ? tab_empty : 0;   // (a wide table needs no assertion: parent's path)
   if (!shmp_args_ok(g, wt_planes) || slots_mfma > 2 || (!out && !pool && !out2))
     return fail(DESCO_EINVAL, (std::string(who) + ": bad argument (slots_mfma <= 2, slots_table <= 2)").c_str());
@@ -991,6 +1016,37 @@ extern "C" int desco_shmp_layer_narrow_f16x3_f32(const float* x, int64_t ldx, co
                               slots_mfma, slots_table, wt_planes, w_scale, bias, ytab, ldy, ytab_row0, out, ldo, out2,
                               ldo2, stream, pool_bits, pool_slot, pool_part, row_absmax, xself, ldxs, self_coef,
                               table_slots_empty);
+}
+
+// The pooled narrow launch on a TABLE of distinct rows: the sources (vcol) and the launch's own rows (self_idx[i] for the
+// global row i, the index that addresses vrowptr) are rows of x.  Arguments of the narrow entry point plus self_idx.
+extern "C" int desco_shmp_layer_selfidx_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr,
+                                                  const int32_t* vcol, int64_t row0, int64_t num_rows,
+                                                  int slots_stored, int slots_mfma, int slots_table,
+                                                  const int16_t* wt_planes, const float* w_scale, const float* bias,
+                                                  const float* ytab, int64_t ldy, int64_t ytab_row0,
+                                                  float* out, int64_t ldo, float* out2, int64_t ldo2,
+                                                  float* row_absmax, const float* xself, int64_t ldxs,
+                                                  const uint32_t* pool_bits, const int32_t* pool_slot,
+                                                  float* pool_part, const float* self_coef, int table_slots_empty,
+                                                  const int32_t* self_idx, desco_stream_t stream) {
+  const char* who = "desco_shmp_layer_selfidx_f16x3_f32";
+  if (!w_scale) return desco::fail(DESCO_EINVAL, "desco_shmp_layer_selfidx_f16x3_f32: w_scale is null");
+  if (!self_idx) return desco::fail(DESCO_EINVAL, "desco_shmp_layer_selfidx_f16x3_f32: self_idx is null");
+  if (xself || self_coef)
+    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_selfidx_f16x3_f32: self_idx excludes xself and self_coef (one source "
+                                     "of the launch's own rows)");
+  if (!pool_part || !pool_bits || !pool_slot)
+    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_selfidx_f16x3_f32: the pooling index (pool_bits, pool_slot, pool_part) "
+                                     "is missing: the form is built pooled only");
+  if (ldx != 64 || ldy != 64 || (out && ldo != 64))
+    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_selfidx_f16x3_f32: row strides other than 64 (ldx, ldy, ldo) are not built");
+  if (slots_table != 2 || table_slots_empty < 1 || table_slots_empty > 2)
+    return desco::fail(DESCO_EINVAL, "desco_shmp_layer_selfidx_f16x3_f32: the narrow table needs slots_table == 2 and exactly "
+                                     "one table slot asserted empty");
+  return desco::shmp16_launch(who, x, ldx, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma, slots_table, wt_planes,
+                              w_scale, bias, ytab, ldy, ytab_row0, out, ldo, out2, ldo2, stream, pool_bits, pool_slot,
+                              pool_part, row_absmax, nullptr, 0, nullptr, table_slots_empty, self_idx);
 }
 
 extern "C" int desco_shmp_pool_tile_rows(void) { return desco::WR; }

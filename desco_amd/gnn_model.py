@@ -748,6 +748,13 @@ TABLE_NARROW = os.environ.get("DESCO_TABLE_NARROW", "1") != "0"
 # pooled partial sums from that table; bit-identical (the layer kernel's arithmetic is row-local), DESIGN.md 4.1
 SECOND_LAYER_TABLE = os.environ.get("DESCO_SECOND_LAYER_TABLE", "1") != "0"
 
+# ... and X_2's count rows are then never written either: every one of them is table2[cls[row]], so the third layer's two
+# launches gather from that table -- the count launch with its own rows addressed through the classes
+# (desco_shmp_layer_selfidx_f16x3_f32), both with the column ids of layer2_table_index's ``vcol_2`` -- and
+# desco_table_rows_pool_f32 leaves the partial sums alone; models of three layers or more, blocks of at least
+# NeighborhoodBatch.LAYER2_GATHER_MIN_ROWS count rows; bit-identical, DESIGN.md 4.1
+SECOND_LAYER_GATHER = os.environ.get("DESCO_SECOND_LAYER_GATHER", "1") != "0"
+
 
 def _layer2_table(canon_uptr: torch.Tensor, S: int, coef: torch.Tensor, planes: torch.Tensor) -> torch.Tensor:
     """the second layer's canonical->count table on the U_c distinct first-layer canonical rows: the closed-form first layer on
@@ -809,6 +816,13 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
     ctab = batch.canonical_table_index() if (temp and tab1 is not None) else None
     # ... and the second layer's count launch on the distinct rows of its OUTPUT (None: the batch is not eligible)
     tab2 = batch.layer2_table_index() if (SECOND_LAYER_TABLE and ctab is not None and fpool and L >= 2) else None
+    # ... whose output stays a table: the third layer's launches gather from it (the fp16 forms of both node types, so that no
+    # launch of layers 2 and 3 reads or writes a row of X_2)
+    gather2, table2 = False, None
+    if SECOND_LAYER_GATHER and tab2 is not None and L >= 3 and Nc >= batch.LAYER2_GATHER_MIN_ROWS:
+        l1, l2 = pk["layers"][1], pk["layers"][2]
+        gather2 = ("wt_tab" in l2["count"] and all(isinstance(e.get(k), ops.F16Planes) for e, k in (
+            (l1["count"], "wt_mfma_x6"), (l2["count"], "wt_mfma_x6"), (l1["canonical"], "wt_x6"), (l2["canonical"], "wt_x6"))))
     pool_parts = {}
     if fpool:
         pbits, pslot, nslots = batch.pool_index()
@@ -861,12 +875,16 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
         last = l == L - 1
         # the last layer's count rows feed nothing but the pooling: with fused pooling they are
         # never stored (the canonical rows still are, they sit at the end of the same tensor)
-        xn = torch.empty((N, H), device=dev)
+        xn = None if (l == 1 and gather2) else torch.empty((N, H), device=dev)      # (gather2: X_2 is never allocated)
         # layer input, column ids and (count rows) self index of this layer's launches: X_l itself, or -- for the second
         # layer when X_1's count rows exist as a table of distinct rows only -- that table
-        x_src, vcol_l, coef_l = X[-1], batch.vcol, None
+        x_src, vcol_l, coef_l, cls_l = X[-1], batch.vcol, None, None
         if l == 1 and tab1 is not None:
             x_src, vcol_l, coef_l = table1, tab1[2], coef_c
+        if l == 2 and gather2:
+            # ... and likewise for the third layer: the table of X_2's distinct count rows (kept alive in table2 since the
+            # second layer), sources and own rows addressed by class; the table slots' sources stay global ids
+            x_src, vcol_l, cls_l = table2, tab2[3], tab2[0]
         for t, r0, r1, su in groups:
             if r1 <= r0:
                 continue
@@ -899,12 +917,12 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                     ops.shmp_layer(x_src, rep_uptr, rep_vcol, 0, table2.shape[0], S, 2, e["wt_mfma_x6"], e["b"], table2,
                                    ytab=ytab, ytab_row0=y_row0, pool=batch.layer2_rep_pool_index(),
                                    self_coef=coef_l, table_empty=tem)
-                    ops.table_rows_pool(table2, cls2, r1 - r0, None if last else xn, pool)
+                    ops.table_rows_pool(table2, cls2, r1 - r0, None if (last or gather2) else xn, pool)
                     continue
                 ops.shmp_layer(x_src, batch.vrowptr, vcol_c, r0, r1 - r0, S, 2,
                                e.get("wt_mfma_x6", e["wt_mfma"]) if SHMP_BF16X6 else e["wt_mfma"],
                                e["b"], None if (pool is not None and last) else xn, ytab=ytab,
-                               ytab_row0=y_row0, pool=pool, self_coef=coef_l, table_empty=tem)
+                               ytab_row0=y_row0, pool=pool, self_coef=coef_l, table_empty=tem, self_index=cls_l)
             else:
                 canonical, w16 = t == "canonical", isinstance(e.get("wt_x6"), ops.F16Planes)
                 once = canon_once and canonical and w16

@@ -419,7 +419,7 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
                ytab_row0: int = 0, out2: Optional[torch.Tensor] = None,
                pool: Optional[tuple] = None, row_absmax: Optional[torch.Tensor] = None,
                xself: Optional[torch.Tensor] = None, self_coef: Optional[torch.Tensor] = None,
-               table_empty: int = 0) -> Optional[torch.Tensor]:
+               table_empty: int = 0, self_index: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """Fused gather + folded Linear + relu for rows [row0, row0+num_rows) (see desco_hip.h).
     ``xself`` [num_rows, >= 64] (f16x3 form): the launch's own rows (self block) read from this view -- row i of the launch
     at xself[i - row0] -- instead of from ``x``; ``out`` may then be None when ``out2`` is given.
@@ -432,6 +432,9 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
     table of the layer input's distinct rows and ``vcol`` addresses its rows).
     ``table_empty`` (f16x3 form, two table slots): bit t set = the caller asserts that table slot t has no entry in the
     block; ``ytab`` may then be the other slot's block alone, [n_src, 64] (desco_shmp_layer_narrow_f16x3_f32: same kernel).
+    ``self_index`` int32 [>= row0 + num_rows] (pooled f16x3 launch on the narrow table): the launch's own row i is
+    ``x[self_index[i]]`` -- ``x`` is a table of the layer input's distinct rows that ``vcol`` and the rows themselves address
+    (desco_shmp_layer_selfidx_f16x3_f32); the caller has checked its range (``index_range_check``).
     ``pool`` = (pool_bits, pool_slot, pool_part): also leave the per-(tile, segment) partial sums of
     the produced rows in ``pool_part`` (fused global_add_pool, finished by ``pool_reduce``); ``out``
     may then be None (rows not stored)."""
@@ -439,7 +442,9 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
     x6 = f16 or wt.dtype == torch.int16
     if pool is not None:
         return _shmp_layer_pool(x, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma, wt, bias, out,
-                                ytab, ytab_row0, pool, xself, self_coef, table_empty)
+                                ytab, ytab_row0, pool, xself, self_coef, table_empty, self_index)
+    if self_index is not None:
+        raise ValueError("shmp_layer: self_index is implemented by the pooled f16x3 launch only")
     if table_empty and not f16:
         raise ValueError("shmp_layer: table_empty is implemented by the f16x3 form only")
     if self_coef is not None:
@@ -491,9 +496,11 @@ def shmp_layer(x: torch.Tensor, vrowptr: torch.Tensor, vcol: torch.Tensor, row0:
 
 
 def _shmp_layer_pool(x, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma, wt, bias, out, ytab,
-                     ytab_row0, pool, xself=None, self_coef=None, table_empty=0):
+                     ytab_row0, pool, xself=None, self_coef=None, table_empty=0, self_index=None):
     bits, slot, part = pool
     f16 = isinstance(wt, F16Planes)
+    if self_index is not None and not (f16 and table_empty):
+        raise ValueError("shmp_layer(pool=...): self_index with the f16x3 form on the narrow table (table_empty) only")
     if table_empty and not f16:
         raise ValueError("shmp_layer(pool=...): table_empty is implemented by the f16x3 form only")
     if xself is not None or (self_coef is not None and not f16):
@@ -507,11 +514,13 @@ def _shmp_layer_pool(x, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma,
     fl = 2.0 * num_rows * (slots_mfma + 1) * 64 * 64
     # x once (+ out once when stored) + indices + the partial rows (about one per 16 rows + one per segment)
     # (table form: the input rows are not read from HBM either -- a few thousand table rows stand for all of them)
-    nb = ((0.0 if self_coef is not None else 256.0) + (0.0 if out is None else 256.0)) * num_rows + 4.0 * (
+    nb = ((0.0 if (self_coef is not None or self_index is not None) else 256.0) + (0.0 if out is None else 256.0)) * num_rows + 4.0 * (
         num_rows * slots_stored + vcol.numel() * num_rows / max((vrowptr.numel() - 1) // max(slots_stored, 1), 1))
     name = shmp_kernel_name(slots_mfma + 1, st, True, f16)
     if self_coef is not None:           # (its own instantiation of the device kernel: listed on its own)
         name = name[:-1] + ",selfdeg>"
+    if self_index is not None:          # (likewise: the own rows gathered from the table x)
+        name = name[:-1] + ",selfidx>"
     with _Timed(name, fl, nb):
         head = (xp, ldx, _dev(vrowptr, "vrowptr", torch.int32), _dev(vcol, "vcol", torch.int32), row0, num_rows,
                 slots_stored, slots_mfma, st)
@@ -519,7 +528,13 @@ def _shmp_layer_pool(x, vrowptr, vcol, row0, num_rows, slots_stored, slots_mfma,
                 _dev(slot, "pool_slot", torch.int32), _dev(part, "pool_part"), _stream())
         if self_coef is not None:
             assert tuple(self_coef.shape) == (slots_stored + 1, 64) and self_coef.is_contiguous()
-        if table_empty:
+        if self_index is not None:
+            assert self_index.is_contiguous() and self_index.numel() >= row0 + num_rows
+            rc = L.desco_shmp_layer_selfidx_f16x3_f32(*head, _dev(wt.planes, "wt", torch.int16), _dev(wt.scale, "w_scale"),
+                                                      *tail[:6], None, 0, None, None, 0, *tail[6:9],
+                                                      _opt(self_coef, "self_coef"), int(table_empty),
+                                                      _dev(self_index, "self_index", torch.int32), tail[-1])
+        elif table_empty:
             rc = L.desco_shmp_layer_narrow_f16x3_f32(*head, _dev(wt.planes, "wt", torch.int16), _dev(wt.scale, "w_scale"),
                                                      *tail[:6], None, 0, None, None, 0, *tail[6:9],
                                                      _opt(self_coef, "self_coef"), int(table_empty), tail[-1])

@@ -639,6 +639,26 @@ int desco_shmp_layer_narrow_f16x3_f32(const float* x, int64_t ldx, const int32_t
                                       const int32_t* pool_slot, float* pool_part, const float* self_coef,
                                       int table_slots_empty, desco_stream_t stream);
 
+/* The pooled narrow launch above for a layer input that exists as a TABLE of its distinct rows only, the launch's own rows
+ * included: x = the table [U, 64], vcol = the column ids with the sources of the MFMA slots replaced by their table rows (the
+ * table slots' sources stay rows of ytab), and the launch's OWN row i (the self block's operand; i = the global row index that
+ * addresses vrowptr) is read at x + self_idx[i] * ldx.  The second layer's output on molecule batches is such a table
+ * (NeighborhoodBatch.layer2_table_index, gnn_model.SECOND_LAYER_GATHER): X_2's count rows are then never written or read.
+ * A kernel instantiation of its own (SELFIDX; the 16 ids of a tile travel with its row pointers); the arithmetic is the
+ * narrow launch's: results are bit-identical to that launch on the materialised rows x[self_idx[.]] with the original ids.
+ * Arguments: those of desco_shmp_layer_narrow_f16x3_f32 plus self_idx [row0 + num_rows] (device; every entry in [0, U): the
+ * caller checks, desco_index_range_check_i32).  DESCO_EINVAL, nothing launched: self_idx NULL; xself or self_coef given (one
+ * source of the own rows); a pooling pointer NULL (built pooled only; out may be NULL); ldx, ldy or (with out) ldo other than
+ * 64; slots_table != 2 or not exactly one table slot asserted empty. */
+int desco_shmp_layer_selfidx_f16x3_f32(const float* x, int64_t ldx, const int32_t* vrowptr, const int32_t* vcol,
+                                       int64_t row0, int64_t num_rows, int slots_stored, int slots_mfma,
+                                       int slots_table, const int16_t* wt_planes, const float* w_scale,
+                                       const float* bias, const float* ytab, int64_t ldy, int64_t ytab_row0,
+                                       float* out, int64_t ldo, float* out2, int64_t ldo2, float* row_absmax,
+                                       const float* xself, int64_t ldxs, const uint32_t* pool_bits,
+                                       const int32_t* pool_slot, float* pool_part, const float* self_coef,
+                                       int table_slots_empty, const int32_t* self_idx, desco_stream_t stream);
+
 int desco_pool_reduce_f32(const float* pool_part, const uint32_t* pool_bits, const int32_t* pool_slot,
                           const int32_t* seg_ptr, int64_t num_seg, const float* extra,
                           int64_t ld_extra, float* out, int64_t ldo, int tile_rows,

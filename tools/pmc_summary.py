@@ -20,9 +20,9 @@ def load(path, cname):
         if r["Counter_Name"] != cname:
             continue
         k = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("desco::", "").replace("gf16::", "").replace("small::", "").strip()
-        if k.startswith("shmp_layer16_kernel<"):           # <NW, KB, ST, LD64, POOL, F16[, SELFDEG]>
+        if k.startswith("shmp_layer16_kernel<"):           # <NW, KB, ST, LD64, POOL, F16[, SELFDEG, NARROW, SELFIDX]>
             a = [t.strip() for t in k[k.index("<") + 1:k.rindex(">")].split(",")]
-            k = f"shmp_layer16_kernel<{a[1]},{a[2]}{',f16x3' if len(a) > 5 and a[5] == 'true' else ''}{',selfdeg' if len(a) > 6 and a[6] == 'true' else ''}>"
+            k = f"shmp_layer16_kernel<{a[1]},{a[2]}{',f16x3' if len(a) > 5 and a[5] == 'true' else ''}{',selfdeg' if len(a) > 6 and a[6] == 'true' else ''}{',selfidx' if len(a) > 8 and a[8] == 'true' else ''}>"
         elif k.startswith("shmp_layer_f32_kernel<"):
             # template <KB, ST, LD64> -> the profiler key of desco_amd/ops.py
             a = [t.strip() for t in k[k.index("<") + 1:k.rindex(">")].split(",")]
