@@ -175,6 +175,192 @@ __global__ __launch_bounds__(GT_THREADS) void gt_count_kernel(GtArgs a) {
   }
 }
 
+// ---- orbit counts (graphlet degree vectors): C ABI desco_orbit_counts_dev ---------------------------------------------
+//   out[v][column] = #{connected subsets S containing v whose induced subgraph is a requested query, v in the position
+//   orbit that the column stands for}; orb[(GT_OFF[k] + mask) * 5 + i] = the column of subset position i, or -1.
+// The enumeration is the one above (same items, same lanes, same order); it is repeated here, not shared through a
+// template, so that the canonical kernel's code stays what it was.  What differs is the tally: a subset of k nodes
+// updates k rows.  Adds that share a destination are summed on chip first:
+//   * S[0] = v and S[1] = u0 belong to the whole wave: 2 x 4 banks of u32 columns per wave in LDS (bank = lane % 4, to
+//     spread lanes that hit one column), added to the two rows with one atomic per non-zero column when the wave ends.
+//     A u32 cell that wraps hands its carry (2^32) to the global cell at once, so no bound on an item's size is needed.
+//   * below that, a lane keeps ONE RUN per level in registers: while the subsets found by the loop that chooses node
+//     number NS have the same table row, they differ only in that last node, so a counter is bumped; the run goes out
+//     (S[0], S[1] to LDS, S[2..NS-1] by one global atomic each, adding the run length) when the table row changes or
+//     the loop ends.  Cliques, stars, paths and the sparse neighbourhoods of molecules give long runs.
+//   * the node chosen last changes with every subset: one global 64-bit atomic per subset.  The rate of scattered
+//     64-bit integer atomics on this chip has not been measured (the published figures are for float adds), so the
+//     cost of this part is known only from tools/bench_groundtruth_orbits.py.
+// Integer adds commute: the result equals the host's bit for bit and does not change from call to call.
+constexpr int GO_MAXC = 73, GO_CPAD = 80, GO_BANKS = 4, GO_WAVES = GT_THREADS / 64;
+
+struct GoArgs {
+  const int64_t* graph_ptr;
+  const int64_t* rowptr;
+  const int32_t* col;
+  const int32_t* node_graph;
+  const int64_t* bit_off;
+  const unsigned long long* bits;
+  const int16_t* orb;                // [1098][5]
+  int kmax, C;
+  int64_t num_nodes, num_entries;
+  unsigned long long* out;           // [N][C]
+};
+
+struct GoCtx {
+  GtCtx g;                           // (cls and cnt unused)
+  const int16_t* orb;
+  unsigned* tally;                   // this lane's bank of the wave's columns: [2][GO_CPAD]
+  unsigned long long* out0;          // out row of S[0]
+  unsigned long long* out1;          // out row of S[1]
+  unsigned long long* outg;          // out row of the graph's first node
+  int C;
+};
+
+struct GoRun {
+  int t;                             // table row of the run
+  unsigned long long n;              // subsets in it
+};
+
+// add n to the wave's column of S[j], j < 2
+__device__ __forceinline__ void go_wave_add(const GoCtx& c, int j, int column, unsigned long long n) {
+  unsigned long long* row = j ? c.out1 : c.out0;
+  if (n >> 32) atomicAdd(row + column, n & ~0xffffffffull);
+  const unsigned lo = (unsigned)n;
+  if (lo == 0) return;
+  const unsigned old = atomicAdd(c.tally + j * GO_CPAD + column, lo);
+  if (old > ~lo) atomicAdd(row + column, 1ull << 32);                      // the cell wrapped
+}
+
+template <int NS>
+__device__ __forceinline__ void go_flush(const GoCtx& c, const int (&S)[GT_KMAX], GoRun& run) {
+  if (run.n == 0) return;
+  const int16_t* row = c.orb + run.t * GT_KMAX;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    const int column = row[j];
+    if (j < 2) go_wave_add(c, j, column, run.n);
+    else atomicAdd(c.outg + (int64_t)S[j] * c.C + column, run.n);
+  }
+  run.n = 0;
+}
+
+template <int NS>
+__device__ void go_extend(const GoCtx& c, const int (&S)[GT_KMAX], unsigned mask, int ci0, int cp0);
+
+// gt_try with the orbit tally; `run` is the run of the loop that chooses node number NS
+template <int NS>
+__device__ __forceinline__ bool go_try(const GoCtx& c, const int (&S)[GT_KMAX], unsigned mask, int ci, int64_t r0,
+                                       int64_t e, GoRun& run) {
+  const int u = (int)(c.g.col[e] - c.g.base);
+  if (u >= c.g.lv) return false;
+  unsigned ab = 0;
+  bool in_s = false;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    in_s |= u == S[j];
+    ab |= gt_adj(c.g, S[j], u) << j;
+  }
+  if (in_s || (ab & ((1u << ci) - 1u))) return true;
+  const unsigned m2 = mask | (ab << (NS * (NS - 1) / 2));
+  const int t = GT_OFF_DEV[NS + 1] + (int)m2;
+  const int last = c.orb[t * GT_KMAX + NS];
+  if (last >= 0) {                                 // (a class is asked for with all its positions or with none)
+    atomicAdd(c.outg + (int64_t)u * c.C + last, 1ull);
+    if (run.n && run.t != t) go_flush<NS>(c, S, run);
+    run.t = t;
+    ++run.n;
+  }
+  if constexpr (NS + 1 < GT_KMAX) {
+    if (NS + 1 < c.g.kmax) {
+      int S2[GT_KMAX];
+#pragma unroll
+      for (int j = 0; j < GT_KMAX; ++j) S2[j] = j < NS ? S[j] : 0;
+      S2[NS] = u;
+      go_extend<NS + 1>(c, S2, m2, ci, (int)(e - r0) + 1);
+    }
+  }
+  return true;
+}
+
+template <int NS>
+__device__ void go_extend(const GoCtx& c, const int (&S)[GT_KMAX], unsigned mask, int ci0, int cp0) {
+  GoRun run{0, 0};
+#pragma unroll
+  for (int ci = 0; ci < NS; ++ci) {
+    if (ci < ci0) continue;
+    const int64_t r0 = c.g.rowptr[c.g.base + S[ci]], r1 = c.g.rowptr[c.g.base + S[ci] + 1];
+    for (int64_t e = r0 + (ci == ci0 ? cp0 : 0); e < r1; ++e)
+      if (!go_try<NS>(c, S, mask, ci, r0, e, run)) break;
+  }
+  go_flush<NS>(c, S, run);
+}
+
+__global__ __launch_bounds__(GT_THREADS) void go_count_kernel(GoArgs a) {
+  __shared__ unsigned tally[GO_WAVES * GO_BANKS * 2 * GO_CPAD];
+  const int tid = threadIdx.x, lane = tid & 63;
+  unsigned* wave_tally = tally + (tid >> 6) * (GO_BANKS * 2 * GO_CPAD);     // private to this wave: no block barrier
+  const int64_t e = (int64_t)blockIdx.x * GO_WAVES + (tid >> 6);            // one wave per entry
+  if (e >= a.num_entries) return;
+  const int64_t v = gt_row_of_entry(a.rowptr, a.num_nodes, e);
+  const int g = a.node_graph[v];
+  GoCtx c;
+  c.g.rowptr = a.rowptr;
+  c.g.col = a.col;
+  c.g.cls = nullptr;
+  c.g.cnt = nullptr;
+  c.g.base = a.graph_ptr[g];
+  c.g.words = (int)((a.graph_ptr[g + 1] - c.g.base + 63) >> 6);
+  c.g.bits = a.bits + a.bit_off[g];
+  c.g.lv = (int)(v - c.g.base);
+  c.g.kmax = a.kmax;
+  c.orb = a.orb;
+  c.C = a.C;
+  c.tally = wave_tally + (lane & (GO_BANKS - 1)) * (2 * GO_CPAD);
+  const int u0 = (int)(a.col[e] - c.g.base);
+  if (u0 >= c.g.lv) return;                        // (wave-uniform) the root is the maximum of its subsets
+  c.outg = a.out + c.g.base * a.C;
+  c.out0 = a.out + v * a.C;
+  c.out1 = c.outg + (int64_t)u0 * a.C;
+  for (int i = lane; i < GO_BANKS * 2 * GO_CPAD; i += 64) wave_tally[i] = 0;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int S[GT_KMAX] = {c.g.lv, u0, 0, 0, 0};
+  if (lane == 0) {
+    const int16_t* row = a.orb + (GT_OFF_DEV[2] + 1) * GT_KMAX;
+    if (row[0] >= 0) {
+      go_wave_add(c, 0, row[0], 1);
+      go_wave_add(c, 1, row[1], 1);
+    }
+  }
+  if (c.g.kmax > 2) {
+    const int64_t v0 = a.rowptr[v], v1 = a.rowptr[v + 1];
+    const int64_t w0 = a.rowptr[c.g.base + u0], w1 = a.rowptr[c.g.base + u0 + 1];
+    const int64_t rest = v1 - (e + 1), total = rest + (w1 - w0);
+    GoRun run{0, 0};                               // the lane's 3-node subsets: they share S[0] and S[1]
+    for (int64_t p = lane; p < total; p += 64) {
+      if (p < rest)
+        go_try<2>(c, S, 1u, 0, v0, e + 1 + p, run);
+      else
+        go_try<2>(c, S, 1u, 1, w0, w0 + (p - rest), run);
+    }
+    go_flush<2>(c, S, run);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (int column = lane; column < a.C; column += 64) {                    // contiguous cells of the two rows
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      unsigned long long n = 0;
+#pragma unroll
+      for (int b = 0; b < GO_BANKS; ++b) n += wave_tally[(b * 2 + j) * GO_CPAD + column];
+      if (n) atomicAdd((j ? c.out1 : c.out0) + column, n);
+    }
+  }
+}
+
 // NON-INDUCED counts of small queries from the census of ALL connected k-node classes (the enumerator above visits
 // every connected k-subset once, so the census costs what one induced column costs):
 //   out[v][q] (+)= sum_c counts[v][c] * m[c][q],   m[c][q] = occurrences of query q in class c (exact, int64).
@@ -315,6 +501,31 @@ extern "C" int desco_canonical_counts_dev(const int64_t* graph_ptr, int64_t num_
            cls, kmax, num_queries, num_nodes, num_entries, reinterpret_cast<unsigned long long*>(out)};
   hipLaunchKernelGGL(gt_count_kernel, dim3((unsigned)wblocks), dim3(GT_THREADS), 0, s, a);
   return launch_status("desco_canonical_counts_dev");
+}
+
+extern "C" int desco_orbit_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                      const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                      const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                      int64_t num_words, const int16_t* orbit_table, int kmax, int num_columns,
+                                      int64_t* out, desco_stream_t stream) {
+  if (num_nodes == 0 || num_columns == 0) return 0;
+  if (!graph_ptr || !rowptr || !node_graph || !bit_off || !bits || !orbit_table || !out || num_graphs < 0 ||
+      num_nodes < 0 || num_entries < 0 || num_words < 0 || kmax < 2 || kmax > GT_KMAX || num_columns < 0 ||
+      num_columns > GO_MAXC || (num_entries > 0 && !col))
+    return fail(DESCO_EINVAL, "desco_orbit_counts_dev: bad argument (queries of 2..5 nodes, at most 73 columns)");
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(out, 0, (size_t)num_nodes * num_columns * 8, s) != hipSuccess)
+    return launch_status("desco_orbit_counts_dev: memset");
+  const int64_t wblocks = (num_entries + GO_WAVES - 1) / GO_WAVES;
+  if (wblocks > INT32_MAX) return fail(DESCO_EINVAL, "desco_orbit_counts_dev: too many edges");
+  if (const int rc = gt_build_bitsets(graph_ptr, rowptr, col, node_graph, bit_off, bits, num_words, num_nodes,
+                                      num_entries, stream, "desco_orbit_counts_dev"))
+    return rc;
+  if (num_entries == 0) return 0;
+  GoArgs a{graph_ptr, rowptr, col, node_graph, bit_off, reinterpret_cast<const unsigned long long*>(bits),
+           orbit_table, kmax, num_columns, num_nodes, num_entries, reinterpret_cast<unsigned long long*>(out)};
+  hipLaunchKernelGGL(go_count_kernel, dim3((unsigned)wblocks), dim3(GT_THREADS), 0, s, a);
+  return launch_status("desco_orbit_counts_dev");
 }
 
 extern "C" int desco_canonical_noninduced_transform_dev(const int64_t* counts, int64_t ldc, const int64_t* m,

@@ -272,6 +272,239 @@ def _induced_host_int64(graphs: GraphSet, flat, num_threads: int) -> np.ndarray:
     return out
 
 
+# ---- orbit counts (graphlet degree vectors) ---------------------------------------------------------------------------
+# Definitions (include/desco_hip.h, "ORBIT COUNTS"):
+#   query: connected, loop-free, 2..5 nodes; an nx.Graph whose positions are list(q.nodes), or (n, edges)
+#   orbits of a query: the orbits of Aut(q) on its node positions, numbered in ascending order of their smallest member
+#   induced:      orbit[v][(q,o)] = #{S containing v : G[S] isomorphic to q by a map that takes v into orbit o}
+#   non-induced:  #{injective edge-preserving f : q -> G with v in f(orbit o)} / |Aut(q)|: copies of q (a copy being its
+#                 edge set) in which v plays role o
+#   columns: the queries in the given order and, inside a query, its orbits in order; queries=None means
+#            census_classes(2) + .. + census_classes(5): 30 classes, 1 + 3 + 11 + 58 = 73 columns.  The numbering is
+#            this project's own (it is not ORCA's).
+#   per graph, sum_v orbit[v][(q,o)] = |o| * sum_v canonical_counts[v][q] (both forms); the 2-node column is the degree;
+#   relabelling the nodes of G permutes the rows and changes nothing else.
+def _pair_bit(a, b):
+    return b * (b - 1) // 2 + a if a < b else a * (a - 1) // 2 + b
+
+
+@functools.lru_cache(maxsize=None)
+def _perms(k: int):
+    import itertools
+    return tuple(itertools.permutations(range(k)))
+
+
+def _relabelled_mask(edges, p) -> int:
+    m = 0
+    for a, b in edges:
+        m |= 1 << _pair_bit(p[a], p[b])
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def _orbit_structure(k: int, edges: tuple):
+    """(orbit index of every position, member positions of every orbit, canonical mask, a relabelling that gives it)
+    of the graph (k, edges); refuses nothing (the callers have checked the query)."""
+    mask = _relabelled_mask(edges, range(k))
+    low = list(range(k))
+    best, best_p = None, None
+    for p in _perms(k):
+        r = _relabelled_mask(edges, p)
+        if r == mask:
+            low = [min(x, y) for x, y in zip(low, p)]
+        if best is None or r < best:
+            best, best_p = r, p
+    firsts = sorted(set(low))
+    orbit_of = tuple(firsts.index(x) for x in low)
+    members = tuple(tuple(i for i in range(k) if orbit_of[i] == o) for o in range(len(firsts)))
+    return orbit_of, members, best, best_p
+
+
+def _orbit_queries(queries):
+    """The flattened, checked queries of an orbit call: [(k, edge tuple)]."""
+    if queries is None:
+        return [(k, tuple(e)) for k in (2, 3, 4, 5) for _, e in census_classes(k)]
+    flat = _flatten_queries(queries)[0]
+    if any(n < 2 or n > 5 for n, _ in flat):
+        raise RuntimeError("orbit counts take queries of 2..5 nodes")
+    if flat:
+        match_plan(flat)                # refuses disconnected queries and loops, naming the reason
+    return [(n, tuple((int(a), int(b)) for a, b in e)) for n, e in flat]
+
+
+def orbit_columns(queries=None):
+    """The columns of ``orbit_counts``: a list of (query index, orbit index, member positions).  ``queries=None``: the
+    30 connected graphs of 2..5 nodes in ``census_classes`` order, 73 columns."""
+    return [(qi, o, mem) for qi, (k, e) in enumerate(_orbit_queries(queries))
+            for o, mem in enumerate(_orbit_structure(k, e)[1])]
+
+
+@functools.lru_cache(maxsize=None)
+def _census_class_of_mask(k: int):
+    """canonical mask -> class index in census_classes(k)"""
+    return {_orbit_structure(k, tuple(e))[2]: ci for ci, (_, e) in enumerate(census_classes(k))}
+
+
+def _orbit_select(flat, induced):
+    """Every query is computed as its census class (so that duplicates and isomorphic queries cost nothing and the C
+    routines get pairwise non-isomorphic ones) and its columns are mapped back through the position relabelling.
+    Returns (reps, index, sizes, first, width): the class representatives handed to the enumerators (size by size, in
+    census order: the classes in use, or for the non-induced form the whole census of every size in use), the index of
+    every output column among the enumerators' columns, the sizes in use and, per size, the first of its columns and
+    their number."""
+    wanted = []                                      # per output column: (k, class, orbit of the class)
+    for k, e in flat:
+        _, members, canon, p = _orbit_structure(k, e)
+        ci = _census_class_of_mask(k)[canon]
+        rep_orbit_of, _, _, r = _orbit_structure(k, tuple(census_classes(k)[ci][1]))
+        r_inv = {x: i for i, x in enumerate(r)}      # query position a -> canonical p[a] -> class position r^-1(p[a])
+        wanted += [(k, ci, rep_orbit_of[r_inv[p[mem[0]]]]) for mem in members]
+    sizes = sorted({k for k, _, _ in wanted})
+    used = {(k, ci) for k, ci, _ in wanted}
+    reps, start, first, width, col = [], {}, {}, {}, 0
+    for k in sizes:
+        first[k] = col
+        for ci, (_, e) in enumerate(census_classes(k)):
+            if induced and (k, ci) not in used:
+                continue
+            reps.append((k, list(e)))
+            start[(k, ci)] = col
+            col += len(_orbit_structure(k, tuple(e))[1])
+        width[k] = col - first[k]
+    index = np.array([start[(k, ci)] + o for k, ci, o in wanted], dtype=np.int64)
+    return reps, index, sizes, first, width
+
+
+_orbit_transform = {}               # k -> int64 [columns of size k, columns of size k]: computed once per process
+
+
+def orbit_noninduced_matrix(k: int) -> np.ndarray:
+    """T_k, int64 [C_k, C_k] over the orbit columns of ``census_classes(k)``: T_k[(c,o')][(q,o)] = the copies of q in
+    the class representative c in which one fixed node of orbit o' has role o.  noninduced = induced @ T_k (a k-subset
+    whose induced subgraph is c, seen from a node of orbit o', holds that many copies of q with the node in role o).
+    By exhaustive enumeration of the k! maps of every pair of classes."""
+    if k not in _orbit_transform:
+        classes = [(tuple(e), _orbit_structure(k, tuple(e))) for _, e in census_classes(k)]
+        starts = np.concatenate([[0], np.cumsum([len(st[1]) for _, st in classes])])
+        T = np.zeros((starts[-1], starts[-1]), dtype=np.int64)
+        for qi, (qe, (q_orbit_of, _, _, _)) in enumerate(classes):
+            aut = sum(1 for p in _perms(k) if _relabelled_mask(qe, p) == _relabelled_mask(qe, range(k)))
+            for ci, (ce, (_, c_members, _, _)) in enumerate(classes):
+                cmask = _relabelled_mask(ce, range(k))
+                hits = np.zeros((k, len(set(q_orbit_of))), dtype=np.int64)        # [node of c][role]
+                for f in _perms(k):
+                    if _relabelled_mask(qe, f) & ~cmask == 0:
+                        for a in range(k):
+                            hits[f[a], q_orbit_of[a]] += 1
+                for o2, mem in enumerate(c_members):
+                    assert (hits[list(mem)] == hits[mem[0]]).all() and (hits[mem[0]] % aut == 0).all()
+                    T[starts[ci] + o2, starts[qi]:starts[qi + 1]] = hits[mem[0]] // aut
+        _orbit_transform[k] = T
+    return _orbit_transform[k]
+
+
+def _orbit_table(reps):
+    _, q_nodes, q_edge_ptr, q_edges = _flatten_queries(reps)
+    table = np.empty((1098, 5), dtype=np.int16)
+    ncol, kmax = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.lib().desco_orbit_table(q_nodes.ctypes.data, q_edge_ptr.ctypes.data,
+                                            q_edges.ctypes.data if len(q_edges) else None, len(q_nodes),
+                                            table.ctypes.data, ctypes.byref(ncol), ctypes.byref(kmax)),
+               "desco_orbit_table")
+    return table, int(ncol.value), int(kmax.value)
+
+
+def _orbit_device_raw(graphs: GraphSet, reps, dev) -> torch.Tensor:
+    """desco_orbit_counts_dev on pairwise non-isomorphic ``reps``: int64 [N, columns of reps] on ``dev``."""
+    table, C, kmax = _orbit_table(reps)
+    L = _lib.lib()
+    n = np.diff(graphs.graph_ptr).astype(np.int64)
+    bit_off = np.concatenate([[0], np.cumsum(n * ((n + 63) // 64))]).astype(np.int64)
+    N, G = graphs.num_nodes, graphs.num_graphs
+    out = torch.empty((N, C), dtype=torch.int64, device=dev)
+    if N == 0 or C == 0:
+        return out.zero_()
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
+    graph_ptr, rowptr = t(graphs.graph_ptr, np.int64), t(graphs.rowptr, np.int64)
+    col, node_graph = t(graphs.col, np.int32), t(graphs.node_graph_ids(), np.int32)
+    bit_off_d, table_d = t(bit_off[:-1] if G else bit_off, np.int64), t(table, np.int16)
+    bits = torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.desco_orbit_counts_dev(
+            graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), int(graphs.col.shape[0]),
+            col.data_ptr() if col.numel() else None, node_graph.data_ptr(), bit_off_d.data_ptr(),
+            bits.data_ptr(), int(bit_off[-1]), table_d.data_ptr(), kmax, C, out.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream), "desco_orbit_counts_dev")
+    return out
+
+
+def _orbit_host_raw(graphs: GraphSet, reps, num_threads: int) -> np.ndarray:
+    """desco_orbit_counts on pairwise non-isomorphic ``reps``: int64 [N, columns of reps]."""
+    _, q_nodes, q_edge_ptr, q_edges = _flatten_queries(reps)
+    out = np.zeros((graphs.num_nodes, _orbit_table(reps)[1]), dtype=np.int64)
+    _lib.check(_lib.lib().desco_orbit_counts(graphs.graph_ptr.ctypes.data, graphs.num_graphs,
+                                             graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
+                                             q_nodes.ctypes.data, q_edge_ptr.ctypes.data,
+                                             q_edges.ctypes.data if len(q_edges) else None, len(reps),
+                                             num_threads, out.ctypes.data), "desco_orbit_counts")
+    return out
+
+
+def orbit_counts_device(graphs: GraphSet, queries=None, device="cuda", induced: bool = True) -> torch.Tensor:
+    """Exact per-node orbit counts (definitions above) on the MI355X (csrc/groundtruth_dev.hip, go_count_kernel):
+    int64 [num_nodes, len(orbit_columns(queries))] on ``device``.  Duplicate and isomorphic queries are accepted: every
+    class is enumerated once.  ``induced=False``: the orbit census of the queries' sizes by the same kernel, then the
+    exact int64 transform ``orbit_noninduced_matrix`` with ``desco_canonical_noninduced_transform_dev`` (source columns
+    in chunks of 32), without a round trip."""
+    flat = _orbit_queries(queries)
+    dev = torch.device(device)
+    if not flat:
+        return torch.zeros((graphs.num_nodes, 0), dtype=torch.int64, device=dev)
+    reps, index, sizes, first, width = _orbit_select(flat, induced)
+    raw = _orbit_device_raw(graphs, reps, dev)
+    if not induced and graphs.num_nodes:
+        full = torch.zeros_like(raw)
+        for k in sizes:
+            T = orbit_noninduced_matrix(k)
+            src, dst = raw[:, first[k]:first[k] + width[k]], full[:, first[k]:first[k] + width[k]]
+            for c0 in range(0, width[k], 32):
+                _transform_device(src[:, c0:c0 + 32], T[c0:c0 + 32], dst, c0 > 0)
+        raw = full
+    return raw.index_select(1, torch.from_numpy(index).to(dev))
+
+
+def orbit_counts(graphs: GraphSet, queries=None, num_threads: int = 0, backend: str = "auto",
+                 induced: bool = True, per_query: bool = False) -> torch.Tensor:
+    """Exact per-node orbit counts -- the graphlet degree vector when ``queries`` is None (73 columns) -- as a double
+    [num_nodes, len(orbit_columns(queries))] tensor on the CPU (definitions above; ``canonical_counts`` returns doubles
+    too).  ``backend``: "host" (OpenMP over graphs, ``num_threads`` threads), "device" (``orbit_counts_device``) or
+    "auto": the device when a GPU is present and the adjacency bitsets fit ``_DEVICE_BITSET_LIMIT_WORDS``.
+    ``induced=False``: the non-induced form.  ``per_query=True``: the orbits of every query summed, [num_nodes,
+    num_queries]: the occurrences of the query that contain v.  Raises RuntimeError for queries outside 2..5 nodes and
+    for disconnected or looped ones."""
+    if backend not in ("auto", "host", "device"):
+        raise ValueError(f"unknown backend {backend!r}")
+    flat = _orbit_queries(queries)
+    if backend == "auto":       # _device_eligible's conditions: a GPU and bitsets within the limit (the sizes are checked)
+        backend = "device" if flat and _device_eligible(graphs, np.array([2], dtype=np.int32)) else "host"
+    if backend == "device":
+        out = orbit_counts_device(graphs, flat, induced=induced).cpu()
+    elif not flat:
+        out = torch.zeros((graphs.num_nodes, 0), dtype=torch.int64)
+    else:
+        reps, index, sizes, first, width = _orbit_select(flat, induced)
+        raw = _orbit_host_raw(graphs, reps, num_threads)
+        if not induced:
+            raw = np.concatenate([raw[:, first[k]:first[k] + width[k]] @ orbit_noninduced_matrix(k) for k in sizes],
+                                 axis=1)
+        out = torch.from_numpy(np.ascontiguousarray(raw[:, index]))
+    if per_query:
+        owner = torch.tensor([qi for qi, _, _ in orbit_columns(flat)], dtype=torch.long)
+        summed = torch.zeros((out.shape[0], len(flat)), dtype=torch.int64)
+        out = summed.index_add_(1, owner, out)
+    return out.double()
+
+
 # ---- large queries: the pattern-guided matcher ------------------------------------------------------------------------
 # One device launch covers the CSR entries of a slice; a slice holds so many entries that entries x anchors (= waves)
 # stays at this bound, so that no single kernel carries the whole of an unbounded search

@@ -245,6 +245,7 @@ class Workload:
         self.node_feat_key = "feat"
         self.queries, self.query_ids = [], []
         self.canonical_count_truth = torch.tensor([[]])
+        self.orbit_count_truth: Optional[torch.Tensor] = None
         self.neighborhood_dataset: Optional[NeighborhoodDataset] = None
         self.gossip_dataset: Optional[GossipDataset] = None
         self.graphlet_count_truth: Optional[torch.Tensor] = None
@@ -305,6 +306,38 @@ class Workload:
         self.query_ids = query_ids
         if save_to_file and self.root:
             path = self._truth_path(query_ids, queries, induced)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            torch.save(truth, path)
+        return truth
+
+    # ---- orbit counts (graphlet degree vectors): node-level truth that does not depend on the node numbering ----------
+    def _orbit_truth_path(self, queries=None, induced=True):
+        """<root>/OrbitCountTruth/orbit_columns_<C>_query_num_<Q>_query_len_sum_<S>[_noninduced].pt (the suffix rule of
+        ``_truth_path``); ``queries=None`` is the 73-column census of 2..5 nodes."""
+        from .groundtruth import _orbit_queries, orbit_columns
+        flat = _orbit_queries(queries)
+        name = "orbit_columns_{:d}_query_num_{:d}_query_len_sum_{:d}{}.pt".format(
+            len(orbit_columns(flat)), len(flat), sum(n for n, _ in flat), "" if induced else "_noninduced")
+        return os.path.join(self.root, "OrbitCountTruth", name)
+
+    def exist_orbit_groundtruth(self, queries=None, induced=True) -> bool:
+        return os.path.exists(self._orbit_truth_path(queries, induced))
+
+    def load_orbit_groundtruth(self, queries=None, induced=True) -> torch.Tensor:
+        self.orbit_count_truth = torch.load(self._orbit_truth_path(queries, induced))
+        return self.orbit_count_truth
+
+    def compute_orbit_groundtruth(self, queries=None, induced=True, save_to_file=True, num_workers=-1) -> torch.Tensor:
+        """Exact per-node orbit counts of the dataset (``groundtruth.orbit_counts``: [N, C] doubles, the 73-column
+        graphlet degree vector when ``queries`` is None), kept in ``self.orbit_count_truth`` and cached under
+        ``<root>/OrbitCountTruth/``.  Unlabelled only."""
+        if self.use_node_feat:
+            raise NotImplementedError("orbit counts of labelled queries (--use_node_feature) are not implemented")
+        from .groundtruth import orbit_counts
+        truth = orbit_counts(self.dataset, queries, num_threads=max(num_workers, 0), induced=induced)
+        self.orbit_count_truth = truth
+        if save_to_file and self.root:
+            path = self._orbit_truth_path(queries, induced)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             torch.save(truth, path)
         return truth

@@ -240,6 +240,37 @@ int desco_canonical_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int
                                int64_t num_words, const int16_t* cls, int kmax, int num_queries,
                                int64_t* out, desco_stream_t stream);
 
+/* ORBIT COUNTS (graphlet degree vectors): how many occurrences of a query contain node v, with v in a given position
+ * of the query -- unlike the canonical counts above they do not depend on the node numbering.
+ *   Query: connected, loop-free, 2..5 nodes, given as for desco_canonical_counts; pairwise non-isomorphic.
+ *   Orbits of a query: the orbits of Aut(q) on its node positions, numbered 0, 1, .. in ascending order of their
+ *     smallest member position.
+ *   out[v][(q,o)] = #{S containing v : G[S] isomorphic to q, and an isomorphism G[S] -> q maps v into orbit o} (well
+ *     defined: two such isomorphisms differ by an automorphism).
+ *   Columns: the queries in the given order and, inside a query, its orbits in order.  The 30 connected graphs of
+ *     2..5 nodes have 1 + 3 + 11 + 58 = 73 orbits.  (The numbering is this library's own.)
+ *   Per graph, sum_v out[v][(q,o)] = |o| * sum_v canonical count[v][q]; the column of the 2-node query is the degree.
+ * HOST helper desco_orbit_table: table[1098][5] = for k = 2..5 nodes and every adjacency mask on k nodes (the
+ *   convention and the offsets 0, 2, 10, 74 of desco_canonical_class_table) the column of every position i < k of the
+ *   subset, or -1 when the mask's class was not asked for; *num_columns, *kmax = the largest query.  DESCO_EINVAL
+ *   naming "2..5 nodes", "connected" or "isomorphic" for queries it does not take.
+ * HOST desco_orbit_counts: the arguments of desco_canonical_counts; out: int64 [num_nodes][num_columns] (the caller
+ *   gets num_columns from desco_orbit_table), zeroed and filled.  OpenMP over graphs; the result does not depend on
+ *   num_threads.
+ * DEVICE desco_orbit_counts_dev (csrc/groundtruth_dev.hip): the arguments of desco_canonical_counts_dev with the
+ *   orbit table (device pointer) in place of cls and num_columns (<= 73) in place of num_queries.  out: int64
+ *   [N][num_columns], zeroed and filled by the call, equal to the host's bit for bit.  Enqueues on `stream`, does not
+ *   allocate or synchronise. */
+int desco_orbit_table(const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges, int num_queries,
+                      int16_t* table, int* num_columns, int* kmax);
+int desco_orbit_counts(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr, const int32_t* col,
+                       const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges, int num_queries,
+                       int num_threads, int64_t* out);
+int desco_orbit_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes, const int64_t* rowptr,
+                           int64_t num_entries, const int32_t* col, const int32_t* node_graph, const int64_t* bit_off,
+                           uint64_t* bits, int64_t num_words, const int16_t* orbit_table, int kmax, int num_columns,
+                           int64_t* out, desco_stream_t stream);
+
 /* LABELLED queries (--use_node_feature): out[v][c] = #{S : max(S) = v, G[S] connected, and G[S] with its node
  * labels isomorphic to the labelled queries of class c} -- the reference's VF2 with node_match on the feature
  * (workload.py:327-348) divided by the labelled symmetry factor (data.py:61-68).  Node and query labels are integer

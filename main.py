@@ -62,6 +62,9 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
     assert args_neighborhood.use_hetero if args_neighborhood.use_tconv else True
     depth, ncpu = args_neighborhood.depth, args_opt.num_cpu
     induced = not getattr(args_opt, "noninduced", False)          # --noninduced: all three splits regress that truth
+    if getattr(args_opt, "orbit_truth", False) and node_feat_len != -1:
+        raise NotImplementedError("--orbit_truth with --use_node_feature: orbit counts of labelled queries are not "
+                                  "implemented")
 
     devices = args_opt.gpu if isinstance(args_opt.gpu, list) else [args_opt.gpu]
     # len(devices) > 1: one process per GPU (started by __main__ below or by torch.distributed.run);
@@ -207,6 +210,16 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
         os.path.join(output_dir, f"neighborhood_node_{ds}_index.csv"))
     with open(os.path.join(output_dir, f"test_nxgraph_{ds}.pk"), "wb") as f:
         pickle.dump(test_w.to_networkx(), f)
+    if getattr(args_opt, "orbit_truth", False):
+        # --orbit_truth: the exact graphlet degree vector of the test set beside the predictions (73 columns, the
+        # orbits of the connected graphs of 2..5 nodes; groundtruth.orbit_counts)
+        from desco_amd.groundtruth import orbit_columns
+        if test_w.exist_orbit_groundtruth(induced=induced):
+            gdv = test_w.load_orbit_groundtruth(induced=induced)
+        else:
+            gdv = test_w.compute_orbit_groundtruth(induced=induced, num_workers=ncpu)
+        pd.DataFrame(gdv.numpy(), columns=[f"({q},{o})" for q, o, _ in orbit_columns()]).to_csv(
+            os.path.join(output_dir, f"orbit_node_{ds}.csv"))
 
     sizes = sorted({len(q) for q in nx_queries})
     groupby = [[i for i, q in enumerate(nx_queries) if len(q) == s] for s in sizes]
@@ -247,11 +260,17 @@ def parse_args(argv=None):
     parser.add_argument("--noninduced", action="store_true",
                         help="train and test on NON-INDUCED ground truth: occurrences that only have to contain the "
                              "query's edges (cached beside the induced truth with a _noninduced suffix)")
+    # (no attribute unless given: without the flag the printed and the written configuration stay what they were)
+    parser.add_argument("--orbit_truth", action="store_true", default=argparse.SUPPRESS,
+                        help="also write the exact per-node orbit counts (73-column graphlet degree vector) of the test "
+                             "set to <output_dir>/orbit_node_<test_dataset>.csv")
     args = parser.parse_args(argv)
     args_neighborhood, args_gossip, args_opt = split_namespaces(args)
     args_opt.precision = args.precision          # this build's flags (not in the reference's groups)
     args_opt.graph_capture = args.graph_capture
     args_opt.noninduced = args.noninduced
+    if getattr(args, "orbit_truth", False):
+        args_opt.orbit_truth = True
     return args, args_neighborhood, args_gossip, args_opt
 
 
