@@ -6,24 +6,23 @@
 // query's symmetry factor (data.py:61-67).  Written from that definition with the ESU enumeration
 // (every connected node subset of size <= kmax is visited exactly once, rooted at its maximum id)
 // and an isomorphism-class lookup over induced adjacency bitmasks (<= 6 nodes -> <= 15 bits).
+// The walk is groundtruth_esu.hpp's; this file holds its canonical and orbit visitors and the class / orbit tables.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <new>
 #include <vector>
 
-#ifdef _OPENMP
-#include <omp.h>
-#endif
-
-#include "../../include/desco_hip.h"
-#include "common_host.hpp"
+#include "groundtruth_esu.hpp"
 
 namespace {
 
-constexpr int KMAX = 6;
-
-inline int pair_bit(int a, int b) { return b * (b - 1) / 2 + a; }   // a < b
+using desco::ESU_ENTRIES;
+using desco::ESU_OFF;
+using desco::GraphBits;
+using desco::pair_bit;
+constexpr int KMAX = desco::ESU_KMAX_HOST;
+constexpr int ORB_KMAX = desco::ESU_KMAX_DEV;     // orbit counts and the device class table: queries of 2..5 nodes
 
 // canonical form of every adjacency mask on k nodes: minimum over all relabelings
 std::vector<uint16_t> canon_table(int k) {
@@ -51,23 +50,6 @@ std::vector<uint16_t> canon_table(int k) {
   return tab;
 }
 
-struct Ctx {
-  int64_t base, n;
-  const int64_t* rowptr;
-  const int32_t* col;
-  int kmax;
-  const std::vector<uint16_t>* canon;               // [k] -> table
-  const std::vector<std::vector<int>>* cls2q;       // [k][canonical mask] -> query ids (flattened below)
-  const std::vector<int32_t>* qlist;                 // per k: offsets into qids
-  std::vector<uint64_t> bits;                        // adjacency bitset rows (n x words)
-  int words;
-  std::vector<uint8_t> seen;
-  int64_t* out;
-  int num_q;
-  const int16_t* orbit = nullptr;                    // orbit table (desco_orbit_table) or null: canonical counts
-  bool adj(int a, int b) const { return bits[(size_t)a * words + (b >> 6)] >> (b & 63) & 1; }
-};
-
 struct Classifier {
   // for size k: map canonical mask -> list of query indices
   std::vector<std::vector<int>> by_mask[KMAX + 1];
@@ -75,101 +57,42 @@ struct Classifier {
   bool used[KMAX + 1] = {false};
 };
 
-// class-table offsets of the device enumerator: the masks of k nodes start at ORB_OFF[k] (k = 2..5)
-constexpr int ORB_KMAX = 5, ORB_ENTRIES = 1098;
-constexpr int ORB_OFF[ORB_KMAX + 2] = {0, 0, 0, 2, 10, 74, ORB_ENTRIES};
+// canonical counts: the subset counts for its root v, in the columns of the queries of its class
+struct CanonicalVisitor {
+  const Classifier& cl;
+  int64_t* out;
+  int num_q;
+  void operator()(const GraphBits& g, const int* sub, int k, int v) const {
+    if (!cl.used[k]) return;
+    for (int q : cl.by_mask[k][cl.canon[k][g.mask_of(sub, k)]]) out[(g.base + v) * num_q + q] += 1;
+  }
+};
 
-void classify(const Ctx& c, const Classifier& cl, const int* sub, int k, int v) {
-  if (!c.orbit && !cl.used[k]) return;
-  uint32_t m = 0;
-  for (int b = 1; b < k; ++b)
-    for (int a = 0; a < b; ++a)
-      if (c.adj(sub[a], sub[b])) m |= 1u << pair_bit(a, b);
-  if (c.orbit) {                                     // orbit counts: every member, by the column of its position
-    if (k < 2) return;
-    const int16_t* row = c.orbit + (size_t)(ORB_OFF[k] + m) * ORB_KMAX;
+// orbit counts: the subset counts for every member, in the column of the member's position (desco_orbit_table)
+struct OrbitVisitor {
+  const int16_t* table;
+  int64_t* out;
+  int num_cols;
+  void operator()(const GraphBits& g, const int* sub, int k, int) const {
+    const int16_t* row = table + (size_t)(ESU_OFF[k] + g.mask_of(sub, k)) * ORB_KMAX;
     if (row[0] < 0) return;
-    for (int i = 0; i < k; ++i) c.out[(c.base + sub[i]) * c.num_q + row[i]] += 1;
-    return;
+    for (int i = 0; i < k; ++i) out[(g.base + sub[i]) * num_cols + row[i]] += 1;
   }
-  const auto& lst = cl.by_mask[k][cl.canon[k][m]];
-  for (int q : lst) c.out[(c.base + v) * c.num_q + q] += 1;
-}
+};
 
-void extend(Ctx& c, const Classifier& cl, int* sub, int nsub, std::vector<int>& ext, int v) {
-  classify(c, cl, sub, nsub, v);
-  if (nsub == c.kmax) return;
-  std::vector<int> newly, ext2;
-  while (!ext.empty()) {
-    const int w = ext.back();
-    ext.pop_back();
-    newly.clear();
-    const int64_t gw = c.base + w;
-    for (int64_t e = c.rowptr[gw]; e < c.rowptr[gw + 1]; ++e) {
-      const int u = (int)(c.col[e] - c.base);
-      if (u >= v) break;                       // rows sorted ascending; only ids below the root
-      if (!c.seen[u]) {
-        c.seen[u] = 1;
-        newly.push_back(u);
-      }
-    }
-    ext2 = ext;
-    ext2.insert(ext2.end(), newly.begin(), newly.end());
-    sub[nsub] = w;
-    extend(c, cl, sub, nsub + 1, ext2, v);
-    for (int u : newly) c.seen[u] = 0;
-  }
-}
-
-// ESU over every graph (OpenMP over graphs: a graph's rows are written by one thread only, so the result does not
-// depend on the number of threads).  `orbit` null: canonical counts through `cl`; else orbit counts through the table.
-void enumerate_graphs(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr, const int32_t* col,
-                      const Classifier& cl, const int16_t* orbit, int kmax, int num_cols, int num_threads,
-                      int64_t* out) {
-#ifdef _OPENMP
-  const int nt = num_threads > 0 ? num_threads : omp_get_max_threads();
-#else
-  const int nt = 1;
-  (void)num_threads;
-#endif
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
-  for (int64_t g = 0; g < num_graphs; ++g) {
-    Ctx c;
-    c.base = graph_ptr[g];
-    c.n = graph_ptr[g + 1] - c.base;
-    c.rowptr = rowptr;
-    c.col = col;
-    c.kmax = kmax;
-    c.out = out;
-    c.num_q = num_cols;
-    c.orbit = orbit;
-    c.words = (int)((c.n + 63) / 64);
-    c.bits.assign((size_t)c.n * c.words, 0);
-    for (int64_t u = 0; u < c.n; ++u)
-      for (int64_t e = rowptr[c.base + u]; e < rowptr[c.base + u + 1]; ++e) {
-        const int w = (int)(col[e] - c.base);
-        c.bits[(size_t)u * c.words + (w >> 6)] |= (uint64_t)1 << (w & 63);
-      }
-    c.seen.assign((size_t)c.n, 0);
-    int sub[KMAX];
-    std::vector<int> ext;
-    for (int v = 0; v < (int)c.n; ++v) {
-      ext.clear();
-      c.seen[v] = 1;
-      const int64_t gv = c.base + v;
-      for (int64_t e = rowptr[gv]; e < rowptr[gv + 1]; ++e) {
-        const int u = (int)(col[e] - c.base);
-        if (u >= v) break;
-        c.seen[u] = 1;
-        ext.push_back(u);
-      }
-      std::vector<int> marked = ext;
-      sub[0] = v;
-      extend(c, cl, sub, 1, ext, v);
-      for (int u : marked) c.seen[u] = 0;
-      c.seen[v] = 0;
-    }
-  }
+// the mask of every relabeling p of the k-node mask m (position a becomes position p[a]), in std::next_permutation
+// order from the identity: f(image, p)
+template <class F>
+void for_each_relabeling(int k, uint32_t m, F f) {
+  int perm[KMAX];
+  for (int i = 0; i < k; ++i) perm[i] = i;
+  do {
+    uint32_t r = 0;
+    for (int b = 1; b < k; ++b)
+      for (int a = 0; a < b; ++a)
+        if (m >> pair_bit(a, b) & 1) r |= 1u << pair_bit(std::min(perm[a], perm[b]), std::max(perm[a], perm[b]));
+    f(r, perm);
+  } while (std::next_permutation(perm, perm + k));
 }
 
 }  // namespace
@@ -195,23 +118,46 @@ extern "C" int desco_canonical_counts(const int64_t* graph_ptr, int64_t num_grap
         cl.by_mask[k].assign((size_t)1 << (k * (k - 1) / 2), {});
       }
       uint32_t m = 0;
-      for (int e = q_edge_ptr[q]; e < q_edge_ptr[q + 1]; ++e) {
-        int a = q_edges[2 * e], b = q_edges[2 * e + 1];
-        if (a == b || a < 0 || b < 0 || a >= k || b >= k)
-          return desco::fail(DESCO_EINVAL, "desco_canonical_counts: bad query edge");
-        if (a > b) std::swap(a, b);
-        m |= 1u << pair_bit(a, b);
-      }
+      if (const int rc = desco::query_mask("desco_canonical_counts", q_edge_ptr, q_edges, q, k, &m)) return rc;
       cl.by_mask[k][cl.canon[k][m]].push_back(q);
     }
     const int64_t total = graph_ptr[num_graphs];
     std::memset(out, 0, sizeof(int64_t) * (size_t)total * (size_t)num_queries);
     if (num_queries == 0) return 0;
-    enumerate_graphs(graph_ptr, num_graphs, rowptr, col, cl, nullptr, kmax, num_queries, num_threads, out);
+    if (!desco::esu_enumerate_graphs(graph_ptr, num_graphs, rowptr, col, kmax, num_threads,
+                                     [&] { return CanonicalVisitor{cl, out, num_queries}; }))
+      return desco::fail(DESCO_ENOMEM, "desco_canonical_counts: out of memory");
     return 0;
   } catch (const std::bad_alloc&) {
     return desco::fail(DESCO_ENOMEM, "desco_canonical_counts: out of memory");
   }
+}
+
+// HOST helper: the class table the device kernel (groundtruth_dev.hip, gt_count_kernel) reads.
+extern "C" int desco_canonical_class_table(const int32_t* q_nodes, const int32_t* q_edge_ptr,
+                                           const int32_t* q_edges, int num_queries, int16_t* table,
+                                           int* kmax_out) {
+  if (!q_nodes || !q_edge_ptr || !table || !kmax_out || num_queries < 0 || num_queries > 32)
+    return desco::fail(DESCO_EINVAL, "desco_canonical_class_table: bad argument (at most 32 queries)");
+  for (int i = 0; i < ESU_ENTRIES; ++i) table[i] = -1;
+  int kmax = 0;
+  for (int q = 0; q < num_queries; ++q) {
+    const int k = q_nodes[q];
+    if (k < 2 || k > ORB_KMAX)
+      return desco::fail(DESCO_EINVAL, "desco_canonical_class_table: the device path takes queries of 2..5 nodes");
+    kmax = std::max(kmax, k);
+    uint32_t m = 0;
+    if (const int rc = desco::query_mask("desco_canonical_class_table", q_edge_ptr, q_edges, q, k, &m)) return rc;
+    bool clash = false;                              // every relabeling of the query is a mask of its class
+    for_each_relabeling(k, m, [&](uint32_t r, const int*) {
+      int16_t& slot = table[ESU_OFF[k] + r];
+      clash |= slot >= 0 && slot != q;
+      slot = (int16_t)q;
+    });
+    if (clash) return desco::fail(DESCO_EINVAL, "desco_canonical_class_table: two queries are isomorphic");
+  }
+  *kmax_out = kmax;
+  return 0;
 }
 
 // ---- orbit counts (graphlet degree vectors) ---------------------------------------------------------------------------
@@ -225,22 +171,16 @@ extern "C" int desco_orbit_table(const int32_t* q_nodes, const int32_t* q_edge_p
                                  int num_queries, int16_t* table, int* num_columns, int* kmax_out) {
   if (!q_nodes || !q_edge_ptr || !table || !num_columns || !kmax_out || num_queries < 0)
     return desco::fail(DESCO_EINVAL, "desco_orbit_table: bad argument");
-  for (int i = 0; i < ORB_ENTRIES * ORB_KMAX; ++i) table[i] = -1;
+  for (int i = 0; i < ESU_ENTRIES * ORB_KMAX; ++i) table[i] = -1;
   int kmax = 0, cols = 0;
-  std::vector<int16_t> owner(ORB_ENTRIES, -1);
+  std::vector<int16_t> owner(ESU_ENTRIES, -1);
   for (int q = 0; q < num_queries; ++q) {
     const int k = q_nodes[q];
     if (k < 2 || k > ORB_KMAX) return desco::fail(DESCO_EINVAL, "desco_orbit_table: orbit counts take queries of 2..5 nodes");
     if (q >= 32767) return desco::fail(DESCO_EINVAL, "desco_orbit_table: too many queries");
     kmax = std::max(kmax, k);
     uint32_t m = 0;
-    for (int e = q_edge_ptr[q]; e < q_edge_ptr[q + 1]; ++e) {
-      int a = q_edges[2 * e], b = q_edges[2 * e + 1];
-      if (a == b || a < 0 || b < 0 || a >= k || b >= k)
-        return desco::fail(DESCO_EINVAL, "desco_orbit_table: bad query edge");
-      if (a > b) std::swap(a, b);
-      m |= 1u << pair_bit(a, b);
-    }
+    if (const int rc = desco::query_mask("desco_orbit_table", q_edge_ptr, q_edges, q, k, &m)) return rc;
     uint32_t reach = 1;                              // positions reachable from position 0
     for (int it = 0; it < k; ++it)
       for (int b = 1; b < k; ++b)
@@ -248,27 +188,23 @@ extern "C" int desco_orbit_table(const int32_t* q_nodes, const int32_t* q_edge_p
           if ((m >> pair_bit(a, b) & 1) && ((reach >> a | reach >> b) & 1)) reach |= 1u << a | 1u << b;
     if (reach != (1u << k) - 1) return desco::fail(DESCO_EINVAL, "desco_orbit_table: a query is not connected");
     // every relabeling p of the query (position a becomes subset position p[a]); those that keep the mask are Aut(q)
-    int perm[ORB_KMAX], orbit_min[ORB_KMAX];
-    for (int i = 0; i < k; ++i) perm[i] = orbit_min[i] = i;
+    int orbit_min[ORB_KMAX];
+    for (int i = 0; i < k; ++i) orbit_min[i] = i;
     std::vector<uint32_t> images;
     std::vector<int> perms;
-    do {
-      uint32_t r = 0;
-      for (int b = 1; b < k; ++b)
-        for (int a = 0; a < b; ++a)
-          if (m >> pair_bit(a, b) & 1) r |= 1u << pair_bit(std::min(perm[a], perm[b]), std::max(perm[a], perm[b]));
+    for_each_relabeling(k, m, [&](uint32_t r, const int* perm) {
       images.push_back(r);
       perms.insert(perms.end(), perm, perm + k);
       if (r == m)
         for (int i = 0; i < k; ++i) orbit_min[i] = std::min(orbit_min[i], perm[i]);   // (Aut is a group: min is exact)
-    } while (std::next_permutation(perm, perm + k));
+    });
     int orbit_of[ORB_KMAX], n_orb = 0;               // numbered in ascending order of the smallest member
     for (int i = 0; i < k; ++i)
       if (orbit_min[i] == i) orbit_of[i] = n_orb++;
     for (int i = 0; i < k; ++i) orbit_of[i] = orbit_of[orbit_min[i]];
     if (cols + n_orb > 32767) return desco::fail(DESCO_EINVAL, "desco_orbit_table: too many columns");
     for (size_t t = 0; t < images.size(); ++t) {
-      const int slot = ORB_OFF[k] + (int)images[t];
+      const int slot = ESU_OFF[k] + (int)images[t];
       if (owner[slot] >= 0 && owner[slot] != q)
         return desco::fail(DESCO_EINVAL, "desco_orbit_table: two queries are isomorphic");
       owner[slot] = (int16_t)q;
@@ -288,13 +224,15 @@ extern "C" int desco_orbit_counts(const int64_t* graph_ptr, int64_t num_graphs, 
   if (!graph_ptr || !rowptr || !q_nodes || !q_edge_ptr || !out || num_graphs < 0 || num_queries < 0)
     return desco::fail(DESCO_EINVAL, "desco_orbit_counts: bad argument");
   try {
-    std::vector<int16_t> table((size_t)ORB_ENTRIES * ORB_KMAX);
+    std::vector<int16_t> table((size_t)ESU_ENTRIES * ORB_KMAX);
     int cols = 0, kmax = 0;
     if (const int rc = desco_orbit_table(q_nodes, q_edge_ptr, q_edges, num_queries, table.data(), &cols, &kmax))
       return rc;
     std::memset(out, 0, sizeof(int64_t) * (size_t)graph_ptr[num_graphs] * (size_t)cols);
     if (cols == 0) return 0;
-    enumerate_graphs(graph_ptr, num_graphs, rowptr, col, Classifier(), table.data(), kmax, cols, num_threads, out);
+    if (!desco::esu_enumerate_graphs(graph_ptr, num_graphs, rowptr, col, kmax, num_threads,
+                                     [&] { return OrbitVisitor{table.data(), out, cols}; }))
+      return desco::fail(DESCO_ENOMEM, "desco_orbit_counts: out of memory");
     return 0;
   } catch (const std::bad_alloc&) {
     return desco::fail(DESCO_ENOMEM, "desco_orbit_counts: out of memory");

@@ -12,7 +12,7 @@
 // over all k! relabelings.  This file holds
 //   desco_canonical_label_classes     queries -> class_of_query, number of classes           (2..6 nodes)
 //   desco_canonical_label_table[_size] the direct lookup table the device kernel classifies with (2..5 nodes)
-//   desco_canonical_counts_labelled   the ESU enumerator of groundtruth.cpp with labels      (2..6 nodes)
+//   desco_canonical_counts_labelled   a visitor with labels over the ESU walk of groundtruth_esu.hpp (2..6 nodes)
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -20,12 +20,7 @@
 #include <unordered_map>
 #include <vector>
 
-#ifdef _OPENMP
-#include <omp.h>
-#endif
-
-#include "../../include/desco_hip.h"
-#include "common_host.hpp"
+#include "groundtruth_esu.hpp"
 #include "groundtruth_label.hpp"
 
 namespace {
@@ -34,9 +29,10 @@ using desco::GTL_AMAX_DEV;
 using desco::GTL_AMAX_HOST;
 using desco::GTL_KMAX_DEV;
 using desco::GTL_KMAX_HOST;
+using desco::GraphBits;
+using desco::pair_bit;
 constexpr int KMAX = GTL_KMAX_HOST;
-
-inline int pair_bit(int a, int b) { return b * (b - 1) / 2 + a; }   // a < b
+static_assert(KMAX == desco::ESU_KMAX_HOST, "the labelled enumerator walks with the shared ESU");
 
 // 64-bit code of a labelled pattern on k nodes: the mask in bits 0..14, label j in bits 15 + 8j (codes of different
 // k live in different maps)
@@ -116,14 +112,7 @@ int read_queries(const char* who, const int32_t* q_nodes, const int32_t* q_edge_
       if (l < 0 || l >= num_labels) return bad("query label id outside 0..num_labels-1");
     }
     if (q_edge_ptr[q + 1] < q_edge_ptr[q]) return bad("q_edge_ptr must not decrease");
-    uint32_t m = 0;
-    for (int e = q_edge_ptr[q]; e < q_edge_ptr[q + 1]; ++e) {
-      int a = q_edges[2 * e], b = q_edges[2 * e + 1];
-      if (a == b || a < 0 || b < 0 || a >= k || b >= k) return bad("bad query edge");
-      if (a > b) std::swap(a, b);
-      m |= 1u << pair_bit(a, b);
-    }
-    out->mask[q] = m;
+    if (const int rc = desco::query_mask(who, q_edge_ptr, q_edges, q, k, &out->mask[q])) return rc;
   }
   return 0;
 }
@@ -134,66 +123,29 @@ inline bool queries_null(const int32_t* q_nodes, const int32_t* q_edge_ptr, cons
   return !q_edges && q_edge_ptr[num_queries] > q_edge_ptr[0];
 }
 
-struct Ctx {
-  int64_t base, n;
-  const int64_t* rowptr;
-  const int32_t* col;
+// the ESU visitor: one per thread, with its memo of the codes it has met
+struct LabelVisitor {
   const int32_t* labels;
-  int kmax;
-  bool used[KMAX + 1];
+  const bool* used;                   // [k]: a query has k nodes
   const ClassMap* classes;            // [k]: canonical code -> class
-  ClassMap memo[KMAX + 1];            // [k]: code as found -> class or -1
-  std::vector<uint64_t> bits;
-  int words;
-  std::vector<uint8_t> seen;
   int64_t* out;
   int64_t num_c;
-  bool adj(int a, int b) const { return bits[(size_t)a * words + (b >> 6)] >> (b & 63) & 1; }
-};
+  ClassMap memo[KMAX + 1];            // [k]: code as found -> class or -1
 
-void classify(Ctx& c, const int* sub, int k, int v) {
-  if (!c.used[k]) return;
-  uint32_t m = 0;
-  int lab[KMAX];
-  for (int b = 0; b < k; ++b) {
-    lab[b] = c.labels[c.base + sub[b]];
-    for (int a = 0; a < b; ++a)
-      if (c.adj(sub[a], sub[b])) m |= 1u << pair_bit(a, b);
-  }
-  const uint64_t code = make_code(k, m, lab);
-  auto it = c.memo[k].find(code);
-  if (it == c.memo[k].end()) {
-    auto cl = c.classes[k].find(canonical_code(k, m, lab));
-    it = c.memo[k].emplace(code, cl == c.classes[k].end() ? -1 : cl->second).first;
-  }
-  if (it->second >= 0) c.out[(c.base + v) * c.num_c + it->second] += 1;
-}
-
-// ESU, as in groundtruth.cpp
-void extend(Ctx& c, int* sub, int nsub, std::vector<int>& ext, int v) {
-  classify(c, sub, nsub, v);
-  if (nsub == c.kmax) return;
-  std::vector<int> newly, ext2;
-  while (!ext.empty()) {
-    const int w = ext.back();
-    ext.pop_back();
-    newly.clear();
-    const int64_t gw = c.base + w;
-    for (int64_t e = c.rowptr[gw]; e < c.rowptr[gw + 1]; ++e) {
-      const int u = (int)(c.col[e] - c.base);
-      if (u >= v) break;                       // rows sorted ascending; only ids below the root
-      if (!c.seen[u]) {
-        c.seen[u] = 1;
-        newly.push_back(u);
-      }
+  void operator()(const GraphBits& g, const int* sub, int k, int v) {
+    if (!used[k]) return;
+    int lab[KMAX];
+    for (int b = 0; b < k; ++b) lab[b] = labels[g.base + sub[b]];
+    const uint32_t m = g.mask_of(sub, k);
+    const uint64_t code = make_code(k, m, lab);
+    auto it = memo[k].find(code);
+    if (it == memo[k].end()) {
+      auto cl = classes[k].find(canonical_code(k, m, lab));
+      it = memo[k].emplace(code, cl == classes[k].end() ? -1 : cl->second).first;
     }
-    ext2 = ext;
-    ext2.insert(ext2.end(), newly.begin(), newly.end());
-    sub[nsub] = w;
-    extend(c, sub, nsub + 1, ext2, v);
-    for (int u : newly) c.seen[u] = 0;
+    if (it->second >= 0) out[(g.base + v) * num_c + it->second] += 1;
   }
-}
+};
 
 }  // namespace
 
@@ -323,62 +275,10 @@ extern "C" int desco_canonical_counts_labelled(const int64_t* graph_ptr, int64_t
                                          "into different classes");
     }
     std::memset(out, 0, sizeof(int64_t) * (size_t)total * (size_t)num_classes);
-#ifdef _OPENMP
-    const int nt = num_threads > 0 ? num_threads : omp_get_max_threads();
-#else
-    const int nt = 1;
-    (void)num_threads;
-#endif
-    bool oom = false;
-#pragma omp parallel num_threads(nt)
-    {
-      Ctx c;
-      {
-        c.rowptr = rowptr;
-        c.col = col;
-        c.labels = labels;
-        c.kmax = kmax;
-        std::copy(used, used + KMAX + 1, c.used);
-        c.classes = classes;
-        c.out = out;
-        c.num_c = num_classes;
-#pragma omp for schedule(dynamic, 1)
-        for (int64_t g = 0; g < num_graphs; ++g) try {
-          c.base = graph_ptr[g];
-          c.n = graph_ptr[g + 1] - c.base;
-          c.words = (int)((c.n + 63) / 64);
-          c.bits.assign((size_t)c.n * c.words, 0);
-          for (int64_t u = 0; u < c.n; ++u)
-            for (int64_t e = rowptr[c.base + u]; e < rowptr[c.base + u + 1]; ++e) {
-              const int w = (int)(col[e] - c.base);
-              c.bits[(size_t)u * c.words + (w >> 6)] |= (uint64_t)1 << (w & 63);
-            }
-          c.seen.assign((size_t)c.n, 0);
-          int sub[KMAX];
-          std::vector<int> ext;
-          for (int v = 0; v < (int)c.n; ++v) {
-            ext.clear();
-            c.seen[v] = 1;
-            const int64_t gv = c.base + v;
-            for (int64_t e = rowptr[gv]; e < rowptr[gv + 1]; ++e) {
-              const int u = (int)(col[e] - c.base);
-              if (u >= v) break;
-              c.seen[u] = 1;
-              ext.push_back(u);
-            }
-            std::vector<int> marked = ext;
-            sub[0] = v;
-            extend(c, sub, 1, ext, v);
-            for (int u : marked) c.seen[u] = 0;
-            c.seen[v] = 0;
-          }
-        } catch (const std::bad_alloc&) {
-#pragma omp atomic write
-          oom = true;
-        }
-      }
-    }
-    if (oom) return desco::fail(DESCO_ENOMEM, "desco_canonical_counts_labelled: out of memory");
+    const bool ok = desco::esu_enumerate_graphs(graph_ptr, num_graphs, rowptr, col, kmax, num_threads, [&] {
+      return LabelVisitor{labels, used, classes, out, num_classes, {}};
+    });
+    if (!ok) return desco::fail(DESCO_ENOMEM, "desco_canonical_counts_labelled: out of memory");
     return 0;
   } catch (const std::bad_alloc&) {
     return desco::fail(DESCO_ENOMEM, "desco_canonical_counts_labelled: out of memory");

@@ -27,11 +27,4 @@ inline GtlLayout gtl_layout(int kmax, int num_labels) {
   return l;
 }
 
-// groundtruth_dev.hip: zero `bits` and build the per-graph adjacency bitset rows from the CSR (the
-// first kernel of desco_canonical_counts_dev).  Returns 0 or a hipError_t with the message set.
-int gt_build_bitsets(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col,
-                     const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
-                     int64_t num_words, int64_t num_nodes, int64_t num_entries, void* stream,
-                     const char* who);
-
 }  // namespace desco

@@ -4,9 +4,9 @@
 //   count[v][c] = #{ node subsets S : max(S) = v, G[S] connected, and G[S] with its node labels
 //                    isomorphic to the labelled queries of class c }
 //
-// Enumeration: the walk of groundtruth_dev.hip (ESU without extension lists; one wave per CSR entry (v, u0) with
-// u0 < v, third-node candidates dealt round-robin to the lanes, subset / mask / cursors in registers, adjacency
-// from per-graph bitset rows built by the same first kernel).  What differs:
+// Enumeration: the shared device walk, groundtruth_esu_dev.hpp (ESU without extension lists; one wave per CSR entry
+// (v, u0) with u0 < v, third-node candidates dealt round-robin to the lanes, subset / mask / cursors in registers,
+// adjacency from per-graph bitset rows built by the same first kernel).  This kernel's visitor adds:
 //
 // Classification.  The label id of a node is gathered once, when the node is chosen, and carried down the levels as
 // the running sum  lab = sum_j l_j A^j ; a found k-subset reads ONE int32 of the direct table at
@@ -18,8 +18,9 @@
 // one lane mostly differ in their last node only and fall into few classes) and adds the run to out[v][c] with one
 // 64-bit global atomic when the class changes.  Integer adds: the result does not depend on arrival order.  All
 // hits of one wave go to the one row v; the entries rooted at a hub spread over that row's classes.
-#include "common_device.hpp"
+#include "groundtruth_esu_dev.hpp"
 #include "groundtruth_label.hpp"
+
 
 namespace desco {
 
@@ -42,135 +43,57 @@ struct GtlArgs {
   unsigned long long* out;           // [N][C]
 };
 
-struct GtlCtx {
-  const int64_t* rowptr;
-  const int32_t* col;
-  const unsigned long long* bits;    // this graph's rows
-  const int32_t* labels;             // this graph's labels
+struct GtlVisitor {
+  using Path = unsigned;             // the running label sum
+  using Level = EsuNone;
   const GtlArgs* a;
-  int64_t base;
-  int words, lv, kmax;
+  const int32_t* labels;             // this graph's labels
   unsigned long long* row;           // out[v]
   int run_c;                         // class of the pending run, -1 = none
   unsigned run_n;
-};
 
-__device__ __forceinline__ int64_t gtl_row_of_entry(const int64_t* __restrict__ rowptr, int64_t n, int64_t e) {
-  int64_t lo = 0, hi = n;            // last row with rowptr[row] <= e
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (rowptr[mid] <= e) lo = mid; else hi = mid;
+  __device__ __forceinline__ void flush() {
+    if (run_c >= 0) atomicAdd(row + run_c, (unsigned long long)run_n);
+    run_c = -1;
+    run_n = 0;
   }
-  return lo;
-}
-
-__device__ __forceinline__ unsigned gtl_adj(const GtlCtx& c, int a, int b) {
-  return (unsigned)(c.bits[(int64_t)a * c.words + (b >> 6)] >> (b & 63)) & 1u;
-}
-
-__device__ __forceinline__ void gtl_flush(GtlCtx& c) {
-  if (c.run_c >= 0) atomicAdd(c.row + c.run_c, (unsigned long long)c.run_n);
-  c.run_c = -1;
-  c.run_n = 0;
-}
-
-template <int K>
-__device__ __forceinline__ void gtl_classify(GtlCtx& c, unsigned mask, unsigned lab) {
-  const unsigned idx = c.a->off[K] + mask * c.a->apow[K] + lab;
-  if (idx >= c.a->table_entries) return;          // (a label id outside 0..A-1: never read past the table)
-  const int cl = c.a->table[idx];
-  if (cl < 0 || cl >= c.a->C) return;
-  if (cl != c.run_c) {
-    gtl_flush(c);
-    c.run_c = cl;
-  }
-  ++c.run_n;
-}
-
-template <int NS>
-__device__ void gtl_extend(GtlCtx& c, const int (&S)[GTL_KMAX_DEV], unsigned mask, unsigned lab, int ci0, int cp0);
-
-// candidate at position e of the adjacency row (starting at r0) of S[ci] for node number NS of the subset: taken iff
-// it is below the root, new, and adjacent to no subset node before S[ci].  Returns false when the row has passed the
-// root's id (rows ascend: nothing further qualifies).
-template <int NS>
-__device__ __forceinline__ bool gtl_try(GtlCtx& c, const int (&S)[GTL_KMAX_DEV], unsigned mask, unsigned lab, int ci,
-                                        int64_t r0, int64_t e) {
-  const int u = (int)(c.col[e] - c.base);
-  if (u >= c.lv) return false;
-  unsigned ab = 0;
-  bool in_s = false;
-#pragma unroll
-  for (int j = 0; j < NS; ++j) {
-    in_s |= u == S[j];
-    ab |= gtl_adj(c, S[j], u) << j;
-  }
-  if (in_s || (ab & ((1u << ci) - 1u))) return true;     // u entered the extension set earlier
-  const unsigned m2 = mask | (ab << (NS * (NS - 1) / 2));
-  const unsigned lab2 = lab + (unsigned)c.labels[u] * c.a->apow[NS];
-  gtl_classify<NS + 1>(c, m2, lab2);
-  if constexpr (NS + 1 < GTL_KMAX_DEV) {
-    if (NS + 1 < c.kmax) {
-      int S2[GTL_KMAX_DEV];
-#pragma unroll
-      for (int j = 0; j < GTL_KMAX_DEV; ++j) S2[j] = j < NS ? S[j] : 0;
-      S2[NS] = u;
-      gtl_extend<NS + 1>(c, S2, m2, lab2, ci, (int)(e - r0) + 1);
+  template <int K>
+  __device__ __forceinline__ void classify(unsigned mask, unsigned lab) {
+    const unsigned idx = a->off[K] + mask * a->apow[K] + lab;
+    if (idx >= a->table_entries) return;          // (a label id outside 0..A-1: never read past the table)
+    const int cl = a->table[idx];
+    if (cl < 0 || cl >= a->C) return;
+    if (cl != run_c) {
+      flush();
+      run_c = cl;
     }
+    ++run_n;
   }
-  return true;
-}
-
-// choose node number NS of the subset (S[0..NS-1] chosen, induced mask `mask`, label sum `lab`); candidates start at
-// key (ci0, cp0)
-template <int NS>
-__device__ void gtl_extend(GtlCtx& c, const int (&S)[GTL_KMAX_DEV], unsigned mask, unsigned lab, int ci0, int cp0) {
-#pragma unroll
-  for (int ci = 0; ci < NS; ++ci) {
-    if (ci < ci0) continue;
-    const int64_t r0 = c.rowptr[c.base + S[ci]], r1 = c.rowptr[c.base + S[ci] + 1];
-    for (int64_t e = r0 + (ci == ci0 ? cp0 : 0); e < r1; ++e)
-      if (!gtl_try<NS>(c, S, mask, lab, ci, r0, e)) break;
+  template <int NS>
+  __device__ __forceinline__ Path push(Path lab, int u) const {
+    return lab + (unsigned)labels[u] * a->apow[NS];
   }
-}
+  template <int K>
+  __device__ __forceinline__ void found(const int (&)[ESU_KMAX], int, unsigned mask, Path lab, Level&) {
+    classify<K>(mask, lab);
+  }
+  template <int NS>
+  __device__ __forceinline__ void close(const int (&)[ESU_KMAX], Level&) const {}
+};
 
 __global__ __launch_bounds__(GTL_THREADS) void gtl_count_kernel(GtlArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int64_t e = (int64_t)blockIdx.x * (GTL_THREADS / 64) + (tid >> 6);     // one wave per entry
   if (e >= a.num_entries) return;
-  const int64_t v = gtl_row_of_entry(a.rowptr, a.num_nodes, e);
-  const int g = a.node_graph[v];
-  GtlCtx c;
-  c.rowptr = a.rowptr;
-  c.col = a.col;
-  c.a = &a;
-  c.base = a.graph_ptr[g];
-  c.words = (int)((a.graph_ptr[g + 1] - c.base + 63) >> 6);
-  c.bits = a.bits + a.bit_off[g];
-  c.labels = a.labels + c.base;
-  c.lv = (int)(v - c.base);
-  c.kmax = a.kmax;
-  c.row = a.out + v * a.C;
-  c.run_c = -1;
-  c.run_n = 0;
+  const int64_t v = esu_row_of_entry(a.rowptr, a.num_nodes, e);
+  const EsuGraph c = esu_graph_of(a.graph_ptr, a.rowptr, a.col, a.node_graph, a.bit_off, a.bits, v, a.kmax);
+  GtlVisitor vis{&a, a.labels + c.base, a.out + v * a.C, -1, 0};
   const int u0 = (int)(a.col[e] - c.base);
   if (u0 >= c.lv) return;                          // the root is the maximum of its subsets
-  const int S[GTL_KMAX_DEV] = {c.lv, u0, 0, 0, 0};
-  const unsigned lab = (unsigned)c.labels[c.lv] + (unsigned)c.labels[u0] * a.apow[1];
-  if (lane == 0) gtl_classify<2>(c, 1u, lab);
-  if (c.kmax > 2) {
-    // candidates for the third node: v's row behind u0, then u0's row; position p -> lane p % 64
-    const int64_t v0 = a.rowptr[v], v1 = a.rowptr[v + 1];
-    const int64_t w0 = a.rowptr[c.base + u0], w1 = a.rowptr[c.base + u0 + 1];
-    const int64_t rest = v1 - (e + 1), total = rest + (w1 - w0);
-    for (int64_t p = lane; p < total; p += 64) {
-      if (p < rest)
-        gtl_try<2>(c, S, 1u, lab, 0, v0, e + 1 + p);
-      else
-        gtl_try<2>(c, S, 1u, lab, 1, w0, w0 + (p - rest));
-    }
-  }
-  gtl_flush(c);
+  const unsigned lab = (unsigned)vis.labels[c.lv] + (unsigned)vis.labels[u0] * a.apow[1];
+  if (lane == 0) vis.classify<2>(1u, lab);
+  esu_wave_walk(c, vis, v, e, u0, lane, lab);
+  vis.flush();
 }
 
 }  // namespace desco

@@ -46,12 +46,7 @@
 #include <string>
 #include <vector>
 
-#ifdef _OPENMP
-#include <omp.h>
-#endif
-
-#include "../../include/desco_hip.h"
-#include "common_host.hpp"
+#include "groundtruth_esu.hpp"
 #include "groundtruth_match.hpp"
 
 namespace {
@@ -348,18 +343,15 @@ int build_plan_labelled(const char* who, const int32_t* q_nodes, const int32_t* 
 // IND: induced matching (a clear GTM_ADJ bit means NOT adjacent); else a clear bit asks nothing.
 template <bool LAB, bool IND>
 struct Matcher {
-  int64_t base;
+  GraphBits g;
   const int64_t* rowptr;
   const int32_t* col;
-  const uint64_t* bits;
-  int words, v;
+  int v;
   const int32_t* rec;
   const int32_t* lab;                  // LAB: this graph's node labels
   int k;
   int img[GTM_KMAX];
   int64_t found;
-
-  bool adj(int a, int b) const { return bits[(size_t)a * words + (b >> 6)] >> (b & 63) & 1; }
 
   bool fits(int level, int u) const {
     if (LAB && lab[u] != rec[GTML_LABEL + level]) return false;
@@ -368,7 +360,7 @@ struct Matcher {
     for (int j = 0; j < level; ++j) {
       const int w = img[j];
       if (u == w) return false;
-      if (IND ? adj(u, w) != (want >> j & 1) : (want >> j & 1) && !adj(u, w)) return false;
+      if (IND ? g.adj(u, w) != (want >> j & 1) : (want >> j & 1) && !g.adj(u, w)) return false;
       if ((lt >> j & 1) && !(u < w)) return false;
       if ((gt >> j & 1) && !(u > w)) return false;
     }
@@ -376,9 +368,9 @@ struct Matcher {
   }
 
   void extend(int level) {
-    const int64_t p = base + img[rec[GTM_PARENT + level]];
+    const int64_t p = g.base + img[rec[GTM_PARENT + level]];
     for (int64_t e = rowptr[p]; e < rowptr[p + 1]; ++e) {
-      const int u = (int)(col[e] - base);
+      const int u = (int)(col[e] - g.base);
       if (u >= v) break;                       // rows ascend: every image but the anchor's is below the root
       if (!fits(level, u)) continue;
       if (level + 1 == k) {
@@ -541,28 +533,18 @@ int counts_match(const std::string& who, const int64_t* graph_ptr, int64_t num_g
 #endif
     bool oom = false;
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
-    for (int64_t g = 0; g < num_graphs; ++g) {
-      const int64_t base = graph_ptr[g], n = graph_ptr[g + 1] - base;
-      const int words = (int)((n + 63) / 64);
-      std::vector<uint64_t> bits;
+    for (int64_t gi = 0; gi < num_graphs; ++gi) {
+      Matcher<false, IND> m;
       try {
-        bits.assign((size_t)n * words, 0);
+        m.g.build(graph_ptr, gi, rowptr, col);
       } catch (const std::bad_alloc&) {
 #pragma omp atomic write
         oom = true;
         continue;
       }
-      for (int64_t u = 0; u < n; ++u)
-        for (int64_t e = rowptr[base + u]; e < rowptr[base + u + 1]; ++e) {
-          const int w = (int)(col[e] - base);
-          bits[(size_t)u * words + (w >> 6)] |= (uint64_t)1 << (w & 63);
-        }
-      Matcher<false, IND> m;
-      m.base = base;
+      const int64_t base = m.g.base, n = m.g.n;
       m.rowptr = rowptr;
       m.col = col;
-      m.bits = bits.data();
-      m.words = words;
       for (int v = 1; v < (int)n; ++v) {
         if (rowptr[base + v] == rowptr[base + v + 1]) continue;
         m.v = v;
@@ -603,28 +585,18 @@ int counts_match_labelled(const std::string& who, const int64_t* graph_ptr, int6
 #endif
     bool oom = false;
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
-    for (int64_t g = 0; g < num_graphs; ++g) {
-      const int64_t base = graph_ptr[g], n = graph_ptr[g + 1] - base;
-      const int words = (int)((n + 63) / 64);
-      std::vector<uint64_t> bits;
+    for (int64_t gi = 0; gi < num_graphs; ++gi) {
+      Matcher<true, IND> m;
       try {
-        bits.assign((size_t)n * words, 0);
+        m.g.build(graph_ptr, gi, rowptr, col);
       } catch (const std::bad_alloc&) {
 #pragma omp atomic write
         oom = true;
         continue;
       }
-      for (int64_t u = 0; u < n; ++u)
-        for (int64_t e = rowptr[base + u]; e < rowptr[base + u + 1]; ++e) {
-          const int w = (int)(col[e] - base);
-          bits[(size_t)u * words + (w >> 6)] |= (uint64_t)1 << (w & 63);
-        }
-      Matcher<true, IND> m;
-      m.base = base;
+      const int64_t base = m.g.base, n = m.g.n;
       m.rowptr = rowptr;
       m.col = col;
-      m.bits = bits.data();
-      m.words = words;
       m.lab = labels + base;
       for (int v = 1; v < (int)n; ++v) {
         if (rowptr[base + v] == rowptr[base + v + 1]) continue;

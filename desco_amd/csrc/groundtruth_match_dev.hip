@@ -38,8 +38,7 @@
 // asks for an edge, a clear bit asks nothing (groundtruth_match.cpp has the argument).
 #include <type_traits>
 
-#include "common_device.hpp"
-#include "groundtruth_label.hpp"
+#include "groundtruth_esu_dev.hpp"
 #include "groundtruth_match.hpp"
 
 namespace desco {
@@ -69,17 +68,9 @@ struct GtmLabArgs : GtmArgs {          // num_anchors = the largest bucket: item
 struct GtmMonoArgs : GtmArgs {};
 struct GtmLabMonoArgs : GtmLabArgs {};
 
-__device__ __forceinline__ int64_t gtm_row_of_entry(const int64_t* __restrict__ rowptr, int64_t n, int64_t e) {
-  int64_t lo = 0, hi = n;            // last row with rowptr[row] <= e
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (rowptr[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// The same row, found by the whole wave: lane i probes the i-th of 64 evenly spaced rows of [lo, hi), so that a dead
-// item of the labelled kernel costs three dependent loads here instead of log2(n).  All 64 lanes are active.
+// The row of esu_row_of_entry (groundtruth_esu_dev.hpp), found by the whole wave: lane i probes the i-th of 64 evenly
+// spaced rows of [lo, hi), so that a dead item of the labelled kernel costs three dependent loads here instead of
+// log2(n).  All 64 lanes are active.
 __device__ __forceinline__ int64_t gtm_row_of_entry_wave(const int64_t* __restrict__ rowptr, int64_t n, int64_t e,
                                                          int lane) {
   int64_t lo = 0, hi = n;            // rowptr[lo] <= e, the answer is in [lo, hi)
@@ -172,7 +163,7 @@ __global__ __launch_bounds__(GTM_THREADS) void gtm_count_kernel(Args a) {
   const int k = rec[GTM_K], q = rec[GTM_QUERY];
   if constexpr (!LAB) {
     e = a.entry_begin + item / a.num_anchors;
-    v = gtm_row_of_entry(a.rowptr, a.num_nodes, e);
+    v = esu_row_of_entry(a.rowptr, a.num_nodes, e);
   }
   const int g = a.node_graph[v];
   const int64_t base = a.graph_ptr[g];

@@ -33,13 +33,42 @@ def _flatten_queries(queries: Sequence):
 _DEVICE_BITSET_LIMIT_WORDS = 1 << 28        # 2 GiB
 
 
+def _bitset_words(graphs: GraphSet) -> np.ndarray:
+    n = np.diff(graphs.graph_ptr).astype(np.int64)
+    return n * ((n + 63) // 64)
+
+
 def _device_eligible(graphs: GraphSet, q_nodes: np.ndarray) -> bool:
     if not torch.cuda.is_available() or len(q_nodes) == 0 or len(q_nodes) > 32:
         return False
     if q_nodes.min() < 2 or q_nodes.max() > 5:
         return False
-    n = np.diff(graphs.graph_ptr).astype(np.int64)
-    return int((n * ((n + 63) // 64)).sum()) <= _DEVICE_BITSET_LIMIT_WORDS
+    return int(_bitset_words(graphs).sum()) <= _DEVICE_BITSET_LIMIT_WORDS
+
+
+def _put(a, dt, dev) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+
+
+class _DeviceGraphs:
+    """A GraphSet on the device as the enumerators' entry points take it: the CSR, the graph of every node, room for
+    the adjacency bitset rows (filled by the entry point), and ``head``, the ten leading ABI arguments."""
+
+    def __init__(self, graphs: GraphSet, dev):
+        self.dev = dev
+        bit_off = np.concatenate([[0], np.cumsum(_bitset_words(graphs))]).astype(np.int64)
+        self.N, self.G, self.E = graphs.num_nodes, graphs.num_graphs, int(graphs.col.shape[0])
+        self._keep = (self.put(graphs.graph_ptr, np.int64), self.put(graphs.rowptr, np.int64),
+                      self.put(graphs.col, np.int32), self.put(graphs.node_graph_ids(), np.int32),
+                      self.put(bit_off[:-1] if self.G else bit_off, np.int64),
+                      torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev))
+        graph_ptr, rowptr, col, node_graph, bit_off_d, bits = self._keep
+        self.head = (graph_ptr.data_ptr(), self.G, self.N, rowptr.data_ptr(), self.E,
+                     col.data_ptr() if col.numel() else None, node_graph.data_ptr(), bit_off_d.data_ptr(),
+                     bits.data_ptr(), int(bit_off[-1]))
+
+    def put(self, a, dt) -> torch.Tensor:
+        return _put(a, dt, self.dev)
 
 
 def canonical_counts_device(graphs: GraphSet, queries: Sequence, device="cuda", induced: bool = True) -> torch.Tensor:
@@ -60,24 +89,16 @@ def canonical_counts_device(graphs: GraphSet, queries: Sequence, device="cuda", 
                                              len(q_nodes), table.ctypes.data, ctypes.byref(kmax)),
                "desco_canonical_class_table")
     dev = torch.device(device)
-    n = np.diff(graphs.graph_ptr).astype(np.int64)
-    words = n * ((n + 63) // 64)
-    bit_off = np.concatenate([[0], np.cumsum(words)]).astype(np.int64)
-    N, G, Q = graphs.num_nodes, graphs.num_graphs, len(q_nodes)
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
-    graph_ptr, rowptr = t(graphs.graph_ptr, np.int64), t(graphs.rowptr, np.int64)
-    col, node_graph = t(graphs.col, np.int32), t(graphs.node_graph_ids(), np.int32)
-    bit_off_d, cls = t(bit_off[:-1] if G else bit_off, np.int64), t(table, np.int16)
-    bits = torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev)
+    N, Q = graphs.num_nodes, len(q_nodes)
     out = torch.empty((N, Q), dtype=torch.int64, device=dev)
     if N == 0 or Q == 0:
         return out.zero_()
+    d = _DeviceGraphs(graphs, dev)
+    cls = d.put(table, np.int16)
     with torch.cuda.device(dev):
-        _lib.check(L.desco_canonical_counts_dev(
-            graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), int(graphs.col.shape[0]),
-            col.data_ptr() if col.numel() else None, node_graph.data_ptr(), bit_off_d.data_ptr(),
-            bits.data_ptr(), int(bit_off[-1]), cls.data_ptr(), int(kmax.value), Q, out.data_ptr(),
-            torch.cuda.current_stream(dev).cuda_stream), "desco_canonical_counts_dev")
+        _lib.check(L.desco_canonical_counts_dev(*d.head, cls.data_ptr(), int(kmax.value), Q, out.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream),
+                   "desco_canonical_counts_dev")
     return out
 
 
@@ -102,7 +123,7 @@ def canonical_counts(graphs: GraphSet, queries: Sequence, num_threads: int = 0,
         return _canonical_counts_vf2(graphs, queries, induced)
     if not induced and backend not in ("auto", "host", "device"):
         raise ValueError(f"unknown backend {backend!r}")
-    flat, q_nodes, q_edge_ptr, q_edges = _flatten_queries(queries)
+    flat, q_nodes, _, _ = _flatten_queries(queries)
     if method == "matcher":
         return canonical_counts_match(graphs, flat, backend, num_threads, induced=induced)
     large = [i for i, k in enumerate(q_nodes) if k > 6]
@@ -121,14 +142,7 @@ def canonical_counts(graphs: GraphSet, queries: Sequence, num_threads: int = 0,
         except RuntimeError as e:
             if backend == "device" or "isomorphic" not in str(e):
                 raise                           # (duplicate query classes: host path below)
-    out = np.zeros((graphs.num_nodes, len(flat)), dtype=np.int64)
-    L = _lib.lib()
-    _lib.check(L.desco_canonical_counts(graphs.graph_ptr.ctypes.data, graphs.num_graphs,
-                                        graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
-                                        q_nodes.ctypes.data, q_edge_ptr.ctypes.data,
-                                        q_edges.ctypes.data if len(q_edges) else None, len(flat),
-                                        num_threads, out.ctypes.data), "desco_canonical_counts")
-    return torch.from_numpy(out).double()
+    return torch.from_numpy(_induced_host_int64(graphs, flat, num_threads)).double()
 
 
 # ---- non-induced counts of small queries: census of all classes + an exact transform ---------------------------------
@@ -417,24 +431,15 @@ def _orbit_table(reps):
 def _orbit_device_raw(graphs: GraphSet, reps, dev) -> torch.Tensor:
     """desco_orbit_counts_dev on pairwise non-isomorphic ``reps``: int64 [N, columns of reps] on ``dev``."""
     table, C, kmax = _orbit_table(reps)
-    L = _lib.lib()
-    n = np.diff(graphs.graph_ptr).astype(np.int64)
-    bit_off = np.concatenate([[0], np.cumsum(n * ((n + 63) // 64))]).astype(np.int64)
-    N, G = graphs.num_nodes, graphs.num_graphs
-    out = torch.empty((N, C), dtype=torch.int64, device=dev)
-    if N == 0 or C == 0:
+    out = torch.empty((graphs.num_nodes, C), dtype=torch.int64, device=dev)
+    if graphs.num_nodes == 0 or C == 0:
         return out.zero_()
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
-    graph_ptr, rowptr = t(graphs.graph_ptr, np.int64), t(graphs.rowptr, np.int64)
-    col, node_graph = t(graphs.col, np.int32), t(graphs.node_graph_ids(), np.int32)
-    bit_off_d, table_d = t(bit_off[:-1] if G else bit_off, np.int64), t(table, np.int16)
-    bits = torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev)
+    d = _DeviceGraphs(graphs, dev)
+    table_d = d.put(table, np.int16)
     with torch.cuda.device(dev):
-        _lib.check(L.desco_orbit_counts_dev(
-            graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), int(graphs.col.shape[0]),
-            col.data_ptr() if col.numel() else None, node_graph.data_ptr(), bit_off_d.data_ptr(),
-            bits.data_ptr(), int(bit_off[-1]), table_d.data_ptr(), kmax, C, out.data_ptr(),
-            torch.cuda.current_stream(dev).cuda_stream), "desco_orbit_counts_dev")
+        _lib.check(_lib.lib().desco_orbit_counts_dev(*d.head, table_d.data_ptr(), kmax, C, out.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream),
+                   "desco_orbit_counts_dev")
     return out
 
 
@@ -528,9 +533,16 @@ def match_plan(queries: Sequence) -> np.ndarray:
     return plan
 
 
-def _bitset_words(graphs: GraphSet) -> np.ndarray:
-    n = np.diff(graphs.graph_ptr).astype(np.int64)
-    return n * ((n + 63) // 64)
+def _sliced(E: int, slice_entries: int, stream, launch):
+    """``launch(e0, e1)`` for consecutive slices of the CSR entries [0, E) (once, empty, when E is 0)."""
+    e0 = 0
+    while True:
+        e1 = min(e0 + slice_entries, E)
+        launch(e0, e1)
+        stream.synchronize()                # a fault of this slice surfaces here, before the next is enqueued
+        e0 = e1
+        if e0 >= E:
+            break
 
 
 def canonical_counts_match_device(graphs: GraphSet, queries: Sequence, device="cuda",
@@ -543,31 +555,22 @@ def canonical_counts_match_device(graphs: GraphSet, queries: Sequence, device="c
     plan = match_plan(queries)
     Q, A = int(plan[0]), int(plan[1])
     dev = torch.device(device)
-    words = _bitset_words(graphs)
-    bit_off = np.concatenate([[0], np.cumsum(words)]).astype(np.int64)
-    N, G, E = graphs.num_nodes, graphs.num_graphs, int(graphs.col.shape[0])
-    out = torch.zeros((N, Q), dtype=torch.int64, device=dev)
-    if N == 0 or Q == 0:
+    out = torch.zeros((graphs.num_nodes, Q), dtype=torch.int64, device=dev)
+    if graphs.num_nodes == 0 or Q == 0:
         return out
     if slice_entries is None:
         slice_entries = max(_MATCH_SLICE_WAVES // max(A, 1), 1)
     slice_entries = int(slice_entries)
     if slice_entries < 1:
         raise ValueError("slice_entries must be positive")
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
-    graph_ptr, rowptr = t(graphs.graph_ptr, np.int64), t(graphs.rowptr, np.int64)
-    col, node_graph = t(graphs.col, np.int32), t(graphs.node_graph_ids(), np.int32)
-    bit_off_d, plan_d = t(bit_off[:-1] if G else bit_off, np.int64), t(plan, np.int32)
-    bits = torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev)
+    d = _DeviceGraphs(graphs, dev)
+    plan_d = d.put(plan, np.int32)
     L = _lib.lib()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        e0 = 0
-        while True:
-            e1 = min(e0 + slice_entries, E)
-            head = (graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), E, col.data_ptr() if col.numel() else None,
-                    node_graph.data_ptr(), bit_off_d.data_ptr(), bits.data_ptr(), int(bit_off[-1]), plan.ctypes.data,
-                    plan_d.data_ptr(), len(plan), Q)
+        head = (*d.head, plan.ctypes.data, plan_d.data_ptr(), len(plan), Q)
+
+        def launch(e0, e1):
             if induced:
                 _lib.check(L.desco_canonical_counts_match_dev(*head, e0, e1, out.data_ptr(), stream.cuda_stream),
                            "desco_canonical_counts_match_dev")
@@ -575,10 +578,7 @@ def canonical_counts_match_device(graphs: GraphSet, queries: Sequence, device="c
                 _lib.check(L.desco_canonical_counts_match_mode_dev(*head, 0, e0, e1, out.data_ptr(),
                                                                    stream.cuda_stream),
                            "desco_canonical_counts_match_mode_dev")
-            stream.synchronize()                # a fault of this slice surfaces here, before the next is enqueued
-            e0 = e1
-            if e0 >= E:
-                break
+        _sliced(d.E, slice_entries, stream, launch)
     return out
 
 
@@ -726,8 +726,7 @@ class _Labelled:
         if self.table_bytes() > _DEVICE_LABEL_TABLE_LIMIT_BYTES:
             return (f"the lookup table for {self.num_labels} labels and {self.kmax}-node queries takes "
                     f"{self.table_bytes()} bytes, above the budget of {_DEVICE_LABEL_TABLE_LIMIT_BYTES}")
-        n = np.diff(graphs.graph_ptr).astype(np.int64)
-        if int((n * ((n + 63) // 64)).sum()) > _DEVICE_BITSET_LIMIT_WORDS:
+        if int(_bitset_words(graphs).sum()) > _DEVICE_BITSET_LIMIT_WORDS:
             return "the adjacency bitsets are above the device path's limit"
         return None
 
@@ -770,9 +769,8 @@ def _labelled_host(graphs: GraphSet, lab: _Labelled, num_threads: int) -> torch.
 def _labelled_device_chunks(graphs: GraphSet, lab: _Labelled, dev, chunk_bytes=None):
     """Yields (first node, end node, [nodes, Q] int64 counts on ``dev``) for consecutive chunks of whole graphs."""
     L = _lib.lib()
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
-    table = t(lab.table(), np.int32)
-    coq = t(lab.classes(), np.int64)
+    table = _put(lab.table(), np.int32, dev)
+    coq = _put(lab.classes(), np.int64, dev)
     C, Q, G = lab.num_classes, lab.num_queries, graphs.num_graphs
     budget = _DEVICE_LABEL_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
     max_nodes = max(budget // (8 * (C + 2 * Q)), 1)
@@ -786,20 +784,13 @@ def _labelled_device_chunks(graphs: GraphSet, lab: _Labelled, dev, chunk_bytes=N
         g0 = g1
         if n1 == n0:
             continue
-        n = np.diff(sub.graph_ptr).astype(np.int64)
-        bit_off = np.concatenate([[0], np.cumsum(n * ((n + 63) // 64))]).astype(np.int64)
-        graph_ptr, rowptr = t(sub.graph_ptr, np.int64), t(sub.rowptr, np.int64)
-        col, node_graph = t(sub.col, np.int32), t(sub.node_graph_ids(), np.int32)
-        labels, bit_off_d = t(lab.node_labels[n0:n1], np.int32), t(bit_off[:-1], np.int64)
-        bits = torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev)
+        d = _DeviceGraphs(sub, dev)
+        labels = d.put(lab.node_labels[n0:n1], np.int32)
         out = torch.empty((n1 - n0, C), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             _lib.check(L.desco_canonical_counts_labelled_dev(
-                graph_ptr.data_ptr(), sub.num_graphs, n1 - n0, rowptr.data_ptr(), int(sub.col.shape[0]),
-                col.data_ptr() if col.numel() else None, node_graph.data_ptr(), bit_off_d.data_ptr(),
-                bits.data_ptr(), int(bit_off[-1]), labels.data_ptr(), lab.num_labels, table.data_ptr(),
-                table.numel(), lab.kmax, C, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                "desco_canonical_counts_labelled_dev")
+                *d.head, labels.data_ptr(), lab.num_labels, table.data_ptr(), table.numel(), lab.kmax, C,
+                out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "desco_canonical_counts_labelled_dev")
         yield n0, n1, out.index_select(1, coq)
 
 
@@ -968,9 +959,7 @@ def _labelled_match_device(graphs: GraphSet, lab: _Labelled, dev, slice_entries=
     """([num_nodes, num_classes] int64 counts on ``dev``, class_of_query)"""
     plan, coq = _match_plan_labelled(lab)
     C, largest = int(plan[0]), int(plan[3])
-    words = _bitset_words(graphs)
-    bit_off = np.concatenate([[0], np.cumsum(words)]).astype(np.int64)
-    N, G, E = graphs.num_nodes, graphs.num_graphs, int(graphs.col.shape[0])
+    N = graphs.num_nodes
     if N == 0 or lab.num_queries == 0:
         return torch.zeros((N, C), dtype=torch.int64, device=dev), coq
     if slice_entries is None:           # waves per launch = entries x largest bucket, whatever the number of records
@@ -978,22 +967,15 @@ def _labelled_match_device(graphs: GraphSet, lab: _Labelled, dev, slice_entries=
     slice_entries = int(slice_entries)
     if slice_entries < 1:
         raise ValueError("slice_entries must be positive")
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
-    graph_ptr, rowptr = t(graphs.graph_ptr, np.int64), t(graphs.rowptr, np.int64)
-    col, node_graph = t(graphs.col, np.int32), t(graphs.node_graph_ids(), np.int32)
-    bit_off_d, plan_d = t(bit_off[:-1] if G else bit_off, np.int64), t(plan, np.int32)
-    labels = t(lab.node_labels, np.int32)
-    bits = torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev)
+    d = _DeviceGraphs(graphs, dev)
+    plan_d, labels = d.put(plan, np.int32), d.put(lab.node_labels, np.int32)
     out = torch.zeros((N, C), dtype=torch.int64, device=dev)
     L = _lib.lib()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        e0 = 0
-        while True:
-            e1 = min(e0 + slice_entries, E)
-            head = (graph_ptr.data_ptr(), G, N, rowptr.data_ptr(), E, col.data_ptr() if col.numel() else None,
-                    node_graph.data_ptr(), bit_off_d.data_ptr(), bits.data_ptr(), int(bit_off[-1]), labels.data_ptr(),
-                    plan.ctypes.data, plan_d.data_ptr(), len(plan), C)
+        head = (*d.head, labels.data_ptr(), plan.ctypes.data, plan_d.data_ptr(), len(plan), C)
+
+        def launch(e0, e1):
             if induced:
                 _lib.check(L.desco_canonical_counts_match_labelled_dev(*head, e0, e1, out.data_ptr(),
                                                                        stream.cuda_stream),
@@ -1002,10 +984,7 @@ def _labelled_match_device(graphs: GraphSet, lab: _Labelled, dev, slice_entries=
                 _lib.check(L.desco_canonical_counts_match_labelled_mode_dev(*head, 0, e0, e1, out.data_ptr(),
                                                                             stream.cuda_stream),
                            "desco_canonical_counts_match_labelled_mode_dev")
-            stream.synchronize()                # a fault of this slice surfaces here, before the next is enqueued
-            e0 = e1
-            if e0 >= E:
-                break
+        _sliced(d.E, slice_entries, stream, launch)
     return out, coq
 
 
