@@ -211,6 +211,37 @@ size_t desco_graph_tconv_dev_workspace(int64_t num_edges);
 int desco_graph_tconv_dev(const int64_t* rowptr, const int32_t* col, int64_t node0, int64_t num_nodes, int64_t edge0,
                           int64_t num_edges, int32_t* vrowptr, int32_t* vcol, void* workspace, desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Data-set statistics: graph features of node sets (csrc/subgraph_stats.cpp, csrc/subgraph_stats_dev.hip).
+ * Input: the CSR of a graph set over global node ids (rowptr int64 [num_nodes + 1], col int32; symmetric, loop free,
+ * rows ascending) and S node sets: set s = set_nodes[set_ptr[s] .. set_ptr[s+1]), global ids of ONE graph, strictly
+ * ascending.  For a set M: H = G[M]; C = the connected component of H with the most nodes, a tie going to the
+ * component that holds the smallest id.  Output per set:
+ *   out_i64[s][6] = { members = |M|, n = |C|, m = edges of C, diameter of C (0 for n = 1),
+ *                     dist_sum = sum of d(s,t) over ORDERED pairs s != t of C, triangles of C }
+ *   out_f64[s]    = clustering_sum = sum over v in C of 2 T(v) / (d(v) (d(v) - 1)), a term being 0 for d(v) < 2.
+ * Each term is one fp64 division of two exact integers; the terms are summed by the balanced pairwise tree over the
+ * positions of the members in M (position i meets position i + s at stride s = 1, 2, 4, ..; positions outside C and
+ * beyond |M| are +0.0), the same on both sides.  An empty set gets zeros.
+ *
+ * desco_subgraph_stats: HOST arrays, sets of any size (queue BFS, no |M|^2 memory); OpenMP over sets, and over the
+ *   sources of a set above 4096 members (num_threads 0 = the runtime's default); the result does not depend on
+ *   num_threads.  DESCO_EINVAL naming the argument for: a null pointer with num_sets > 0, a set_ptr that is not
+ *   monotone, an id outside the graph, a set that is not strictly ascending -- before any work.
+ * desco_subgraph_stats_dev: DEVICE arrays.  One launch on `stream` for the sets set_ids[0 .. num_ids) (int64 indices
+ *   into set_ptr, the caller's responsibility), each of at most 64 * words members, words in {1, 2, 4, 8, 16} (any
+ *   other value: DESCO_EINVAL naming `words`); only the rows of those sets are written.  A set with more members than
+ *   64 * words, with an id outside the graph or not strictly ascending gets members and n = -1 (the rest 0) and no
+ *   other work: the caller passes those rows to desco_subgraph_stats.  Null pointers and misaligned 64-bit arrays are
+ *   refused by name before any launch.  No allocation, no synchronisation, no atomics on global memory; equal to the
+ *   host routine bit for bit, the fp64 field included, whichever bucket a set runs in.
+ * ------------------------------------------------------------------------------------------ */
+int desco_subgraph_stats(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, const int64_t* set_ptr,
+                         const int32_t* set_nodes, int64_t num_sets, int num_threads, int64_t* out_i64, double* out_f64);
+int desco_subgraph_stats_dev(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, const int64_t* set_ptr,
+                             const int32_t* set_nodes, const int64_t* set_ids, int64_t num_ids, int words,
+                             int64_t* out_i64, double* out_f64, desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
