@@ -82,6 +82,9 @@ SIGNATURES = {
     "desco_orbit_table": (c_int, [vp, vp, vp, i32, vp, vp, vp]),
     "desco_orbit_counts": (c_int, [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
     "desco_orbit_counts_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, vp, vp]),
+    "desco_edge_orbit_table": (c_int, [vp, vp, vp, i32, vp, vp, vp]),
+    "desco_edge_orbit_counts": (c_int, [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "desco_edge_orbit_counts_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i32, i32, vp, vp]),
     "desco_canonical_label_classes": (c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     "desco_canonical_counts_labelled": (c_int, [vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp]),
     "desco_canonical_label_table_size": (i64, [i32, i32]),

@@ -211,6 +211,159 @@ __global__ __launch_bounds__(GT_THREADS) void go_count_kernel(GoArgs a) {
   }
 }
 
+// ---- edge orbit counts (edge graphlet degree vectors): C ABI desco_edge_orbit_counts_dev -------------------------------
+//   out[row of {a,b}][column] = #{connected subsets S containing a and b whose induced subgraph is a requested query,
+//   the edge {a,b} in the edge orbit that the column stands for}; eorb[(ESU_OFF[k] + mask) * 10 + p] = the column of
+//   the pair with pair bit p of the subset's positions, or -1 (class not asked for, or the pair is no edge).
+// The enumeration is the one above (same items, same lanes, same order).  A subset of k nodes updates up to k(k-1)/2
+// rows, and a row has to be found from two node ids.  As in the node-orbit kernel, adds that share a destination are
+// summed on chip first:
+//   * the item's own edge {S[0], S[1]} (pair bit 0; its row is entry_row[e]) belongs to the whole wave: 4 banks of u32
+//     columns per wave in LDS, flushed with one atomic per non-zero column when the wave ends.
+//     NO COUNT IS LOST in a u32 cell: every update is one LDS atomic add of lo < 2^32 that returns the cell's old value,
+//     so old + lo < 2^33 and the add wraps at most once, exactly when old > ~lo; the updates of a cell are serialised,
+//     so every wrap is seen by the one update that caused it, and that update hands 2^32 to the global cell at once
+//     (the part of n above 2^32 goes there directly).  The cell keeps the sum modulo 2^32 and the flush adds that
+//     remainder: the global cell receives the exact sum.
+//   * the edges among the nodes chosen before the last one are shared by the subsets of a candidate loop that have the
+//     same table row: ONE RUN per level in registers, flushed (one global atomic per edge, adding the run length; the
+//     own edge to LDS) when the table row changes or the loop ends.  Their rows were found when the nodes were pushed
+//     and travel in the path value (GePath), indexed by pair bit.
+//   * the edges at the node chosen last change with every subset: one global 64-bit atomic each.  The row of
+//     {S[ci], u} is the row of the CSR entry at which the candidate was found; the rows of the other edges at u are
+//     found by bisection in the (ascending) adjacency row of the earlier node, where the bitset says u is.
+// Integer adds commute: the result equals the host's bit for bit and does not change from call to call.
+constexpr int GE_MAXC = 69, GE_CPAD = 72, GE_BANKS = 4, GE_WAVES = GT_THREADS / 64, GE_PAIRS = 10;
+
+struct GeArgs {
+  const int64_t* graph_ptr;
+  const int64_t* rowptr;
+  const int32_t* col;
+  const int32_t* node_graph;
+  const int64_t* bit_off;
+  const unsigned long long* bits;
+  const int32_t* entry_row;          // [num_entries] out row of the entry's edge
+  const int16_t* eorb;               // [1098][10]
+  int kmax, C;
+  int64_t num_nodes, num_entries;
+  unsigned long long* out;           // [num_rows][C]
+};
+
+struct GePath {
+  int r[GE_PAIRS];                   // out row of the pair with that pair bit, where the pair is an edge
+};
+
+struct GeVisitor {
+  static constexpr bool kWithEntry = true;
+  using Path = GePath;
+  using Level = GoRun;
+  const int16_t* eorb;
+  const int32_t* entry_row;
+  const int64_t* rowptr;             // of this graph's nodes (local id)
+  const int32_t* col;
+  int32_t base;                      // the graph's first node
+  unsigned* tally;                   // this lane's bank of the wave's columns: [GE_CPAD]
+  unsigned long long* out;
+  unsigned long long* out_own;       // out row of the item's edge
+  int C;
+
+  // add n to the wave's column of the item's own edge (see NO COUNT IS LOST above)
+  __device__ __forceinline__ void wave_add(int column, unsigned long long n) const {
+    if (n >> 32) atomicAdd(out_own + column, n & ~0xffffffffull);
+    const unsigned lo = (unsigned)n;
+    if (lo == 0) return;
+    const unsigned old = atomicAdd(tally + column, lo);
+    if (old > ~lo) atomicAdd(out_own + column, 1ull << 32);                  // the cell wrapped
+  }
+  // the CSR entry (s, u) for an edge {s, u}: u is in the ascending row of s, which therefore is not empty
+  __device__ __forceinline__ int64_t entry_of(int s, int u) const {
+    int64_t lo = rowptr[s], hi = rowptr[s + 1];
+    const int32_t want = base + u;
+    while (hi - lo > 1) {            // last entry with col <= want
+      const int64_t mid = (lo + hi) >> 1;
+      if (col[mid] <= want) lo = mid; else hi = mid;
+    }
+    return lo;
+  }
+  // u becomes node number NS: the rows of its edges to S[0..NS-1]
+  template <int NS>
+  __device__ __forceinline__ Path push_at(Path p, const int (&S)[ESU_KMAX], int u, unsigned ab, int ci,
+                                          int64_t e) const {
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+      if (ab >> j & 1) p.r[NS * (NS - 1) / 2 + j] = entry_row[j == ci ? e : entry_of(S[j], u)];
+    return p;
+  }
+  // the run of the loop that chose node number NS goes out: the edges among S[0..NS-1]
+  template <int NS>
+  __device__ __forceinline__ void close_at(const int (&)[ESU_KMAX], const Path& p, GoRun& run) const {
+    if (run.n == 0) return;
+    const int16_t* row = eorb + run.t * GE_PAIRS;
+    wave_add(row[0], run.n);
+#pragma unroll
+    for (int b = 1; b < NS * (NS - 1) / 2; ++b) {
+      const int column = row[b];
+      if (column >= 0) atomicAdd(out + (int64_t)p.r[b] * C + column, run.n);
+    }
+    run.n = 0;
+  }
+  template <int K>
+  __device__ __forceinline__ void found(const int (&S)[ESU_KMAX], int, unsigned mask, const Path& p, GoRun& run) const {
+    const int t = GT_OFF_DEV[K] + (int)mask;
+    const int16_t* row = eorb + t * GE_PAIRS;
+    if (row[0] < 0) return;          // pair bit 0 is the item's edge: set in every mask, so this is "class not asked for"
+#pragma unroll
+    for (int b = (K - 1) * (K - 2) / 2; b < K * (K - 1) / 2; ++b) {
+      const int column = row[b];
+      if (column >= 0) atomicAdd(out + (int64_t)p.r[b] * C + column, 1ull);
+    }
+    if (run.n && run.t != t) close_at<K - 1>(S, p, run);
+    run.t = t;
+    ++run.n;
+  }
+};
+
+__global__ __launch_bounds__(GT_THREADS) void ge_count_kernel(GeArgs a) {
+  __shared__ unsigned tally[GE_WAVES * GE_BANKS * GE_CPAD];
+  const int tid = threadIdx.x, lane = tid & 63;
+  unsigned* wave_tally = tally + (tid >> 6) * (GE_BANKS * GE_CPAD);         // private to this wave: no block barrier
+  const int64_t e = (int64_t)blockIdx.x * GE_WAVES + (tid >> 6);            // one wave per entry
+  if (e >= a.num_entries) return;
+  const int64_t v = esu_row_of_entry(a.rowptr, a.num_nodes, e);
+  const EsuGraph c = esu_graph_of(a.graph_ptr, a.rowptr, a.col, a.node_graph, a.bit_off, a.bits, v, a.kmax);
+  const int u0 = (int)(a.col[e] - c.base);
+  if (u0 >= c.lv) return;                          // (wave-uniform) the root is the maximum of its subsets
+  GeVisitor vis;
+  vis.eorb = a.eorb;
+  vis.entry_row = a.entry_row;
+  vis.rowptr = a.rowptr + c.base;
+  vis.col = a.col;
+  vis.base = (int32_t)c.base;
+  vis.C = a.C;
+  vis.tally = wave_tally + (lane & (GE_BANKS - 1)) * GE_CPAD;
+  vis.out = a.out;
+  vis.out_own = a.out + (int64_t)a.entry_row[e] * a.C;
+  for (int i = lane; i < GE_BANKS * GE_CPAD; i += 64) wave_tally[i] = 0;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (lane == 0) {
+    const int column = a.eorb[(GT_OFF_DEV[2] + 1) * GE_PAIRS];
+    if (column >= 0) vis.wave_add(column, 1);
+  }
+  GePath path{};
+  esu_wave_walk(c, vis, v, e, u0, lane, path);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (int column = lane; column < a.C; column += 64) {                    // contiguous cells of the item's row
+    unsigned long long n = 0;
+#pragma unroll
+    for (int b = 0; b < GE_BANKS; ++b) n += wave_tally[b * GE_CPAD + column];
+    if (n) atomicAdd(vis.out_own + column, n);
+  }
+}
+
 // NON-INDUCED counts of small queries from the census of ALL connected k-node classes (the enumerator above visits
 // every connected k-subset once, so the census costs what one induced column costs):
 //   out[v][q] (+)= sum_c counts[v][c] * m[c][q],   m[c][q] = occurrences of query q in class c (exact, int64).
@@ -319,6 +472,33 @@ extern "C" int desco_orbit_counts_dev(const int64_t* graph_ptr, int64_t num_grap
            orbit_table, kmax, num_columns, num_nodes, num_entries, reinterpret_cast<unsigned long long*>(out)};
   hipLaunchKernelGGL(go_count_kernel, dim3((unsigned)wblocks), dim3(GT_THREADS), 0, s, a);
   return launch_status("desco_orbit_counts_dev");
+}
+
+extern "C" int desco_edge_orbit_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                           const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                           const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                           int64_t num_words, const int32_t* entry_row, int64_t num_rows,
+                                           const int16_t* edge_orbit_table, int kmax, int num_columns, int64_t* out,
+                                           desco_stream_t stream) {
+  if (num_nodes == 0 || num_columns == 0 || num_rows == 0 || num_entries == 0) return 0;
+  if (!graph_ptr || !rowptr || !col || !node_graph || !bit_off || !bits || !entry_row || !edge_orbit_table || !out ||
+      num_graphs < 0 || num_nodes < 0 || num_entries < 0 || num_words < 0 || num_rows < 0 || num_rows > num_entries ||
+      kmax < 2 || kmax > GT_KMAX || num_columns < 0 || num_columns > GE_MAXC)
+    return fail(DESCO_EINVAL,
+                "desco_edge_orbit_counts_dev: bad argument (queries of 2..5 nodes, at most 69 columns)");
+  if (num_entries > INT32_MAX) return fail(DESCO_EINVAL, "desco_edge_orbit_counts_dev: too many edges");
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(out, 0, (size_t)num_rows * num_columns * 8, s) != hipSuccess)
+    return launch_status("desco_edge_orbit_counts_dev: memset");
+  if (const int rc = gt_build_bitsets(graph_ptr, rowptr, col, node_graph, bit_off, bits, num_words, num_nodes,
+                                      num_entries, stream, "desco_edge_orbit_counts_dev"))
+    return rc;
+  const int64_t wblocks = (num_entries + GE_WAVES - 1) / GE_WAVES;
+  GeArgs a{graph_ptr, rowptr, col, node_graph, bit_off, reinterpret_cast<const unsigned long long*>(bits),
+           entry_row, edge_orbit_table, kmax, num_columns, num_nodes, num_entries,
+           reinterpret_cast<unsigned long long*>(out)};
+  hipLaunchKernelGGL(ge_count_kernel, dim3((unsigned)wblocks), dim3(GT_THREADS), 0, s, a);
+  return launch_status("desco_edge_orbit_counts_dev");
 }
 
 extern "C" int desco_canonical_noninduced_transform_dev(const int64_t* counts, int64_t ldc, const int64_t* m,

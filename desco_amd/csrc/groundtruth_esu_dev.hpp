@@ -1,5 +1,5 @@
-// THE device ESU walk of the exact ground-truth kernels (gt_count_kernel and go_count_kernel in groundtruth_dev.hip,
-// gtl_count_kernel in groundtruth_label_dev.hip): each kernel is a visitor over it.
+// THE device ESU walk of the exact ground-truth kernels (gt_count_kernel, go_count_kernel and ge_count_kernel in
+// groundtruth_dev.hip, gtl_count_kernel in groundtruth_label_dev.hip): each kernel is a visitor over it.
 //
 // Enumeration: ESU without extension lists.  In ESU a node u enters the extension set when the FIRST subset node
 // adjacent to it is added, and choices are made in list order; with key(u) = (insertion index of that first
@@ -20,7 +20,13 @@
 //   push<NS>(path, u)                 the path value with u as node number NS
 //   found<K>(S, u, mask, path, level) the K-subset S[0..K-2] + u with induced mask `mask` was found
 //   close<NS>(S, level)               the loop that chose node number NS of S[0..NS-1] has ended
+// A visitor that declares `static constexpr bool kWithEntry = true` (the edge-orbit kernel) is told where a candidate
+// was found and gets the path value when a loop ends; it supplies, in place of push and close,
+//   push_at<NS>(path, S, u, ab, ci, e)  ab = adjacency bits of u to S[0..NS-1]; e = the CSR entry (S[ci], u)
+//   close_at<NS>(S, path, level)        path = the path value of S[0..NS-1]
 #pragma once
+#include <type_traits>
+
 #include "common_device.hpp"
 #include "groundtruth_esu.hpp"
 
@@ -74,6 +80,25 @@ __device__ __forceinline__ unsigned esu_adj(const EsuGraph& g, int a, int b) {
   return (unsigned)(g.bits[(int64_t)a * g.words + (b >> 6)] >> (b & 63)) & 1u;
 }
 
+template <class V, class = void>
+struct esu_with_entry : std::false_type {};
+template <class V>
+struct esu_with_entry<V, std::void_t<decltype(V::kWithEntry)>> : std::true_type {};
+
+template <int NS, class V>
+__device__ __forceinline__ typename V::Path esu_push(V& vis, const int (&S)[ESU_KMAX], typename V::Path path, int u,
+                                                     unsigned ab, int ci, int64_t e) {
+  if constexpr (esu_with_entry<V>::value) return vis.template push_at<NS>(path, S, u, ab, ci, e);
+  else return vis.template push<NS>(path, u);
+}
+
+template <int NS, class V>
+__device__ __forceinline__ void esu_close(V& vis, const int (&S)[ESU_KMAX], typename V::Path path,
+                                          typename V::Level& level) {
+  if constexpr (esu_with_entry<V>::value) vis.template close_at<NS>(S, path, level);
+  else vis.template close<NS>(S, level);
+}
+
 template <int NS, class V>
 __device__ void esu_extend(const EsuGraph& g, V& vis, const int (&S)[ESU_KMAX], unsigned mask, typename V::Path path,
                            int ci0, int cp0);
@@ -96,7 +121,7 @@ __device__ __forceinline__ bool esu_try(const EsuGraph& g, V& vis, const int (&S
   }
   if (in_s || (ab & ((1u << ci) - 1u))) return true;     // u entered the extension set earlier
   const unsigned m2 = mask | (ab << (NS * (NS - 1) / 2));
-  const typename V::Path p2 = vis.template push<NS>(path, u);
+  const typename V::Path p2 = esu_push<NS>(vis, S, path, u, ab, ci, e);
   vis.template found<NS + 1>(S, u, m2, p2, level);
   if constexpr (NS + 1 < ESU_KMAX) {
     if (NS + 1 < g.kmax) {
@@ -122,7 +147,7 @@ __device__ void esu_extend(const EsuGraph& g, V& vis, const int (&S)[ESU_KMAX], 
     for (int64_t e = r0 + (ci == ci0 ? cp0 : 0); e < r1; ++e)
       if (!esu_try<NS>(g, vis, S, mask, path, ci, r0, e, level)) break;
   }
-  vis.template close<NS>(S, level);
+  esu_close<NS>(vis, S, path, level);
 }
 
 // The wave's part of the item (v, u0) at CSR entry e: the candidates for the third node -- v's row behind u0, then
@@ -142,7 +167,7 @@ __device__ __forceinline__ void esu_wave_walk(const EsuGraph& g, V& vis, int64_t
     else
       esu_try<2>(g, vis, S, 1u, path, 1, w0, w0 + (p - rest), level);
   }
-  vis.template close<2>(S, level);
+  esu_close<2>(vis, S, path, level);
 }
 
 }  // namespace desco

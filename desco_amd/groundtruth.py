@@ -334,13 +334,13 @@ def _orbit_structure(k: int, edges: tuple):
     return orbit_of, members, best, best_p
 
 
-def _orbit_queries(queries):
+def _orbit_queries(queries, what="orbit counts"):
     """The flattened, checked queries of an orbit call: [(k, edge tuple)]."""
     if queries is None:
         return [(k, tuple(e)) for k in (2, 3, 4, 5) for _, e in census_classes(k)]
     flat = _flatten_queries(queries)[0]
     if any(n < 2 or n > 5 for n, _ in flat):
-        raise RuntimeError("orbit counts take queries of 2..5 nodes")
+        raise RuntimeError(what + " take queries of 2..5 nodes")
     if flat:
         match_plan(flat)                # refuses disconnected queries and loops, naming the reason
     return [(n, tuple((int(a), int(b)) for a, b in e)) for n, e in flat]
@@ -373,6 +373,12 @@ def _orbit_select(flat, induced):
         rep_orbit_of, _, _, r = _orbit_structure(k, tuple(census_classes(k)[ci][1]))
         r_inv = {x: i for i, x in enumerate(r)}      # query position a -> canonical p[a] -> class position r^-1(p[a])
         wanted += [(k, ci, rep_orbit_of[r_inv[p[mem[0]]]]) for mem in members]
+    return _class_columns(wanted, induced, lambda k, e: len(_orbit_structure(k, e)[1]))
+
+
+def _class_columns(wanted, induced, orbits_of):
+    """The second half of ``_orbit_select``, for node and edge orbits alike: ``wanted`` = per output column (k, class,
+    orbit of the class), ``orbits_of(k, edges)`` = the number of orbits of a class representative."""
     sizes = sorted({k for k, _, _ in wanted})
     used = {(k, ci) for k, ci, _ in wanted}
     reps, start, first, width, col = [], {}, {}, {}, 0
@@ -383,7 +389,7 @@ def _orbit_select(flat, induced):
                 continue
             reps.append((k, list(e)))
             start[(k, ci)] = col
-            col += len(_orbit_structure(k, tuple(e))[1])
+            col += orbits_of(k, tuple(e))
         width[k] = col - first[k]
     index = np.array([start[(k, ci)] + o for k, ci, o in wanted], dtype=np.int64)
     return reps, index, sizes, first, width
@@ -505,6 +511,222 @@ def orbit_counts(graphs: GraphSet, queries=None, num_threads: int = 0, backend: 
         out = torch.from_numpy(np.ascontiguousarray(raw[:, index]))
     if per_query:
         owner = torch.tensor([qi for qi, _, _ in orbit_columns(flat)], dtype=torch.long)
+        summed = torch.zeros((out.shape[0], len(flat)), dtype=torch.int64)
+        out = summed.index_add_(1, owner, out)
+    return out.double()
+
+
+# ---- edge orbit counts (edge graphlet degree vectors) ------------------------------------------------------------------
+# Definitions (include/desco_hip.h, "EDGE ORBIT COUNTS"):
+#   query: connected, loop-free, 2..5 nodes; an nx.Graph whose positions are list(q.nodes), or (n, edges)
+#   edge orbits of a query: the orbits of Aut(q) on its edge set; the edges are ordered by pair_bit(a, b) = b(b-1)/2 + a
+#                 (a < b) and the orbits numbered in ascending order of their smallest member
+#   rows: one per undirected edge of the GraphSet, in the order of the CSR entries (v, u) with u < v (ascending v, then
+#                 ascending u: the work items of the ESU walk); ``edge_orbit_rows`` gives their endpoints
+#   induced:      eorb[e][(q,o)] = #{connected S containing both ends of e : G[S] isomorphic to q by a map that takes e
+#                 into orbit o}
+#   non-induced:  #{injective edge-preserving f : q -> G with e in f(orbit o)} / |Aut(q)|: copies of q (a copy being its
+#                 edge set) in which e is an edge of the copy and plays role o
+#   columns: the queries in the given order and, inside a query, its edge orbits in order; queries=None means
+#            census_classes(2) + .. + census_classes(5): 30 classes, 1 + 2 + 10 + 56 = 69 columns.  The numbering is this
+#            project's own (ORCA's 68 edge orbits leave out the single edge).
+#   both forms: per graph, sum_e eorb[e][(q,o)] = |o| * sum_v canonical_counts[v][q]; the 2-node column is 1; the
+#   triangle column is the number of common neighbours of the ends; the P3 column is deg(a) + deg(b) - 2 (induced: less
+#   twice the triangles); for every node v, sum_{e at v} eorb[e][(q,o)] = sum_p orbit_counts[v][(q,p)] * inc_q[p][o] with
+#   inc_q[p][o] = the edges of orbit o at a node of node orbit p; relabelling the nodes of G permutes the rows.
+@functools.lru_cache(maxsize=None)
+def _edge_orbit_structure(k: int, edges: tuple):
+    """({edge (a, b), a < b: its orbit}, member edges of every orbit in pair-bit order) of the graph (k, edges)."""
+    mine = sorted({(min(a, b), max(a, b)) for a, b in edges}, key=lambda e: _pair_bit(*e))
+    mask = _relabelled_mask(edges, range(k))
+    low = {e: _pair_bit(*e) for e in mine}
+    for p in _perms(k):
+        if _relabelled_mask(edges, p) == mask:
+            for a, b in mine:
+                low[(a, b)] = min(low[(a, b)], _pair_bit(p[a], p[b]))
+    firsts = sorted(set(low.values()))
+    orbit_of = {e: firsts.index(low[e]) for e in mine}
+    return orbit_of, tuple(tuple(e for e in mine if orbit_of[e] == o) for o in range(len(firsts)))
+
+
+def edge_orbit_columns(queries=None):
+    """The columns of ``edge_orbit_counts``: a list of (query index, orbit index, member edges (a, b) with a < b).
+    ``queries=None``: the 30 connected graphs of 2..5 nodes in ``census_classes`` order, 69 columns."""
+    return [(qi, o, mem) for qi, (k, e) in enumerate(_orbit_queries(queries, "edge orbit counts"))
+            for o, mem in enumerate(_edge_orbit_structure(k, e)[1])]
+
+
+def edge_orbit_rows(graphs: GraphSet) -> torch.Tensor:
+    """The rows of ``edge_orbit_counts``: int64 [M, 2], the endpoints (u, v), u < v, global ids, of every undirected
+    edge in the order of the CSR entries (v, u) with u < v."""
+    rows = np.repeat(np.arange(graphs.num_nodes, dtype=np.int64), np.diff(graphs.rowptr))
+    col = np.asarray(graphs.col, dtype=np.int64)
+    lower = col < rows
+    return torch.from_numpy(np.stack([col[lower], rows[lower]], axis=1))
+
+
+def _num_edges(graphs: GraphSet) -> int:
+    """M, the number of rows: the CSR entries (v, u) with u < v."""
+    rows = np.repeat(np.arange(graphs.num_nodes, dtype=np.int64), np.diff(graphs.rowptr))
+    return int((np.asarray(graphs.col) < rows).sum())
+
+
+def _entry_rows_device(d: "_DeviceGraphs"):
+    """(int32 [E] on the device: the row of the edge of every CSR entry, both directions of an edge naming one row; M).
+    Index plumbing on the device (the CSR is there already): a lower entry's row is its rank among the lower entries;
+    an upper entry (v, u) takes the row of its twin (u, v), found among the ascending keys of the lower entries."""
+    _, rowptr, col = d._keep[:3]
+    if d.E == 0:
+        return torch.zeros(0, dtype=torch.int32, device=d.dev), 0
+    rows = torch.repeat_interleave(torch.arange(d.N, device=d.dev), rowptr[1:] - rowptr[:-1], output_size=d.E)
+    c = col.long()
+    lower = c < rows
+    entry = torch.cumsum(lower, 0) - 1
+    keys, twin = (rows * d.N + c)[lower], (c * d.N + rows)[~lower]
+    M = int(keys.numel())
+    found = torch.searchsorted(keys, twin)
+    if 2 * M != d.E or M >= 2 ** 30 or not bool((keys[found.clamp(max=M - 1)] == twin).all()):
+        raise RuntimeError("edge orbit counts take a symmetric, loop-free CSR of fewer than 2^30 edges")
+    entry[~lower] = found
+    return entry.int(), M
+
+
+def _edge_orbit_select(flat, induced):
+    """``_orbit_select`` for edge orbits: every query is computed as its census class and its columns are mapped back
+    through the position relabelling (query edge (a, b) -> the class representative's edge at the same place)."""
+    wanted = []
+    for k, e in flat:
+        _, _, canon, p = _orbit_structure(k, e)
+        ci = _census_class_of_mask(k)[canon]
+        rep_edges = tuple(census_classes(k)[ci][1])
+        rep_orbit_of = _edge_orbit_structure(k, rep_edges)[0]
+        r = _orbit_structure(k, rep_edges)[3]
+        r_inv = {x: i for i, x in enumerate(r)}
+        for mem in _edge_orbit_structure(k, e)[1]:
+            a, b = (r_inv[p[x]] for x in mem[0])
+            wanted.append((k, ci, rep_orbit_of[(min(a, b), max(a, b))]))
+    return _class_columns(wanted, induced, lambda k, e: len(_edge_orbit_structure(k, e)[1]))
+
+
+_edge_orbit_transform = {}          # k -> int64 [columns of size k, columns of size k]: computed once per process
+
+
+def edge_orbit_noninduced_matrix(k: int) -> np.ndarray:
+    """T_k, int64 [C_k, C_k] over the edge-orbit columns of ``census_classes(k)``: T_k[(c,o')][(q,o)] = the copies of q
+    in the class representative c in which one fixed edge of orbit o' has role o.  noninduced = induced @ T_k (a
+    k-subset whose induced subgraph is c, seen from an edge of orbit o', holds that many copies of q with the edge in
+    role o).  By exhaustive enumeration of the k! maps of every pair of classes."""
+    if k not in _edge_orbit_transform:
+        classes = [(tuple(e), _edge_orbit_structure(k, tuple(e))) for _, e in census_classes(k)]
+        starts = np.concatenate([[0], np.cumsum([len(st[1]) for _, st in classes])])
+        T = np.zeros((starts[-1], starts[-1]), dtype=np.int64)
+        for qi, (qe, (q_orbit_of, q_members)) in enumerate(classes):
+            aut = sum(1 for p in _perms(k) if _relabelled_mask(qe, p) == _relabelled_mask(qe, range(k)))
+            for ci, (ce, (_, c_members)) in enumerate(classes):
+                cmask = _relabelled_mask(ce, range(k))
+                hits = np.zeros((k * (k - 1) // 2, len(q_members)), dtype=np.int64)     # [pair bit of c][role]
+                for f in _perms(k):
+                    if _relabelled_mask(qe, f) & ~cmask == 0:
+                        for (a, b), o in q_orbit_of.items():
+                            hits[_pair_bit(f[a], f[b]), o] += 1
+                for o2, mem in enumerate(c_members):
+                    bits = [_pair_bit(a, b) for a, b in mem]
+                    assert (hits[bits] == hits[bits[0]]).all() and (hits[bits[0]] % aut == 0).all()
+                    T[starts[ci] + o2, starts[qi]:starts[qi + 1]] = hits[bits[0]] // aut
+        _edge_orbit_transform[k] = T
+    return _edge_orbit_transform[k]
+
+
+def _edge_orbit_table(reps):
+    _, q_nodes, q_edge_ptr, q_edges = _flatten_queries(reps)
+    table = np.empty((1098, 10), dtype=np.int16)
+    ncol, kmax = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.lib().desco_edge_orbit_table(q_nodes.ctypes.data, q_edge_ptr.ctypes.data,
+                                                 q_edges.ctypes.data if len(q_edges) else None, len(q_nodes),
+                                                 table.ctypes.data, ctypes.byref(ncol), ctypes.byref(kmax)),
+               "desco_edge_orbit_table")
+    return table, int(ncol.value), int(kmax.value)
+
+
+def _edge_orbit_device_raw(graphs: GraphSet, reps, dev) -> torch.Tensor:
+    """desco_edge_orbit_counts_dev on pairwise non-isomorphic ``reps``: int64 [M, columns of reps] on ``dev``."""
+    table, C, kmax = _edge_orbit_table(reps)
+    if graphs.col.shape[0] == 0 or C == 0:           # no edges: no rows
+        return torch.zeros((_num_edges(graphs), C), dtype=torch.int64, device=dev)
+    d = _DeviceGraphs(graphs, dev)
+    entry_row_d, M = _entry_rows_device(d)
+    out = torch.empty((M, C), dtype=torch.int64, device=dev)
+    table_d = d.put(table, np.int16)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().desco_edge_orbit_counts_dev(*d.head, entry_row_d.data_ptr(), M, table_d.data_ptr(), kmax,
+                                                          C, out.data_ptr(),
+                                                          torch.cuda.current_stream(dev).cuda_stream),
+                   "desco_edge_orbit_counts_dev")
+    return out
+
+
+def _edge_orbit_host_raw(graphs: GraphSet, reps, num_threads: int) -> np.ndarray:
+    """desco_edge_orbit_counts on pairwise non-isomorphic ``reps``: int64 [M, columns of reps]."""
+    _, q_nodes, q_edge_ptr, q_edges = _flatten_queries(reps)
+    out = np.zeros((_num_edges(graphs), _edge_orbit_table(reps)[1]), dtype=np.int64)
+    _lib.check(_lib.lib().desco_edge_orbit_counts(graphs.graph_ptr.ctypes.data, graphs.num_graphs,
+                                                  graphs.rowptr.ctypes.data, graphs.col.ctypes.data,
+                                                  q_nodes.ctypes.data, q_edge_ptr.ctypes.data,
+                                                  q_edges.ctypes.data if len(q_edges) else None, len(reps),
+                                                  num_threads, out.ctypes.data), "desco_edge_orbit_counts")
+    return out
+
+
+def edge_orbit_counts_device(graphs: GraphSet, queries=None, device="cuda", induced: bool = True) -> torch.Tensor:
+    """Exact per-edge orbit counts (definitions above) on the MI355X (csrc/groundtruth_dev.hip, ge_count_kernel): int64
+    [M, len(edge_orbit_columns(queries))] on ``device``, rows as ``edge_orbit_rows``.  Duplicate and isomorphic queries
+    are accepted: every class is enumerated once.  ``induced=False``: the edge-orbit census of the queries' sizes by the
+    same kernel, then the exact int64 transform ``edge_orbit_noninduced_matrix`` with
+    ``desco_canonical_noninduced_transform_dev`` (source columns in chunks of 32), without a round trip."""
+    flat = _orbit_queries(queries, "edge orbit counts")
+    dev = torch.device(device)
+    if not flat:
+        return torch.zeros((_num_edges(graphs), 0), dtype=torch.int64, device=dev)
+    reps, index, sizes, first, width = _edge_orbit_select(flat, induced)
+    raw = _edge_orbit_device_raw(graphs, reps, dev)
+    if not induced and raw.shape[0]:
+        full = torch.zeros_like(raw)
+        for k in sizes:
+            T = edge_orbit_noninduced_matrix(k)
+            src, dst = raw[:, first[k]:first[k] + width[k]], full[:, first[k]:first[k] + width[k]]
+            for c0 in range(0, width[k], 32):
+                _transform_device(src[:, c0:c0 + 32], T[c0:c0 + 32], dst, c0 > 0)
+        raw = full
+    return raw.index_select(1, torch.from_numpy(index).to(dev))
+
+
+def edge_orbit_counts(graphs: GraphSet, queries=None, num_threads: int = 0, backend: str = "auto",
+                      induced: bool = True, per_query: bool = False) -> torch.Tensor:
+    """Exact per-edge orbit counts -- the edge graphlet degree vector when ``queries`` is None (69 columns) -- as a
+    double [M, len(edge_orbit_columns(queries))] tensor on the CPU, one row per undirected edge (``edge_orbit_rows``;
+    definitions above).  ``backend``: "host" (OpenMP over graphs, ``num_threads`` threads), "device"
+    (``edge_orbit_counts_device``) or "auto": the device when a GPU is present and the adjacency bitsets fit
+    ``_DEVICE_BITSET_LIMIT_WORDS``.  ``induced=False``: the non-induced form.  ``per_query=True``: the orbits of every
+    query summed, [M, num_queries]: the copies of the query through the edge, the motif weight of that adjacent pair.
+    Raises RuntimeError for queries outside 2..5 nodes and for disconnected or looped ones."""
+    if backend not in ("auto", "host", "device"):
+        raise ValueError(f"unknown backend {backend!r}")
+    flat = _orbit_queries(queries, "edge orbit counts")
+    if backend == "auto":       # _device_eligible's conditions: a GPU and bitsets within the limit (the sizes are checked)
+        backend = "device" if flat and _device_eligible(graphs, np.array([2], dtype=np.int32)) else "host"
+    if backend == "device":
+        out = edge_orbit_counts_device(graphs, flat, induced=induced).cpu()
+    elif not flat:
+        out = torch.zeros((_num_edges(graphs), 0), dtype=torch.int64)
+    else:
+        reps, index, sizes, first, width = _edge_orbit_select(flat, induced)
+        raw = _edge_orbit_host_raw(graphs, reps, num_threads)
+        if not induced:
+            raw = np.concatenate([raw[:, first[k]:first[k] + width[k]] @ edge_orbit_noninduced_matrix(k)
+                                  for k in sizes], axis=1)
+        out = torch.from_numpy(np.ascontiguousarray(raw[:, index]))
+    if per_query:
+        owner = torch.tensor([qi for qi, _, _ in edge_orbit_columns(flat)], dtype=torch.long)
         summed = torch.zeros((out.shape[0], len(flat)), dtype=torch.int64)
         out = summed.index_add_(1, owner, out)
     return out.double()

@@ -246,6 +246,7 @@ class Workload:
         self.queries, self.query_ids = [], []
         self.canonical_count_truth = torch.tensor([[]])
         self.orbit_count_truth: Optional[torch.Tensor] = None
+        self.edge_orbit_count_truth: Optional[torch.Tensor] = None
         self.neighborhood_dataset: Optional[NeighborhoodDataset] = None
         self.gossip_dataset: Optional[GossipDataset] = None
         self.graphlet_count_truth: Optional[torch.Tensor] = None
@@ -338,6 +339,39 @@ class Workload:
         self.orbit_count_truth = truth
         if save_to_file and self.root:
             path = self._orbit_truth_path(queries, induced)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            torch.save(truth, path)
+        return truth
+
+    # ---- edge orbit counts (edge graphlet degree vectors): one row per undirected edge ---------------------------------
+    def _edge_orbit_truth_path(self, queries=None, induced=True):
+        """<root>/EdgeOrbitCountTruth/edge_orbit_columns_<C>_query_num_<Q>_query_len_sum_<S>[_noninduced].pt (the
+        file-name rule of the orbit cache); ``queries=None`` is the 69-column census of 2..5 nodes."""
+        from .groundtruth import _orbit_queries, edge_orbit_columns
+        flat = _orbit_queries(queries, "edge orbit counts")
+        name = "edge_orbit_columns_{:d}_query_num_{:d}_query_len_sum_{:d}{}.pt".format(
+            len(edge_orbit_columns(flat)), len(flat), sum(n for n, _ in flat), "" if induced else "_noninduced")
+        return os.path.join(self.root, "EdgeOrbitCountTruth", name)
+
+    def exist_edge_orbit_groundtruth(self, queries=None, induced=True) -> bool:
+        return os.path.exists(self._edge_orbit_truth_path(queries, induced))
+
+    def load_edge_orbit_groundtruth(self, queries=None, induced=True) -> torch.Tensor:
+        self.edge_orbit_count_truth = torch.load(self._edge_orbit_truth_path(queries, induced))
+        return self.edge_orbit_count_truth
+
+    def compute_edge_orbit_groundtruth(self, queries=None, induced=True, save_to_file=True,
+                                       num_workers=-1) -> torch.Tensor:
+        """Exact per-edge orbit counts of the dataset (``groundtruth.edge_orbit_counts``: [M, C] doubles, rows as
+        ``groundtruth.edge_orbit_rows``, the 69-column edge graphlet degree vector when ``queries`` is None), kept in
+        ``self.edge_orbit_count_truth`` and cached under ``<root>/EdgeOrbitCountTruth/``.  Unlabelled only."""
+        if self.use_node_feat:
+            raise NotImplementedError("edge orbit counts of labelled queries (--use_node_feature) are not implemented")
+        from .groundtruth import edge_orbit_counts
+        truth = edge_orbit_counts(self.dataset, queries, num_threads=max(num_workers, 0), induced=induced)
+        self.edge_orbit_count_truth = truth
+        if save_to_file and self.root:
+            path = self._edge_orbit_truth_path(queries, induced)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             torch.save(truth, path)
         return truth

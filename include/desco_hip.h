@@ -302,6 +302,43 @@ int desco_orbit_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t
                            uint64_t* bits, int64_t num_words, const int16_t* orbit_table, int kmax, int num_columns,
                            int64_t* out, desco_stream_t stream);
 
+/* EDGE ORBIT COUNTS (edge graphlet degree vectors): how many occurrences of a query run through the edge {a, b} of a
+ * graph, with the edge in a given role of the query (the chord of a diamond or its rim, ..).
+ *   Query: as for the orbit counts: connected, loop-free, 2..5 nodes, pairwise non-isomorphic.
+ *   Edge orbits of a query: the orbits of Aut(q) on the query's EDGE set.  The edges are ordered by their pair bit
+ *     b(b-1)/2 + a (a < b, the convention of the adjacency masks); the orbits are numbered 0, 1, .. in ascending order
+ *     of their smallest member.
+ *   Rows: one per undirected edge of the graph set, in the order of the CSR entries (v, u) with u < v (ascending v, then
+ *     ascending u) -- the work items of the ESU walk.
+ *   out[e][(q,o)] = #{connected node subsets S that contain both ends of e : G[S] isomorphic to q by a map that takes e
+ *     into edge orbit o}.
+ *   Columns: the queries in the given order and, inside a query, its edge orbits in order.  The 30 connected graphs of
+ *     2..5 nodes have 1 + 2 + 10 + 56 = 69 edge orbits.  (The numbering is this library's own; ORCA's 68 edge orbits
+ *     leave out the single edge.)
+ *   Per graph, sum_e out[e][(q,o)] = |o| * sum_v canonical count[v][q]; the column of the 2-node query is 1; the
+ *     triangle's is the number of common neighbours of a and b.
+ * HOST helper desco_edge_orbit_table: table[1098][10] = for k = 2..5 nodes and every adjacency mask on k nodes (the
+ *   offsets of desco_canonical_class_table) and every pair bit p of k nodes the column of that pair, when the mask's
+ *   class was asked for and the pair is an edge of the mask; else -1.  *num_columns, *kmax = the largest query.
+ *   DESCO_EINVAL naming "2..5 nodes", "connected", "isomorphic" or "bad query edge" for queries it does not take.
+ * HOST desco_edge_orbit_counts: the arguments of desco_orbit_counts; out: int64 [num_edges][num_columns], num_edges =
+ *   the number of CSR entries (v, u) with u < v, zeroed and filled.  OpenMP over graphs; the result does not depend on num_threads.
+ * DEVICE desco_edge_orbit_counts_dev (csrc/groundtruth_dev.hip): the arguments of desco_orbit_counts_dev, and after
+ *   num_words: entry_row, int32 [num_entries], the row of the edge of every CSR entry (both directions of an edge name
+ *   one row; every value in [0, num_rows)), and num_rows.  At most 69 columns, num_entries below 2^31.  out: int64
+ *   [num_rows][num_columns], zeroed and filled by the call, equal to the host's bit for bit.  Enqueues on `stream`,
+ *   does not allocate or synchronise. */
+int desco_edge_orbit_table(const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges, int num_queries,
+                           int16_t* table, int* num_columns, int* kmax);
+int desco_edge_orbit_counts(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr, const int32_t* col,
+                            const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges, int num_queries,
+                            int num_threads, int64_t* out);
+int desco_edge_orbit_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes, const int64_t* rowptr,
+                                int64_t num_entries, const int32_t* col, const int32_t* node_graph,
+                                const int64_t* bit_off, uint64_t* bits, int64_t num_words, const int32_t* entry_row,
+                                int64_t num_rows, const int16_t* edge_orbit_table, int kmax, int num_columns,
+                                int64_t* out, desco_stream_t stream);
+
 /* LABELLED queries (--use_node_feature): out[v][c] = #{S : max(S) = v, G[S] connected, and G[S] with its node
  * labels isomorphic to the labelled queries of class c} -- the reference's VF2 with node_match on the feature
  * (workload.py:327-348) divided by the labelled symmetry factor (data.py:61-68).  Node and query labels are integer

@@ -65,6 +65,9 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
     if getattr(args_opt, "orbit_truth", False) and node_feat_len != -1:
         raise NotImplementedError("--orbit_truth with --use_node_feature: orbit counts of labelled queries are not "
                                   "implemented")
+    if getattr(args_opt, "edge_orbit_truth", False) and node_feat_len != -1:
+        raise NotImplementedError("--edge_orbit_truth with --use_node_feature: edge orbit counts of labelled queries "
+                                  "are not implemented")
 
     devices = args_opt.gpu if isinstance(args_opt.gpu, list) else [args_opt.gpu]
     # len(devices) > 1: one process per GPU (started by __main__ below or by torch.distributed.run);
@@ -220,6 +223,8 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
             gdv = test_w.compute_orbit_groundtruth(induced=induced, num_workers=ncpu)
         pd.DataFrame(gdv.numpy(), columns=[f"({q},{o})" for q, o, _ in orbit_columns()]).to_csv(
             os.path.join(output_dir, f"orbit_node_{ds}.csv"))
+    if getattr(args_opt, "edge_orbit_truth", False):
+        write_edge_orbit_truth(test_w, output_dir, ds, induced, ncpu)
 
     sizes = sorted({len(q) for q in nx_queries})
     groupby = [[i for i, q in enumerate(nx_queries) if len(q) == s] for s in sizes]
@@ -243,6 +248,24 @@ def main(args_neighborhood, args_gossip, args_opt, train_neighborhood=True, trai
     return report
 
 
+def write_edge_orbit_truth(test_w, output_dir, ds, induced=True, num_workers=-1):
+    """--edge_orbit_truth: the exact edge graphlet degree vectors of the test set beside the predictions, one row per
+    undirected edge: its endpoints u < v (global node ids), then the 69 columns of the edge orbits of the connected graphs
+    of 2..5 nodes (groundtruth.edge_orbit_counts).  Returns the file's path."""
+    from desco_amd.groundtruth import edge_orbit_columns, edge_orbit_rows
+    if test_w.exist_edge_orbit_groundtruth(induced=induced):
+        egdv = test_w.load_edge_orbit_groundtruth(induced=induced)
+    else:
+        egdv = test_w.compute_edge_orbit_groundtruth(induced=induced, num_workers=num_workers)
+    table = pd.DataFrame(egdv.numpy(), columns=[f"({q},{o})" for q, o, _ in edge_orbit_columns()])
+    ends = edge_orbit_rows(test_w.dataset).numpy()
+    table.insert(0, "u", ends[:, 0])
+    table.insert(1, "v", ends[:, 1])
+    path = os.path.join(output_dir, f"orbit_edge_{ds}.csv")
+    table.to_csv(path)
+    return path
+
+
 def parse_args(argv=None):
     """(args, args_neighborhood, args_gossip, args_opt) of a command line: the reference's flag groups plus this
     build's own flags, which travel on ``args_opt``."""
@@ -264,6 +287,9 @@ def parse_args(argv=None):
     parser.add_argument("--orbit_truth", action="store_true", default=argparse.SUPPRESS,
                         help="also write the exact per-node orbit counts (73-column graphlet degree vector) of the test "
                              "set to <output_dir>/orbit_node_<test_dataset>.csv")
+    parser.add_argument("--edge_orbit_truth", action="store_true", default=argparse.SUPPRESS,
+                        help="also write the exact per-edge orbit counts (two endpoint columns, then the 69-column edge "
+                             "graphlet degree vector) of the test set to <output_dir>/orbit_edge_<test_dataset>.csv")
     args = parser.parse_args(argv)
     args_neighborhood, args_gossip, args_opt = split_namespaces(args)
     args_opt.precision = args.precision          # this build's flags (not in the reference's groups)
@@ -271,6 +297,8 @@ def parse_args(argv=None):
     args_opt.noninduced = args.noninduced
     if getattr(args, "orbit_truth", False):
         args_opt.orbit_truth = True
+    if getattr(args, "edge_orbit_truth", False):
+        args_opt.edge_orbit_truth = True
     return args, args_neighborhood, args_gossip, args_opt
 
 
