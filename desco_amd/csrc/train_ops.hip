@@ -402,8 +402,8 @@ extern "C" size_t desco_gemm_tn_workspace(int64_t m, int k, int n, int* splits_o
 extern "C" int desco_gemm_tn_f32(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t m,
                                  int k, int n, float* out, int64_t ldo, int accumulate,
                                  float* workspace, desco_stream_t stream) {
-  if (!a || !b || !out || !workspace || m < 0 || k <= 0 || n <= 0 || k % TK || n % TN || lda % 4 ||
-      ldb % 4 || mis16(a) || mis16(b))
+  if ((m > 0 && (!a || !b)) || !out || !workspace || m < 0 || k <= 0 || n <= 0 || k % TK || n % TN || lda % 4 ||
+      ldb % 4 || mis16(a) || mis16(b))   // (m == 0 reads no row and writes zeros: torch's empty tensors are NULL)
     return fail(DESCO_EINVAL, "desco_gemm_tn_f32: bad argument (k%64, n%64, 16-byte alignment)");
   int splits = 1;
   desco_gemm_tn_workspace(m, k, n, &splits);
@@ -506,7 +506,7 @@ extern "C" int desco_linear_bwd_w_multi_f32(int num, const desco_bwd_w_desc* d, 
 
 extern "C" int desco_colsum_f32(const float* x, int64_t ldx, int64_t m, int n, float* out,
                                 int accumulate, float* workspace, desco_stream_t stream) {
-  if (!x || !out || !workspace || m < 0 || n <= 0)
+  if ((m > 0 && !x) || !out || !workspace || m < 0 || n <= 0)   // (m == 0: zeros, as desco_gemm_tn_f32)
     return fail(DESCO_EINVAL, "desco_colsum_f32: bad argument");
   int64_t splits = (m + 255) / 256;          // enough slabs to fill the chip (workspace: 512 * n floats)
   if (splits > 512) splits = 512;
@@ -625,8 +625,8 @@ __global__ __launch_bounds__(256) void rowdot_bwd_kernel(const float* __restrict
 extern "C" int desco_rowdot_bwd_f32(const float* y, int64_t ldy, int n, const float* w, const float* dout,
                                     int64_t num_rows, float* dz, int64_t lddz, float* dwb, float* workspace,
                                     desco_stream_t stream) {
-  if (!y || !w || !dout || !dz || !dwb || !workspace || num_rows < 0 || n < 16 || n > 1024 || n % 16 || 256 % (n / 4) ||
-      ldy % 4 || lddz % 4 || mis16(y) || mis16(w) || mis16(dz) || mis16(workspace))
+  if ((num_rows > 0 && (!y || !dout || !dz)) || !w || !dwb || !workspace || num_rows < 0 || n < 16 || n > 1024 ||
+      n % 16 || 256 % (n / 4) || ldy % 4 || lddz % 4 || mis16(y) || mis16(w) || mis16(dz) || mis16(workspace))   // (no rows: dwb = 0)
     return fail(DESCO_EINVAL, "desco_rowdot_bwd_f32: bad argument (n = 16, 32, 64, ..., 1024: at most 64 row groups per pass; 16-byte alignment)");
   int64_t splits = (num_rows + 255) / 256;
   if (splits > 1024) splits = 1024;
