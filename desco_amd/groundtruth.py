@@ -56,13 +56,26 @@ class _DeviceGraphs:
 
     def __init__(self, graphs: GraphSet, dev):
         self.dev = dev
-        bit_off = np.concatenate([[0], np.cumsum(_bitset_words(graphs))]).astype(np.int64)
-        self.N, self.G, self.E = graphs.num_nodes, graphs.num_graphs, int(graphs.col.shape[0])
-        self._keep = (self.put(graphs.graph_ptr, np.int64), self.put(graphs.rowptr, np.int64),
-                      self.put(graphs.col, np.int32), self.put(graphs.node_graph_ids(), np.int32),
-                      self.put(bit_off[:-1] if self.G else bit_off, np.int64),
-                      torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=dev))
-        graph_ptr, rowptr, col, node_graph, bit_off_d, bits = self._keep
+        self._bind(self.put(graphs.graph_ptr, np.int64), self.put(graphs.rowptr, np.int64),
+                   self.put(graphs.col, np.int32), self.put(graphs.node_graph_ids(), np.int32), _bitset_words(graphs))
+
+    @classmethod
+    def from_device(cls, graph_ptr: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, node_graph: torch.Tensor,
+                    bitset_words: np.ndarray) -> "_DeviceGraphs":
+        """A graph set that is on the device already: contiguous int64 ``graph_ptr`` [G + 1] and ``rowptr`` [N + 1],
+        int32 ``col`` [E] (global ids) and ``node_graph`` [N]; ``bitset_words`` (host, per graph) as ``_bitset_words``
+        gives it."""
+        self = cls.__new__(cls)
+        self.dev = col.device
+        self._bind(graph_ptr, rowptr, col, node_graph, bitset_words)
+        return self
+
+    def _bind(self, graph_ptr, rowptr, col, node_graph, bitset_words):
+        bit_off = np.concatenate([[0], np.cumsum(bitset_words)]).astype(np.int64)
+        self.N, self.G, self.E = int(rowptr.numel()) - 1, int(graph_ptr.numel()) - 1, int(col.numel())
+        self._keep = (graph_ptr, rowptr, col, node_graph, self.put(bit_off[:-1] if self.G else bit_off, np.int64),
+                      torch.empty(max(int(bit_off[-1]), 1), dtype=torch.int64, device=self.dev))
+        bit_off_d, bits = self._keep[4:]
         self.head = (graph_ptr.data_ptr(), self.G, self.N, rowptr.data_ptr(), self.E,
                      col.data_ptr() if col.numel() else None, node_graph.data_ptr(), bit_off_d.data_ptr(),
                      bits.data_ptr(), int(bit_off[-1]))
@@ -80,24 +93,33 @@ def canonical_counts_device(graphs: GraphSet, queries: Sequence, device="cuda", 
     int64 transform on the device (``desco_canonical_noninduced_transform_dev``), without a round trip."""
     if not induced:
         return _noninduced_device(graphs, _flatten_queries(queries)[0], torch.device(device))
+    dev = torch.device(device)
+    table, kmax, Q = _class_table(queries)
+    if graphs.num_nodes == 0 or Q == 0:
+        return torch.zeros((graphs.num_nodes, Q), dtype=torch.int64, device=dev)
+    return _census_on(_DeviceGraphs(graphs, dev), table, kmax, Q)
+
+
+def _class_table(queries: Sequence):
+    """(int16 [1098] class table of the census kernel, its largest query size, the number of queries); refuses what
+    the kernel does not take, naming the reason."""
     _, q_nodes, q_edge_ptr, q_edges = _flatten_queries(queries)
-    L = _lib.lib()
     table = np.empty(1098, dtype=np.int16)
     kmax = ctypes.c_int(0)
-    _lib.check(L.desco_canonical_class_table(q_nodes.ctypes.data, q_edge_ptr.ctypes.data,
-                                             q_edges.ctypes.data if len(q_edges) else None,
-                                             len(q_nodes), table.ctypes.data, ctypes.byref(kmax)),
+    _lib.check(_lib.lib().desco_canonical_class_table(q_nodes.ctypes.data, q_edge_ptr.ctypes.data,
+                                                      q_edges.ctypes.data if len(q_edges) else None,
+                                                      len(q_nodes), table.ctypes.data, ctypes.byref(kmax)),
                "desco_canonical_class_table")
-    dev = torch.device(device)
-    N, Q = graphs.num_nodes, len(q_nodes)
-    out = torch.empty((N, Q), dtype=torch.int64, device=dev)
-    if N == 0 or Q == 0:
-        return out.zero_()
-    d = _DeviceGraphs(graphs, dev)
+    return table, int(kmax.value), len(q_nodes)
+
+
+def _census_on(d: _DeviceGraphs, table: np.ndarray, kmax: int, Q: int) -> torch.Tensor:
+    """The induced census kernel on a graph set that is on the device (d.N > 0, Q > 0): int64 [d.N, Q]."""
+    out = torch.empty((d.N, Q), dtype=torch.int64, device=d.dev)
     cls = d.put(table, np.int16)
-    with torch.cuda.device(dev):
-        _lib.check(L.desco_canonical_counts_dev(*d.head, cls.data_ptr(), int(kmax.value), Q, out.data_ptr(),
-                                                torch.cuda.current_stream(dev).cuda_stream),
+    with torch.cuda.device(d.dev):
+        _lib.check(_lib.lib().desco_canonical_counts_dev(*d.head, cls.data_ptr(), kmax, Q, out.data_ptr(),
+                                                         torch.cuda.current_stream(d.dev).cuda_stream),
                    "desco_canonical_counts_dev")
     return out
 

@@ -242,6 +242,51 @@ int desco_subgraph_stats_dev(const int64_t* rowptr, const int32_t* col, int64_t 
                              const int32_t* set_nodes, const int64_t* set_ids, int64_t num_ids, int words,
                              int64_t* out_i64, double* out_f64, desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * NULL MODEL: degree-preserving rewiring by double edge switches (csrc/null_model.hpp, csrc/null_model.cpp,
+ * csrc/null_model_dev.hip).  Input: a graph set (graph_ptr int64 [G + 1], rowptr int64 [N + 1] from 0, col int32 global
+ * ids; symmetric, loop free, rows strictly ascending).  Every (graph g, replica r) pair is ONE sequential Markov chain:
+ *   edge slots: a graph with m undirected edges has m slots; slot i holds an ORDERED pair (a_i, b_i), at first the CSR
+ *     entries (v, u) with u < v in CSR order as (a, b) = (u, v).  A slot keeps the orientation it was last written with.
+ *   attempt t = 0 .. swaps_per_edge * m - 1:
+ *     w = Philox4x32-10(counter = {lo32(t), hi32(t), lo32(graph_base + g), lo32(replica_base + r)},
+ *                       key = {lo32(seed), hi32(seed)});
+ *     i = (uint64(w0) * m) >> 32, j = (uint64(w1) * m) >> 32, flip = w2 & 1;  reject if i == j;
+ *     (a, b) = slot i, (c, d) = slot j, c and d exchanged if flip;  the proposed edges are {a, d} and {c, b}: reject
+ *     if a == d or c == b, or if either is an edge of the current graph;  else slot i <- (a, d), slot j <- (c, b), and
+ *     the graph loses {a, b}, {c, d} and gains the two new edges.
+ *   Graphs with m < 2 come back unchanged.
+ * Output: col_out int32 [replicas][E] (E = rowptr[N]; replica r's col for the SAME graph_ptr / rowptr -- degrees are
+ * preserved -- every row ascending) and accepted int32 [replicas][G], the accepted switches of every chain.
+ * graph_base / replica_base offset the counter, so that a slice of the graphs or a chunk of the replicas reproduces
+ * the bits of the whole call.
+ *
+ * HOST desco_null_model_rewire: OpenMP over chains (num_threads 0 = the runtime's default); the result does not depend
+ *   on num_threads.  DESCO_EINVAL naming the entry point for: negative counts or bases, swaps_per_edge < 0, a null
+ *   pointer with non-empty input, a graph_ptr / rowptr that is not monotone from 0, ids outside the node's graph,
+ *   loops, rows that are not strictly ascending (unsorted), an asymmetric adjacency, a graph of 2^32 edges or more,
+ *   swaps_per_edge * m beyond 2^63.
+ * HOST desco_null_model_draw: out[3] = (i, j, flip) of attempt t of chain (graph, replica) over m slots, 1 <= m < 2^32.
+ * DEVICE desco_null_model_rewire_dev (gfx950): device arrays; ONE launch on `stream` for the graphs graph_ids[0 ..
+ *   num_ids) (int64, device; NULL = all num_graphs), one wavefront per chain, the chain's adjacency bitset and slots in
+ *   LDS.  A graph of n nodes and m edges needs a workspace of n * (ceil(n / 32) | 1) + m 32-bit words; max_words is
+ *   the caller's bound on that over the launch's graphs and sizes the launch's LDS.  A bound above
+ *   DESCO_NULL_MODEL_DEV_MAX_WORDS is refused (DESCO_EINVAL naming the limit): a graph that needs more goes to the
+ *   host routine.  num_edges = E, the row length of col_out.  A graph that breaks the bound, holds
+ *   an id outside itself or a loop, or whose entries do not pair up gets accepted = -1 and its col_out untouched.  Only
+ *   the rows of the launch's graphs are written.  No allocation, no synchronisation, no global atomics; equal to the
+ *   host routine bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+#define DESCO_NULL_MODEL_DEV_MAX_WORDS 40960 /* 160 KiB of LDS: e.g. 1104 nodes with 2320 edges */
+int desco_null_model_rewire(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col, int64_t num_graphs,
+                            int64_t graph_base, int replicas, int64_t replica_base, int64_t swaps_per_edge,
+                            uint64_t seed, int num_threads, int32_t* col_out, int32_t* accepted);
+int desco_null_model_draw(uint64_t seed, int64_t graph, int64_t replica, uint64_t t, int64_t m, int64_t* out);
+int desco_null_model_rewire_dev(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col, int64_t num_graphs,
+                                int64_t num_edges, const int64_t* graph_ids, int64_t num_ids, int64_t max_words,
+                                int64_t graph_base, int replicas, int64_t replica_base, int64_t swaps_per_edge,
+                                uint64_t seed, int32_t* col_out, int32_t* accepted, desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
