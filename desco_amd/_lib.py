@@ -176,6 +176,8 @@ SIGNATURES = {
     "desco_null_model_draw": (c_int, [ctypes.c_uint64, i64, i64, ctypes.c_uint64, i64, vp]),
     "desco_null_model_rewire_dev": (c_int, [vp, vp, vp, i64, i64, vp, i64, i64, i64, i32, i64, i64,
                                             ctypes.c_uint64, vp, vp, vp]),
+    "desco_core_truss": (c_int, [vp, vp, vp, i64, i32, vp, vp, vp]),
+    "desco_core_truss_dev": (c_int, [vp, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
     "desco_vcsr_transpose_sym": (c_int, [vp, vp, i64, i32, i64, vp, vp, vp]),
     "desco_segment_ids": (c_int, [vp, i64, vp, vp]),
     "desco_gossip_fused_f32": (c_int, [vp, vp, vp, i64, i32] + [vp] * 16 + [f32, vp, vp, vp]),

@@ -287,6 +287,44 @@ int desco_null_model_rewire_dev(const int64_t* graph_ptr, const int64_t* rowptr,
                                 int64_t graph_base, int replicas, int64_t replica_base, int64_t swaps_per_edge,
                                 uint64_t seed, int32_t* col_out, int32_t* accepted, desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CORE / TRUSS: k-core and k-truss decomposition of every graph of a set (csrc/core_truss.hpp, csrc/core_truss.cpp,
+ * csrc/core_truss_dev.hip).  Input: a graph set (graph_ptr int64 [G + 1], rowptr int64 [N + 1] from 0, col int32 global
+ * ids; symmetric, loop free, rows strictly ascending).  Exact integer functions of the graph:
+ *   core[v]     the largest k such that v lies in a subgraph whose every node has degree >= k inside it; an isolated
+ *               node has 0 (networkx.core_number).
+ *   support[e]  the triangles through edge e = the common neighbours of its ends (the non-induced triangle column of
+ *               the edge orbit counts).
+ *   truss[e]    >= 2: the largest k such that e lies in a subgraph whose every edge is in >= k - 2 triangles inside it
+ *               (e is an edge of networkx.k_truss(G, k) iff truss[e] >= k).
+ * core has one row per node; truss and support one row per undirected edge, M = E / 2 rows in the order of the CSR
+ * entries (v, u) with u < v (the rows of the edge orbit counts).  Both decompositions are unique: they do not depend on
+ * the order in which a level is peeled.  Any output may be NULL, and nothing is computed for it that no other needs.
+ *
+ * HOST desco_core_truss: OpenMP over graphs (num_threads 0 = the runtime's default); the result does not depend on
+ *   num_threads.  DESCO_EINVAL naming the entry point for: a negative count, a null pointer with non-empty input, a
+ *   graph_ptr / rowptr that is not monotone from 0, ids outside the node's graph, loops, rows that are not strictly
+ *   ascending (unsorted), an asymmetric adjacency -- before any output is written.
+ * DEVICE desco_core_truss_dev (gfx950): device arrays; ONE launch on `stream` for the graphs graph_ids[0 .. num_ids)
+ *   (int64, device; NULL = all num_graphs), one workgroup per graph, the graph and its peel in LDS.  num_edges = M;
+ *   entry_row int32 [E]: the row of the edge of every CSR entry, both directions of an edge naming one row.  A graph of
+ *   n nodes and m edges needs a workspace of n + 4 + 3 m + max(3 m, n) 32-bit words (csrc/core_truss.hpp); max_words
+ *   is the caller's bound on that over the launch's graphs and sizes the launch's LDS (one wave per graph up to
+ *   DESCO_CORE_TRUSS_WAVE_WORDS, four above).  A bound above DESCO_CORE_TRUSS_DEV_MAX_WORDS is refused (DESCO_EINVAL
+ *   naming the limit): a graph that needs more goes to the host routine.  status int32 [G]: 0 for a graph that was
+ *   decomposed; -1, and no other word of it written, for a graph that breaks the bound, holds an id outside itself, a
+ *   loop or an unsorted row, or whose entries do not pair up through entry_row.  Only the rows of the launch's graphs
+ *   are written.  No allocation, no synchronisation, no global atomics; equal to the host routine bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+#define DESCO_CORE_TRUSS_DEV_MAX_WORDS 40960 /* 160 KiB of LDS: e.g. 4000 nodes with 6100 edges */
+#define DESCO_CORE_TRUSS_WAVE_WORDS 512
+int desco_core_truss(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col, int64_t num_graphs,
+                     int num_threads, int32_t* core_out, int32_t* truss_out, int32_t* support_out);
+int desco_core_truss_dev(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col, int64_t num_graphs,
+                         int64_t num_edges, const int32_t* entry_row, const int64_t* graph_ids, int64_t num_ids,
+                         int64_t max_words, int32_t* core_out, int32_t* truss_out, int32_t* support_out,
+                         int32_t* status, desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
