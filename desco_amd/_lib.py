@@ -178,6 +178,8 @@ SIGNATURES = {
                                             ctypes.c_uint64, vp, vp, vp]),
     "desco_core_truss": (c_int, [vp, vp, vp, i64, i32, vp, vp, vp]),
     "desco_core_truss_dev": (c_int, [vp, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
+    "desco_wl_refine": (c_int, [vp, vp, i64, i32, vp, vp, i64, i64, vp, i32, i32, vp, vp, vp]),
+    "desco_wl_refine_dev": (c_int, [vp, vp, i64, i32, vp, vp, i64, i64, vp, i32, vp, i64, i64, vp, vp, vp, vp]),
     "desco_vcsr_transpose_sym": (c_int, [vp, vp, i64, i32, i64, vp, vp, vp]),
     "desco_segment_ids": (c_int, [vp, i64, vp, vp]),
     "desco_gossip_fused_f32": (c_int, [vp, vp, vp, i64, i32] + [vp] * 16 + [f32, vp, vp, vp]),

@@ -325,6 +325,58 @@ int desco_core_truss_dev(const int64_t* graph_ptr, const int64_t* rowptr, const 
                          int64_t max_words, int32_t* core_out, int32_t* truss_out, int32_t* support_out,
                          int32_t* status, desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * COLOUR REFINEMENT: 1-WL colour classes of the segments of a typed CSR block (csrc/wl_refine.hpp, csrc/wl_refine.cpp,
+ * csrc/wl_refine_dev.hip).  Two segments with equal signatures after L rounds get the same prediction from every
+ * L-layer model that maps a row to a function of its own state and, per GROUP of relation slots, the sum over its
+ * neighbours' states, and whose head reads the anchor row and the sum over the other rows.
+ *
+ * All arithmetic is on uint64 with wrap-around; values are stored as int64 bit patterns.
+ *   G      = 0x9E3779B97F4A7C15
+ *   mix(x) = the splitmix64 finaliser: x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB;
+ *            x ^= x >> 31.  mix(0) = 0, hence the "+ G" below.
+ * Input: vrowptr int32 [slots * R + 1] from 0 and vcol int32 [E], row r slot s at virtual row r * slots + s (the
+ *   layout of the SHMP layer kernels); slots in 1..4; group int32 [slots] (a HOST array in both entry points), every
+ *   entry < slots: the slots with one group value are pooled together.  Segments: seg_ptr int32 [S + 1] over rows and
+ *   anchor_base.  Segment i is the rows seg_ptr[i] .. seg_ptr[i + 1] - 1 and, when anchor_base >= 0, the one row
+ *   anchor_base + i, its anchor (a neighborhood block: seg_ptr = count_ptr, anchor_base = N_c; a whole-graph block:
+ *   seg_ptr = graph_ptr, anchor_base = -1).  init int64 [R] or NULL.
+ * Initial colour: init[r] when given; otherwise 1 for an anchor row and 0 for any other row.
+ * One round, for a row of colour c:  m_g = sum of mix(c[src] + G) over the row's entries whose slot maps to group g;
+ *   h = mix(c + G);  for g = 0 .. slots - 1 in order: h = mix(h ^ (m_g + (g + 1) * G));  the new colour is h.  Every
+ *   row of a segment is updated from the previous round's colours.  rounds in 0..DESCO_WL_MAX_ROUNDS.
+ * Signature of a segment after the last round:  p = sum of mix(c[r] + G) over its non-anchor rows;  with an anchor a:
+ *   sig = mix(mix(c[a] + G) ^ (p + G));  without: sig = mix(p + G).
+ * ORDER INDEPENDENCE: every sum is commutative modulo 2^64, so any evaluation order -- the twin's sequential walk, the
+ *   kernel's lanes and its wave reductions -- gives the same bits, and so does any order of the rows inside a segment.
+ * COLLISIONS: the colours are 64-bit hashes; a collision would merge two classes.  The partition into equal-signature
+ *   classes is exact up to such a collision (the tests hold it to an exact tuple-colour refinement).
+ * GUARD: an entry of vcol may point only into its own segment, anchor included.  A segment that breaks this -- or whose
+ *   rows, anchor or row pointers lie outside the block -- gets status[i] = -1 and nothing else written; otherwise
+ *   status[i] = 0, sig[i] and, when colours != NULL, the final colours of its rows (int64 [R]) are written.
+ *
+ * HOST desco_wl_refine: OpenMP over segments (num_threads 0 = the runtime's default); the result does not depend on
+ *   num_threads.  DESCO_EINVAL naming the entry point for: slots or rounds out of range, a group entry >= slots, a
+ *   negative count, a null pointer where an array is required, a vrowptr that is not monotone from 0.
+ * DEVICE desco_wl_refine_dev (gfx950): device arrays (group on the host); ONE launch on `stream` for the segments
+ *   seg_ids[0 .. num_ids) (int64, device; NULL = all num_segs).  All rounds and the signature of a segment run in this
+ *   one launch: both colour buffers of the segment sit in LDS (16 bytes per row + 64) and ping-pong.  max_rows is the
+ *   caller's bound on the rows of a segment (anchor included) over the launch and sizes its LDS: one wave per segment
+ *   up to DESCO_WL_WAVE_ROWS, one workgroup of four above.  A bound above DESCO_WL_DEV_MAX_ROWS is refused
+ *   (DESCO_EINVAL naming the limit): a larger segment goes to the host routine.  A segment over the launch's bound
+ *   gets status -1.  No allocation, no synchronisation, no atomics; equal to the host routine bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+#define DESCO_WL_MAX_ROUNDS 64
+#define DESCO_WL_DEV_MAX_ROWS 10236 /* 64 + 16 * rows bytes = 160 KiB of LDS */
+#define DESCO_WL_WAVE_ROWS 128
+int desco_wl_refine(const int32_t* vrowptr, const int32_t* vcol, int64_t num_rows, int slots, const int32_t* group,
+                    const int32_t* seg_ptr, int64_t num_segs, int64_t anchor_base, const int64_t* init, int rounds,
+                    int num_threads, int64_t* sig, int64_t* colours, int32_t* status);
+int desco_wl_refine_dev(const int32_t* vrowptr, const int32_t* vcol, int64_t num_rows, int slots, const int32_t* group,
+                        const int32_t* seg_ptr, int64_t num_segs, int64_t anchor_base, const int64_t* init, int rounds,
+                        const int64_t* seg_ids, int64_t num_ids, int64_t max_rows, int64_t* sig, int64_t* colours,
+                        int32_t* status, desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
