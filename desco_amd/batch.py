@@ -275,6 +275,11 @@ class NeighborhoodBatch(_TrainIndexMixin):
     # cache -- below 2^18 count rows (64 MiB) the pass measures the same either way (real-size COX2, 130 022 rows: replayed pass
     # 0.760 against 0.762 ms), and the rows stay where a caller can look at them.  About profit only, like the bound above
     LAYER2_GATHER_MIN_ROWS = 1 << 18
+    # ... and of gnn_model.POOL_TABLES (the partial sums of X_1 and X_2 from one walk with both tables in LDS): every block of
+    # that launch -- one per CU -- first copies the tables, up to 156 KiB each time, about 40 MB through L2 in all, a fixed
+    # ten microseconds or so; what the walk saves grows with the rows, about 0.03 us per thousand (0.27 ms on 8.3 M), and
+    # passes that cost near 2^18 count rows.  Smaller blocks keep the two launches.  About profit only
+    POOL_TABLES_MIN_ROWS = 1 << 18
 
     def layer2_table_index(self):
         """The count rows' classes under the SECOND layer (built once per batch, on the batch's device): ``(cls, rep_uptr,

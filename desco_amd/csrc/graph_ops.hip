@@ -1009,6 +1009,183 @@ extern "C" int desco_table_rows_pool_f32(const float* table, int64_t ldt, int64_
   return launch_status("desco_table_rows_pool_f32");
 }
 
+// The pooled partial sums of TWO table layers in one walk (gnn_model.POOL_TABLES: on a molecule batch the count rows of X_1
+// and X_2 are table1[row_id] and table2[cls]; degree_affine_pool_kernel and table_rows_pool_kernel used to walk the same
+// tiles with the same pooling index, one after the other, the first re-evaluating the affine map per row, the second
+// aiming 256 bytes per row at a table in L2 from every CU).  The tile walk, the running sums and the stores are those
+// of table_rows_pool_kernel, twice per tile; what differs is where a row comes from and when the tile's index arrives:
+//  * a table that fits is copied into LDS at block start (one 1024-thread block per CU: 16 waves, the whole LDS);
+//    a row is then one conflict-free 256-byte ds_read_b32 per lane.  A table that does not fit stays in global memory
+//    and is read as table_rows_pool_kernel reads it (LA / LB: decided per table by the entry point);
+//  * lanes 0-15 hold the first layer's ids of the tile's rows, lanes 16-31 the second layer's (one load), and a wave takes
+//    its tiles in groups of POOL2_GROUP: the NEXT group's ids, pool_bits and pool_slot are requested before the current
+//    group's sums, so that the global round trip is covered -- and is waited for once per group: stores count in vmcnt
+//    with the loads on gfx9, so that wait is also a wait for the acknowledgement of the group's stores, which one tile
+//    per wait exposed once per tile (0.31 ms per COX2 x64 pass against 0.26 ms, profiles/pool_tables_ab.md).
+namespace desco {
+constexpr int POOL2_LDS_BYTES = 156 * 1024;                // of the CU's 160 KiB; the kernel keeps nothing else there
+constexpr int POOL2_THREADS = 1024, POOL2_WAVES = POOL2_THREADS / 64;
+constexpr int POOL2_GROUP = 4;                             // tiles a wave takes between two waits for its global loads
+
+struct PoolTable {
+  const float* table;      // [num, >= 64], row stride ld
+  int64_t ld;
+  int num;
+  const int32_t* ids;      // [num_rows] in [0, num)
+  float* part;             // [nslots, 64]
+};
+
+__device__ __forceinline__ void pool2_stage(float* lds, const PoolTable& p) {
+  // (four 16-byte pieces per thread in flight: the copy is a few dependent round trips, not one per piece)
+  const int n = p.num * 16;
+  auto piece = [&](int i) { return *reinterpret_cast<const float4*>(p.table + (int64_t)(i >> 4) * p.ld + (i & 15) * 4); };
+  int i = threadIdx.x;
+  for (; i + 3 * POOL2_THREADS < n; i += 4 * POOL2_THREADS) {
+    float4 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = piece(i + k * POOL2_THREADS);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(lds + (i + k * POOL2_THREADS) * 4) = v[k];
+  }
+  for (; i < n; i += POOL2_THREADS) *reinterpret_cast<float4*>(lds + i * 4) = piece(i);
+}
+
+template <bool LA, bool LB>
+__global__ __launch_bounds__(POOL2_THREADS) void table_rows_pool2_kernel(PoolTable a, PoolTable b, int64_t num_rows,
+                                                                         float* __restrict__ out, int64_t ldo,
+                                                                         const uint32_t* __restrict__ pool_bits,
+                                                                         const int32_t* __restrict__ pool_slot) {
+  extern __shared__ float4 pool2_lds[];
+  float* la = reinterpret_cast<float*>(pool2_lds);
+  float* lb = la + (LA ? a.num * 64 : 0);
+  if (LA) pool2_stage(la, a);
+  if (LB) pool2_stage(lb, b);
+  if (LA || LB) __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t ntiles = (num_rows + 15) / 16, step = (int64_t)gridDim.x * POOL2_WAVES;
+  int64_t t = (int64_t)blockIdx.x * POOL2_WAVES + wave;
+  if (t >= ntiles) return;
+  const float* ra = (LA ? la : a.table) + lane;
+  const float* rb = (LB ? lb : b.table) + lane;
+  const int64_t sa = LA ? 64 : a.ld, sb = LB ? 64 : b.ld;
+  const int32_t* ids = (lane & 16) ? b.ids : a.ids;        // (lanes 32-63 repeat lanes 0-31; their ids are not used)
+  const int top = ((lane & 16) ? b.num : a.num) - 1;
+  int cn[POOL2_GROUP], sn[POOL2_GROUP];
+  uint32_t En[POOL2_GROUP];
+  // the index of the group of tiles t0, t0 + step, ...: ids, pool_bits, pool_slot (a tile past the end repeats t0, a row past
+  // the end the last row: read, never stored or summed)
+  auto request = [&](int64_t t0) {
+#pragma unroll
+    for (int g = 0; g < POOL2_GROUP; ++g) {
+      const int64_t tg = t0 + g * step < ntiles ? t0 + g * step : t0, ri = tg * 16 + (lane & 15);
+      cn[g] = ids[ri < num_rows ? ri : num_rows - 1];
+      En[g] = pool_bits[tg];
+      sn[g] = pool_slot[tg];
+    }
+  };
+  request(t);
+  for (; t < ntiles; t += step * POOL2_GROUP) {
+    int c[POOL2_GROUP], slot0[POOL2_GROUP];
+    uint32_t Eg[POOL2_GROUP];
+#pragma unroll
+    for (int g = 0; g < POOL2_GROUP; ++g) {
+      // (an id outside its table -- the caller's error, desco_index_range_check_i32 finds it -- reads the nearest table row)
+      c[g] = cn[g] < 0 ? 0 : (cn[g] < top ? cn[g] : top);
+      Eg[g] = __builtin_amdgcn_readfirstlane(En[g]);
+      slot0[g] = __builtin_amdgcn_readfirstlane(sn[g]);
+    }
+    // the next group's index, on its way during this group's sums
+    request(t + step * POOL2_GROUP < ntiles ? t + step * POOL2_GROUP : t);
+#pragma unroll
+    for (int g = 0; g < POOL2_GROUP; ++g) {
+      const int64_t tg = t + g * step;
+      if (tg >= ntiles) break;                             // (wave-uniform)
+      const uint32_t E = Eg[g];
+      int slot = slot0[g];
+      const int nr = (int)((num_rows - tg * 16) < 16 ? (num_rows - tg * 16) : 16);
+      float va[16], vb[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        va[r] = ra[(int64_t)__builtin_amdgcn_readlane(c[g], r) * sa];
+        vb[r] = rb[(int64_t)__builtin_amdgcn_readlane(c[g], 16 + r) * sb];
+      }
+      float* o = out ? out + tg * 16 * ldo + lane : nullptr;
+      float* pa = a.part + lane;
+      float* pb = b.part + lane;
+      float runa = 0.f, runb = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (r < nr) {                                      // (wave-uniform)
+          if (o) o[r * ldo] = vb[r];
+          runa += va[r];
+          runb += vb[r];
+          if ((E >> r) & 1u) {                             // row r ends its segment (wave-uniform)
+            pa[(int64_t)slot * 64] = runa;
+            pb[(int64_t)slot * 64] = runb;
+            ++slot;
+            runa = runb = 0.f;
+          }
+        }
+      }
+      if (nr > 0 && !((E >> (nr - 1)) & 1u)) {
+        pa[(int64_t)slot * 64] = runa;
+        pb[(int64_t)slot * 64] = runb;
+      }
+    }
+  }
+}
+
+template <bool LA, bool LB>
+int launch_pool2(const PoolTable& a, const PoolTable& b, int64_t num_rows, float* out, int64_t ldo,
+                 const uint32_t* pool_bits, const int32_t* pool_slot, hipStream_t st) {
+  const size_t lds = (size_t)((LA ? a.num : 0) + (LB ? b.num : 0)) * 256;
+  if (lds > 0)
+    if (const hipError_t e = size_dynamic_lds<table_rows_pool2_kernel<LA, LB>>(POOL2_LDS_BYTES); e != hipSuccess)
+      return fail((int)e, "desco_table_rows_pool2_f32: cannot size LDS");
+  const int64_t ntiles = (num_rows + 15) / 16;
+  const unsigned grid = persistent_grid((ntiles + POOL2_WAVES - 1) / POOL2_WAVES);
+  hipLaunchKernelGGL((table_rows_pool2_kernel<LA, LB>), dim3(grid), dim3(POOL2_THREADS), lds, st, a, b, num_rows, out, ldo,
+                     pool_bits, pool_slot);
+  return launch_status("desco_table_rows_pool2_f32");
+}
+}  // namespace desco
+
+extern "C" int desco_table_rows_pool2_lds_bytes(void) { return POOL2_LDS_BYTES; }
+
+extern "C" int desco_table_rows_pool2_f32(const float* table1, int64_t ldt1, int64_t num_table1, const int32_t* ids1,
+                                          float* pool_part1, const float* table2, int64_t ldt2, int64_t num_table2,
+                                          const int32_t* ids2, float* pool_part2, int64_t num_rows, float* out2,
+                                          int64_t ldo2, const uint32_t* pool_bits, const int32_t* pool_slot,
+                                          desco_stream_t stream) {
+  if (num_rows == 0) return 0;
+  auto bad_table = [](const float* t, int64_t ld, int64_t n, const int32_t* ids, const float* part) {
+    return !t || !ids || !part || n < 1 || n > INT32_MAX || ld < 64 || ld % 4 || mis16(t) || mis16(part);
+  };
+  if (bad_table(table1, ldt1, num_table1, ids1, pool_part1) || bad_table(table2, ldt2, num_table2, ids2, pool_part2) ||
+      !pool_bits || !pool_slot || num_rows < 0 || pool_part1 == pool_part2 ||
+      (out2 && (ldo2 < 64 || ldo2 % 4 || mis16(out2) || out2 == table1 || out2 == table2)))
+    return fail(DESCO_EINVAL, "desco_table_rows_pool2_f32: bad argument (per layer a table, ids and partial rows of their "
+                              "own, the pooling index present, tables of 1 .. 2^31 - 1 rows, 16-byte rows of at least 64 "
+                              "floats, out2 not a table)");
+  // which tables live in LDS: both when they fit together, else the larger one that fits alone (the smaller one is the
+  // kinder of the two to the caches), else the smaller one, else neither
+  const int64_t cap = POOL2_LDS_BYTES / 256;
+  bool in1 = num_table1 + num_table2 <= cap, in2 = in1;
+  if (!in1) {
+    const bool first_larger = num_table1 > num_table2;
+    const int64_t large = first_larger ? num_table1 : num_table2, small = first_larger ? num_table2 : num_table1;
+    const bool take_large = large <= cap, take_small = !take_large && small <= cap;
+    in1 = first_larger ? take_large : take_small;
+    in2 = first_larger ? take_small : take_large;
+  }
+  const PoolTable a{table1, ldt1, (int)num_table1, ids1, pool_part1}, b{table2, ldt2, (int)num_table2, ids2, pool_part2};
+  hipStream_t st = (hipStream_t)stream;
+  if (in1 && in2) return launch_pool2<true, true>(a, b, num_rows, out2, ldo2, pool_bits, pool_slot, st);
+  if (in1) return launch_pool2<true, false>(a, b, num_rows, out2, ldo2, pool_bits, pool_slot, st);
+  if (in2) return launch_pool2<false, true>(a, b, num_rows, out2, ldo2, pool_bits, pool_slot, st);
+  return launch_pool2<false, false>(a, b, num_rows, out2, ldo2, pool_bits, pool_slot, st);
+}
+
 extern "C" int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch,
                                            desco_stream_t stream) {
   if (n == 0) return 0;

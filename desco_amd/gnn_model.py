@@ -755,6 +755,12 @@ SECOND_LAYER_TABLE = os.environ.get("DESCO_SECOND_LAYER_TABLE", "1") != "0"
 # NeighborhoodBatch.LAYER2_GATHER_MIN_ROWS count rows; bit-identical, DESIGN.md 4.1
 SECOND_LAYER_GATHER = os.environ.get("DESCO_SECOND_LAYER_GATHER", "1") != "0"
 
+# with both tables the pooled partial sums of X_1 and X_2 come from ONE walk over the count rows, both tables staged in LDS
+# (desco_table_rows_pool2_f32 through ops.table_rows_pool) -- the first layer's own pooled launch (desco_degree_affine_pool_f32
+# with out = NULL: the affine map evaluated per row for rows that are table1[row_id]) is then not issued; blocks of at least
+# NeighborhoodBatch.POOL_TABLES_MIN_ROWS count rows; the same sums in the same order: bit-identical, DESIGN.md 4.1
+POOL_TABLES = os.environ.get("DESCO_POOL_TABLES", "1") != "0"
+
 
 def _layer2_table(canon_uptr: torch.Tensor, S: int, coef: torch.Tensor, planes: torch.Tensor) -> torch.Tensor:
     """the second layer's canonical->count table on the U_c distinct first-layer canonical rows: the closed-form first layer on
@@ -823,6 +829,9 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
         l1, l2 = pk["layers"][1], pk["layers"][2]
         gather2 = ("wt_tab" in l2["count"] and all(isinstance(e.get(k), ops.F16Planes) for e, k in (
             (l1["count"], "wt_mfma_x6"), (l2["count"], "wt_mfma_x6"), (l1["canonical"], "wt_x6"), (l2["canonical"], "wt_x6"))))
+    # ... and the first layer's partial sums left by the second layer's table walk (first_pool: what that launch still owes)
+    pool_tables = POOL_TABLES and pool1 and tab1 is not None and tab2 is not None and Nc >= batch.POOL_TABLES_MIN_ROWS
+    first_pool = None
     pool_parts = {}
     if fpool:
         pbits, pslot, nslots = batch.pool_index()
@@ -841,7 +850,9 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
             if r1 <= r0:
                 continue
             coef = _first_layer_coef(pk, t, su, S, x0, src_of_slot, dev)
-            if pool1 and t == "count":
+            if pool1 and t == "count" and pool_tables:
+                first_pool = (table1, tab1[1], pool_parts[1])
+            elif pool1 and t == "count":
                 ops.degree_affine_pool(batch.vrowptr, r1, S, coef, ops.ACT_RELU, 0.0, xn, (pbits, pslot, pool_parts[1]))
             elif t == "canonical" and canon_once:
                 pass                                   # (written below, straight into the anchor operand's block 1)
@@ -917,6 +928,8 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                     ops.shmp_layer(x_src, rep_uptr, rep_vcol, 0, table2.shape[0], S, 2, e["wt_mfma_x6"], e["b"], table2,
                                    ytab=ytab, ytab_row0=y_row0, pool=batch.layer2_rep_pool_index(),
                                    self_coef=coef_l, table_empty=tem)
+                    if first_pool is not None:
+                        pool, first_pool = pool + first_pool, None
                     ops.table_rows_pool(table2, cls2, r1 - r0, None if (last or gather2) else xn, pool)
                     continue
                 ops.shmp_layer(x_src, batch.vrowptr, vcol_c, r0, r1 - r0, S, 2,
@@ -932,6 +945,7 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                                row_absmax=canon_max if (canonical and w16) else None,
                                xself=canon[:, l * H:(l + 1) * H] if once else None)
         X.append(xn)
+        assert first_pool is None, "the first layer's partial sums were left to a launch that was not issued"
         if l in pool_parts:
             # layer l's rows have been consumed (their pooled sums sit in pool_parts[l], their canonical
             # rows in `canon`): release them -- a block then holds three [N, 64] tensors instead of nine,

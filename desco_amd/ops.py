@@ -764,11 +764,26 @@ def degree_affine_pool(vrowptr: torch.Tensor, num_rows: int, slots: int, coef: t
 def table_rows_pool(table: torch.Tensor, cls: torch.Tensor, num_rows: int, out: Optional[torch.Tensor],
                     pool: tuple) -> None:
     """rows [0, num_rows) of a layer computed on its distinct rows only: out[i] = table[cls[i]], with the rows' segment sums
-    fused in as in ``degree_affine_pool`` (desco_table_rows_pool_f32); ``out`` may be None (partials only)."""
-    bits, slot, part = pool
+    fused in as in ``degree_affine_pool`` (desco_table_rows_pool_f32); ``out`` may be None (partials only).
+
+    ``pool`` = (pool_bits, pool_slot, pool_part), or with three more entries (..., table1, ids1, pool_part1) the same walk
+    also leaves the partial sums of a FIRST table layer over the same rows, X_1[i] = table1[ids1[i]], in ``pool_part1``
+    (desco_table_rows_pool2_f32: one launch, tables in LDS where they fit).  The first layer rides in ``pool`` because it
+    shares the pooling index and nothing else of the call changes: same table, classes, ``out`` and partial rows."""
+    bits, slot, part = pool[:3]
     tp, ldt = _rows(table, "table")
     assert cls.is_contiguous() and cls.numel() >= num_rows and table.shape[1] >= 64
     op, ldo = (None, 64) if out is None else _rows(out, "out")
+    if len(pool) != 3:
+        table1, ids1, part1 = pool[3:]
+        tp1, ldt1 = _rows(table1, "table1")
+        assert ids1.is_contiguous() and ids1.numel() >= num_rows and table1.shape[1] >= 64 and part1.shape == part.shape
+        with _Timed("table_rows_pool_kernel", 0.0, (0.0 if out is None else 256.0) * num_rows + 8.0 * num_rows):
+            _lib.check(_lib.lib().desco_table_rows_pool2_f32(
+                tp1, ldt1, table1.shape[0], _dev(ids1, "ids1", torch.int32), _dev(part1, "pool_part1"),
+                tp, ldt, table.shape[0], _dev(cls, "cls", torch.int32), _dev(part, "pool_part"), num_rows, op, ldo,
+                _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32), _stream()), "table_rows_pool2")
+        return
     with _Timed("table_rows_pool_kernel", 0.0, (0.0 if out is None else 256.0) * num_rows + 4.0 * num_rows):
         _lib.check(_lib.lib().desco_table_rows_pool_f32(
             tp, ldt, table.shape[0], _dev(cls, "cls", torch.int32), num_rows, op, ldo,

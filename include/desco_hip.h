@@ -985,6 +985,17 @@ int desco_degree_affine_pool_f32(const int32_t* vrowptr, int64_t num_rows, int s
 int desco_table_rows_pool_f32(const float* table, int64_t ldt, int64_t num_table, const int32_t* cls, int64_t num_rows,
                               float* out, int64_t ldo, const uint32_t* pool_bits, const int32_t* pool_slot,
                               float* pool_part, desco_stream_t stream);
+/* The partial rows of TWO table layers over the same rows in one walk (gnn_model.POOL_TABLES: X_1 = table1[ids1] and X_2 =
+ * table2[ids2] on a molecule batch): pool_part1 and pool_part2 receive, bit for bit, what desco_degree_affine_pool_f32 /
+ * desco_table_rows_pool_f32 leave for the same rows and the same pool_bits / pool_slot index; out2 (optional) the second
+ * layer's rows as desco_table_rows_pool_f32 writes them.  One 1024-thread block per CU; a table is staged in LDS when it
+ * fits in desco_table_rows_pool2_lds_bytes() -- both tables together, else the larger one that fits alone, else the smaller
+ * -- and is read from global memory otherwise.  Ids outside their table read the nearest table row (never out of bounds). */
+int desco_table_rows_pool2_f32(const float* table1, int64_t ldt1, int64_t num_table1, const int32_t* ids1,
+                               float* pool_part1, const float* table2, int64_t ldt2, int64_t num_table2,
+                               const int32_t* ids2, float* pool_part2, int64_t num_rows, float* out2, int64_t ldo2,
+                               const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream);
+int desco_table_rows_pool2_lds_bytes(void);
 /* DESCO_EINVAL when one of idx[0 .. n) (device) lies outside [0, bound); scratch: one device word.  Synchronises the
  * stream: for indices built once per batch, not for the pass. */
 int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch, desco_stream_t stream);
