@@ -1972,3 +1972,37 @@ def count_head_wide(t: torch.Tensor, qh: torch.Tensor, w2: torch.Tensor, b2, slo
                                                        slope, int(exp2_minus_1), op, ldo, B, Q, _stream()),
                    "count_head_wide")
     return out
+
+
+def graph_gen_dev(family: torch.Tensor, n: torch.Tensor, param: torch.Tensor, threshold: torch.Tensor,
+                  graph_ids: Optional[torch.Tensor], graph_base: int, seed: int, graph_ptr: torch.Tensor,
+                  bit_ptr: torch.Tensor, max_words: int, waves: int, flags: int, bits: torch.Tensor, deg: torch.Tensor,
+                  status: torch.Tensor) -> None:
+    """desco_graph_gen_dev (include/desco_hip.h, "GRAPH GENERATORS"): one launch for the graphs ``graph_ids`` (int64;
+    None = all) of the set described by ``family`` / ``n`` int32 [G], ``param`` int64 [G, 2] and ``threshold`` (the
+    uint64 [G, 2] thresholds as int64 bit patterns); packed bitsets into ``bits`` int32 [bit_ptr[G]], degrees into
+    ``deg`` int32 [N], status words into ``status`` int32 [G]."""
+    G = n.numel()
+    if not (family.numel() == G and param.numel() == 2 * G and threshold.numel() == 2 * G and
+            graph_ptr.numel() == G + 1 and bit_ptr.numel() == G + 1 and status.numel() >= G):
+        raise ValueError("desco_amd.ops: graph_gen_dev: arrays of different graph counts")
+    i32, i64 = torch.int32, torch.int64
+    _lib.check(_lib.lib().desco_graph_gen_dev(
+        _dev(family, "family", i32), _dev(n, "n", i32), _dev(param, "param", i64), _dev(threshold, "threshold", i64), G,
+        _opt(graph_ids, "graph_ids", i64), 0 if graph_ids is None else graph_ids.numel(), graph_base, seed,
+        _dev(graph_ptr, "graph_ptr", i64), _dev(bit_ptr, "bit_ptr", i64), deg.numel(), bits.numel(), max_words, waves,
+        flags, _dev(bits, "bits", i32), _dev(deg, "deg", i32), _dev(status, "status", i32), _stream()),
+        "desco_graph_gen_dev")
+
+
+def graph_gen_expand_dev(graph_ptr: torch.Tensor, bit_ptr: torch.Tensor, bits: torch.Tensor, rowptr: torch.Tensor,
+                         num_entries: int, col: torch.Tensor) -> None:
+    """desco_graph_gen_expand_dev: ``col`` int32 [num_entries] from the packed bitsets and ``rowptr`` int64 [N + 1] =
+    the prefix sums of the degrees."""
+    i32, i64 = torch.int32, torch.int64
+    if col.numel() < num_entries:
+        raise ValueError("desco_amd.ops: graph_gen_expand_dev: col is shorter than num_entries")
+    _lib.check(_lib.lib().desco_graph_gen_expand_dev(
+        _dev(graph_ptr, "graph_ptr", i64), _dev(bit_ptr, "bit_ptr", i64), _dev(bits, "bits", i32),
+        _dev(rowptr, "rowptr", i64), graph_ptr.numel() - 1, rowptr.numel() - 1, bits.numel(), num_entries,
+        _dev(col, "col", i32), _stream()), "desco_graph_gen_expand_dev")

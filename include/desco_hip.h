@@ -377,6 +377,103 @@ int desco_wl_refine_dev(const int32_t* vrowptr, const int32_t* vcol, int64_t num
                         const int64_t* seg_ids, int64_t num_ids, int64_t max_rows, int64_t* sig, int64_t* colours,
                         int32_t* status, desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GRAPH GENERATORS: the six families of the synthetic training sets -- ER, WS, Random = G(n, m), BA, EBA = extended
+ * Barabasi-Albert, Power = Holme-Kim power-law cluster -- every graph forced connected through a random tree over its
+ * components and randomly relabelled (csrc/graph_gen.hpp is this definition as code, shared by csrc/graph_gen.cpp and
+ * csrc/graph_gen_dev.hip).  The families are sequential restatements of the textbook algorithms, equal in distribution
+ * to networkx's generators; no bit of any other generator is reproduced.
+ *
+ * INPUT, per graph, integers only: family int32 (0 ER, 1 WS, 2 Random, 3 BA, 4 EBA, 5 Power), n int32 >= 1, param
+ *   int64 [2], threshold uint64 [2] in [0, 2^32].  A Bernoulli(p) draw is uint64(word) < threshold = floor(p 2^32); the
+ *   caller does all float arithmetic (desco_amd/generators.py: family_params).
+ *     ER      threshold[0] = p.            WS     param = (k, edge target of the fallback), threshold[0] = p.
+ *     Random  param[0] = m.                BA     param[0] = m, 1 <= m < n.
+ *     EBA     param[0] = m, 1 <= m < n, threshold = (p, p + q).        Power  param[0] = m, 1 <= m <= n, threshold[0] = p.
+ *   n = 1 is the single node whatever the parameters say.
+ * DRAWS: word i of the sequence (graph, stream) is word i & 3 of
+ *     Philox4x32-10(counter = {lo32(i >> 2), hi32(i >> 2), lo32(graph_base + g), stream}, key = {lo32(seed), hi32(seed)})
+ *   (the Philox of the null model).  stream: 0 the family's body, 1 the Random body (as a family and as WS's fallback),
+ *   2 connection, 3 relabel, 16 + i the i-th WS try.  Unless said otherwise a phase takes its words in order, one per
+ *   draw.  A uniform integer in [0, W) is (uint64(word) * W) >> 32.  No draw depends on another graph.
+ * PREFERENTIAL CHOICE over the nodes below c with integer weights: r uniform in [0, sum of the weights); the node
+ *   whose interval of the prefix sums in id order holds r.  "m distinct targets": choices are repeated until m distinct
+ *   nodes were seen; they are kept in the order of their first draw.
+ * FAMILIES (node ids before the relabelling):
+ *   ER      the pair (u < v) has index v (v - 1) / 2 + u and is an edge iff word[index] of stream 0 < threshold.
+ *   Random  complete if m >= n (n - 1) / 2.  Otherwise attempts (u, v) = two uniform nodes, skipped if u == v or the
+ *           edge exists, until m edges stand.
+ *   WS      h = k / 2 (integer).  A try: the ring lattice {u, (u + j) mod n}, j = 1 .. h; then for j = 1 .. h and
+ *           u = 0 .. n - 1 in that order one Bernoulli word; if selected and deg(u) < n - 1: w uniform, redrawn while
+ *           w == u or {u, w} is an edge; the edge {u, (u + j) mod n} is replaced by {u, w}.  Tries i = 0 .. 99, each on
+ *           stream 16 + i, until one is connected.  After 100, or when h == 0: the Random family with the edge target.
+ *   BA      the star of node 0 and nodes 1 .. m; every node s = m + 1 .. n - 1 joins m distinct targets among the nodes
+ *           below s, weight = degree.
+ *   EBA     m isolated nodes; for s = m .. n - 1 with c = s existing nodes, E edges, full = c - 1, room = c full / 2:
+ *           one word a.  a < threshold[0] and E + m <= room: flag every node of degree < full; m times (stop when no
+ *           node is flagged): src = the k-th flagged node in id order, k uniform; dst = preferential with weight
+ *           deg + 1, zero for src and its neighbours; add {src, dst}; unflag src if saturated, unflag dst if saturated.
+ *           Else threshold[0] <= a < threshold[1] and m <= E < room: flag every node with 0 < degree < full; m times:
+ *           node = the k-th flagged; old = its k'-th neighbour in id order; dst = preferential as above around node;
+ *           {node, old} becomes {node, dst}; unflag old if it is isolated now; dst: unflagged if it was flagged and is
+ *           saturated now, flagged if it was not and has degree 1 now (a node that merely leaves saturation is not
+ *           flagged again).  Always: s joins m distinct targets, weight deg + 1.  The weight deg + 1 is exactly the
+ *           multiplicity of a node in the model's attachment list (shown in csrc/graph_gen.hpp); where that list or
+ *           the flagged set would be empty the remaining iterations of the step are skipped.
+ *   Power   m isolated nodes of weight 1; for s = m .. n - 1: m distinct targets by weight, taken in draw order.  The
+ *           first is joined.  Until m targets were taken: one Bernoulli word; if selected and the last target has
+ *           neighbours that are neither s nor joined to s, the k-th of them in id order, k uniform, is joined and gains
+ *           one weight, and this does not count; otherwise the next target is joined (or stands already) and gains one
+ *           weight either way.  Then s gains weight m.
+ * CONNECTION: components numbered 0 .. c - 1 by their smallest member.  c > 1: a Pruefer sequence of c - 2 uniform
+ *   draws in [0, c) is decoded (every entry is joined to the smallest node that is a leaf by then; the last leaf to
+ *   c - 1); for every tree edge (i, j) as decoded, the k-th member of i and then the k'-th member of j in id order, k
+ *   and k' uniform over the components as they were before the connection, are joined.
+ * RELABEL: key[v] = word[v] of stream 3; the new id of v is the rank of (key[v], v).
+ * flags: DESCO_GRAPH_GEN_NO_CONNECT leaves the connection out, DESCO_GRAPH_GEN_NO_RELABEL the relabelling (what the
+ *   distribution tests compare with other generators); 0 is the recipe.
+ * OUTPUT: graph_ptr int64 [G + 1] = the prefix sums of n and bit_ptr int64 [G + 1] = the prefix sums of
+ *   n * (ceil(n / 32) | 1), both computed by the caller from n.  bits uint32 [bit_ptr[G]]: graph g's adjacency as n
+ *   rows of ceil(n / 32) | 1 words over the new ids; deg int32 [N]; status int32 [G] = tries | added << 8 with tries =
+ *   the WS tries used (101: fell back to Random; 0 for other families) and added = the edges of the connection; -1
+ *   for a refused graph.  One call into caller-sized rows: the caller forms rowptr = the prefix sums of deg, and
+ *   desco_graph_gen_expand(_dev) writes col int32 [rowptr[N]] (global ids, rows strictly ascending, symmetric, loop
+ *   free).  graph_base offsets the counter, so that a slice of the graphs reproduces the bits of the whole call.
+ *
+ * HOST desco_graph_gen / desco_graph_gen_expand: OpenMP over graphs (num_threads 0 = the runtime's default); the
+ *   result does not depend on num_threads.  DESCO_EINVAL naming the entry point for: negative counts, a null pointer
+ *   with non-empty input, an unknown family, n < 1, a threshold above 2^32, m outside its family's range, pointer
+ *   arrays that are not the prefix sums of n -- before anything is written.
+ * HOST desco_graph_gen_draw: out[0] = word i of (graph, stream), out[1] = (out[0] * bound) >> 32.
+ * DEVICE desco_graph_gen_dev (gfx950): device arrays; ONE launch on `stream` for the graphs graph_ids[0 .. num_ids)
+ *   (int64, device; NULL = all num_graphs), one workgroup per graph, the graph's whole state in LDS.  A graph of n nodes needs a workspace of n * (ceil(n / 32) | 1) + 4 n + 4 32-bit words;
+ *   max_words is the caller's bound on that over the launch's graphs and sizes the launch's LDS (waves: 1 or 4 waves
+ *   per graph; 0: one up to DESCO_GRAPH_GEN_WAVE_WORDS, four above).  A bound above DESCO_GRAPH_GEN_DEV_MAX_WORDS is
+ *   refused (DESCO_EINVAL naming the limit): a graph that needs more goes to the host routine.  A graph that breaks
+ *   the launch's bound, whose parameters the host routine would refuse, or whose graph_ptr / bit_ptr entries are not
+ *   those of its n gets status -1 and nothing else written.  desco_graph_gen_expand_dev: one launch; a row whose
+ *   bitset population is not its rowptr span is not written.  No allocation, no synchronisation, no global atomics;
+ *   equal to the host routines bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+#define DESCO_GRAPH_GEN_DEV_MAX_WORDS 40960 /* 160 KiB of LDS: up to 1056 nodes */
+#define DESCO_GRAPH_GEN_WAVE_WORDS 2048
+#define DESCO_GRAPH_GEN_NO_CONNECT 1 /* flags: the family's body alone, components stay apart */
+#define DESCO_GRAPH_GEN_NO_RELABEL 2 /* flags: the ids of the definition, no relabelling */
+int desco_graph_gen(const int32_t* family, const int32_t* n, const int64_t* param, const uint64_t* threshold,
+                    int64_t num_graphs, int64_t graph_base, uint64_t seed, int num_threads, int flags,
+                    const int64_t* graph_ptr, const int64_t* bit_ptr, uint32_t* bits, int32_t* deg, int32_t* status);
+int desco_graph_gen_expand(const int64_t* graph_ptr, const int64_t* bit_ptr, const uint32_t* bits,
+                           const int64_t* rowptr, int64_t num_graphs, int num_threads, int32_t* col);
+int desco_graph_gen_draw(uint64_t seed, int64_t graph, int64_t stream, uint64_t i, int64_t bound, int64_t* out);
+int desco_graph_gen_dev(const int32_t* family, const int32_t* n, const int64_t* param, const uint64_t* threshold,
+                        int64_t num_graphs, const int64_t* graph_ids, int64_t num_ids, int64_t graph_base,
+                        uint64_t seed, const int64_t* graph_ptr, const int64_t* bit_ptr, int64_t num_nodes,
+                        int64_t num_bit_words, int64_t max_words, int waves, int flags, uint32_t* bits,
+                        int32_t* deg, int32_t* status, desco_stream_t stream);
+int desco_graph_gen_expand_dev(const int64_t* graph_ptr, const int64_t* bit_ptr, const uint32_t* bits,
+                               const int64_t* rowptr, int64_t num_graphs, int64_t num_nodes, int64_t num_bit_words,
+                               int64_t num_entries, int32_t* col, desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
