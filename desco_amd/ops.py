@@ -283,7 +283,8 @@ def split_bf16_planes_t(wt: torch.Tensor) -> torch.Tensor:
 
 def gemm_split_desc(pr: dict, planes: torch.Tensor) -> None:
     """One ``gemm_multi`` problem (dict: a1, a2, bias, act, slope, out, gate / gate_act / gate_slope, drop -- no accum)
-    on the bf16x6 pipe (desco_gemm_bf16x6_desc_f32); ``planes`` [3, n, k1 + k2] = the n-major split weight.
+    on the bf16x6 pipe (desco_gemm_bf16x6_desc_f32); ``planes`` [3, n, k1 + k2] = the n-major split weight; ``bias`` [n]
+    or [bias_rows, n].
     ``s`` [m, ns] with ``ws`` [QV, ns, n]: out = act(product + bias + sum_j s[r, j] ws[r % QV, j, :]) -- ``affine_rows`` on
     the product, in its epilogue."""
     a1, out, a2, bias = pr["a1"], pr["out"], pr.get("a2"), pr.get("bias")
@@ -301,9 +302,9 @@ def gemm_split_desc(pr: dict, planes: torch.Tensor) -> None:
     if a2 is not None:
         d.a2, d.lda2 = _rows(a2, "a2")
     d.n = n
-    if bias is not None:
-        assert bias.is_contiguous() and bias.dim() == 1
-        d.bias, d.bias_rows = _dev(bias, "bias"), 1
+    if bias is not None:          # [n], or [bias_rows, n]: row r takes bias[r % bias_rows], as in ``gemm``
+        assert bias.is_contiguous() and bias.dim() in (1, 2) and bias.shape[-1] == n
+        d.bias, d.bias_rows = _dev(bias, "bias"), (1 if bias.dim() == 1 else bias.shape[0])
     d.act, d.slope = pr.get("act", ACT_NONE), pr.get("slope", 0.0)
     d.c, d.ldc = _rows(out, "out")
     gate = pr.get("gate")
