@@ -365,6 +365,135 @@ class NeighborhoodBatch(_TrainIndexMixin):
                                                        torch.empty((nt, 64), device=dev))
         return idx
 
+    # eligibility bounds of layer3_table_index, the path's own (tests lower LAYER2_* on small blocks and pin their launches): a
+    # [16384, 64] fp32 table is one XCD's L2; fewer than 8 rows per class leave too little to save (MUTAG shapes: 3.5)
+    LAYER3_MAX_CLASSES = 1 << 14
+    LAYER3_MIN_ROWS_PER_CLASS = 8
+    # ... and of gnn_model.THIRD_LAYER_TABLE as a whole: what it saves -- the store and the read-back of X_3, all but U_3 rows
+    # of the third layer's count launch -- grows with the rows, what it adds (a 12 k-row launch, a third table in the pooling
+    # walk, a gather of the canonical representatives) does not.  Measured break-even on COX2-shaped blocks between 390 066
+    # count rows (neighborhood model +0.024 ms, 1.050 against 1.026) and 520 088 (-0.080 ms, 1.245 against 1.325), 780 132:
+    # -0.12 ms (profiles/layer3_table_ab.md); the next power of two above it.  Smaller blocks -- the real-size COX2 pass, the
+    # blocks on which tests pin the launches of the LAYER2_* paths -- do not build the index.  About profit only
+    LAYER3_MIN_ROWS = 1 << 19
+
+    @staticmethod
+    def _refine_classes(key, nkey, start, tdeg, ent, dmax, width, umax):
+        """pair refinement of the classes ``key`` (ids below ``nkey``) by the rows' ordered segments: rows of one class in the
+        result agree in ``key`` and in ``ent[start : start + tdeg]`` (entries in [0, width - 1); a position past the row's end
+        counts as -1).  As many segment positions per sorted ``torch.unique`` as fit a 62-bit key; exact, no hashing.
+        -> (key, nkey), or None as soon as there are more than ``umax`` classes"""
+        ne = ent.numel()
+        j = 0
+        while j < dmax:
+            if nkey > umax:
+                return None
+            packed, bound = key, nkey
+            while j < dmax and bound * width < 2 ** 62:
+                e = torch.where(tdeg > j, ent[(start + j).clamp(max=max(ne - 1, 0))] + 1, torch.zeros_like(tdeg))
+                packed, bound, j = packed * width + e, bound * width, j + 1
+            assert bound > nkey, "a segment entry does not fit the key"
+            uniq, key = torch.unique(packed, return_inverse=True)
+            nkey = uniq.numel()
+        return None if nkey > umax else (key, nkey)
+
+    @staticmethod
+    def _lowest_rows(key, nkey):
+        """the lowest row of every class: the first of its run in a STABLE sort by class"""
+        order = torch.argsort(key, stable=True)
+        size = torch.bincount(key, minlength=nkey)
+        return order[torch.cumsum(size, 0) - size]
+
+    def layer3_table_index(self):
+        """The count rows' classes under the THIRD layer (built once per batch, on the batch's device): ``(cls3, rep_uptr,
+        rep_vcol, rep_self, vcol_3, ccls2, crep)`` or None; defined only where ``layer2_table_index`` is.
+
+        The canonical rows of X_2 are a function of their degree tuple (``canon_id``) and their ordered segment of first-layer
+        table ids (``vcol_tc``): ``ccls2`` [B] int32 is each canonical row's class under that pair and ``crep`` [U_c2] int64 the
+        lowest canonical row of each class (an index into the B canonical rows).  A count row of X_3 is a function of its
+        own X_2 row (``cls2``) and, per CSR entry in order, of the source's X_2 row: ``cls2[src]`` in slots 0 and 1,
+        ``ccls2[src - num_count]`` in the table slots.  ``cls3`` [num_count] int32 is the class under that tuple (exact: the
+        segment packed into 62-bit keys, one sorted ``torch.unique`` per key word), ``rep_uptr`` [U_3 S + 1] / ``rep_vcol`` the
+        compact 4-slot CSR of one representative per class (its lowest row) with the sources remapped as above -- table2 rows in
+        slots 0 and 1, rows of the [U_c2, 64] table product in the table slots -- ``rep_self`` [U_3] the representatives'
+        ``cls2`` (their own rows in table2), and ``vcol_3`` = ``vcol`` with the sources of slots 0 and 1 replaced by ``cls3``
+        (the fourth layer gathers from the table of X_3's distinct rows).  None unless the canonical rows, too, have at most 8
+        sources (their gather order is then a function of the row alone as well), U_3 <= LAYER3_MAX_CLASSES,
+        LAYER3_MIN_ROWS_PER_CLASS U_3 <= num_count and num_count >= LAYER3_MIN_ROWS (the last two about profit only; tests on
+        small blocks lower them on their batch object)."""
+        if "_layer3_table" in self.__dict__:
+            return self.__dict__["_layer3_table"]
+        self.__dict__["_layer3_table"] = res = self._build_layer3_table()
+        if res is not None and res[0].is_cuda:
+            from . import ops
+            # every id that a kernel uses as an address, checked once per batch: cls3 (table3: the pooling walk, the fourth
+            # layer's own rows), the representatives' sources and own rows (table2, the table product)
+            u3, u2 = res[3].numel(), (self.layer2_table_index()[1].numel() - 1) // self.slots
+            ops.index_range_check(res[0], u3)
+            ops.index_range_check(res[3], u2)
+            ops.index_range_check(res[2], max(u2, res[6].numel()))
+            ops.index_range_check(res[5], res[6].numel())
+        return res
+
+    def _build_layer3_table(self):
+        S, nc, n = self.slots, self.num_count, self.num_rows
+        tab2 = self.layer2_table_index() if nc >= self.LAYER3_MIN_ROWS else None    # (small blocks leave before any work)
+        if tab2 is None:
+            return None
+        B = n - nc
+        ctab = self.canonical_table_index()
+        vr = self.vrowptr.to(torch.int64)
+        dev = vr.device
+        # canonical classes of X_2
+        cstart = vr[S * nc:S * n:S]
+        ctdeg = vr[S * nc + S::S] - cstart
+        cdmax = int(ctdeg.max().item()) if B else 0
+        if B == 0 or cdmax > self.LAYER2_MAX_DEGREE:
+            return None
+        vcol_tc = ctab[2].to(torch.int64)
+        ne = vcol_tc.numel()
+        r = self._refine_classes(ctab[1].to(torch.int64), (ctab[0].numel() - 1) // S, cstart, ctdeg, vcol_tc, cdmax,
+                                 (int(vcol_tc.max().item()) + 2) if ne else 1, B)
+        ckey, uc2 = r
+        crep = self._lowest_rows(ckey, uc2)
+        # count classes of X_3: the own class, then per entry the source's class (count rows) or canonical class
+        cls2 = tab2[0].to(torch.int64)
+        u2 = (tab2[1].numel() - 1) // S
+        col = self.vcol.to(torch.int64)
+        dall = vr[1:] - vr[:-1]
+        low = (torch.repeat_interleave(torch.arange(n * S, device=dev), dall) % S) < 2
+        ent = torch.where(low, cls2[col.clamp(max=nc - 1)], ckey[(col - nc).clamp(min=0, max=B - 1)])
+        start = vr[0:S * nc:S]
+        tdeg = vr[S:S * nc + 1:S] - start
+        dmax = int(tdeg.max().item())
+        umax = min(self.LAYER3_MAX_CLASSES, nc // self.LAYER3_MIN_ROWS_PER_CLASS)
+        r = self._refine_classes(cls2, u2, start, tdeg, ent, dmax, max(u2, uc2) + 1, umax)
+        if r is None:
+            return None
+        key, u3 = r
+        rep = self._lowest_rows(key, u3)
+        deg = dall[:S * nc].view(nc, S)
+        rep_uptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), deg[rep].reshape(-1).cumsum(0)])
+        pos = torch.arange(max(dmax, 1), device=dev)
+        idx = start[rep][:, None] + pos[None, :]
+        rep_vcol = ent[idx.clamp(max=max(ne - 1, 0))][pos[None, :] < tdeg[rep][:, None]] if ne else ent
+        vcol_3 = torch.where(low, key[col.clamp(max=nc - 1)], col).to(torch.int32)
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        return (i32(key), i32(rep_uptr), i32(rep_vcol), i32(cls2[rep]), vcol_3.contiguous(), i32(ckey), crep.contiguous())
+
+    def layer3_rep_pool_index(self):
+        """``layer2_rep_pool_index`` for the U_3 representatives of ``layer3_table_index``"""
+        idx = self.__dict__.get("_layer3_rep_pool")
+        if idx is None:
+            u3 = self.layer3_table_index()[3].numel()
+            nt = (u3 + 15) // 16
+            dev = self.vrowptr.device
+            bits = torch.zeros(nt, dtype=torch.int32, device=dev)
+            bits[nt - 1] = 1 << ((u3 - 1) % 16)
+            idx = self.__dict__["_layer3_rep_pool"] = (bits, torch.arange(nt, dtype=torch.int32, device=dev),
+                                                       torch.empty((nt, 64), device=dev))
+        return idx
+
     @property
     def table_empty(self) -> int:
         """Which of the count rows' two TABLE slots -- the canonical->count relations: CSR slot 2 (triangle, table slot 0) and

@@ -770,11 +770,31 @@ def table_rows_pool(table: torch.Tensor, cls: torch.Tensor, num_rows: int, out: 
     ``pool`` = (pool_bits, pool_slot, pool_part), or with three more entries (..., table1, ids1, pool_part1) the same walk
     also leaves the partial sums of a FIRST table layer over the same rows, X_1[i] = table1[ids1[i]], in ``pool_part1``
     (desco_table_rows_pool2_f32: one launch, tables in LDS where they fit).  The first layer rides in ``pool`` because it
-    shares the pooling index and nothing else of the call changes: same table, classes, ``out`` and partial rows."""
+    shares the pooling index and nothing else of the call changes: same table, classes, ``out`` and partial rows.  With six
+    more entries (..., table_a, ids_a, pool_part_a, table_b, ids_b, pool_part_b) it leaves the partial sums of two more table
+    layers (desco_table_rows_pool3_f32; ``out`` must then be None)."""
     bits, slot, part = pool[:3]
     tp, ldt = _rows(table, "table")
     assert cls.is_contiguous() and cls.numel() >= num_rows and table.shape[1] >= 64
     op, ldo = (None, 64) if out is None else _rows(out, "out")
+    if len(pool) == 9:
+        # (..., table_a, ids_a, pool_part_a, table_b, ids_b, pool_part_b): two more table layers over the same rows, their
+        # partial sums and this table's from one walk (desco_table_rows_pool3_f32, which writes no rows)
+        if out is not None:
+            raise ValueError("table_rows_pool: the three-table walk leaves partial sums only (out must be None)")
+        layers = [pool[3:6], pool[6:9], (table, cls, part)]
+        for tk, ik, pk_ in layers:
+            assert ik.is_contiguous() and ik.numel() >= num_rows and tk.shape[1] >= 64 and pk_.shape == part.shape
+        rows = [_rows(tk, "table") for tk, _, _ in layers]
+        arr = lambda ct, vals: (ct * 3)(*vals)
+        with _Timed("table_rows_pool_kernel", 0.0, 12.0 * num_rows):
+            _lib.check(_lib.lib().desco_table_rows_pool3_f32(
+                arr(ctypes.c_void_p, [r[0] for r in rows]), arr(ctypes.c_int64, [r[1] for r in rows]),
+                arr(ctypes.c_int64, [tk.shape[0] for tk, _, _ in layers]),
+                arr(ctypes.c_void_p, [_dev(ik, "ids", torch.int32) for _, ik, _ in layers]),
+                arr(ctypes.c_void_p, [_dev(pk_, "pool_part") for _, _, pk_ in layers]), num_rows,
+                _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32), _stream()), "table_rows_pool3")
+        return
     if len(pool) != 3:
         table1, ids1, part1 = pool[3:]
         tp1, ldt1 = _rows(table1, "table1")

@@ -1093,6 +1093,15 @@ int desco_table_rows_pool2_f32(const float* table1, int64_t ldt1, int64_t num_ta
                                const int32_t* ids2, float* pool_part2, int64_t num_rows, float* out2, int64_t ldo2,
                                const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream);
 int desco_table_rows_pool2_lds_bytes(void);
+/* ... and of THREE table layers (gnn_model.THIRD_LAYER_TABLE: X_3 = table3[cls3] as well): tables, ldts, num_tables, ids and
+ * pool_parts are HOST arrays of three entries, one per layer, read before the call returns; pool_parts[k] receives, bit for
+ * bit, what desco_table_rows_pool_f32 leaves for table k, its ids and the same pool_bits / pool_slot index.  No rows are
+ * written.  The same walk as desco_table_rows_pool2_f32 (one 1024-thread block per CU, four tiles per wait); the tables are
+ * staged in LDS smallest first while they fit together in desco_table_rows_pool2_lds_bytes(), the others are read from global
+ * memory.  Ids outside their table read the nearest table row (never out of bounds). */
+int desco_table_rows_pool3_f32(const float* const* tables, const int64_t* ldts, const int64_t* num_tables,
+                               const int32_t* const* ids, float* const* pool_parts, int64_t num_rows,
+                               const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream);
 /* DESCO_EINVAL when one of idx[0 .. n) (device) lies outside [0, bound); scratch: one device word.  Synchronises the
  * stream: for indices built once per batch, not for the pass. */
 int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch, desco_stream_t stream);
