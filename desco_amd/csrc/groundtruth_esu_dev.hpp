@@ -24,6 +24,9 @@
 // was found and gets the path value when a loop ends; it supplies, in place of push and close,
 //   push_at<NS>(path, S, u, ab, ci, e)  ab = adjacency bits of u to S[0..NS-1]; e = the CSR entry (S[ci], u)
 //   close_at<NS>(S, path, level)        path = the path value of S[0..NS-1]
+// A visitor that declares `static constexpr bool kWithVeto = true` (the sampling kernel, sampled_counts_dev.hip) may
+// drop a candidate with its whole subtree: it supplies
+//   keep<K>(path)                       path = the pushed path value of the K-subset; false: neither found nor descended
 #pragma once
 #include <type_traits>
 
@@ -85,6 +88,11 @@ struct esu_with_entry : std::false_type {};
 template <class V>
 struct esu_with_entry<V, std::void_t<decltype(V::kWithEntry)>> : std::true_type {};
 
+template <class V, class = void>
+struct esu_with_veto : std::false_type {};
+template <class V>
+struct esu_with_veto<V, std::void_t<decltype(V::kWithVeto)>> : std::true_type {};
+
 template <int NS, class V>
 __device__ __forceinline__ typename V::Path esu_push(V& vis, const int (&S)[ESU_KMAX], typename V::Path path, int u,
                                                      unsigned ab, int ci, int64_t e) {
@@ -122,6 +130,9 @@ __device__ __forceinline__ bool esu_try(const EsuGraph& g, V& vis, const int (&S
   if (in_s || (ab & ((1u << ci) - 1u))) return true;     // u entered the extension set earlier
   const unsigned m2 = mask | (ab << (NS * (NS - 1) / 2));
   const typename V::Path p2 = esu_push<NS>(vis, S, path, u, ab, ci, e);
+  if constexpr (esu_with_veto<V>::value) {
+    if (!vis.template keep<NS + 1>(p2)) return true;
+  }
   vis.template found<NS + 1>(S, u, m2, p2, level);
   if constexpr (NS + 1 < ESU_KMAX) {
     if (NS + 1 < g.kmax) {

@@ -474,6 +474,58 @@ int desco_graph_gen_expand_dev(const int64_t* graph_ptr, const int64_t* bit_ptr,
                                const int64_t* rowptr, int64_t num_graphs, int64_t num_nodes, int64_t num_bit_words,
                                int64_t num_entries, int32_t* col, desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SAMPLED COUNTS: RAND-ESU (Wernicke 2006) estimates of the canonical counts below (csrc/sampled_counts.hpp,
+ * csrc/sampled_counts.cpp, csrc/sampled_counts_dev.hip).  The exact enumerators visit every connected node subset
+ * once; here every edge of the enumeration tree is kept with a probability that depends only on its depth, and the
+ * kept subsets are tallied.  Dividing a tally by the product of the probabilities along the path gives an unbiased
+ * estimate of the exact count.  Unlabelled graphs, canonical (induced) counts only.
+ *
+ * The tree is the one the device walk enumerates (csrc/groundtruth_esu_dev.hpp), node ids local to the graph:
+ *   a tree node is a sequence (s_0 = v, s_1, .., s_{j-1}), j <= kmax; the roots are the nodes v of the graph.
+ *   The key of a candidate u (u < v, u not in S, u adjacent to a member of S) is the pair (index i of the first member
+ *   of S adjacent to u, position of u in s_i's ascending adjacency row), ordered lexicographically.  The children of
+ *   the sequence are its candidates whose key is larger than the key that s_{j-1} had when it was chosen (for j = 1:
+ *   all the neighbours u < v), in key order.  Every connected subset with maximum v is exactly one tree node.
+ *   (The host's exact walk, csrc/groundtruth_esu.hpp, builds ANOTHER tree over the same subsets: which subsets a
+ *   sampled walk keeps depends on the tree, so the host twin restates the device walk.)
+ * The decision whether u is kept as node number d (d = 2 .. kmax; s_1 is node number 2) of (s_0, .., s_{d-2}, u), with
+ * G and mix of COLOUR REFINEMENT above and the Philox of NULL MODEL:
+ *   w   = Philox4x32-10(counter = {s_0, lo32(graph_base + g), lo32(replica_base + r), 0x53414D50},
+ *                       key = {lo32(seed), hi32(seed)});   h_1 = w0 | w1 << 32
+ *   h_d = mix(h_{d-1} ^ (uint64(u + 1) * G))          (h_{d-1}: the value of the sequence's last member)
+ *   keep iff (h_d >> 32) < thr[d];   thr[d] an integer in 0 .. 2^32: probability thr[d] / 2^32, 2^32 = always, 0 = never
+ * -- a function of (seed, replica, graph, the sequence, u) alone.  A kept child is tallied and descended; a dropped
+ * child is neither: its whole subtree goes.
+ * Output: tally int64 [num_replicas][N][Q], tally[r][v][q] = the kept subsets with maximum v whose induced subgraph is
+ * of query q's class, zeroed and filled by the call.  With W_j = prod_{d=2..j} 2^32 / thr[d], tally * W_size(q) is the
+ * unbiased estimate.  per_graph = 1: out is int64 [num_replicas][G][Q], the rows of every graph summed (the node rows
+ * are never stored); 0: the layout above.  thr int64 [kmax + 1] is a HOST array in both entry points (entries 0 and 1
+ * are not read).  All thresholds 2^32: every replica is the exact count.  graph_base / replica_base offset the counter,
+ * so that a slice of the graphs or a chunk of the replicas reproduces the bits of the whole call.
+ *
+ * HOST desco_sampled_counts: queries as for desco_canonical_counts below, 2..kmax nodes, kmax in 2..6, pairwise
+ *   non-isomorphic; OpenMP over (graph, replica) (num_threads 0 = the runtime's default); the result does not depend on
+ *   num_threads.
+ * DEVICE desco_sampled_counts_dev (gfx950): the device arguments of desco_canonical_counts_dev below up to num_queries
+ *   (kmax in 2..5, at most 32 queries), one launch on `stream`, one wavefront per (CSR entry (v, u) with u < v,
+ *   replica): a dropped level-2 decision ends the wavefront at once.  Does not allocate or synchronise; equal to the
+ *   host routine bit for bit (integer adds commute), and the same from call to call.
+ * Both: DESCO_EINVAL naming the entry point for a null pointer, kmax or num_queries out of range, a threshold outside
+ *   0 .. 2^32, a negative count or base, and (device) more than (2^31 - 1) * 4 work items (entries x replicas).
+ *   num_replicas == 0, no queries or an empty set: nothing is done, 0 is returned.
+ * ------------------------------------------------------------------------------------------ */
+int desco_sampled_counts(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr, const int32_t* col,
+                         const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges, int num_queries,
+                         int kmax, const int64_t* thr, uint64_t seed, int64_t graph_base, int64_t replica_base,
+                         int num_replicas, int per_graph, int num_threads, int64_t* out);
+int desco_sampled_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes, const int64_t* rowptr,
+                             int64_t num_entries, const int32_t* col, const int32_t* node_graph,
+                             const int64_t* bit_off, uint64_t* bits, int64_t num_words, const int16_t* cls, int kmax,
+                             int num_queries, const int64_t* thr, uint64_t seed, int64_t graph_base,
+                             int64_t replica_base, int num_replicas, int per_graph, int64_t* out,
+                             desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
