@@ -83,6 +83,11 @@ SIGNATURES = {
                                      i32, vp]),
     "desco_sampled_counts_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, vp, ctypes.c_uint64,
                                          i64, i64, i32, i32, vp, vp]),
+    "desco_graphlet_correlation": (c_int, [vp, i64, vp, i64, vp, i32, i32, vp, vp, i32]),
+    "desco_gcd_matrix": (c_int, [vp, i64, vp, i64, i64, vp, i64, i32]),
+    "desco_graphlet_correlation_dev": (c_int, [vp, i64, i64, vp, i64, vp, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp,
+                                               vp]),
+    "desco_gcd_matrix_dev": (c_int, [vp, i64, vp, i64, i64, vp, i64, vp]),
     "desco_orbit_table": (c_int, [vp, vp, vp, i32, vp, vp, vp]),
     "desco_orbit_counts": (c_int, [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
     "desco_orbit_counts_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, vp, vp]),

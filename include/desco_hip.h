@@ -526,6 +526,65 @@ int desco_sampled_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int64
                              int64_t replica_base, int num_replicas, int per_graph, int64_t* out,
                              desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GRAPHLET CORRELATION: graphlet correlation matrices of the segments of an orbit table and the graphlet correlation
+ * distance between them (GCD; Yaveroglu et al., "Revealing the hidden language of complex networks", 2014;
+ * csrc/graphlet_correlation.hpp, csrc/graphlet_correlation.cpp, csrc/graphlet_correlation_dev.hip).
+ *
+ * INPUT: an orbit table counts int64 [N][ld] (desco_orbit_counts below); columns int32 [C], entries in 0 .. ld - 1, C
+ *   in 0 .. DESCO_GCM_MAX_COLUMNS (a HOST array in both entry points); seg_ptr int64 [S + 1], monotone: segment s is
+ *   the rows seg_ptr[s] .. seg_ptr[s + 1] - 1 (seg_ptr = graph_ptr: one segment per graph).  dummy_row = 1: every
+ *   segment gets one extra row whose value is 1 in every column, so that a column of zeros is not constant.  That is
+ *   the convention of the published GCD scripts as far as it is known to this project; it is STATED here, not pinned
+ *   against a copy of them.  n' = the rows of a segment, the extra row included.
+ * CENTRED DOUBLED RANK: for column c and row i of a segment, less = the rows of the segment with a smaller value,
+ *   equal = those with the same value, i itself included:  d[i][c] = 2 less + equal - n'  -- twice the average rank
+ *   (ties share the mean of their positions less + 1 .. less + equal) minus n' + 1.  An integer; every column sums to 0.
+ * INTEGER MATRIX: S[a][b] = sum over the segment's rows of d[i][a] d[i][b], int64, exact while n'^3 < 2^63: a segment
+ *   of more than 2097151 rows is refused.  Integer sums commute: S does not depend on the order of the rows or on any
+ *   tiling, and relabelling a graph does not change it.
+ * CORRELATION (Spearman's rho of the columns): rho[a][b] = (double)S[a][b] / sqrt((double)S[a][a] * (double)S[b][b]);
+ *   rho[a][a] = 1; rho[a][b] = 0 where S[a][a] or S[b][b] is 0 (a column that is constant even with the dummy row).
+ *   One correctly rounded IEEE operation per step, none of them contractible.
+ * VECTOR: the upper triangle a < b of rho in row-major order, P = C (C - 1) / 2 doubles.
+ * DISTANCE: gcd(x, y) = sqrt(acc); acc starts at 0 and runs acc = fma(t, t, acc), t = x[p] - y[p], for p = 0 .. P - 1
+ *   IN THAT ORDER.  x double [Gx][P], y double [Gy][P], out[i * ldo + j] = gcd(x_i, y_j), ldo >= Gy: out may be a
+ *   strided view, and only those Gx * Gy elements are written.
+ *
+ * HOST desco_graphlet_correlation: S_out int64 [S][C][C], rho_out double [S][C][C], either may be NULL.  OpenMP over
+ *   segments (num_threads 0 = the runtime's default), ranks by a sort and its tie groups; the result does not depend
+ *   on num_threads.  DESCO_EINVAL naming the entry point for: a negative count, C or dummy_row out of range, a null
+ *   pointer where an array is needed, a column index outside the table, a seg_ptr that is negative or not monotone, a
+ *   segment above the row limit -- before anything is written.
+ * HOST desco_gcd_matrix: OpenMP over the rows of x.
+ * DEVICE desco_graphlet_correlation_dev (gfx950): device arrays (columns on the host); two launches on `stream` for
+ *   the segments seg_ids[0 .. num_ids) (int64, device; NULL = all num_segs): the ranks, one block per (segment,
+ *   column) with the column's values in LDS, into work int32 [num_rows + num_segs][C] (segment s at row seg_ptr[s] +
+ *   s); then S = D^T D, rho and the vector, one block per segment.  vec_out double [S][P]; S_out, rho_out and vec_out
+ *   may each be NULL.  max_rows is the caller's bound on n' over the launch and sizes its LDS (one wave per column up
+ *   to DESCO_GCM_WAVE_ROWS, four above).  A bound above DESCO_GCM_DEV_MAX_ROWS is refused (DESCO_EINVAL naming the
+ *   limit): a larger segment goes to the host routine.  status int32 [S]: 0 for a segment that was computed; -1, and
+ *   none of its outputs written, for one over the launch's bound or with rows outside 0 .. num_rows.  Only the
+ *   launch's segments are written.  No allocation, no synchronisation, no global atomics; S equals the host routine
+ *   bit for bit.
+ * DEVICE desco_gcd_matrix_dev (gfx950): one launch, a 32 x 32 tile of pairs per block, every pair's fma chain in
+ *   ascending p on the fp64 vector pipe (no matrix instruction: its order of summation is not the defined one).
+ * ------------------------------------------------------------------------------------------ */
+#define DESCO_GCM_MAX_COLUMNS 128
+#define DESCO_GCM_DEV_MAX_ROWS 20480 /* one int64 column = 160 KiB of LDS */
+#define DESCO_GCM_WAVE_ROWS 256
+int desco_graphlet_correlation(const int64_t* seg_ptr, int64_t num_segs, const int64_t* counts, int64_t ld,
+                               const int32_t* columns, int C, int dummy_row, int64_t* S_out, double* rho_out,
+                               int num_threads);
+int desco_gcd_matrix(const double* x, int64_t Gx, const double* y, int64_t Gy, int64_t P, double* out, int64_t ldo,
+                     int num_threads);
+int desco_graphlet_correlation_dev(const int64_t* seg_ptr, int64_t num_segs, int64_t num_rows, const int64_t* counts,
+                                   int64_t ld, const int32_t* columns, int C, int dummy_row, const int64_t* seg_ids,
+                                   int64_t num_ids, int64_t max_rows, int32_t* work, int64_t* S_out, double* rho_out,
+                                   double* vec_out, int32_t* status, desco_stream_t stream);
+int desco_gcd_matrix_dev(const double* x, int64_t Gx, const double* y, int64_t Gy, int64_t P, double* out, int64_t ldo,
+                         desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
