@@ -494,6 +494,108 @@ class NeighborhoodBatch(_TrainIndexMixin):
                                                        torch.empty((nt, 64), device=dev))
         return idx
 
+    # eligibility bounds of deep_table_index, the path's own (tests lower LAYER2_* / LAYER3_* on small blocks and pin the launches
+    # that result), all about profit only and all measured (profiles/deep_layer_tables_ab.md).  The deepest level built: on
+    # COX2-shaped x64 every level up to the eighth made the pass faster than the level before it (22.03, 20.93, 19.71, 18.44,
+    # 17.63, 16.74 ms for K = 3 .. 8).  The most classes of a level: the largest table measured, 37 756 rows (9.7 MB, beyond one
+    # XCD's L2), costs the walk no more per row than the 3 MB one; the next power of two above it.  The fewest rows per class: as
+    # the third layer's.  The fewest count rows: the path already pays at 650 110 rows (neighborhood model 1.331 -> 1.218 ms), the
+    # smallest block that has the third layer's table at its default bounds; the tests that pin the launches of a 525 460-row
+    # block at the default bounds want at least 2^20
+    DEEP_TABLE_MAX_LEVEL = 8
+    DEEP_TABLE_MAX_CLASSES = 1 << 16
+    DEEP_TABLE_MIN_ROWS_PER_CLASS = 8
+    DEEP_TABLE_MIN_ROWS = 1 << 20
+
+    def deep_table_index(self):
+        """The count rows' classes under the layers BEYOND the third (built once per batch, on the batch's device): a list with
+        one tuple ``(cls_k, rep_uptr, rep_vcol, rep_self, vcol_k, ccls_km1, crep_km1)`` per level k = 4, 5, ..., each laid out
+        as ``layer3_table_index`` lays out k = 3; empty where ``layer3_table_index`` is None.
+
+        The recurrence is the third layer's: a canonical row of X_{k-1} is a function of its own canonical class of X_{k-2} and,
+        per CSR entry in order, of the source's count class of X_{k-2} (``ccls_km1`` [B], ``crep_km1`` the lowest canonical row of
+        each class); a count row of X_k is a function of its own class of X_{k-1} and, per entry, of the source's class of
+        X_{k-1} -- the count class in slots 0 and 1, the canonical class in the table slots.  ``rep_uptr`` / ``rep_vcol`` are the
+        compact CSR of the lowest row of each class with the sources so remapped (rows of table_{k-1}; rows of the table product
+        on the ``crep_km1`` rows), ``rep_self`` the representatives' own rows in table_{k-1}, ``vcol_k`` = ``vcol`` with the
+        sources of slots 0 and 1 replaced by ``cls_k``.  Exact (``_refine_classes``).  The list stops before the first level
+        with more than DEEP_TABLE_MAX_CLASSES classes or fewer than DEEP_TABLE_MIN_ROWS_PER_CLASS rows per class, and at
+        DEEP_TABLE_MAX_LEVEL; blocks of fewer than DEEP_TABLE_MIN_ROWS count rows build nothing."""
+        if "_deep_table" in self.__dict__:
+            return self.__dict__["_deep_table"]
+        self.__dict__["_deep_table"] = res = self._build_deep_tables()
+        if res and res[0][0].is_cuda:
+            from . import ops
+            # every id that a kernel uses as an address, checked once per batch (as layer3_table_index checks its own)
+            u_prev = self.layer3_table_index()[3].numel()
+            for cls_k, _, rep_vcol, rep_self, _, ccls, crep in res:
+                ops.index_range_check(cls_k, rep_self.numel())
+                ops.index_range_check(rep_self, u_prev)
+                ops.index_range_check(rep_vcol, max(u_prev, crep.numel()))
+                ops.index_range_check(ccls, crep.numel())
+                u_prev = rep_self.numel()
+        return res
+
+    def _build_deep_tables(self):
+        S, nc, n = self.slots, self.num_count, self.num_rows
+        levels = []
+        if nc < self.DEEP_TABLE_MIN_ROWS or self.DEEP_TABLE_MAX_LEVEL < 4:      # (small blocks leave before any work)
+            return levels
+        tab3 = self.layer3_table_index()
+        if tab3 is None:
+            return levels
+        B = n - nc
+        vr = self.vrowptr.to(torch.int64)
+        dev = vr.device
+        col = self.vcol.to(torch.int64)
+        dall = vr[1:] - vr[:-1]
+        low = (torch.repeat_interleave(torch.arange(n * S, device=dev), dall) % S) < 2
+        csrc, qsrc = col.clamp(max=nc - 1), (col - nc).clamp(min=0, max=B - 1)
+        start, cstart = vr[0:S * nc:S], vr[S * nc:S * n:S]
+        tdeg, ctdeg = vr[S:S * nc + 1:S] - start, vr[S * nc + S::S] - cstart
+        dmax, cdmax = int(tdeg.max().item()), int(ctdeg.max().item())
+        deg = dall[:S * nc].view(nc, S)
+        ne = col.numel()
+        pos = torch.arange(max(dmax, 1), device=dev)
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        umax = min(self.DEEP_TABLE_MAX_CLASSES, nc // self.DEEP_TABLE_MIN_ROWS_PER_CLASS)
+        # level k from level k - 1: ``key`` the count classes of X_{k-1}, ``ckey`` the canonical classes of X_{k-2}, ``ent`` per CSR
+        # entry the source's class of X_{k-2} (count class in slots 0 and 1, canonical class in the table slots)
+        key, u = tab3[0].to(torch.int64), tab3[3].numel()
+        ckey, uc = tab3[5].to(torch.int64), tab3[6].numel()
+        u_pp = (self.layer2_table_index()[1].numel() - 1) // S
+        ent = torch.where(low, self.layer2_table_index()[0].to(torch.int64)[csrc], ckey[qsrc])
+        for k in range(4, self.DEEP_TABLE_MAX_LEVEL + 1):
+            ckey, uc_new = self._refine_classes(ckey, uc, cstart, ctdeg, ent, cdmax, max(u_pp, uc) + 1, B)
+            crep = self._lowest_rows(ckey, uc_new)
+            ent = torch.where(low, key[csrc], ckey[qsrc])
+            r = self._refine_classes(key, u, start, tdeg, ent, dmax, max(u, uc_new) + 1, umax)
+            if r is None:
+                break
+            key_k, u_k = r
+            rep = self._lowest_rows(key_k, u_k)
+            rep_uptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), deg[rep].reshape(-1).cumsum(0)])
+            idx = start[rep][:, None] + pos[None, :]
+            rep_vcol = ent[idx.clamp(max=max(ne - 1, 0))][pos[None, :] < tdeg[rep][:, None]] if ne else ent
+            vcol_k = torch.where(low, key_k[csrc], col).to(torch.int32)
+            levels.append((i32(key_k), i32(rep_uptr), i32(rep_vcol), i32(key[rep]), vcol_k.contiguous(), i32(ckey),
+                           crep.contiguous()))
+            u_pp, uc, key, u = u, uc_new, key_k, u_k
+        return levels
+
+    def deep_rep_pool_index(self, level: int):
+        """``layer2_rep_pool_index`` for the representatives of table level ``level`` (>= 4) of ``deep_table_index``"""
+        cache = self.__dict__.setdefault("_deep_rep_pool", {})
+        idx = cache.get(level)
+        if idx is None:
+            uk = self.deep_table_index()[level - 4][3].numel()
+            nt = (uk + 15) // 16
+            dev = self.vrowptr.device
+            bits = torch.zeros(nt, dtype=torch.int32, device=dev)
+            bits[nt - 1] = 1 << ((uk - 1) % 16)
+            idx = cache[level] = (bits, torch.arange(nt, dtype=torch.int32, device=dev), torch.empty((nt, 64), device=dev))
+        return idx
+
     @property
     def table_empty(self) -> int:
         """Which of the count rows' two TABLE slots -- the canonical->count relations: CSR slot 2 (triangle, table slot 0) and

@@ -1337,6 +1337,207 @@ extern "C" int desco_table_rows_pool3_f32(const float* const* tables, const int6
   }
 }
 
+// ... and of UP TO EIGHT table layers (gnn_model.DEEP_LAYER_TABLES: X_4 .. X_8 are tables of their distinct rows as well).
+// The walk of table_rows_pool3_kernel -- same tiles, same groups of POOL2_GROUP tiles per wait, a running sum per layer, no
+// rows stored -- with the number of layers a template parameter:
+//  * four layers' ids fill the 64 lanes of one load (lanes 16 q .. 16 q + 15: layer q of the four); layers 4 .. 7 take a
+//    second id load per tile, requested with the first;
+//  * a tile's rows are read and summed at most POOLN_BATCH layers at a time, so that the rows in flight stay within the 128
+//    VGPRs of a 1024-thread block whatever the number of layers (no instantiation spills);
+//  * where a layer's table lives -- staged in LDS or read from global memory -- is a wave-uniform branch per layer and tile
+//    (lds_off), not a template parameter: eight layers would have 256 instantiations.
+namespace desco {
+constexpr int POOLN_MAX = 8;                               // layers per walk
+// layers whose 16 rows of a tile are in flight together: four spill (28 .. 108 bytes of scratch per lane), three spill from five
+// layers on; two fit up to six layers (100 VGPRs at four, 123 at six), seven and eight layers take one (115 and 113 VGPRs)
+constexpr int POOLN_BATCH = 2;
+
+struct PoolTables {
+  PoolTable t[POOLN_MAX];
+  int lds_off[POOLN_MAX];                                  // the table's copy in LDS starts at this float, or -1: global memory
+};
+
+template <int NT>
+__global__ __launch_bounds__(POOL2_THREADS) void table_rows_pooln_kernel(PoolTables p, int64_t num_rows,
+                                                                         const uint32_t* __restrict__ pool_bits,
+                                                                         const int32_t* __restrict__ pool_slot) {
+  static_assert(NT >= 1 && NT <= POOLN_MAX, "one to eight layers");
+  constexpr int NH = (NT + 3) / 4;                         // id loads per tile
+  constexpr int TB = NT > 6 ? 1 : (NT < POOLN_BATCH ? NT : POOLN_BATCH);
+  extern __shared__ float4 pool2_lds[];
+  float* lds = reinterpret_cast<float*>(pool2_lds);
+  bool staged = false;                                     // (block-uniform: kernel arguments only)
+#pragma unroll
+  for (int k = 0; k < NT; ++k)
+    if (p.lds_off[k] >= 0) {
+      pool2_stage(lds + p.lds_off[k], p.t[k]);
+      staged = true;
+    }
+  if (staged) __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t ntiles = (num_rows + 15) / 16, step = (int64_t)gridDim.x * POOL2_WAVES;
+  int64_t t = (int64_t)blockIdx.x * POOL2_WAVES + wave;
+  if (t >= ntiles) return;
+  // id load h: lanes 16 q .. 16 q + 15 hold layer 4 h + q's ids (a q past the last layer repeats it; those ids are not used)
+  const int32_t* ids[NH];
+  int top[NH];
+#pragma unroll
+  for (int h = 0; h < NH; ++h) {
+    ids[h] = p.t[4 * h].ids;
+    top[h] = p.t[4 * h].num - 1;
+#pragma unroll
+    for (int q = 1; q < 4; ++q) {
+      const int k = 4 * h + q < NT ? 4 * h + q : NT - 1;
+      if ((lane >> 4) == q) {
+        ids[h] = p.t[k].ids;
+        top[h] = p.t[k].num - 1;
+      }
+    }
+  }
+  int cn[NH][POOL2_GROUP], sn[POOL2_GROUP];
+  uint32_t En[POOL2_GROUP];
+  auto request = [&](int64_t t0) {
+#pragma unroll
+    for (int g = 0; g < POOL2_GROUP; ++g) {
+      const int64_t tg = t0 + g * step < ntiles ? t0 + g * step : t0, ri = tg * 16 + (lane & 15);
+#pragma unroll
+      for (int h = 0; h < NH; ++h) cn[h][g] = ids[h][ri < num_rows ? ri : num_rows - 1];
+      En[g] = pool_bits[tg];
+      sn[g] = pool_slot[tg];
+    }
+  };
+  request(t);
+  for (; t < ntiles; t += step * POOL2_GROUP) {
+    int id[NH][POOL2_GROUP], slot0[POOL2_GROUP];
+    uint32_t Eg[POOL2_GROUP];
+#pragma unroll
+    for (int g = 0; g < POOL2_GROUP; ++g) {
+      // (an id outside its table -- the caller's error, desco_index_range_check_i32 finds it -- reads the nearest table row)
+#pragma unroll
+      for (int h = 0; h < NH; ++h) id[h][g] = cn[h][g] < 0 ? 0 : (cn[h][g] < top[h] ? cn[h][g] : top[h]);
+      Eg[g] = __builtin_amdgcn_readfirstlane(En[g]);
+      slot0[g] = __builtin_amdgcn_readfirstlane(sn[g]);
+    }
+    request(t + step * POOL2_GROUP < ntiles ? t + step * POOL2_GROUP : t);
+#pragma unroll
+    for (int g = 0; g < POOL2_GROUP; ++g) {
+      const int64_t tg = t + g * step;
+      if (tg >= ntiles) break;                             // (wave-uniform)
+      const uint32_t E = Eg[g];
+      const int nr = (int)((num_rows - tg * 16) < 16 ? (num_rows - tg * 16) : 16);
+#pragma unroll
+      for (int k0 = 0; k0 < NT; k0 += TB) {
+        float v[TB][16];
+#pragma unroll
+        for (int q = 0; q < TB; ++q) {
+          const int k = k0 + q;
+          if (k >= NT) break;                              // (the last batch may be short)
+          const int idk = id[k >> 2][g], l0 = 16 * (k & 3);
+          if (p.lds_off[k] >= 0) {                         // (wave-uniform)
+            const float* rl = lds + p.lds_off[k] + lane;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[q][r] = rl[__builtin_amdgcn_readlane(idk, l0 + r) * 64];
+          } else {
+            const float* rg = p.t[k].table + lane;
+            const int64_t ld = p.t[k].ld;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[q][r] = rg[(int64_t)__builtin_amdgcn_readlane(idk, l0 + r) * ld];
+          }
+        }
+        int slot = slot0[g];
+        float run[TB];
+#pragma unroll
+        for (int q = 0; q < TB; ++q) run[q] = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if (r < nr) {                                    // (wave-uniform)
+#pragma unroll
+            for (int q = 0; q < TB; ++q)
+              if (k0 + q < NT) run[q] += v[q][r];
+            if ((E >> r) & 1u) {                           // row r ends its segment (wave-uniform)
+#pragma unroll
+              for (int q = 0; q < TB; ++q)
+                if (k0 + q < NT) p.t[k0 + q].part[(int64_t)slot * 64 + lane] = run[q];
+              ++slot;
+#pragma unroll
+              for (int q = 0; q < TB; ++q) run[q] = 0.f;
+            }
+          }
+        }
+        if (nr > 0 && !((E >> (nr - 1)) & 1u)) {
+#pragma unroll
+          for (int q = 0; q < TB; ++q)
+            if (k0 + q < NT) p.t[k0 + q].part[(int64_t)slot * 64 + lane] = run[q];
+        }
+      }
+    }
+  }
+}
+
+template <int NT>
+int launch_pooln(const PoolTables& p, size_t lds, int64_t num_rows, const uint32_t* pool_bits, const int32_t* pool_slot,
+                 hipStream_t st) {
+  if (lds > 0)
+    if (const hipError_t e = size_dynamic_lds<table_rows_pooln_kernel<NT>>(POOL2_LDS_BYTES); e != hipSuccess)
+      return fail((int)e, "desco_table_rows_pooln_f32: cannot size LDS");
+  const int64_t ntiles = (num_rows + 15) / 16;
+  const unsigned grid = persistent_grid((ntiles + POOL2_WAVES - 1) / POOL2_WAVES);
+  hipLaunchKernelGGL((table_rows_pooln_kernel<NT>), dim3(grid), dim3(POOL2_THREADS), lds, st, p, num_rows, pool_bits,
+                     pool_slot);
+  return launch_status("desco_table_rows_pooln_f32");
+}
+}  // namespace desco
+
+extern "C" int desco_table_rows_pooln_max_layers(void) { return desco::POOLN_MAX; }
+
+extern "C" int desco_table_rows_pooln_f32(int num_layers, const float* const* tables, const int64_t* ldts,
+                                          const int64_t* num_tables, const int32_t* const* ids, float* const* pool_parts,
+                                          int64_t num_rows, const uint32_t* pool_bits, const int32_t* pool_slot,
+                                          desco_stream_t stream) {
+  if (num_rows == 0) return 0;
+  const int nl = num_layers;
+  bool bad = nl < 1 || nl > desco::POOLN_MAX || !tables || !ldts || !num_tables || !ids || !pool_parts || !pool_bits ||
+             !pool_slot || num_rows < 0;
+  for (int k = 0; k < nl && !bad; ++k) {
+    bad = !tables[k] || !ids[k] || !pool_parts[k] || num_tables[k] < 1 || num_tables[k] > INT32_MAX || ldts[k] < 64 ||
+          ldts[k] % 4 || mis16(tables[k]) || mis16(pool_parts[k]);
+    for (int j = 0; j < k && !bad; ++j) bad = pool_parts[j] == pool_parts[k];
+  }
+  if (bad)
+    return fail(DESCO_EINVAL, "desco_table_rows_pooln_f32: bad argument (one to eight layers, per layer a table, ids and "
+                              "partial rows of their own, the pooling index present, tables of 1 .. 2^31 - 1 rows, 16-byte "
+                              "rows of at least 64 floats)");
+  // which tables live in LDS: smallest first while they fit together (as desco_table_rows_pool3_f32 chooses)
+  const int64_t cap = POOL2_LDS_BYTES / 256;
+  desco::PoolTables p{};
+  for (int k = 0; k < desco::POOLN_MAX; ++k) {
+    const int s = k < nl ? k : nl - 1;                     // (entries past the last layer repeat it: never used, never null)
+    p.t[k] = desco::PoolTable{tables[s], ldts[s], (int)num_tables[s], ids[s], pool_parts[s]};
+    p.lds_off[k] = -1;
+  }
+  int64_t used = 0;
+  for (int n = 0; n < nl; ++n) {
+    int best = -1;
+    for (int k = 0; k < nl; ++k)
+      if (p.lds_off[k] < 0 && (best < 0 || num_tables[k] < num_tables[best])) best = k;
+    if (used + num_tables[best] > cap) break;
+    p.lds_off[best] = (int)(used * 64);
+    used += num_tables[best];
+  }
+  const size_t lds = (size_t)used * 256;
+  hipStream_t st = (hipStream_t)stream;
+  switch (nl) {
+    case 1: return desco::launch_pooln<1>(p, lds, num_rows, pool_bits, pool_slot, st);
+    case 2: return desco::launch_pooln<2>(p, lds, num_rows, pool_bits, pool_slot, st);
+    case 3: return desco::launch_pooln<3>(p, lds, num_rows, pool_bits, pool_slot, st);
+    case 4: return desco::launch_pooln<4>(p, lds, num_rows, pool_bits, pool_slot, st);
+    case 5: return desco::launch_pooln<5>(p, lds, num_rows, pool_bits, pool_slot, st);
+    case 6: return desco::launch_pooln<6>(p, lds, num_rows, pool_bits, pool_slot, st);
+    case 7: return desco::launch_pooln<7>(p, lds, num_rows, pool_bits, pool_slot, st);
+    default: return desco::launch_pooln<8>(p, lds, num_rows, pool_bits, pool_slot, st);
+  }
+}
+
 extern "C" int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch,
                                            desco_stream_t stream) {
   if (n == 0) return 0;

@@ -770,6 +770,15 @@ POOL_TABLES = os.environ.get("DESCO_POOL_TABLES", "1") != "0"
 # bit-identical, DESIGN.md 4.1
 THIRD_LAYER_TABLE = os.environ.get("DESCO_THIRD_LAYER_TABLE", "1") != "0"
 
+# ... and so on down the trunk: the classes stop growing (COX2-shaped: 28 561 distinct rows of X_4, 37 756 of X_8, for millions
+# of count rows), so every further layer with a class index (NeighborhoodBatch.deep_table_index: levels 4 .. K) runs its count
+# launch on the representatives as the third does -- sources and own rows in the table before it, the table product on the
+# distinct canonical rows -- and X_4 .. X_K are never written either; layer K + 1, if the model has one, gathers from table K,
+# and the partial sums of all table layers come from the walk behind the last representatives' launch
+# (desco_table_rows_pooln_f32).  Where THIRD_LAYER_TABLE is active and the batch has the index (blocks of at least
+# NeighborhoodBatch.DEEP_TABLE_MIN_ROWS count rows); bit-identical, DESIGN.md 4.1
+DEEP_LAYER_TABLES = os.environ.get("DESCO_DEEP_LAYER_TABLES", "1") != "0"
+
 
 def _layer2_table(canon_uptr: torch.Tensor, S: int, coef: torch.Tensor, planes: torch.Tensor) -> torch.Tensor:
     """the second layer's canonical->count table on the U_c distinct first-layer canonical rows: the closed-form first layer on
@@ -839,12 +848,19 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
         gather2 = ("wt_tab" in l2["count"] and all(isinstance(e.get(k), ops.F16Planes) for e, k in (
             (l1["count"], "wt_mfma_x6"), (l2["count"], "wt_mfma_x6"), (l1["canonical"], "wt_x6"), (l2["canonical"], "wt_x6"))))
     # ... and the third layer on the distinct rows of ITS output, which stays a table as well (tab3: the class index)
-    tab3, table3 = None, None
+    tab3 = None
+    fp16_form = lambda e: ("wt_tab" in e["count"] and isinstance(e["count"].get("wt_mfma_x6"), ops.F16Planes)
+                           and isinstance(e["canonical"].get("wt_x6"), ops.F16Planes))
     if THIRD_LAYER_TABLE and gather2:
-        l3 = pk["layers"][3] if L >= 4 else None
-        if l3 is None or ("wt_tab" in l3["count"] and isinstance(l3["count"].get("wt_mfma_x6"), ops.F16Planes)
-                          and isinstance(l3["canonical"].get("wt_x6"), ops.F16Planes)):
+        if L < 4 or fp16_form(pk["layers"][3]):
             tab3 = batch.layer3_table_index()
+    # tabs[k]: the class index of table level k >= 3 (same layout at every level), ttab[k]: the table of X_k's distinct count rows
+    tabs, ttab = ({} if tab3 is None else {3: tab3}), {}
+    if DEEP_LAYER_TABLES and tab3 is not None and L >= 4:
+        for k, tk in enumerate(batch.deep_table_index(), 4):
+            if k > L or (k < L and not fp16_form(pk["layers"][k])):    # (layer k, if any, gathers from table k)
+                break
+            tabs[k] = tk
     # ... and the first layer's partial sums left by the second layer's table walk (first_pool: what that launch still owes)
     pool_tables = POOL_TABLES and pool1 and tab1 is not None and tab2 is not None and Nc >= batch.POOL_TABLES_MIN_ROWS
     first_pool = None
@@ -902,8 +918,8 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
         last = l == L - 1
         # the last layer's count rows feed nothing but the pooling: with fused pooling they are
         # never stored (the canonical rows still are, they sit at the end of the same tensor)
-        # (gather2: X_2 is never allocated; tab3: neither is X_3)
-        xn = None if ((l == 1 and gather2) or (l == 2 and tab3 is not None)) else torch.empty((N, H), device=dev)
+        # (gather2: X_2 is never allocated; a table level: neither is X_3, X_4, ...)
+        xn = None if ((l == 1 and gather2) or (l + 1) in tabs) else torch.empty((N, H), device=dev)
         # layer input, column ids and (count rows) self index of this layer's launches: X_l itself, or -- for the second
         # layer when X_1's count rows exist as a table of distinct rows only -- that table
         x_src, vcol_l, coef_l, cls_l = X[-1], batch.vcol, None, None
@@ -913,8 +929,8 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
             # ... and likewise for the third layer: the table of X_2's distinct count rows (kept alive in table2 since the
             # second layer), sources and own rows addressed by class; the table slots' sources stay global ids
             x_src, vcol_l, cls_l = table2, tab2[3], tab2[0]
-        if l == 3 and tab3 is not None:
-            x_src, vcol_l, cls_l = table3, tab3[4], tab3[0]                          # ... and for the fourth
+        if l >= 3 and l in tabs:
+            x_src, vcol_l, cls_l = ttab[l], tabs[l][4], tabs[l][0]                   # ... and for the fourth, and every table level
         for t, r0, r1, su in groups:
             if r1 <= r0:
                 continue
@@ -930,9 +946,9 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                     # (ctab[2] is tab1[2] with the TABLE slots' sources remapped as well; the canonical launch of this layer
                     #  reads slots 0 and 1 only and keeps tab1[2])
                     vcol_c, y_row0 = ctab[2], 0
-                elif tem and l == 2 and tab3 is not None:
-                    # (the representatives' table sources are canonical CLASSES of X_2: the product on their U_c2 lowest rows)
-                    ytab = ops.linear64(crows.index_select(0, tab3[6]), e["wt_tab_l64"][tblock:tblock + 1])
+                elif tem and (l + 1) in tabs:
+                    # (the representatives' table sources are canonical CLASSES of X_l: the product on their lowest rows)
+                    ytab = ops.linear64(crows.index_select(0, tabs[l + 1][6]), e["wt_tab_l64"][tblock:tblock + 1])
                     y_row0 = 0
                 elif tem:
                     ytab = ops.linear64(crows, e["wt_tab_l64"][tblock:tblock + 1])   # canonical rows x W2 or W3: [B, 64]
@@ -957,18 +973,23 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                         pool, first_pool = pool + first_pool, None
                     ops.table_rows_pool(table2, cls2, r1 - r0, None if (last or gather2) else xn, pool)
                     continue
-                if l == 2 and tab3 is not None:
-                    # the same once more: the launch on the U_3 representatives (sources and own rows in table2), then ONE walk
-                    # for the partial sums of every table layer
-                    cls3, rep_uptr, rep_vcol, rep_self = tab3[:4]
-                    table3 = torch.empty((rep_self.numel(), H), device=dev)
-                    ops.shmp_layer(x_src, rep_uptr, rep_vcol, 0, table3.shape[0], S, 2, e["wt_mfma_x6"], e["b"], table3,
-                                   ytab=ytab, ytab_row0=y_row0, pool=batch.layer3_rep_pool_index(), table_empty=tem,
-                                   self_index=rep_self)
+                if (l + 1) in tabs:
+                    # the same once more: the launch on the U_k representatives (sources and own rows in the table before), then
+                    # -- behind the deepest level's launch -- the walk(s) for the partial sums of every table layer
+                    k = l + 1
+                    cls_k, rep_uptr, rep_vcol, rep_self = tabs[k][:4]
+                    ttab[k] = torch.empty((rep_self.numel(), H), device=dev)
+                    ops.shmp_layer(x_src, rep_uptr, rep_vcol, 0, ttab[k].shape[0], S, 2, e["wt_mfma_x6"], e["b"], ttab[k],
+                                   ytab=ytab, ytab_row0=y_row0, table_empty=tem, self_index=rep_self,
+                                   pool=batch.layer3_rep_pool_index() if k == 3 else batch.deep_rep_pool_index(k))
+                    if (k + 1) in tabs:
+                        continue
                     pool = pool + (table2, tab2[0], pool_parts[2])
+                    for j in range(3, k):
+                        pool = pool + (ttab[j], tabs[j][0], pool_parts[j])
                     if first_pool is not None:
                         pool, first_pool = pool + first_pool, None
-                    ops.table_rows_pool(table3, cls3, r1 - r0, None, pool)
+                    ops.table_rows_pool(ttab[k], cls_k, r1 - r0, None, pool)
                     continue
                 ops.shmp_layer(x_src, batch.vrowptr, vcol_c, r0, r1 - r0, S, 2,
                                e.get("wt_mfma_x6", e["wt_mfma"]) if SHMP_BF16X6 else e["wt_mfma"],
@@ -983,7 +1004,7 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                                row_absmax=canon_max if (canonical and w16) else None,
                                xself=canon[:, l * H:(l + 1) * H] if once else None)
         X.append(xn)
-        assert first_pool is None or (l == 1 and tab3 is not None), "the first layer's partial sums were left to a launch that was not issued"
+        assert first_pool is None or (l + 2) in tabs, "the first layer's partial sums were left to a launch that was not issued"
         if l in pool_parts:
             # layer l's rows have been consumed (their pooled sums sit in pool_parts[l], their canonical
             # rows in `canon`): release them -- a block then holds three [N, 64] tensors instead of nine,

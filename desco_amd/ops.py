@@ -762,6 +762,30 @@ def degree_affine_pool(vrowptr: torch.Tensor, num_rows: int, slots: int, coef: t
             _stream()), "degree_affine_pool")
 
 
+# table layers per launch of desco_table_rows_pooln_f32 (at most desco_table_rows_pooln_max_layers() = 8).  Beyond four the kernel
+# takes a second id load per tile, and up to six layers that is faster than a second walk (COX2 x64: 0.918 against 0.964 ms for
+# five layers, 1.069 against 1.126 for six); seven and eight layers keep the rows of one layer in flight at a time and lose to
+# two walks (1.809 against 1.540 ms for eight): profiles/deep_layer_tables_ab.md
+POOL_WALK_LAYERS = 6
+
+
+def _table_rows_pooln(layers, num_rows: int, bits: torch.Tensor, slot: torch.Tensor) -> None:
+    """the pooled partial sums of 1 .. 8 table layers ``(table, ids, pool_part)`` over rows [0, num_rows) from one walk
+    (desco_table_rows_pooln_f32); pool_part of each layer as ``table_rows_pool`` leaves it for that layer alone"""
+    n = len(layers)
+    for tk, ik, pk_ in layers:
+        assert ik.is_contiguous() and ik.numel() >= num_rows and tk.shape[1] >= 64 and pk_.shape == layers[0][2].shape
+    rows = [_rows(tk, "table") for tk, _, _ in layers]
+    arr = lambda ct, vals: (ct * n)(*vals)
+    with _Timed("table_rows_pool_kernel", 0.0, 4.0 * n * num_rows):
+        _lib.check(_lib.lib().desco_table_rows_pooln_f32(
+            n, arr(ctypes.c_void_p, [r[0] for r in rows]), arr(ctypes.c_int64, [r[1] for r in rows]),
+            arr(ctypes.c_int64, [tk.shape[0] for tk, _, _ in layers]),
+            arr(ctypes.c_void_p, [_dev(ik, "ids", torch.int32) for _, ik, _ in layers]),
+            arr(ctypes.c_void_p, [_dev(pk_, "pool_part") for _, _, pk_ in layers]), num_rows,
+            _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32), _stream()), "table_rows_pooln")
+
+
 def table_rows_pool(table: torch.Tensor, cls: torch.Tensor, num_rows: int, out: Optional[torch.Tensor],
                     pool: tuple) -> None:
     """rows [0, num_rows) of a layer computed on its distinct rows only: out[i] = table[cls[i]], with the rows' segment sums
@@ -772,11 +796,20 @@ def table_rows_pool(table: torch.Tensor, cls: torch.Tensor, num_rows: int, out: 
     (desco_table_rows_pool2_f32: one launch, tables in LDS where they fit).  The first layer rides in ``pool`` because it
     shares the pooling index and nothing else of the call changes: same table, classes, ``out`` and partial rows.  With six
     more entries (..., table_a, ids_a, pool_part_a, table_b, ids_b, pool_part_b) it leaves the partial sums of two more table
-    layers (desco_table_rows_pool3_f32; ``out`` must then be None)."""
+    layers (desco_table_rows_pool3_f32; ``out`` must then be None), and with nine or more -- three per further layer -- of
+    all of them (``_table_rows_pooln``)."""
     bits, slot, part = pool[:3]
     tp, ldt = _rows(table, "table")
     assert cls.is_contiguous() and cls.numel() >= num_rows and table.shape[1] >= 64
     op, ldo = (None, 64) if out is None else _rows(out, "out")
+    if len(pool) > 9:
+        # three more table layers or more: four or more in all (desco_table_rows_pooln_f32, at most POOL_WALK_LAYERS per walk)
+        if out is not None or len(pool) % 3:
+            raise ValueError("table_rows_pool: (table, ids, pool_part) per further layer; such a walk leaves partial sums only")
+        layers = [pool[i:i + 3] for i in range(3, len(pool), 3)] + [(table, cls, part)]
+        for i in range(0, len(layers), POOL_WALK_LAYERS):
+            _table_rows_pooln(layers[i:i + POOL_WALK_LAYERS], num_rows, bits, slot)
+        return
     if len(pool) == 9:
         # (..., table_a, ids_a, pool_part_a, table_b, ids_b, pool_part_b): two more table layers over the same rows, their
         # partial sums and this table's from one walk (desco_table_rows_pool3_f32, which writes no rows)

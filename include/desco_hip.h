@@ -1213,6 +1213,17 @@ int desco_table_rows_pool2_lds_bytes(void);
 int desco_table_rows_pool3_f32(const float* const* tables, const int64_t* ldts, const int64_t* num_tables,
                                const int32_t* const* ids, float* const* pool_parts, int64_t num_rows,
                                const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream);
+/* ... and of num_layers = 1 .. desco_table_rows_pooln_max_layers() (8) table layers (gnn_model.DEEP_LAYER_TABLES: the layers
+ * beyond the third as tables of their distinct rows): the arrays are HOST arrays of num_layers entries, read before the call
+ * returns; pool_parts[k] receives, bit for bit, what desco_table_rows_pool_f32 leaves for table k, its ids and the same
+ * pool_bits / pool_slot index.  No rows are written.  The same walk (one 1024-thread block per CU, four tiles per wait): four
+ * layers' ids per id load, a second load per tile beyond four layers, the rows of four layers in flight at a time; the tables
+ * are staged in LDS smallest first while they fit together in desco_table_rows_pool2_lds_bytes(), the others are read from
+ * global memory.  Ids outside their table read the nearest table row (never out of bounds). */
+int desco_table_rows_pooln_f32(int num_layers, const float* const* tables, const int64_t* ldts, const int64_t* num_tables,
+                               const int32_t* const* ids, float* const* pool_parts, int64_t num_rows,
+                               const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream);
+int desco_table_rows_pooln_max_layers(void);
 /* DESCO_EINVAL when one of idx[0 .. n) (device) lies outside [0, bound); scratch: one device word.  Synchronises the
  * stream: for indices built once per batch, not for the pass. */
 int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch, desco_stream_t stream);
