@@ -7,6 +7,7 @@ kept as (lazy, host-side) properties for interop and tests.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -26,6 +27,10 @@ def _norm_device(device) -> torch.device:
 
 def _i32(a, device):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+
+
+# NeighborhoodBatch._level_csr
+_LevelCSR = namedtuple("_LevelCSR", "col low csrc qsrc start tdeg dmax cstart ctdeg cdmax deg pos")
 
 
 def _transpose_index(vrowptr: np.ndarray, vcol: np.ndarray, n_src: int):
@@ -286,8 +291,8 @@ class NeighborhoodBatch(_TrainIndexMixin):
         rep_vcol, vcol_2)`` or None.  With the first layer a table of degree tuples (``degree_table_index``,
         ``canonical_table_index``), the second layer's count row i is a function of its four slot degrees and of its remapped
         CSR segment ``vcol_tc`` -- table ids, the same in whichever neighborhood the row sits -- so rows that agree in both get
-        bit-equal X_2 rows: ``cls`` [num_count] int32 is each count row's class (exact: iterated pair refinement, one sorted
-        ``torch.unique`` per segment position, no hashing), ``rep_uptr`` [U_2 S + 1] / ``rep_vcol`` the compact 4-slot CSR of one
+        bit-equal X_2 rows: ``cls`` [num_count] int32 is each count row's class (exact: iterated pair refinement,
+        ``_refine_classes``, no hashing), ``rep_uptr`` [U_2 S + 1] / ``rep_vcol`` the compact 4-slot CSR of one
         representative per class (its lowest row; the segment copied from ``vcol_tc``), on which the layer runs, and ``vcol_2``
         = ``vcol`` with the sources of slots 0 and 1 replaced by their class.  None unless the block has an empty table slot
         (``table_empty``) and both first-layer tables, no count row has more than 8 sources (tested before any sort), U_2 <=
@@ -303,66 +308,84 @@ class NeighborhoodBatch(_TrainIndexMixin):
             ops.index_range_check(res[0], (res[1].numel() - 1) // self.slots)
         return res
 
-    def _build_layer2_table(self):
+    def _level_csr(self):
+        """what every table level reads of the block's CSR, whatever the level: per entry ``low`` (the source is a count row:
+        slots 0 and 1) and the source as a count row ``csrc`` / as a canonical row ``qsrc`` (clamped; ``low`` says which one
+        holds), per count row its segment ``start`` / ``tdeg`` (the longest: ``dmax``) and slot degrees ``deg``, per canonical
+        row ``cstart`` / ``ctdeg`` (``cdmax``), and ``pos`` = 0 .. dmax - 1.  None where a count row has more than
+        LAYER2_MAX_DEGREE sources (dense graphs leave here, before any sort)"""
         S, nc, n = self.slots, self.num_count, self.num_rows
-        if nc == 0 or not self.table_empty:                     # (the narrow-table case only: a table slot without entries)
-            return None
         vr = self.vrowptr.to(torch.int64)
         start = vr[0:S * nc:S]
         tdeg = vr[S:S * nc + 1:S] - start                       # total degree of every count row
         dmax = int(tdeg.max().item())
-        if dmax > self.LAYER2_MAX_DEGREE:                       # (dense graphs leave here, before any sort)
+        if dmax > self.LAYER2_MAX_DEGREE:
+            return None
+        dev = vr.device
+        col = self.vcol.to(torch.int64)
+        dall = vr[1:] - vr[:-1]
+        low = (torch.repeat_interleave(torch.arange(n * S, device=dev), dall) % S) < 2
+        cstart = vr[S * nc:S * n:S]
+        ctdeg = vr[S * nc + S::S] - cstart
+        return _LevelCSR(col, low, col.clamp(max=nc - 1), (col - nc).clamp(min=0, max=max(n - nc - 1, 0)), start, tdeg, dmax,
+                         cstart, ctdeg, int(ctdeg.max().item()) if n > nc else 0, dall[:S * nc].view(nc, S),
+                         torch.arange(max(dmax, 1), device=dev))
+
+    @staticmethod
+    def _rep_csr(c, rep, ent):
+        """(rep_uptr, rep_vcol): the compact CSR of the count rows ``rep``, their segments copied from ``ent``"""
+        rep_uptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=rep.device), c.deg[rep].reshape(-1).cumsum(0)])
+        ne = ent.numel()
+        if not ne:
+            return rep_uptr, ent
+        idx = c.start[rep][:, None] + c.pos[None, :]
+        return rep_uptr, ent[idx.clamp(max=ne - 1)][c.pos[None, :] < c.tdeg[rep][:, None]]
+
+    def _build_layer2_table(self):
+        S, nc = self.slots, self.num_count
+        if nc == 0 or not self.table_empty:                     # (the narrow-table case only: a table slot without entries)
+            return None
+        c = self._level_csr()
+        if c is None:
             return None
         tab1, ctab = self._table_indices()
         if tab1 is None or ctab is None:
             return None
-        umax = min(self.LAYER2_MAX_CLASSES, nc // self.LAYER2_MIN_ROWS_PER_CLASS)
+        # rows of one class agree in their degree tuple and in their segment of table ids (the slot boundaries inside the
+        # segment follow from the degree tuple)
         vcol_tc = ctab[2].to(torch.int64)
-        ne = vcol_tc.numel()
-        # pair refinement: rows of one class after step j agree in their degree tuple and in segment entries 0 .. j (the slot
-        # boundaries inside the segment follow from the degree tuple); an entry past the row's end counts as -1
-        key = tab1[1].to(torch.int64)
-        nkey = tab1[0].numel() // S
-        width = (int(vcol_tc.max().item()) + 2) if ne else 1
-        for j in range(dmax):
-            if nkey > umax:
-                return None
-            ent = torch.where(tdeg > j, vcol_tc[(start + j).clamp(max=max(ne - 1, 0))] + 1, torch.zeros_like(tdeg))
-            assert nkey * width < 2 ** 62
-            uniq, key = torch.unique(key * width + ent, return_inverse=True)
-            nkey = uniq.numel()
-        if nkey > umax:
+        r = self._refine_classes(tab1[1].to(torch.int64), tab1[0].numel() // S, c.start, c.tdeg, vcol_tc, c.dmax,
+                                 (int(vcol_tc.max().item()) + 2) if vcol_tc.numel() else 1,
+                                 min(self.LAYER2_MAX_CLASSES, nc // self.LAYER2_MIN_ROWS_PER_CLASS))
+        if r is None:
             return None
-        dev = vr.device
-        # the lowest row of every class: the first of its run in a STABLE sort by class (an atomic-min scatter of millions of
-        # rows onto a thousand addresses takes ten times as long)
-        order = torch.argsort(key, stable=True)
-        size = torch.bincount(key, minlength=nkey)
-        rep = order[torch.cumsum(size, 0) - size]
-        deg = (vr[1:S * nc + 1] - vr[:S * nc]).view(nc, S)
-        rep_uptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), deg[rep].reshape(-1).cumsum(0)])
-        pos = torch.arange(max(dmax, 1), device=dev)
-        idx = start[rep][:, None] + pos[None, :]
-        rep_vcol = vcol_tc[idx.clamp(max=max(ne - 1, 0))][pos[None, :] < tdeg[rep][:, None]] if ne else vcol_tc
-        cls = key.to(torch.int32).contiguous()
-        dall = vr[1:] - vr[:-1]
-        low = (torch.repeat_interleave(torch.arange(n * S, device=dev), dall) % S) < 2
-        col = self.vcol.to(torch.int64)
-        vcol_2 = torch.where(low, key[col.clamp(max=nc - 1)], col).to(torch.int32)
-        return (cls, rep_uptr.to(torch.int32).contiguous(), rep_vcol.to(torch.int32).contiguous(), vcol_2.contiguous())
+        key, u2 = r
+        rep_uptr, rep_vcol = self._rep_csr(c, self._lowest_rows(key, u2), vcol_tc)
+        vcol_2 = torch.where(c.low, key[c.csrc], c.col).to(torch.int32)
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        return (i32(key), i32(rep_uptr), i32(rep_vcol), vcol_2.contiguous())
 
-    def layer2_rep_pool_index(self):
-        """the fused-pooling index of ONE segment over the U_2 representatives (the pooled layer launch that computes their
-        rows wants one; its partial rows are discarded): (pool_bits, pool_slot, a [slots, 64] buffer for them), cached"""
-        idx = self.__dict__.get("_layer2_rep_pool")
+    def _table_level(self, level: int):
+        """the class index of table level ``level`` >= 2 (``layer2_table_index``, ``layer3_table_index``, an entry of
+        ``deep_table_index``), or None"""
+        if level <= 3:
+            return self.layer2_table_index() if level == 2 else self.layer3_table_index()
+        deep = self.deep_table_index()
+        return deep[level - 4] if level - 4 < len(deep) else None
+
+    def rep_pool_index(self, level: int):
+        """the fused-pooling index of ONE segment over the representatives of table level ``level`` (the pooled layer launch
+        that computes their rows wants one; its partial rows are discarded): (pool_bits, pool_slot, a [slots, 64] buffer for
+        them), cached per level"""
+        cache = self.__dict__.setdefault("_rep_pool", {})
+        idx = cache.get(level)
         if idx is None:
-            u2 = (self.layer2_table_index()[1].numel() - 1) // self.slots
-            nt = (u2 + 15) // 16
+            u = (self._table_level(level)[1].numel() - 1) // self.slots
+            nt = (u + 15) // 16
             dev = self.vrowptr.device
             bits = torch.zeros(nt, dtype=torch.int32, device=dev)
-            bits[nt - 1] = 1 << ((u2 - 1) % 16)
-            idx = self.__dict__["_layer2_rep_pool"] = (bits, torch.arange(nt, dtype=torch.int32, device=dev),
-                                                       torch.empty((nt, 64), device=dev))
+            bits[nt - 1] = 1 << ((u - 1) % 16)
+            idx = cache[level] = (bits, torch.arange(nt, dtype=torch.int32, device=dev), torch.empty((nt, 64), device=dev))
         return idx
 
     # eligibility bounds of layer3_table_index, the path's own (tests lower LAYER2_* on small blocks and pin their launches): a
@@ -424,75 +447,57 @@ class NeighborhoodBatch(_TrainIndexMixin):
         if "_layer3_table" in self.__dict__:
             return self.__dict__["_layer3_table"]
         self.__dict__["_layer3_table"] = res = self._build_layer3_table()
-        if res is not None and res[0].is_cuda:
-            from . import ops
-            # every id that a kernel uses as an address, checked once per batch: cls3 (table3: the pooling walk, the fourth
-            # layer's own rows), the representatives' sources and own rows (table2, the table product)
-            u3, u2 = res[3].numel(), (self.layer2_table_index()[1].numel() - 1) // self.slots
-            ops.index_range_check(res[0], u3)
-            ops.index_range_check(res[3], u2)
-            ops.index_range_check(res[2], max(u2, res[6].numel()))
-            ops.index_range_check(res[5], res[6].numel())
+        if res is not None:
+            self._check_level_ids(res, (self.layer2_table_index()[1].numel() - 1) // self.slots)
         return res
+
+    @staticmethod
+    def _check_level_ids(level, u_prev):
+        """every id of a level's tuple that a kernel uses as an address, checked once per batch against the sizes of the level
+        before it (``u_prev`` rows in its table): the classes (this level's table: the pooling walk, the next layer's own
+        rows), the representatives' own rows and sources (the table before, the table product), the canonical classes"""
+        cls_k, _, rep_vcol, rep_self, _, ccls, crep = level
+        if cls_k.is_cuda:
+            from . import ops
+            ops.index_range_check(cls_k, rep_self.numel())
+            ops.index_range_check(rep_self, u_prev)
+            ops.index_range_check(rep_vcol, max(u_prev, crep.numel()))
+            ops.index_range_check(ccls, crep.numel())
+
+    def _next_level(self, c, key, u, ckey, uc, ent, ebound, umax):
+        """One step of the recurrence that every level k >= 3 shares: ``key`` the count classes of X_{k-1} (``u`` of them),
+        ``ckey`` the canonical classes of X_{k-2} (``uc``), ``ent`` per CSR entry the source's class of X_{k-2} -- the count
+        class in slots 0 and 1, the canonical class in the table slots, ids below ``ebound`` -- and ``c`` = ``_level_csr()``.
+        -> level k's tuple as ``layer3_table_index`` lays it out, or None where level k has more than ``umax`` classes"""
+        # canonical classes of X_{k-1}: the own class, then per entry the source's class
+        ckey, uc = self._refine_classes(ckey, uc, c.cstart, c.ctdeg, ent, c.cdmax, ebound + 1, ckey.numel())
+        crep = self._lowest_rows(ckey, uc)
+        # count classes of X_k: the same one level on
+        ent = torch.where(c.low, key[c.csrc], ckey[c.qsrc])
+        r = self._refine_classes(key, u, c.start, c.tdeg, ent, c.dmax, max(u, uc) + 1, umax)
+        if r is None:
+            return None
+        key_k, u_k = r
+        rep = self._lowest_rows(key_k, u_k)
+        rep_uptr, rep_vcol = self._rep_csr(c, rep, ent)
+        vcol_k = torch.where(c.low, key_k[c.csrc], c.col).to(torch.int32)
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        return (i32(key_k), i32(rep_uptr), i32(rep_vcol), i32(key[rep]), vcol_k.contiguous(), i32(ckey), crep.contiguous())
 
     def _build_layer3_table(self):
         S, nc, n = self.slots, self.num_count, self.num_rows
         tab2 = self.layer2_table_index() if nc >= self.LAYER3_MIN_ROWS else None    # (small blocks leave before any work)
-        if tab2 is None:
+        if tab2 is None or n == nc:
             return None
-        B = n - nc
-        ctab = self.canonical_table_index()
-        vr = self.vrowptr.to(torch.int64)
-        dev = vr.device
-        # canonical classes of X_2
-        cstart = vr[S * nc:S * n:S]
-        ctdeg = vr[S * nc + S::S] - cstart
-        cdmax = int(ctdeg.max().item()) if B else 0
-        if B == 0 or cdmax > self.LAYER2_MAX_DEGREE:
+        c = self._level_csr()
+        if c.cdmax > self.LAYER2_MAX_DEGREE:
             return None
-        vcol_tc = ctab[2].to(torch.int64)
-        ne = vcol_tc.numel()
-        r = self._refine_classes(ctab[1].to(torch.int64), (ctab[0].numel() - 1) // S, cstart, ctdeg, vcol_tc, cdmax,
-                                 (int(vcol_tc.max().item()) + 2) if ne else 1, B)
-        ckey, uc2 = r
-        crep = self._lowest_rows(ckey, uc2)
-        # count classes of X_3: the own class, then per entry the source's class (count rows) or canonical class
-        cls2 = tab2[0].to(torch.int64)
-        u2 = (tab2[1].numel() - 1) // S
-        col = self.vcol.to(torch.int64)
-        dall = vr[1:] - vr[:-1]
-        low = (torch.repeat_interleave(torch.arange(n * S, device=dev), dall) % S) < 2
-        ent = torch.where(low, cls2[col.clamp(max=nc - 1)], ckey[(col - nc).clamp(min=0, max=B - 1)])
-        start = vr[0:S * nc:S]
-        tdeg = vr[S:S * nc + 1:S] - start
-        dmax = int(tdeg.max().item())
-        umax = min(self.LAYER3_MAX_CLASSES, nc // self.LAYER3_MIN_ROWS_PER_CLASS)
-        r = self._refine_classes(cls2, u2, start, tdeg, ent, dmax, max(u2, uc2) + 1, umax)
-        if r is None:
-            return None
-        key, u3 = r
-        rep = self._lowest_rows(key, u3)
-        deg = dall[:S * nc].view(nc, S)
-        rep_uptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), deg[rep].reshape(-1).cumsum(0)])
-        pos = torch.arange(max(dmax, 1), device=dev)
-        idx = start[rep][:, None] + pos[None, :]
-        rep_vcol = ent[idx.clamp(max=max(ne - 1, 0))][pos[None, :] < tdeg[rep][:, None]] if ne else ent
-        vcol_3 = torch.where(low, key[col.clamp(max=nc - 1)], col).to(torch.int32)
-        i32 = lambda t: t.to(torch.int32).contiguous()
-        return (i32(key), i32(rep_uptr), i32(rep_vcol), i32(cls2[rep]), vcol_3.contiguous(), i32(ckey), crep.contiguous())
-
-    def layer3_rep_pool_index(self):
-        """``layer2_rep_pool_index`` for the U_3 representatives of ``layer3_table_index``"""
-        idx = self.__dict__.get("_layer3_rep_pool")
-        if idx is None:
-            u3 = self.layer3_table_index()[3].numel()
-            nt = (u3 + 15) // 16
-            dev = self.vrowptr.device
-            bits = torch.zeros(nt, dtype=torch.int32, device=dev)
-            bits[nt - 1] = 1 << ((u3 - 1) % 16)
-            idx = self.__dict__["_layer3_rep_pool"] = (bits, torch.arange(nt, dtype=torch.int32, device=dev),
-                                                       torch.empty((nt, 64), device=dev))
-        return idx
+        # level 3 from the first layer's tables: canonical classes of X_1 = degree tuples, entries = first-layer table ids
+        tab1, ctab = self._table_indices()
+        u1, uc1 = tab1[0].numel() // S, (ctab[0].numel() - 1) // S
+        return self._next_level(c, tab2[0].to(torch.int64), (tab2[1].numel() - 1) // S, ctab[1].to(torch.int64), uc1,
+                                ctab[2].to(torch.int64), max(u1, uc1),
+                                min(self.LAYER3_MAX_CLASSES, nc // self.LAYER3_MIN_ROWS_PER_CLASS))
 
     # eligibility bounds of deep_table_index, the path's own (tests lower LAYER2_* / LAYER3_* on small blocks and pin the launches
     # that result), all about profit only and all measured (profiles/deep_layer_tables_ab.md).  The deepest level built: on
@@ -524,77 +529,32 @@ class NeighborhoodBatch(_TrainIndexMixin):
         if "_deep_table" in self.__dict__:
             return self.__dict__["_deep_table"]
         self.__dict__["_deep_table"] = res = self._build_deep_tables()
-        if res and res[0][0].is_cuda:
-            from . import ops
-            # every id that a kernel uses as an address, checked once per batch (as layer3_table_index checks its own)
-            u_prev = self.layer3_table_index()[3].numel()
-            for cls_k, _, rep_vcol, rep_self, _, ccls, crep in res:
-                ops.index_range_check(cls_k, rep_self.numel())
-                ops.index_range_check(rep_self, u_prev)
-                ops.index_range_check(rep_vcol, max(u_prev, crep.numel()))
-                ops.index_range_check(ccls, crep.numel())
-                u_prev = rep_self.numel()
+        for k, level in enumerate(res, 4):
+            self._check_level_ids(level, self._table_level(k - 1)[3].numel())
         return res
 
     def _build_deep_tables(self):
-        S, nc, n = self.slots, self.num_count, self.num_rows
+        nc = self.num_count
         levels = []
         if nc < self.DEEP_TABLE_MIN_ROWS or self.DEEP_TABLE_MAX_LEVEL < 4:      # (small blocks leave before any work)
             return levels
-        tab3 = self.layer3_table_index()
-        if tab3 is None:
+        prev = self.layer3_table_index()
+        if prev is None:
             return levels
-        B = n - nc
-        vr = self.vrowptr.to(torch.int64)
-        dev = vr.device
-        col = self.vcol.to(torch.int64)
-        dall = vr[1:] - vr[:-1]
-        low = (torch.repeat_interleave(torch.arange(n * S, device=dev), dall) % S) < 2
-        csrc, qsrc = col.clamp(max=nc - 1), (col - nc).clamp(min=0, max=B - 1)
-        start, cstart = vr[0:S * nc:S], vr[S * nc:S * n:S]
-        tdeg, ctdeg = vr[S:S * nc + 1:S] - start, vr[S * nc + S::S] - cstart
-        dmax, cdmax = int(tdeg.max().item()), int(ctdeg.max().item())
-        deg = dall[:S * nc].view(nc, S)
-        ne = col.numel()
-        pos = torch.arange(max(dmax, 1), device=dev)
-        i32 = lambda t: t.to(torch.int32).contiguous()
+        before, c = self.layer2_table_index(), self._level_csr()
         umax = min(self.DEEP_TABLE_MAX_CLASSES, nc // self.DEEP_TABLE_MIN_ROWS_PER_CLASS)
-        # level k from level k - 1: ``key`` the count classes of X_{k-1}, ``ckey`` the canonical classes of X_{k-2}, ``ent`` per CSR
-        # entry the source's class of X_{k-2} (count class in slots 0 and 1, canonical class in the table slots)
-        key, u = tab3[0].to(torch.int64), tab3[3].numel()
-        ckey, uc = tab3[5].to(torch.int64), tab3[6].numel()
-        u_pp = (self.layer2_table_index()[1].numel() - 1) // S
-        ent = torch.where(low, self.layer2_table_index()[0].to(torch.int64)[csrc], ckey[qsrc])
+        size = lambda level: (level[1].numel() - 1) // self.slots
         for k in range(4, self.DEEP_TABLE_MAX_LEVEL + 1):
-            ckey, uc_new = self._refine_classes(ckey, uc, cstart, ctdeg, ent, cdmax, max(u_pp, uc) + 1, B)
-            crep = self._lowest_rows(ckey, uc_new)
-            ent = torch.where(low, key[csrc], ckey[qsrc])
-            r = self._refine_classes(key, u, start, tdeg, ent, dmax, max(u, uc_new) + 1, umax)
+            # level k from level k - 1 (``prev``: its count classes, the canonical classes it was built on) and the count classes
+            # of level k - 2 (``before``), which with those canonical classes are what the entries' sources were at level k - 1
+            key, ckey, uc = prev[0].to(torch.int64), prev[5].to(torch.int64), prev[6].numel()
+            ent = torch.where(c.low, before[0].to(torch.int64)[c.csrc], ckey[c.qsrc])
+            r = self._next_level(c, key, size(prev), ckey, uc, ent, max(size(before), uc), umax)
             if r is None:
                 break
-            key_k, u_k = r
-            rep = self._lowest_rows(key_k, u_k)
-            rep_uptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), deg[rep].reshape(-1).cumsum(0)])
-            idx = start[rep][:, None] + pos[None, :]
-            rep_vcol = ent[idx.clamp(max=max(ne - 1, 0))][pos[None, :] < tdeg[rep][:, None]] if ne else ent
-            vcol_k = torch.where(low, key_k[csrc], col).to(torch.int32)
-            levels.append((i32(key_k), i32(rep_uptr), i32(rep_vcol), i32(key[rep]), vcol_k.contiguous(), i32(ckey),
-                           crep.contiguous()))
-            u_pp, uc, key, u = u, uc_new, key_k, u_k
+            levels.append(r)
+            before, prev = prev, r
         return levels
-
-    def deep_rep_pool_index(self, level: int):
-        """``layer2_rep_pool_index`` for the representatives of table level ``level`` (>= 4) of ``deep_table_index``"""
-        cache = self.__dict__.setdefault("_deep_rep_pool", {})
-        idx = cache.get(level)
-        if idx is None:
-            uk = self.deep_table_index()[level - 4][3].numel()
-            nt = (uk + 15) // 16
-            dev = self.vrowptr.device
-            bits = torch.zeros(nt, dtype=torch.int32, device=dev)
-            bits[nt - 1] = 1 << ((uk - 1) % 16)
-            idx = cache[level] = (bits, torch.arange(nt, dtype=torch.int32, device=dev), torch.empty((nt, 64), device=dev))
-        return idx
 
     @property
     def table_empty(self) -> int:

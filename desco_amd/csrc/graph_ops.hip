@@ -1186,160 +1186,9 @@ extern "C" int desco_table_rows_pool2_f32(const float* table1, int64_t ldt1, int
   return launch_pool2<false, false>(a, b, num_rows, out2, ldo2, pool_bits, pool_slot, st);
 }
 
-// ... and of THREE table layers (gnn_model.THIRD_LAYER_TABLE: X_3's count rows are table3[cls3] as well).  The walk of
-// table_rows_pool2_kernel with a third running sum: same tiles, same groups of POOL2_GROUP tiles per wait, lanes 32-47 hold
-// the third layer's ids (still one load per tile), no rows stored.  Which tables are staged in LDS is decided per table
-// (LA / LB / LC); the third layer's table is a few MB on the shapes that take the path and is read through L2.
-namespace desco {
-template <bool LA, bool LB, bool LC>
-__global__ __launch_bounds__(POOL2_THREADS) void table_rows_pool3_kernel(PoolTable a, PoolTable b, PoolTable c,
-                                                                         int64_t num_rows,
-                                                                         const uint32_t* __restrict__ pool_bits,
-                                                                         const int32_t* __restrict__ pool_slot) {
-  extern __shared__ float4 pool2_lds[];
-  float* la = reinterpret_cast<float*>(pool2_lds);
-  float* lb = la + (LA ? a.num * 64 : 0);
-  float* lc = lb + (LB ? b.num * 64 : 0);
-  if (LA) pool2_stage(la, a);
-  if (LB) pool2_stage(lb, b);
-  if (LC) pool2_stage(lc, c);
-  if (LA || LB || LC) __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t ntiles = (num_rows + 15) / 16, step = (int64_t)gridDim.x * POOL2_WAVES;
-  int64_t t = (int64_t)blockIdx.x * POOL2_WAVES + wave;
-  if (t >= ntiles) return;
-  const float* ra = (LA ? la : a.table) + lane;
-  const float* rb = (LB ? lb : b.table) + lane;
-  const float* rc = (LC ? lc : c.table) + lane;
-  const int64_t sa = LA ? 64 : a.ld, sb = LB ? 64 : b.ld, sc = LC ? 64 : c.ld;
-  // (lanes 48-63 repeat lanes 32-47; their ids are not used)
-  const int32_t* ids = (lane & 32) ? c.ids : ((lane & 16) ? b.ids : a.ids);
-  const int top = ((lane & 32) ? c.num : ((lane & 16) ? b.num : a.num)) - 1;
-  int cn[POOL2_GROUP], sn[POOL2_GROUP];
-  uint32_t En[POOL2_GROUP];
-  auto request = [&](int64_t t0) {
-#pragma unroll
-    for (int g = 0; g < POOL2_GROUP; ++g) {
-      const int64_t tg = t0 + g * step < ntiles ? t0 + g * step : t0, ri = tg * 16 + (lane & 15);
-      cn[g] = ids[ri < num_rows ? ri : num_rows - 1];
-      En[g] = pool_bits[tg];
-      sn[g] = pool_slot[tg];
-    }
-  };
-  request(t);
-  for (; t < ntiles; t += step * POOL2_GROUP) {
-    int id[POOL2_GROUP], slot0[POOL2_GROUP];
-    uint32_t Eg[POOL2_GROUP];
-#pragma unroll
-    for (int g = 0; g < POOL2_GROUP; ++g) {
-      // (an id outside its table -- the caller's error, desco_index_range_check_i32 finds it -- reads the nearest table row)
-      id[g] = cn[g] < 0 ? 0 : (cn[g] < top ? cn[g] : top);
-      Eg[g] = __builtin_amdgcn_readfirstlane(En[g]);
-      slot0[g] = __builtin_amdgcn_readfirstlane(sn[g]);
-    }
-    request(t + step * POOL2_GROUP < ntiles ? t + step * POOL2_GROUP : t);
-#pragma unroll
-    for (int g = 0; g < POOL2_GROUP; ++g) {
-      const int64_t tg = t + g * step;
-      if (tg >= ntiles) break;                             // (wave-uniform)
-      const uint32_t E = Eg[g];
-      int slot = slot0[g];
-      const int nr = (int)((num_rows - tg * 16) < 16 ? (num_rows - tg * 16) : 16);
-      float va[16], vb[16], vc[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        vc[r] = rc[(int64_t)__builtin_amdgcn_readlane(id[g], 32 + r) * sc];
-        va[r] = ra[(int64_t)__builtin_amdgcn_readlane(id[g], r) * sa];
-        vb[r] = rb[(int64_t)__builtin_amdgcn_readlane(id[g], 16 + r) * sb];
-      }
-      float* pa = a.part + lane;
-      float* pb = b.part + lane;
-      float* pc = c.part + lane;
-      float runa = 0.f, runb = 0.f, runc = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (r < nr) {                                      // (wave-uniform)
-          runa += va[r];
-          runb += vb[r];
-          runc += vc[r];
-          if ((E >> r) & 1u) {                             // row r ends its segment (wave-uniform)
-            pa[(int64_t)slot * 64] = runa;
-            pb[(int64_t)slot * 64] = runb;
-            pc[(int64_t)slot * 64] = runc;
-            ++slot;
-            runa = runb = runc = 0.f;
-          }
-        }
-      }
-      if (nr > 0 && !((E >> (nr - 1)) & 1u)) {
-        pa[(int64_t)slot * 64] = runa;
-        pb[(int64_t)slot * 64] = runb;
-        pc[(int64_t)slot * 64] = runc;
-      }
-    }
-  }
-}
-
-template <bool LA, bool LB, bool LC>
-int launch_pool3(const PoolTable& a, const PoolTable& b, const PoolTable& c, int64_t num_rows, const uint32_t* pool_bits,
-                 const int32_t* pool_slot, hipStream_t st) {
-  const size_t lds = (size_t)((LA ? a.num : 0) + (LB ? b.num : 0) + (LC ? c.num : 0)) * 256;
-  if (lds > 0)
-    if (const hipError_t e = size_dynamic_lds<table_rows_pool3_kernel<LA, LB, LC>>(POOL2_LDS_BYTES); e != hipSuccess)
-      return fail((int)e, "desco_table_rows_pool3_f32: cannot size LDS");
-  const int64_t ntiles = (num_rows + 15) / 16;
-  const unsigned grid = persistent_grid((ntiles + POOL2_WAVES - 1) / POOL2_WAVES);
-  hipLaunchKernelGGL((table_rows_pool3_kernel<LA, LB, LC>), dim3(grid), dim3(POOL2_THREADS), lds, st, a, b, c, num_rows,
-                     pool_bits, pool_slot);
-  return launch_status("desco_table_rows_pool3_f32");
-}
-}  // namespace desco
-
-extern "C" int desco_table_rows_pool3_f32(const float* const* tables, const int64_t* ldts, const int64_t* num_tables,
-                                          const int32_t* const* ids, float* const* pool_parts, int64_t num_rows,
-                                          const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream) {
-  if (num_rows == 0) return 0;
-  bool bad = !tables || !ldts || !num_tables || !ids || !pool_parts || !pool_bits || !pool_slot || num_rows < 0;
-  for (int k = 0; k < 3 && !bad; ++k) {
-    bad = !tables[k] || !ids[k] || !pool_parts[k] || num_tables[k] < 1 || num_tables[k] > INT32_MAX || ldts[k] < 64 ||
-          ldts[k] % 4 || mis16(tables[k]) || mis16(pool_parts[k]);
-    for (int j = 0; j < k && !bad; ++j) bad = pool_parts[j] == pool_parts[k];
-  }
-  if (bad)
-    return fail(DESCO_EINVAL, "desco_table_rows_pool3_f32: bad argument (per layer a table, ids and partial rows of their "
-                              "own, the pooling index present, tables of 1 .. 2^31 - 1 rows, 16-byte rows of at least 64 "
-                              "floats)");
-  // which tables live in LDS: smallest first while they fit together (a small table is the one every tile reads again and
-  // again; the ties go to the earlier layer)
-  const int64_t cap = POOL2_LDS_BYTES / 256;
-  bool in[3] = {false, false, false};
-  int64_t used = 0;
-  for (int n = 0; n < 3; ++n) {
-    int best = -1;
-    for (int k = 0; k < 3; ++k)
-      if (!in[k] && (best < 0 || num_tables[k] < num_tables[best])) best = k;
-    if (used + num_tables[best] > cap) break;
-    in[best] = true;
-    used += num_tables[best];
-  }
-  desco::PoolTable p[3];
-  for (int k = 0; k < 3; ++k) p[k] = desco::PoolTable{tables[k], ldts[k], (int)num_tables[k], ids[k], pool_parts[k]};
-  hipStream_t st = (hipStream_t)stream;
-  switch ((in[0] ? 1 : 0) | (in[1] ? 2 : 0) | (in[2] ? 4 : 0)) {
-    case 0: return desco::launch_pool3<false, false, false>(p[0], p[1], p[2], num_rows, pool_bits, pool_slot, st);
-    case 1: return desco::launch_pool3<true, false, false>(p[0], p[1], p[2], num_rows, pool_bits, pool_slot, st);
-    case 2: return desco::launch_pool3<false, true, false>(p[0], p[1], p[2], num_rows, pool_bits, pool_slot, st);
-    case 3: return desco::launch_pool3<true, true, false>(p[0], p[1], p[2], num_rows, pool_bits, pool_slot, st);
-    case 4: return desco::launch_pool3<false, false, true>(p[0], p[1], p[2], num_rows, pool_bits, pool_slot, st);
-    case 5: return desco::launch_pool3<true, false, true>(p[0], p[1], p[2], num_rows, pool_bits, pool_slot, st);
-    case 6: return desco::launch_pool3<false, true, true>(p[0], p[1], p[2], num_rows, pool_bits, pool_slot, st);
-    default: return desco::launch_pool3<true, true, true>(p[0], p[1], p[2], num_rows, pool_bits, pool_slot, st);
-  }
-}
-
-// ... and of UP TO EIGHT table layers (gnn_model.DEEP_LAYER_TABLES: X_4 .. X_8 are tables of their distinct rows as well).
-// The walk of table_rows_pool3_kernel -- same tiles, same groups of POOL2_GROUP tiles per wait, a running sum per layer, no
-// rows stored -- with the number of layers a template parameter:
+// ... and of UP TO EIGHT table layers (gnn_model.THIRD_LAYER_TABLE, DEEP_LAYER_TABLES: X_3 .. X_8 are tables of their distinct
+// rows as well).  The walk of table_rows_pool2_kernel -- same tiles, same groups of POOL2_GROUP tiles per wait, a running sum
+// per layer -- that stores no rows, with the number of layers a template parameter:
 //  * four layers' ids fill the 64 lanes of one load (lanes 16 q .. 16 q + 15: layer q of the four); layers 4 .. 7 take a
 //    second id load per tile, requested with the first;
 //  * a tile's rows are read and summed at most POOLN_BATCH layers at a time, so that the rows in flight stay within the 128
@@ -1349,7 +1198,8 @@ extern "C" int desco_table_rows_pool3_f32(const float* const* tables, const int6
 namespace desco {
 constexpr int POOLN_MAX = 8;                               // layers per walk
 // layers whose 16 rows of a tile are in flight together: four spill (28 .. 108 bytes of scratch per lane), three spill from five
-// layers on; two fit up to six layers (100 VGPRs at four, 123 at six), seven and eight layers take one (115 and 113 VGPRs)
+// layers on; two fit up to six layers (100 VGPRs at four, 123 at six), seven and eight layers take one (115 and 113 VGPRs).
+// A walk of three layers has them all in flight (116 VGPRs)
 constexpr int POOLN_BATCH = 2;
 
 struct PoolTables {
@@ -1363,7 +1213,7 @@ __global__ __launch_bounds__(POOL2_THREADS) void table_rows_pooln_kernel(PoolTab
                                                                          const int32_t* __restrict__ pool_slot) {
   static_assert(NT >= 1 && NT <= POOLN_MAX, "one to eight layers");
   constexpr int NH = (NT + 3) / 4;                         // id loads per tile
-  constexpr int TB = NT > 6 ? 1 : (NT < POOLN_BATCH ? NT : POOLN_BATCH);
+  constexpr int TB = NT <= 3 ? NT : (NT > 6 ? 1 : POOLN_BATCH);
   extern __shared__ float4 pool2_lds[];
   float* lds = reinterpret_cast<float*>(pool2_lds);
   bool staged = false;                                     // (block-uniform: kernel arguments only)
@@ -1475,44 +1325,42 @@ __global__ __launch_bounds__(POOL2_THREADS) void table_rows_pooln_kernel(PoolTab
 }
 
 template <int NT>
-int launch_pooln(const PoolTables& p, size_t lds, int64_t num_rows, const uint32_t* pool_bits, const int32_t* pool_slot,
-                 hipStream_t st) {
+int launch_pooln(const char* who, const PoolTables& p, size_t lds, int64_t num_rows, const uint32_t* pool_bits,
+                 const int32_t* pool_slot, hipStream_t st) {
   if (lds > 0)
     if (const hipError_t e = size_dynamic_lds<table_rows_pooln_kernel<NT>>(POOL2_LDS_BYTES); e != hipSuccess)
-      return fail((int)e, "desco_table_rows_pooln_f32: cannot size LDS");
+      return fail((int)e, (std::string(who) + ": cannot size LDS").c_str());
   const int64_t ntiles = (num_rows + 15) / 16;
   const unsigned grid = persistent_grid((ntiles + POOL2_WAVES - 1) / POOL2_WAVES);
   hipLaunchKernelGGL((table_rows_pooln_kernel<NT>), dim3(grid), dim3(POOL2_THREADS), lds, st, p, num_rows, pool_bits,
                      pool_slot);
-  return launch_status("desco_table_rows_pooln_f32");
+  return launch_status(who);
 }
-}  // namespace desco
 
-extern "C" int desco_table_rows_pooln_max_layers(void) { return desco::POOLN_MAX; }
-
-extern "C" int desco_table_rows_pooln_f32(int num_layers, const float* const* tables, const int64_t* ldts,
-                                          const int64_t* num_tables, const int32_t* const* ids, float* const* pool_parts,
-                                          int64_t num_rows, const uint32_t* pool_bits, const int32_t* pool_slot,
-                                          desco_stream_t stream) {
+// the body of both entry points, desco_table_rows_pooln_f32 and (three layers) desco_table_rows_pool3_f32; `who` names the one
+// that was called in the messages
+static int table_rows_pool_walk(const char* who, int nl, const float* const* tables, const int64_t* ldts,
+                                const int64_t* num_tables, const int32_t* const* ids, float* const* pool_parts,
+                                int64_t num_rows, const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream) {
   if (num_rows == 0) return 0;
-  const int nl = num_layers;
-  bool bad = nl < 1 || nl > desco::POOLN_MAX || !tables || !ldts || !num_tables || !ids || !pool_parts || !pool_bits ||
-             !pool_slot || num_rows < 0;
+  bool bad = nl < 1 || nl > POOLN_MAX || !tables || !ldts || !num_tables || !ids || !pool_parts || !pool_bits || !pool_slot ||
+             num_rows < 0;
   for (int k = 0; k < nl && !bad; ++k) {
     bad = !tables[k] || !ids[k] || !pool_parts[k] || num_tables[k] < 1 || num_tables[k] > INT32_MAX || ldts[k] < 64 ||
           ldts[k] % 4 || mis16(tables[k]) || mis16(pool_parts[k]);
     for (int j = 0; j < k && !bad; ++j) bad = pool_parts[j] == pool_parts[k];
   }
   if (bad)
-    return fail(DESCO_EINVAL, "desco_table_rows_pooln_f32: bad argument (one to eight layers, per layer a table, ids and "
-                              "partial rows of their own, the pooling index present, tables of 1 .. 2^31 - 1 rows, 16-byte "
-                              "rows of at least 64 floats)");
-  // which tables live in LDS: smallest first while they fit together (as desco_table_rows_pool3_f32 chooses)
+    return fail(DESCO_EINVAL, (std::string(who) + ": bad argument (one to eight layers, per layer a table, ids and partial "
+                               "rows of their own, the pooling index present, tables of 1 .. 2^31 - 1 rows, 16-byte rows of "
+                               "at least 64 floats)").c_str());
+  // which tables live in LDS: smallest first while they fit together (a small table is the one every tile reads again and
+  // again; the ties go to the earlier layer)
   const int64_t cap = POOL2_LDS_BYTES / 256;
-  desco::PoolTables p{};
-  for (int k = 0; k < desco::POOLN_MAX; ++k) {
+  PoolTables p{};
+  for (int k = 0; k < POOLN_MAX; ++k) {
     const int s = k < nl ? k : nl - 1;                     // (entries past the last layer repeat it: never used, never null)
-    p.t[k] = desco::PoolTable{tables[s], ldts[s], (int)num_tables[s], ids[s], pool_parts[s]};
+    p.t[k] = PoolTable{tables[s], ldts[s], (int)num_tables[s], ids[s], pool_parts[s]};
     p.lds_off[k] = -1;
   }
   int64_t used = 0;
@@ -1527,15 +1375,34 @@ extern "C" int desco_table_rows_pooln_f32(int num_layers, const float* const* ta
   const size_t lds = (size_t)used * 256;
   hipStream_t st = (hipStream_t)stream;
   switch (nl) {
-    case 1: return desco::launch_pooln<1>(p, lds, num_rows, pool_bits, pool_slot, st);
-    case 2: return desco::launch_pooln<2>(p, lds, num_rows, pool_bits, pool_slot, st);
-    case 3: return desco::launch_pooln<3>(p, lds, num_rows, pool_bits, pool_slot, st);
-    case 4: return desco::launch_pooln<4>(p, lds, num_rows, pool_bits, pool_slot, st);
-    case 5: return desco::launch_pooln<5>(p, lds, num_rows, pool_bits, pool_slot, st);
-    case 6: return desco::launch_pooln<6>(p, lds, num_rows, pool_bits, pool_slot, st);
-    case 7: return desco::launch_pooln<7>(p, lds, num_rows, pool_bits, pool_slot, st);
-    default: return desco::launch_pooln<8>(p, lds, num_rows, pool_bits, pool_slot, st);
+    case 1: return launch_pooln<1>(who, p, lds, num_rows, pool_bits, pool_slot, st);
+    case 2: return launch_pooln<2>(who, p, lds, num_rows, pool_bits, pool_slot, st);
+    case 3: return launch_pooln<3>(who, p, lds, num_rows, pool_bits, pool_slot, st);
+    case 4: return launch_pooln<4>(who, p, lds, num_rows, pool_bits, pool_slot, st);
+    case 5: return launch_pooln<5>(who, p, lds, num_rows, pool_bits, pool_slot, st);
+    case 6: return launch_pooln<6>(who, p, lds, num_rows, pool_bits, pool_slot, st);
+    case 7: return launch_pooln<7>(who, p, lds, num_rows, pool_bits, pool_slot, st);
+    default: return launch_pooln<8>(who, p, lds, num_rows, pool_bits, pool_slot, st);
   }
+}
+}  // namespace desco
+
+extern "C" int desco_table_rows_pooln_max_layers(void) { return desco::POOLN_MAX; }
+
+extern "C" int desco_table_rows_pooln_f32(int num_layers, const float* const* tables, const int64_t* ldts,
+                                          const int64_t* num_tables, const int32_t* const* ids, float* const* pool_parts,
+                                          int64_t num_rows, const uint32_t* pool_bits, const int32_t* pool_slot,
+                                          desco_stream_t stream) {
+  return desco::table_rows_pool_walk("desco_table_rows_pooln_f32", num_layers, tables, ldts, num_tables, ids, pool_parts,
+                                     num_rows, pool_bits, pool_slot, stream);
+}
+
+// (gnn_model.THIRD_LAYER_TABLE: the walk of exactly three layers under its own name)
+extern "C" int desco_table_rows_pool3_f32(const float* const* tables, const int64_t* ldts, const int64_t* num_tables,
+                                          const int32_t* const* ids, float* const* pool_parts, int64_t num_rows,
+                                          const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream) {
+  return desco::table_rows_pool_walk("desco_table_rows_pool3_f32", 3, tables, ldts, num_tables, ids, pool_parts, num_rows,
+                                     pool_bits, pool_slot, stream);
 }
 
 extern "C" int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch,

@@ -14,6 +14,7 @@ There is no CPU / eager fallback: inputs must live on the GPU.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import os
@@ -730,54 +731,57 @@ def _anchor_const_input(pk, gnn, canon, row_bound=None):
     return _gemm_planes(canon[:, H:], *pk["anchor_nk_const"], act=ops.ACT_LEAKY, slope=0.1, **kw)
 
 
-# X_1's count rows are never written: the closed-form first layer's output is a function of a row's four slot degrees, so
-# the second layer gathers the few thousand DISTINCT rows from a table and recomputes its own rows from their degrees
-# (NeighborhoodBatch.degree_table_index, desco_shmp_layer_pool_table_f16x3_f32); bit-identical to the launch on the
-# materialised tensor
+# The trunk on tables of distinct rows.  Under ZeroNodeFeat the count rows of X_k are a function of far fewer
+# things than there are rows -- a molecule batch has a few thousand to a few ten thousand distinct ones per layer for millions
+# of rows (COX2-shaped: 531 of X_1, 1 427 of X_2, 12 316 of X_3, 28 561 of X_4, 37 756 of X_8; the classes stop growing) -- so
+# _shmp_pooled keeps X_k's count rows as a table of the distinct rows, table k, and a class per row.  Every path below is
+# bit-identical to the launches on the materialised tensors (the layer kernels' arithmetic is row-local, the sums keep their
+# order), has its own switch, and stacks on the one before it; the tests flip the switches to get the earlier launches back.
+#
+# Level 1: X_1 is the closed-form first layer, a function of a row's four slot degrees (NeighborhoodBatch.degree_table_index).
+# X_1's count rows are never written: the second layer gathers from table 1 and recomputes its own rows from their degrees
+# (desco_shmp_layer_pool_table_f16x3_f32)
 FIRST_LAYER_TABLE = os.environ.get("DESCO_FIRST_LAYER_TABLE", "1") != "0"
 
-# a block without an entry in one of the two table slots (molecule graphs: table slot 0, the canonical->count TRIANGLE
+# The table slots: a block without an entry in one of the two (molecule graphs: table slot 0, the canonical->count TRIANGLE
 # relation) gets no table columns for it -- the canonical->count product writes [B, 64] instead of [B, 128], the count launches
-# read the narrow table (desco_shmp_layer_narrow_f16x3_f32, NeighborhoodBatch.table_empty) -- and the second layer's product runs on the DISTINCT
-# first-layer canonical rows only (NeighborhoodBatch.canonical_table_index); bit-identical, DESIGN.md 4.1
+# read the narrow table (desco_shmp_layer_narrow_f16x3_f32, NeighborhoodBatch.table_empty) -- and the second layer's product
+# runs on the DISTINCT first-layer canonical rows only (NeighborhoodBatch.canonical_table_index)
 TABLE_NARROW = os.environ.get("DESCO_TABLE_NARROW", "1") != "0"
 
-# with both first-layer tables the SECOND layer's count rows are a function of their slot degrees and their remapped CSR
-# segment: a molecule batch has about a thousand distinct ones for millions of rows (NeighborhoodBatch.layer2_table_index).
-# The layer's count launch then runs on one representative per class, and desco_table_rows_pool_f32 writes the rows and their
-# pooled partial sums from that table; bit-identical (the layer kernel's arithmetic is row-local), DESIGN.md 4.1
+# Level k >= 2, one recurrence (NeighborhoodBatch.layer2_table_index, layer3_table_index, deep_table_index): a count row of X_k
+# is a function of its own row of X_{k-1} and, per CSR entry in order, of the source's row of X_{k-1} -- at k = 2 of its slot
+# degrees and its segment of first-layer table ids.  Layer k's count launch runs on one representative per class, sources and
+# own rows in table k - 1 (own rows from their degrees at k = 2; desco_shmp_layer_selfidx_f16x3_f32 above that), the table
+# product on the distinct canonical rows of X_{k-1} only, and leaves table k.  Behind the deepest level's launch one walk over
+# the count rows leaves the pooled partial sums of every table layer (ops.table_rows_pool: desco_table_rows_pool_f32 for one
+# table, desco_table_rows_pool2_f32 for two, desco_table_rows_pool3_f32 / desco_table_rows_pooln_f32 for more).  Layer K + 1,
+# if the model has one, gathers from table K with the column ids of that level's ``vcol_k``, its own rows through the classes.
+# Level 2, where both first-layer tables exist: the walk writes the rows of X_2 as well
 SECOND_LAYER_TABLE = os.environ.get("DESCO_SECOND_LAYER_TABLE", "1") != "0"
 
-# ... and X_2's count rows are then never written either: every one of them is table2[cls[row]], so the third layer's two
-# launches gather from that table -- the count launch with its own rows addressed through the classes
-# (desco_shmp_layer_selfidx_f16x3_f32), both with the column ids of layer2_table_index's ``vcol_2`` -- and
-# desco_table_rows_pool_f32 leaves the partial sums alone; models of three layers or more, blocks of at least
-# NeighborhoodBatch.LAYER2_GATHER_MIN_ROWS count rows; bit-identical, DESIGN.md 4.1
+# ... unless X_2's count rows are never written either -- the third layer's two launches gather from table 2 and the walk
+# leaves the partial sums alone; models of three layers or more, blocks of at least NeighborhoodBatch.LAYER2_GATHER_MIN_ROWS
+# count rows
 SECOND_LAYER_GATHER = os.environ.get("DESCO_SECOND_LAYER_GATHER", "1") != "0"
 
-# with both tables the pooled partial sums of X_1 and X_2 come from ONE walk over the count rows, both tables staged in LDS
-# (desco_table_rows_pool2_f32 through ops.table_rows_pool) -- the first layer's own pooled launch (desco_degree_affine_pool_f32
-# with out = NULL: the affine map evaluated per row for rows that are table1[row_id]) is then not issued; blocks of at least
-# NeighborhoodBatch.POOL_TABLES_MIN_ROWS count rows; the same sums in the same order: bit-identical, DESIGN.md 4.1
+# The first layer's pooled partial sums from the same walk, both tables staged in LDS -- the first layer's own pooled launch
+# (desco_degree_affine_pool_f32 with out = NULL: the affine map evaluated per row for rows that are table1[row_id]) is then
+# not issued; blocks of at least NeighborhoodBatch.POOL_TABLES_MIN_ROWS count rows
 POOL_TABLES = os.environ.get("DESCO_POOL_TABLES", "1") != "0"
 
-# ... and the THIRD layer's count rows are a function of their own X_2 class and their sources' classes, a few thousand distinct
-# rows again (NeighborhoodBatch.layer3_table_index): its count launch runs on one representative per class -- gathering from
-# table2, the table product on the distinct canonical rows of X_2 only -- and leaves table3; X_3's count rows are never
-# written, the fourth layer's launches gather from table3 as the third layer's do from table2, and the partial sums of all
-# three table layers come from one walk (desco_table_rows_pool3_f32), which therefore follows this launch.  Where
-# SECOND_LAYER_GATHER is active and the batch has the index (blocks of at least NeighborhoodBatch.LAYER3_MIN_ROWS count rows);
-# bit-identical, DESIGN.md 4.1
+# Level 3: X_3's count rows are never written, the fourth layer gathers from table 3, and the walk -- now of three tables --
+# follows this level's launch.  Where SECOND_LAYER_GATHER is active and the batch has the index (blocks of at least
+# NeighborhoodBatch.LAYER3_MIN_ROWS count rows)
 THIRD_LAYER_TABLE = os.environ.get("DESCO_THIRD_LAYER_TABLE", "1") != "0"
 
-# ... and so on down the trunk: the classes stop growing (COX2-shaped: 28 561 distinct rows of X_4, 37 756 of X_8, for millions
-# of count rows), so every further layer with a class index (NeighborhoodBatch.deep_table_index: levels 4 .. K) runs its count
-# launch on the representatives as the third does -- sources and own rows in the table before it, the table product on the
-# distinct canonical rows -- and X_4 .. X_K are never written either; layer K + 1, if the model has one, gathers from table K,
-# and the partial sums of all table layers come from the walk behind the last representatives' launch
-# (desco_table_rows_pooln_f32).  Where THIRD_LAYER_TABLE is active and the batch has the index (blocks of at least
-# NeighborhoodBatch.DEEP_TABLE_MIN_ROWS count rows); bit-identical, DESIGN.md 4.1
+# Levels 4 .. K: the same for every further layer with a class index.  Where THIRD_LAYER_TABLE is active and the batch has the
+# index (blocks of at least NeighborhoodBatch.DEEP_TABLE_MIN_ROWS count rows)
 DEEP_LAYER_TABLES = os.environ.get("DESCO_DEEP_LAYER_TABLES", "1") != "0"
+
+# a table level as _shmp_pooled reads it, the layout of layer3_table_index and deep_table_index (level 2 has no ``rep_self`` and
+# no canonical classes: its own rows come from the degrees, its table product from canonical_table_index)
+_TableLevel = namedtuple("_TableLevel", "cls rep_uptr rep_vcol rep_self vcol ccls crep")
 
 
 def _layer2_table(canon_uptr: torch.Tensor, S: int, coef: torch.Tensor, planes: torch.Tensor) -> torch.Tensor:
@@ -838,33 +842,41 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
     temp = batch.table_empty if (TABLE_NARROW and nb and f16 and Nc > 0) else 0      # (bit t: table slot t is empty)
     tblock = 1 if temp == 1 else 0                                                  # the 64-row block of wt_tab_l64 still needed
     ctab = batch.canonical_table_index() if (temp and tab1 is not None) else None
-    # ... and the second layer's count launch on the distinct rows of its OUTPUT (None: the batch is not eligible)
-    tab2 = batch.layer2_table_index() if (SECOND_LAYER_TABLE and ctab is not None and fpool and L >= 2) else None
-    # ... whose output stays a table: the third layer's launches gather from it (the fp16 forms of both node types, so that no
-    # launch of layers 2 and 3 reads or writes a row of X_2)
-    gather2, table2 = False, None
-    if SECOND_LAYER_GATHER and tab2 is not None and L >= 3 and Nc >= batch.LAYER2_GATHER_MIN_ROWS:
-        l1, l2 = pk["layers"][1], pk["layers"][2]
-        gather2 = ("wt_tab" in l2["count"] and all(isinstance(e.get(k), ops.F16Planes) for e, k in (
-            (l1["count"], "wt_mfma_x6"), (l2["count"], "wt_mfma_x6"), (l1["canonical"], "wt_x6"), (l2["canonical"], "wt_x6"))))
-    # ... and the third layer on the distinct rows of ITS output, which stays a table as well (tab3: the class index)
-    tab3 = None
+    # lev[k]: the class index of table level k = 2 .. K -- layer k's count launch runs on the distinct rows of its OUTPUT -- and
+    # tbl[k], k = 1 .. K: the table of X_k's distinct count rows.  Levels stack: each needs the one below and its own switch
+    lev, tbl = {}, {}
     fp16_form = lambda e: ("wt_tab" in e["count"] and isinstance(e["count"].get("wt_mfma_x6"), ops.F16Planes)
                            and isinstance(e["canonical"].get("wt_x6"), ops.F16Planes))
-    if THIRD_LAYER_TABLE and gather2:
-        if L < 4 or fp16_form(pk["layers"][3]):
-            tab3 = batch.layer3_table_index()
-    # tabs[k]: the class index of table level k >= 3 (same layout at every level), ttab[k]: the table of X_k's distinct count rows
-    tabs, ttab = ({} if tab3 is None else {3: tab3}), {}
-    if DEEP_LAYER_TABLES and tab3 is not None and L >= 4:
+    if SECOND_LAYER_TABLE and ctab is not None and fpool and L >= 2:
+        t2 = batch.layer2_table_index()                          # (None: the batch is not eligible)
+        if t2 is not None:
+            lev[2] = _TableLevel(t2[0], t2[1], t2[2], None, t2[3], None, None)
+    # gather2: table 2 is all there is of X_2's count rows, the third layer's launches gather from it (the fp16 forms of both
+    # node types, so that no launch of layers 2 and 3 reads or writes a row of X_2); otherwise the level-2 walk writes X_2
+    gather2 = False
+    if SECOND_LAYER_GATHER and 2 in lev and L >= 3 and Nc >= batch.LAYER2_GATHER_MIN_ROWS:
+        l1, l2 = pk["layers"][1], pk["layers"][2]
+        gather2 = fp16_form(l2) and all(isinstance(l1[t].get(k), ops.F16Planes) for t, k in (("count", "wt_mfma_x6"),
+                                                                                           ("canonical", "wt_x6")))
+    if THIRD_LAYER_TABLE and gather2 and (L < 4 or fp16_form(pk["layers"][3])):
+        t3 = batch.layer3_table_index()
+        if t3 is not None:
+            lev[3] = _TableLevel(*t3)
+    if DEEP_LAYER_TABLES and 3 in lev and L >= 4:
         for k, tk in enumerate(batch.deep_table_index(), 4):
             if k > L or (k < L and not fp16_form(pk["layers"][k])):    # (layer k, if any, gathers from table k)
                 break
-            tabs[k] = tk
-    # ... and the first layer's partial sums left by the second layer's table walk (first_pool: what that launch still owes)
-    pool_tables = POOL_TABLES and pool1 and tab1 is not None and tab2 is not None and Nc >= batch.POOL_TABLES_MIN_ROWS
+            lev[k] = _TableLevel(*tk)
+    # X_k's count rows exist as table k only (never allocated, never written): every level but a second without gather2
+    table_only = lambda k: k in lev and (k > 2 or gather2)
+    # ... and the first layer's partial sums left by the table walk (first_pool: what that launch still owes)
+    pool_tables = POOL_TABLES and pool1 and tab1 is not None and 2 in lev and Nc >= batch.POOL_TABLES_MIN_ROWS
     first_pool = None
     pool_parts = {}
+    # src[l]: how layer l's launches read tbl[l] where X_l's count rows exist as that table only -- the column ids with the count
+    # slots' sources remapped to its rows, and the count launch's OWN rows: from their degrees by these coefficients (l = 1), or
+    # through these ids (above that)
+    src = {}
     if fpool:
         pbits, pslot, nslots = batch.pool_index()
     if const_input:
@@ -875,15 +887,16 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
             pool_parts[1] = torch.empty((nslots, H), device=dev)
         if tab1 is not None:
             coef_c = _first_layer_coef(pk, "count", 4, S, x0, src_of_slot, dev)
-            table1 = torch.empty((tab1[0].numel() // S, H), device=dev)
-            ops.degree_affine(tab1[0], 0, table1.shape[0], S, coef_c, ops.ACT_RELU, 0.0, table1)
+            tbl[1] = torch.empty((tab1[0].numel() // S, H), device=dev)
+            ops.degree_affine(tab1[0], 0, tbl[1].shape[0], S, coef_c, ops.ACT_RELU, 0.0, tbl[1])
+            src[1] = (tab1[2], coef_c, None)
             xn = None
         for t, r0, r1, su in groups:
             if r1 <= r0:
                 continue
             coef = _first_layer_coef(pk, t, su, S, x0, src_of_slot, dev)
             if pool1 and t == "count" and pool_tables:
-                first_pool = (table1, tab1[1], pool_parts[1])
+                first_pool = (tbl[1], tab1[1], pool_parts[1])
             elif pool1 and t == "count":
                 ops.degree_affine_pool(batch.vrowptr, r1, S, coef, ops.ACT_RELU, 0.0, xn, (pbits, pslot, pool_parts[1]))
             elif t == "canonical" and canon_once:
@@ -918,19 +931,10 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
         last = l == L - 1
         # the last layer's count rows feed nothing but the pooling: with fused pooling they are
         # never stored (the canonical rows still are, they sit at the end of the same tensor)
-        # (gather2: X_2 is never allocated; a table level: neither is X_3, X_4, ...)
-        xn = None if ((l == 1 and gather2) or (l + 1) in tabs) else torch.empty((N, H), device=dev)
-        # layer input, column ids and (count rows) self index of this layer's launches: X_l itself, or -- for the second
-        # layer when X_1's count rows exist as a table of distinct rows only -- that table
-        x_src, vcol_l, coef_l, cls_l = X[-1], batch.vcol, None, None
-        if l == 1 and tab1 is not None:
-            x_src, vcol_l, coef_l = table1, tab1[2], coef_c
-        if l == 2 and gather2:
-            # ... and likewise for the third layer: the table of X_2's distinct count rows (kept alive in table2 since the
-            # second layer), sources and own rows addressed by class; the table slots' sources stay global ids
-            x_src, vcol_l, cls_l = table2, tab2[3], tab2[0]
-        if l >= 3 and l in tabs:
-            x_src, vcol_l, cls_l = ttab[l], tabs[l][4], tabs[l][0]                   # ... and for the fourth, and every table level
+        xn = None if table_only(l + 1) else torch.empty((N, H), device=dev)
+        # layer input, column ids and (count rows) own rows of this layer's launches: X_l itself, or the table of its distinct
+        # count rows (src); the table slots' sources stay global ids
+        x_src, (vcol_l, coef_l, cls_l) = (tbl[l], src[l]) if l in src else (X[-1], (batch.vcol, None, None))
         for t, r0, r1, su in groups:
             if r1 <= r0:
                 continue
@@ -946,9 +950,9 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                     # (ctab[2] is tab1[2] with the TABLE slots' sources remapped as well; the canonical launch of this layer
                     #  reads slots 0 and 1 only and keeps tab1[2])
                     vcol_c, y_row0 = ctab[2], 0
-                elif tem and (l + 1) in tabs:
+                elif tem and (l + 1) in lev:
                     # (the representatives' table sources are canonical CLASSES of X_l: the product on their lowest rows)
-                    ytab = ops.linear64(crows.index_select(0, tabs[l + 1][6]), e["wt_tab_l64"][tblock:tblock + 1])
+                    ytab = ops.linear64(crows.index_select(0, lev[l + 1].crep), e["wt_tab_l64"][tblock:tblock + 1])
                     y_row0 = 0
                 elif tem:
                     ytab = ops.linear64(crows, e["wt_tab_l64"][tblock:tblock + 1])   # canonical rows x W2 or W3: [B, 64]
@@ -959,37 +963,26 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                 if fpool and "wt_mfma_x6" in e:
                     pool_parts[l + 1] = torch.empty((nslots, H), device=dev)
                     pool = (pbits, pslot, pool_parts[l + 1])
-                if l == 1 and tab2 is not None and tem and pool is not None:
-                    # the launch on the U_2 representatives' compact CSR (its pooled partials -- one segment -- are not used),
-                    # then every count row and the neighborhoods' partial sums from the table of their rows
-                    cls2, rep_uptr, rep_vcol, _ = tab2
-                    table2 = torch.empty(((rep_uptr.numel() - 1) // S, H), device=dev)
-                    ops.shmp_layer(x_src, rep_uptr, rep_vcol, 0, table2.shape[0], S, 2, e["wt_mfma_x6"], e["b"], table2,
-                                   ytab=ytab, ytab_row0=y_row0, pool=batch.layer2_rep_pool_index(),
-                                   self_coef=coef_l, table_empty=tem)
-                    if tab3 is not None:
-                        continue                       # (the walk follows the third layer's representative launch)
-                    if first_pool is not None:
-                        pool, first_pool = pool + first_pool, None
-                    ops.table_rows_pool(table2, cls2, r1 - r0, None if (last or gather2) else xn, pool)
-                    continue
-                if (l + 1) in tabs:
-                    # the same once more: the launch on the U_k representatives (sources and own rows in the table before), then
-                    # -- behind the deepest level's launch -- the walk(s) for the partial sums of every table layer
-                    k = l + 1
-                    cls_k, rep_uptr, rep_vcol, rep_self = tabs[k][:4]
-                    ttab[k] = torch.empty((rep_self.numel(), H), device=dev)
-                    ops.shmp_layer(x_src, rep_uptr, rep_vcol, 0, ttab[k].shape[0], S, 2, e["wt_mfma_x6"], e["b"], ttab[k],
-                                   ytab=ytab, ytab_row0=y_row0, table_empty=tem, self_index=rep_self,
-                                   pool=batch.layer3_rep_pool_index() if k == 3 else batch.deep_rep_pool_index(k))
-                    if (k + 1) in tabs:
+                if (l + 1) in lev:
+                    # table level k: the launch on the U_k representatives' compact CSR, sources and own rows in the table before
+                    # (own rows from their degrees at k = 2; its pooled partials -- one segment -- are not used), which leaves
+                    # table k; then, behind the deepest level's launch, the walk(s) for the partial sums of every table layer --
+                    # and the rows of X_2 where the second layer is the only level and they are kept
+                    k, lv = l + 1, lev[l + 1]
+                    assert tem and pool is not None, "a table level without the narrow fp16 count launch or the fused pooling"
+                    tbl[k] = torch.empty(((lv.rep_uptr.numel() - 1) // S, H), device=dev)
+                    ops.shmp_layer(x_src, lv.rep_uptr, lv.rep_vcol, 0, tbl[k].shape[0], S, 2, e["wt_mfma_x6"], e["b"], tbl[k],
+                                   ytab=ytab, ytab_row0=y_row0, pool=batch.rep_pool_index(k), self_coef=coef_l,
+                                   table_empty=tem, self_index=lv.rep_self)
+                    if table_only(k):
+                        src[k] = (lv.vcol, None, lv.cls)
+                    if (k + 1) in lev:
                         continue
-                    pool = pool + (table2, tab2[0], pool_parts[2])
-                    for j in range(3, k):
-                        pool = pool + (ttab[j], tabs[j][0], pool_parts[j])
+                    for j in range(2, k):
+                        pool = pool + (tbl[j], lev[j].cls, pool_parts[j])
                     if first_pool is not None:
                         pool, first_pool = pool + first_pool, None
-                    ops.table_rows_pool(ttab[k], cls_k, r1 - r0, None, pool)
+                    ops.table_rows_pool(tbl[k], lv.cls, r1 - r0, None if (last or table_only(k)) else xn, pool)
                     continue
                 ops.shmp_layer(x_src, batch.vrowptr, vcol_c, r0, r1 - r0, S, 2,
                                e.get("wt_mfma_x6", e["wt_mfma"]) if SHMP_BF16X6 else e["wt_mfma"],
@@ -1004,7 +997,7 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                                row_absmax=canon_max if (canonical and w16) else None,
                                xself=canon[:, l * H:(l + 1) * H] if once else None)
         X.append(xn)
-        assert first_pool is None or (l + 2) in tabs, "the first layer's partial sums were left to a launch that was not issued"
+        assert first_pool is None or (l + 2) in lev, "the first layer's partial sums were left to a launch that was not issued"
         if l in pool_parts:
             # layer l's rows have been consumed (their pooled sums sit in pool_parts[l], their canonical
             # rows in `canon`): release them -- a block then holds three [N, 64] tensors instead of nine,

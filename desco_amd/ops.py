@@ -770,20 +770,24 @@ POOL_WALK_LAYERS = 6
 
 
 def _table_rows_pooln(layers, num_rows: int, bits: torch.Tensor, slot: torch.Tensor) -> None:
-    """the pooled partial sums of 1 .. 8 table layers ``(table, ids, pool_part)`` over rows [0, num_rows) from one walk
-    (desco_table_rows_pooln_f32); pool_part of each layer as ``table_rows_pool`` leaves it for that layer alone"""
+    """the pooled partial sums of 1 .. 8 table layers ``(table, ids, pool_part)`` over rows [0, num_rows) from one walk that
+    writes no rows (desco_table_rows_pooln_f32; exactly three layers through desco_table_rows_pool3_f32, the same walk under
+    its own name); pool_part of each layer as ``table_rows_pool`` leaves it for that layer alone"""
     n = len(layers)
     for tk, ik, pk_ in layers:
         assert ik.is_contiguous() and ik.numel() >= num_rows and tk.shape[1] >= 64 and pk_.shape == layers[0][2].shape
     rows = [_rows(tk, "table") for tk, _, _ in layers]
     arr = lambda ct, vals: (ct * n)(*vals)
-    with _Timed("table_rows_pool_kernel", 0.0, 4.0 * n * num_rows):
-        _lib.check(_lib.lib().desco_table_rows_pooln_f32(
-            n, arr(ctypes.c_void_p, [r[0] for r in rows]), arr(ctypes.c_int64, [r[1] for r in rows]),
+    args = (arr(ctypes.c_void_p, [r[0] for r in rows]), arr(ctypes.c_int64, [r[1] for r in rows]),
             arr(ctypes.c_int64, [tk.shape[0] for tk, _, _ in layers]),
             arr(ctypes.c_void_p, [_dev(ik, "ids", torch.int32) for _, ik, _ in layers]),
             arr(ctypes.c_void_p, [_dev(pk_, "pool_part") for _, _, pk_ in layers]), num_rows,
-            _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32), _stream()), "table_rows_pooln")
+            _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32), _stream())
+    with _Timed("table_rows_pool_kernel", 0.0, 4.0 * n * num_rows):
+        if n == 3:
+            _lib.check(_lib.lib().desco_table_rows_pool3_f32(*args), "table_rows_pool3")
+        else:
+            _lib.check(_lib.lib().desco_table_rows_pooln_f32(n, *args), "table_rows_pooln")
 
 
 def table_rows_pool(table: torch.Tensor, cls: torch.Tensor, num_rows: int, out: Optional[torch.Tensor],
@@ -799,50 +803,29 @@ def table_rows_pool(table: torch.Tensor, cls: torch.Tensor, num_rows: int, out: 
     layers (desco_table_rows_pool3_f32; ``out`` must then be None), and with nine or more -- three per further layer -- of
     all of them (``_table_rows_pooln``)."""
     bits, slot, part = pool[:3]
-    tp, ldt = _rows(table, "table")
-    assert cls.is_contiguous() and cls.numel() >= num_rows and table.shape[1] >= 64
-    op, ldo = (None, 64) if out is None else _rows(out, "out")
-    if len(pool) > 9:
-        # three more table layers or more: four or more in all (desco_table_rows_pooln_f32, at most POOL_WALK_LAYERS per walk)
-        if out is not None or len(pool) % 3:
-            raise ValueError("table_rows_pool: (table, ids, pool_part) per further layer; such a walk leaves partial sums only")
-        layers = [pool[i:i + 3] for i in range(3, len(pool), 3)] + [(table, cls, part)]
+    if len(pool) == 9 and out is not None:
+        raise ValueError("table_rows_pool: the three-table walk leaves partial sums only (out must be None)")
+    if len(pool) > 9 and (out is not None or len(pool) % 3):
+        raise ValueError("table_rows_pool: (table, ids, pool_part) per further layer; such a walk leaves partial sums only")
+    # one (table, ids, pool_part) per layer, this call's own last; only the walks of one and two tables write rows
+    layers = [tuple(pool[i:i + 3]) for i in range(3, len(pool), 3)] + [(table, cls, part)]
+    if len(layers) >= 3:
         for i in range(0, len(layers), POOL_WALK_LAYERS):
             _table_rows_pooln(layers[i:i + POOL_WALK_LAYERS], num_rows, bits, slot)
         return
-    if len(pool) == 9:
-        # (..., table_a, ids_a, pool_part_a, table_b, ids_b, pool_part_b): two more table layers over the same rows, their
-        # partial sums and this table's from one walk (desco_table_rows_pool3_f32, which writes no rows)
-        if out is not None:
-            raise ValueError("table_rows_pool: the three-table walk leaves partial sums only (out must be None)")
-        layers = [pool[3:6], pool[6:9], (table, cls, part)]
-        for tk, ik, pk_ in layers:
-            assert ik.is_contiguous() and ik.numel() >= num_rows and tk.shape[1] >= 64 and pk_.shape == part.shape
-        rows = [_rows(tk, "table") for tk, _, _ in layers]
-        arr = lambda ct, vals: (ct * 3)(*vals)
-        with _Timed("table_rows_pool_kernel", 0.0, 12.0 * num_rows):
-            _lib.check(_lib.lib().desco_table_rows_pool3_f32(
-                arr(ctypes.c_void_p, [r[0] for r in rows]), arr(ctypes.c_int64, [r[1] for r in rows]),
-                arr(ctypes.c_int64, [tk.shape[0] for tk, _, _ in layers]),
-                arr(ctypes.c_void_p, [_dev(ik, "ids", torch.int32) for _, ik, _ in layers]),
-                arr(ctypes.c_void_p, [_dev(pk_, "pool_part") for _, _, pk_ in layers]), num_rows,
-                _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32), _stream()), "table_rows_pool3")
-        return
-    if len(pool) != 3:
-        table1, ids1, part1 = pool[3:]
-        tp1, ldt1 = _rows(table1, "table1")
-        assert ids1.is_contiguous() and ids1.numel() >= num_rows and table1.shape[1] >= 64 and part1.shape == part.shape
-        with _Timed("table_rows_pool_kernel", 0.0, (0.0 if out is None else 256.0) * num_rows + 8.0 * num_rows):
-            _lib.check(_lib.lib().desco_table_rows_pool2_f32(
-                tp1, ldt1, table1.shape[0], _dev(ids1, "ids1", torch.int32), _dev(part1, "pool_part1"),
-                tp, ldt, table.shape[0], _dev(cls, "cls", torch.int32), _dev(part, "pool_part"), num_rows, op, ldo,
-                _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32), _stream()), "table_rows_pool2")
-        return
-    with _Timed("table_rows_pool_kernel", 0.0, (0.0 if out is None else 256.0) * num_rows + 4.0 * num_rows):
-        _lib.check(_lib.lib().desco_table_rows_pool_f32(
-            tp, ldt, table.shape[0], _dev(cls, "cls", torch.int32), num_rows, op, ldo,
-            _dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32), _dev(part, "pool_part"),
-            _stream()), "table_rows_pool")
+    for tk, ik, pk_ in layers:
+        assert ik.is_contiguous() and ik.numel() >= num_rows and tk.shape[1] >= 64 and pk_.shape == part.shape
+    op, ldo = (None, 64) if out is None else _rows(out, "out")
+    dev = lambda t, ik, pk_: (*_rows(t, "table"), t.shape[0], _dev(ik, "ids", torch.int32), _dev(pk_, "pool_part"))
+    tail = (_dev(bits, "pool_bits", torch.int32), _dev(slot, "pool_slot", torch.int32))
+    with _Timed("table_rows_pool_kernel", 0.0, (0.0 if out is None else 256.0) * num_rows + 4.0 * len(layers) * num_rows):
+        if len(layers) == 2:
+            _lib.check(_lib.lib().desco_table_rows_pool2_f32(*dev(*layers[0]), *dev(*layers[1]), num_rows, op, ldo, *tail,
+                                                             _stream()), "table_rows_pool2")
+        else:
+            tp, ldt, nt, ids, pp = dev(*layers[0])
+            _lib.check(_lib.lib().desco_table_rows_pool_f32(tp, ldt, nt, ids, num_rows, op, ldo, *tail, pp, _stream()),
+                       "table_rows_pool")
 
 
 def index_range_check(idx: torch.Tensor, bound: int) -> None:

@@ -1207,9 +1207,8 @@ int desco_table_rows_pool2_lds_bytes(void);
 /* ... and of THREE table layers (gnn_model.THIRD_LAYER_TABLE: X_3 = table3[cls3] as well): tables, ldts, num_tables, ids and
  * pool_parts are HOST arrays of three entries, one per layer, read before the call returns; pool_parts[k] receives, bit for
  * bit, what desco_table_rows_pool_f32 leaves for table k, its ids and the same pool_bits / pool_slot index.  No rows are
- * written.  The same walk as desco_table_rows_pool2_f32 (one 1024-thread block per CU, four tiles per wait); the tables are
- * staged in LDS smallest first while they fit together in desco_table_rows_pool2_lds_bytes(), the others are read from global
- * memory.  Ids outside their table read the nearest table row (never out of bounds). */
+ * written.  It is desco_table_rows_pooln_f32 below with num_layers = 3 -- the same launch, all three layers' rows in flight --
+ * under its own name, which is the one its error messages carry. */
 int desco_table_rows_pool3_f32(const float* const* tables, const int64_t* ldts, const int64_t* num_tables,
                                const int32_t* const* ids, float* const* pool_parts, int64_t num_rows,
                                const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream);
@@ -1217,7 +1216,8 @@ int desco_table_rows_pool3_f32(const float* const* tables, const int64_t* ldts, 
  * beyond the third as tables of their distinct rows): the arrays are HOST arrays of num_layers entries, read before the call
  * returns; pool_parts[k] receives, bit for bit, what desco_table_rows_pool_f32 leaves for table k, its ids and the same
  * pool_bits / pool_slot index.  No rows are written.  The same walk (one 1024-thread block per CU, four tiles per wait): four
- * layers' ids per id load, a second load per tile beyond four layers, the rows of four layers in flight at a time; the tables
+ * layers' ids per id load, a second load per tile beyond four layers, the rows of one to three layers in flight at a time (all
+ * of them up to three layers, two up to six, one beyond); the tables
  * are staged in LDS smallest first while they fit together in desco_table_rows_pool2_lds_bytes(), the others are read from
  * global memory.  Ids outside their table read the nearest table row (never out of bounds). */
 int desco_table_rows_pooln_f32(int num_layers, const float* const* tables, const int64_t* ldts, const int64_t* num_tables,
