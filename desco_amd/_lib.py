@@ -127,6 +127,8 @@ SIGNATURES = {
     "desco_shmp_layer_pool_bf16x6_f32": (c_int, [vp, i64, vp, vp, i64, i64, i32, i32, i32, vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
     "desco_pool_reduce_f32": (c_int, [vp, vp, vp, vp, i64, vp, i64, vp, i64, i32, vp]),
     "desco_pool_post_bf16x6_f32": (c_int, [vp, i64, i32, vp, i32, vp, i32, f32, vp, i64, i64, vp, vp, vp, POINTER(vp), vp, i32, vp]),
+    "desco_pool_post_rows_bf16x6_f32": (c_int, [vp, i64, vp, i32, vp, i32, vp, i32, f32, vp, i64, i64, vp, vp, vp, POINTER(vp), vp,
+                                                i32, vp]),
     "desco_anchor_pool_post_f16x3_f32": (c_int, [vp, i64, i32, vp, vp, vp, i32, f32, vp, i32, vp, vp, i32, f32, vp, i64,
                                                  i64, vp, vp, vp, POINTER(vp), vp, i32, vp]),
     "desco_post_mp_tail_f16x3_f32": (c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),

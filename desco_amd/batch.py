@@ -31,6 +31,7 @@ def _i32(a, device):
 
 # NeighborhoodBatch._level_csr
 _LevelCSR = namedtuple("_LevelCSR", "col low csrc qsrc start tdeg dmax cstart ctdeg cdmax deg pos")
+_CanonTables = namedtuple("_CanonTables", "uptr1 levels size offset anchor_rows")
 
 
 def _transpose_index(vrowptr: np.ndarray, vcol: np.ndarray, n_src: int):
@@ -555,6 +556,116 @@ class NeighborhoodBatch(_TrainIndexMixin):
             levels.append(r)
             before, prev = prev, r
         return levels
+
+    # eligibility bounds of anchor_class_index, the path's own and about profit only (tests lower the bounds above on small
+    # blocks and pin the launches that result; this index stays off there).  Both apply to the NEIGHBORHOODS, one canonical row
+    # each: what the table form saves -- the anchor MLP on all but U_a rows -- grows with them, what it adds (a gather of U_a
+    # rows, a U_a-row GEMM launch) does not
+    ANCHOR_CLASS_MIN_ROWS = 1 << 20
+    ANCHOR_CLASS_MIN_ROWS_PER_CLASS = 8
+
+    def anchor_class_index(self, layer_num: int):
+        """The canonical rows' classes under the LAST layer of a model of ``layer_num`` = L layers (built once per batch and L,
+        on the batch's device): ``(acls, arep)`` or None.  The recurrence of ``deep_table_index`` one step on: a canonical row
+        of X_L is a function of its own canonical class of X_{L-1} (the deepest level's ``ccls``) and, per CSR entry in order,
+        of the source's count class of X_{L-1}.  The classes of each level refine those of the level before, so rows of one
+        class agree in their canonical rows of EVERY layer -- in the whole anchor operand [X_1 | ... | X_L] and in its row
+        bound: ``acls`` [B] int32 is each neighborhood's class, ``arep`` [U_a] int64 the lowest canonical row of each class
+        (an index into the B canonical rows).  Exact (``_refine_classes``).  None unless the table levels reach the model's
+        last layer (``len(deep_table_index()) == L - 3``), the block has at least ANCHOR_CLASS_MIN_ROWS neighborhoods and
+        ANCHOR_CLASS_MIN_ROWS_PER_CLASS U_a <= B."""
+        cache = self.__dict__.setdefault("_anchor_class", {})
+        if layer_num not in cache:
+            cache[layer_num] = res = self._build_anchor_classes(layer_num)
+            if res is not None and res[0].is_cuda:
+                from . import ops
+                # the classes address the table of the distinct anchor rows (desco_pool_post_rows_bf16x6_f32)
+                ops.index_range_check(res[0], res[1].numel())
+        return cache[layer_num]
+
+    def _build_anchor_classes(self, L):
+        B = self.num_rows - self.num_count
+        if L < 4 or B < self.ANCHOR_CLASS_MIN_ROWS:                             # (small blocks leave before any work)
+            return None
+        deep = self.deep_table_index()
+        if len(deep) != L - 3:
+            return None
+        top, below, c = deep[-1], self._table_level(L - 1), self._level_csr()
+        key, u = below[0].to(torch.int64), (below[1].numel() - 1) // self.slots    # count classes of X_{L-1}
+        ckey, uc = top[5].to(torch.int64), top[6].numel()                          # canonical classes of X_{L-1}
+        ent = torch.where(c.low, key[c.csrc], ckey[c.qsrc])
+        r = self._refine_classes(ckey, uc, c.cstart, c.ctdeg, ent, c.cdmax, max(u, uc) + 1,
+                                 B // self.ANCHOR_CLASS_MIN_ROWS_PER_CLASS)
+        if r is None:
+            return None
+        acls, ua = r
+        return (acls.to(torch.int32).contiguous(), self._lowest_rows(acls, ua).contiguous())
+
+    def canonical_class_tables(self, layer_num: int):
+        """What the pass needs to keep the canonical rows of X_1 .. X_L as tables of their distinct rows (built once per batch
+        and L = ``layer_num``, on the batch's device; gnn_model.CANON_CLASS_TABLES): a ``_CanonTables`` or None; defined only
+        where ``anchor_class_index(L)`` is.  The canonical classes exist already -- level 1: ``canonical_table_index()[1]``,
+        levels 2 .. L - 1: the ``ccls`` / ``crep`` of the table levels, level L: ``anchor_class_index`` -- and nest.
+
+        ``size[l - 1]`` = U_c,l, the classes of level l = 1 .. L, and ``offset[l - 1]`` the first row of table l in ONE
+        [sum U_c,l, 64] buffer of all of them.  ``uptr1`` [U_c,1 S + 1] is the row-pointer array of the distinct canonical
+        degree tuples (input of desco_degree_affine_f32: table 1).  ``levels[l - 2]``, l = 2 .. L, = ``(rep_uptr, rep_vcol,
+        below)``: the compact 4-slot CSR of the lowest canonical row of each class of level l, its sources -- count rows --
+        remapped to their count classes of X_{l-1} (rows of the count rows' table l - 1), and ``below`` [U_c,l] int64 the
+        representatives' own classes of level l - 1 (their own rows in table l - 1).  ``anchor_rows`` [U_a L] int64: per
+        anchor class and level the buffer row of the representative's class of that level -- the anchor operand's blocks."""
+        cache = self.__dict__.setdefault("_canon_tables", {})
+        if layer_num not in cache:
+            cache[layer_num] = self._build_canonical_tables(layer_num)
+        return cache[layer_num]
+
+    def _build_canonical_tables(self, L):
+        ac = self.anchor_class_index(L)
+        if ac is None:
+            return None
+        S, nc = self.slots, self.num_count
+        c = self._level_csr()
+        tab1, ctab = self._table_indices()
+        vr = self.vrowptr.to(torch.int64)
+        ne = c.col.numel()
+        if ne == 0 or not bool(c.low[int(vr[S * nc]):].all()):           # (a canonical row's sources are count rows)
+            return None
+        cdeg = (vr[1:] - vr[:-1])[S * nc:].view(-1, S)
+        # count classes of X_1 .. X_{L-1} and their number; canonical classes of X_1 .. X_L and their lowest rows
+        cls, u = {1: tab1[1]}, {1: tab1[0].numel() // S}
+        for k in range(2, L):
+            t = self._table_level(k)
+            cls[k], u[k] = t[0], (t[1].numel() - 1) // S
+        ccls, crep = {1: ctab[1].to(torch.int64), L: ac[0].to(torch.int64)}, {L: ac[1]}
+        for l in range(2, L):
+            t = self._table_level(l + 1)
+            ccls[l], crep[l] = t[5].to(torch.int64), t[6]
+        size = [(ctab[0].numel() - 1) // S] + [crep[l].numel() for l in range(2, L + 1)]
+        offset = [sum(size[:l]) for l in range(L)]
+        pos = torch.arange(max(c.cdmax, 1), device=vr.device)
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        levels = []
+        for l in range(2, L + 1):
+            rep = crep[l]
+            ent = cls[l - 1].to(torch.int64)[c.csrc]
+            rep_uptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=vr.device), cdeg[rep].reshape(-1).cumsum(0)])
+            idx = c.cstart[rep][:, None] + pos[None, :]
+            rep_vcol = i32(ent[idx.clamp(max=ne - 1)][pos[None, :] < c.ctdeg[rep][:, None]])
+            below = ccls[l - 1][rep].contiguous()
+            # every id that a kernel uses as an address, checked once: the sources (rows of the count table l - 1) and the
+            # representatives' own rows (rows of the canonical table l - 1)
+            if rep_vcol.is_cuda:
+                from . import ops
+                ops.index_range_check(rep_vcol, u[l - 1])
+                ops.index_range_check(i32(below), size[l - 2])
+            levels.append((i32(rep_uptr), rep_vcol, below))
+        arep = ac[1]
+        anchor_rows = torch.stack([offset[l - 1] + ccls[l][arep] for l in range(1, L + 1)], dim=1).reshape(-1).contiguous()
+        if anchor_rows.is_cuda:
+            from . import ops
+            for l in range(1, L + 1):
+                ops.index_range_check(i32(ccls[l][arep]), size[l - 1])
+        return _CanonTables(ctab[0], levels, size, offset, anchor_rows)
 
     @property
     def table_empty(self) -> int:

@@ -54,6 +54,9 @@ struct GemmSplitArgs {
   DropArgs drop;
   int ws_rows;              // > 1: the scalar tail's matrix is per row class, ws[row % ws_rows][ns][n] (the gossip step's
                             // per-query tables: desco_affine_rows_f32 fused into the product's epilogue)
+  // POOLA only (desco_pool_post_rows_bf16x6_f32): row b's anchor row is a1[anch_row[b]] -- the anchor rows as a table of
+  // their distinct values; NULL: a1[b]
+  const int32_t* anch_row;
 };
 
 __device__ __attribute__((aligned(16))) float gs_zero_row[64] = {};
@@ -107,10 +110,18 @@ __device__ __forceinline__ void gemm_split_body(const GemmSplitArgs& g, const in
   r2 = r2 < g.m ? r2 : mlast;
   r3 = r3 < g.m ? r3 : mlast;
   // (named scalars, not arrays: hipcc parks indexed register arrays in scratch)
-  const float* p10 = g.a1 + r0 * g.lda1 + 4 * ac4;
-  const float* p11 = g.a1 + r1 * g.lda1 + 4 * ac4;
-  const float* p12 = g.a1 + r2 * g.lda1 + 4 * ac4;
-  const float* p13 = g.a1 + r3 * g.lda1 + 4 * ac4;
+  const float *p10, *p11, *p12, *p13;
+  if (POOLA && g.anch_row) {                   // (read once, here: the anchor rows through their table ids)
+    p10 = g.a1 + (int64_t)g.anch_row[r0] * g.lda1 + 4 * ac4;
+    p11 = g.a1 + (int64_t)g.anch_row[r1] * g.lda1 + 4 * ac4;
+    p12 = g.a1 + (int64_t)g.anch_row[r2] * g.lda1 + 4 * ac4;
+    p13 = g.a1 + (int64_t)g.anch_row[r3] * g.lda1 + 4 * ac4;
+  } else {
+    p10 = g.a1 + r0 * g.lda1 + 4 * ac4;
+    p11 = g.a1 + r1 * g.lda1 + 4 * ac4;
+    p12 = g.a1 + r2 * g.lda1 + 4 * ac4;
+    p13 = g.a1 + r3 * g.lda1 + 4 * ac4;
+  }
   const float* p20 = g.k2 ? g.a2 + r0 * g.lda2 + 4 * ac4 - g.k1 : p10;
   const float* p21 = g.k2 ? g.a2 + r1 * g.lda2 + 4 * ac4 - g.k1 : p11;
   const float* p22 = g.k2 ? g.a2 + r2 * g.lda2 + 4 * ac4 - g.k1 : p12;
@@ -704,11 +715,23 @@ static int gemm_planes_multi(int np, int num, const desco_gemm_desc* descs, cons
 // partial sums was written by desco_pool_reduce_f32 and read straight back by this product -- 5.5 GB per COX2 x64 pass.
 // The POOLA instantiation forms the operand's chunks in its load phase: per row the (at most three) slots of its
 // segment are looked up once, a chunk of layer l is the anchor chunk + the segment's partial rows of that layer.
+// ... and with the anchor rows as a TABLE of their distinct values (desco_pool_post_rows_bf16x6_f32): row b reads
+// anch[anch_row[b]]; the ids are the caller's to range-check (once per batch: desco_index_range_check_i32).
 extern "C" int desco_pool_post_bf16x6_f32(const float* anch, int64_t lda, int num_layers, const int16_t* w_planes, int n,
                                           const float* bias, int act, float slope, float* c, int64_t ldc, int64_t m,
                                           const int32_t* seg_ptr, const uint32_t* pool_bits, const int32_t* pool_slot,
                                           const float* const* parts, const float* x0, int tile_rows,
                                           desco_stream_t stream) {
+  return desco_pool_post_rows_bf16x6_f32(anch, lda, nullptr, num_layers, w_planes, n, bias, act, slope, c, ldc, m, seg_ptr,
+                                         pool_bits, pool_slot, parts, x0, tile_rows, stream);
+}
+
+extern "C" int desco_pool_post_rows_bf16x6_f32(const float* anch, int64_t lda, const int32_t* anch_row, int num_layers,
+                                               const int16_t* w_planes, int n, const float* bias, int act, float slope,
+                                               float* c, int64_t ldc, int64_t m, const int32_t* seg_ptr,
+                                               const uint32_t* pool_bits, const int32_t* pool_slot,
+                                               const float* const* parts, const float* x0, int tile_rows,
+                                               desco_stream_t stream) {
   using namespace desco;
   if (m == 0) return 0;
   if (m > (int64_t)(1 << 24)) return fail(DESCO_EINVAL, "desco_pool_post_bf16x6_f32: more than 2^24 segments (slot offsets are 31 bits)");
@@ -722,6 +745,7 @@ extern "C" int desco_pool_post_bf16x6_f32(const float* anch, int64_t lda, int nu
     if (!parts[l - 1] || mis16(parts[l - 1])) return fail(DESCO_EINVAL, "desco_pool_post_bf16x6_f32: NULL / misaligned partial array");
     g.part[l] = parts[l - 1];
   }
+  g.anch_row = anch_row;
   constexpr int BM = 128;
   constexpr size_t stage_bytes = (size_t)(3 * BM * SST + 3 * 64 * SST) * sizeof(short);
   constexpr size_t epi_bytes = (size_t)(BM / 32) * 32 * 32 * sizeof(float);

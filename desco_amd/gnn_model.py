@@ -801,6 +801,21 @@ POOL_POST_FUSED = os.environ.get("DESCO_POOL_POST_FUSED", "1") != "0"
 # never written either (f16x3 anchor on the producer-written row bound, first block folded, L in {2, 5, 8})
 ANCHOR_POST_FUSED = os.environ.get("DESCO_ANCHOR_POST_FUSED", "1") != "0"
 
+# ... unless the anchor operands are a table too: where the table levels reach the last layer, the canonical rows' classes of
+# X_L (NeighborhoodBatch.anchor_class_index: COX2-shaped x64 has a few thousand for 1.2 M neighborhoods) determine the whole
+# anchor operand [X_1 | ... | X_L] and its row bound, so the anchor MLP runs on one representative per class -- a gather and a
+# U_a-row f16x3 GEMM -- and post_mp.0 reads its rows through the classes (desco_pool_post_rows_bf16x6_f32).  Taken exactly
+# where the fused launch above would be, on blocks of at least NeighborhoodBatch.ANCHOR_CLASS_MIN_ROWS neighborhoods; off
+# wherever DEEP_LAYER_TABLES is off
+ANCHOR_CLASS_TABLE = os.environ.get("DESCO_ANCHOR_CLASS_TABLE", "1") != "0"
+
+# ... and the canonical rows themselves: X_l's canonical rows exist as a table of their distinct rows per level only
+# (NeighborhoodBatch.canonical_class_tables), written by the closed-form first layer on the distinct degree tuples and by the
+# canonical launches on one representative per class -- sources in the count rows' table, own rows gathered from the table
+# before --; the table products read them as they are, the anchor operand's U_a rows are gathered from them, and neither the
+# [B, 64 (L + 1)] operand nor its [B] row bound is allocated.  Where ANCHOR_CLASS_TABLE is taken
+CANON_CLASS_TABLES = os.environ.get("DESCO_CANON_CLASS_TABLES", "1") != "0"
+
 
 def shmp_forward(gnn: BaseGNN, batch) -> torch.Tensor:
     """BaseGNN.forward, hetero path (gnn_model.py:58-109) -> graph embeddings [B, 64]."""
@@ -914,13 +929,32 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
             ops.linear_smallk(feat[r0:r1], wt, b, out=x[r0:r1])               # :231
         X = [x]
     first = len(X) - 1
+    # post_mp.0 can form its operand itself (POOL_POST_FUSED) -- given the partial sums of every layer, see below
+    post_fusable = (nb and fuse_post0 and POOL_POST_FUSED and const_input and GEMM_BF16X6 and "post_nk" in pk and L <= 8
+                    and batch.max_count_rows() <= 33)
+    # the anchor MLP on the classes of anchor operands (acls: the index), the canonical rows as tables per level (ctabs)
+    acls = ctabs = None
+    if (ANCHOR_CLASS_TABLE and DEEP_LAYER_TABLES and L in lev and post_fusable and ANCHOR_POST_FUSED and canon_once
+            and L in (2, 5, 8)):
+        acls = batch.anchor_class_index(L)
+        if CANON_CLASS_TABLES and acls is not None:
+            ctabs = batch.canonical_class_tables(L)
     # emb["canonical"] [B, P] (operand of the anchor MLP): the canonical launches write their column block directly
     # (out2), so no concatenation pass is needed
-    canon = torch.empty((B, P), device=dev) if nb else None
+    canon = torch.empty((B, P), device=dev) if (nb and ctabs is None) else None
     # per-row bound of the anchor operand, left by the launches that write its column blocks (saves the f16x3 GEMM's
     # pre-pass over the operand): only when every block comes from such a launch (constant input, fp16 layer form)
-    canon_max = torch.empty((B,), device=dev) if (nb and const_input and f16) else None
-    if nb and const_input:
+    canon_max = torch.empty((B,), device=dev) if (nb and const_input and f16 and ctabs is None) else None
+    if ctabs is not None:
+        # ct[l], l = 1 .. L: the distinct canonical rows of X_l, row slices of one buffer; cm[l]: their largest magnitudes
+        # (the launches accumulate into zeros what the anchor operand's launches accumulate into the first layer's)
+        cbuf, cmax = torch.empty((sum(ctabs.size), H), device=dev), torch.zeros((sum(ctabs.size),), device=dev)
+        ct = [None] + [cbuf[o:o + n_] for o, n_ in zip(ctabs.offset, ctabs.size)]
+        cm = [None] + [cmax[o:o + n_] for o, n_ in zip(ctabs.offset, ctabs.size)]
+        t, r0, r1, su = groups[1]
+        ops.degree_affine(ctabs.uptr1, 0, ctabs.size[0], S, _first_layer_coef(pk, t, su, S, x0, src_of_slot, dev),
+                          ops.ACT_RELU, 0.0, ct[1], row_absmax=cm[1])
+    elif nb and const_input:
         # the closed-form first layer once more for the canonical rows, straight into its column block of the anchor
         # operand (a 1/9-size launch of our own instead of a strided torch copy per pass); it WRITES the row bound the
         # canonical launches below accumulate into, so it runs before them
@@ -940,7 +974,8 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                 continue
             e = pk["layers"][l][t]
             if "wt_tab" in e:
-                crows = canon[:, l * H:(l + 1) * H] if canon_once else X[-1][Nc:]     # canonical rows of X_l
+                # canonical rows of X_l
+                crows = None if ctabs is not None else canon[:, l * H:(l + 1) * H] if canon_once else X[-1][Nc:]
                 tem = temp if isinstance(e.get("wt_mfma_x6"), ops.F16Planes) else 0
                 y_row0, vcol_c = Nc, vcol_l
                 if tem and l == 1 and ctab is not None:
@@ -952,7 +987,8 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                     vcol_c, y_row0 = ctab[2], 0
                 elif tem and (l + 1) in lev:
                     # (the representatives' table sources are canonical CLASSES of X_l: the product on their lowest rows)
-                    ytab = ops.linear64(crows.index_select(0, lev[l + 1].crep), e["wt_tab_l64"][tblock:tblock + 1])
+                    ytab = ops.linear64(ct[l] if ctabs is not None else crows.index_select(0, lev[l + 1].crep),
+                                        e["wt_tab_l64"][tblock:tblock + 1])
                     y_row0 = 0
                 elif tem:
                     ytab = ops.linear64(crows, e["wt_tab_l64"][tblock:tblock + 1])   # canonical rows x W2 or W3: [B, 64]
@@ -988,6 +1024,12 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                                e.get("wt_mfma_x6", e["wt_mfma"]) if SHMP_BF16X6 else e["wt_mfma"],
                                e["b"], None if (pool is not None and last) else xn, ytab=ytab,
                                ytab_row0=y_row0, pool=pool, self_coef=coef_l, table_empty=tem, self_index=cls_l)
+            elif ctabs is not None and t == "canonical":
+                # the distinct canonical rows of X_{l+1}: the launch on the representatives' compact CSR, sources in table l of
+                # the count rows, own rows gathered from table l of the canonical rows
+                rep_uptr, rep_vcol, below = ctabs.levels[l - 1]
+                ops.shmp_layer(x_src, rep_uptr, rep_vcol, 0, ctabs.size[l], S, su, e["wt_x6"], e["b"], None, out2=ct[l + 1],
+                               row_absmax=cm[l + 1], xself=ct[l].index_select(0, below))
             else:
                 canonical, w16 = t == "canonical", isinstance(e.get("wt_x6"), ops.F16Planes)
                 once = canon_once and canonical and w16
@@ -1008,12 +1050,23 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
         if not folded_x0:
             canon[:, :H] = x0["canonical"].expand(B, H) if const_input else X[0][Nc:]
         seg_ptr = batch.count_ptr
-        pool_post = (fuse_post0 and POOL_POST_FUSED and const_input and GEMM_BF16X6 and "post_nk" in pk
-                     and sorted(pool_parts) == list(range(1, L + 1)) and L <= 8 and batch.max_count_rows() <= 33)
-        if pool_post and ANCHOR_POST_FUSED and canon_max is not None and L in (2, 5, 8):
+        pool_post = post_fusable and sorted(pool_parts) == list(range(1, L + 1))
+        assert pool_post or acls is None, "anchor classes without the partial sums of every layer"
+        if pool_post and ANCHOR_POST_FUSED and (canon_max is not None or ctabs is not None) and L in (2, 5, 8):
             _anchor_const_input_weights(pk, gnn)
             aw16, ab16 = pk["anchor_nk_const"]
             w0, b0 = pk["post_nk"][0]
+            if acls is not None:
+                # the anchor MLP on one representative per class of anchor operands, post_mp.0 reading its rows through the
+                # classes: row-local arithmetic on bit-equal operands and row bounds, the pooled sums per neighborhood as before
+                if ctabs is not None:
+                    a_u = cbuf.index_select(0, ctabs.anchor_rows).view(-1, L * H)
+                    bound_u = cmax.index_select(0, ctabs.anchor_rows).view(-1, L).amax(dim=1)
+                else:
+                    a_u, bound_u = canon[:, H:].index_select(0, acls[1]), canon_max.index_select(0, acls[1])
+                anch_tab = ops.gemm_f16x3(a_u, aw16, ab16, act=ops.ACT_LEAKY, slope=0.1, row_scale=bound_u)
+                return _PostMp0(ops.pool_post(anch_tab, [pool_parts[l] for l in range(1, L + 1)], pbits, pslot, seg_ptr,
+                                              x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1, anch_row=acls[0]))
             return _PostMp0(ops.anchor_pool_post(canon[:, H:], aw16, ab16, canon_max,
                                                  [pool_parts[l] for l in range(1, L + 1)], pbits, pslot,
                                                  seg_ptr, x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1))

@@ -601,24 +601,31 @@ def pool_reduce_multi(parts, bits: torch.Tensor, slot: torch.Tensor, seg_ptr: to
 
 def pool_post(anch: torch.Tensor, parts, bits: torch.Tensor, slot: torch.Tensor, seg_ptr: torch.Tensor, x0: torch.Tensor,
               w_planes: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: float = 0.0,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, anch_row: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(pooled @ W^T + bias) [B, 64] with pooled = [anch block 0 + rows * x0 | anch block l + segment sums of parts[l-1]]
     formed inside the product (desco_pool_post_bf16x6_f32): ``parts`` = the pooled layers' partial arrays (layers 1..L),
     ``w_planes`` = split_bf16_planes(W) [3, 64, 64 (L + 1)].  Every segment must span at most three 16-row tiles.
-    ``out`` [B, 64] (optional): any row stride >= 64 and any alignment (a misaligned one is stored element by element)."""
-    B, L = anch.shape[0], len(parts)
+    ``out`` [B, 64] (optional): any row stride >= 64 and any alignment (a misaligned one is stored element by element).
+    ``anch_row`` [B] int32 (optional): ``anch`` is a TABLE [U, 64 (L + 1)] of the distinct anchor rows and neighborhood b
+    reads ``anch[anch_row[b]]`` (desco_pool_post_rows_bf16x6_f32) -- equal to ``pool_post(anch[anch_row], ...)`` bit for bit.
+    The ids are not checked here: the caller range-checks them once where it builds them (``index_range_check``)."""
+    B, L = (anch.shape[0] if anch_row is None else anch_row.numel()), len(parts)
     assert tuple(w_planes.shape) == (3, 64, 64 * (L + 1)) and w_planes.is_contiguous() and anch.shape[1] >= 64 * (L + 1)
     assert x0.is_contiguous() and x0.numel() == 64
+    assert anch_row is None or (anch_row.dim() == 1 and anch_row.is_contiguous() and (B == 0 or anch.shape[0] > 0))
     if out is None:
         out = torch.empty((B, 64), device=anch.device, dtype=torch.float32)
     assert tuple(out.shape) == (B, 64)
+    if B == 0:
+        return out
     op, ldo = _rows(out, "out")
     ap, lda = _rows(anch, "anch")
     pa = (ctypes.c_void_p * L)(*[_dev(p_, "pool_part") for p_ in parts])
     with _Timed("gemm_split_kernel", 2.0 * B * 64 * 64 * (L + 1),
                 4.0 * B * 64 * (L + 2) + sum(256.0 * p_.shape[0] for p_ in parts)):
-        _lib.check(_lib.lib().desco_pool_post_bf16x6_f32(
-            ap, lda, L, _dev(w_planes, "w_planes", torch.int16), 64, _opt(None if bias is None else bias.contiguous(), "bias"),
+        _lib.check(_lib.lib().desco_pool_post_rows_bf16x6_f32(
+            ap, lda, _opt(anch_row, "anch_row", torch.int32), L, _dev(w_planes, "w_planes", torch.int16), 64,
+            _opt(None if bias is None else bias.contiguous(), "bias"),
             act, slope, op, ldo, B, _dev(seg_ptr, "seg_ptr", torch.int32), _dev(bits, "pool_bits", torch.int32),
             _dev(slot, "pool_slot", torch.int32), pa, _dev(x0, "x0"), 16, _stream()), "pool_post")
     return out

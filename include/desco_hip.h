@@ -1126,6 +1126,17 @@ int desco_pool_post_bf16x6_f32(const float* anch, int64_t lda, int num_layers, c
                                const int32_t* seg_ptr, const uint32_t* pool_bits, const int32_t* pool_slot,
                                const float* const* parts, const float* x0, int tile_rows, desco_stream_t stream);
 
+/* desco_pool_post_bf16x6_f32 with the anchor rows as a TABLE of their distinct values: row b of the operand reads
+ * anch[anch_row[b], :] where the call above reads anch[b, :] (anch_row: [m] int32 DEVICE ids into anch's rows, or NULL =
+ * the call above).  Everything else -- the partial-sum lookup, the order of the sums, the split, the products -- is that
+ * call's, so out equals its out on the gathered rows bit for bit.  The ids are NOT checked here: the caller range-checks
+ * them once where it builds them (desco_index_range_check_i32). */
+int desco_pool_post_rows_bf16x6_f32(const float* anch, int64_t lda, const int32_t* anch_row, int num_layers,
+                                    const int16_t* w_planes, int n, const float* bias, int act, float slope, float* c,
+                                    int64_t ldc, int64_t m, const int32_t* seg_ptr, const uint32_t* pool_bits,
+                                    const int32_t* pool_slot, const float* const* parts, const float* x0, int tile_rows,
+                                    desco_stream_t stream);
+
 /* The anchor MLP and desco_pool_post_bf16x6_f32 in ONE launch: anch = act(a[:, 0:k] * Wa^T + anchor_bias) on the f16x3
  * pipe (desco_gemm_f16x3_f32's arithmetic, bit for bit: anchor_planes / anchor_scale from desco_split_f16x2_f32 of the
  * [64 (L + 1), k] weight, row_scale = a bound of each row's largest |a|), then out[b, 0:64] = post_act( operand[b, :] *
