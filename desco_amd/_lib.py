@@ -194,6 +194,10 @@ SIGNATURES = {
                                             ctypes.c_uint64, vp, vp, vp]),
     "desco_core_truss": (c_int, [vp, vp, vp, i64, i32, vp, vp, vp]),
     "desco_core_truss_dev": (c_int, [vp, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
+    "desco_peel_order": (c_int, [vp, vp, vp, i64, i32, vp, vp]),
+    "desco_clique_census": (c_int, [vp, vp, vp, i64, vp, i32, i32, vp, vp, vp]),
+    "desco_peel_order_dev": (c_int, [vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp]),
+    "desco_clique_census_dev": (c_int, [vp, vp, vp, i64, vp, i32, vp, i64, i32, vp, vp, vp, vp, vp]),
     "desco_graph_gen": (c_int, [vp, vp, vp, vp, i64, i64, ctypes.c_uint64, i32, i32, vp, vp, vp, vp, vp]),
     "desco_graph_gen_expand": (c_int, [vp, vp, vp, vp, i64, i32, vp]),
     "desco_graph_gen_draw": (c_int, [ctypes.c_uint64, i64, i64, ctypes.c_uint64, i64, vp]),

@@ -326,6 +326,72 @@ int desco_core_truss_dev(const int64_t* graph_ptr, const int64_t* rowptr, const 
                          int32_t* status, desco_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CLIQUE CENSUS: the exact number of k-cliques for every k = 1 .. kmax of every graph of a set, per graph and per node,
+ * and the clique number (csrc/clique_census.hpp, csrc/clique_census.cpp, csrc/clique_census_dev.hip).  Counted by
+ * pivoting (Jain and Seshadhri, "The power of pivoting for exact clique counting", WSDM 2020): no clique is listed, a
+ * clique K_n is a single branch.  Input: a graph set as in CORE / TRUSS.
+ *
+ * Outputs (any may be NULL), kmax in 1..DESCO_CLIQUE_MAX_K.  All clique arithmetic is on uint64 with wrap-around, stored
+ * as int64 bit patterns: exact wherever the true value is below 2^64 (every column of every graph whose cliques have at
+ * most 66 nodes).
+ *   graph_cliques int64 [G, kmax]  column k - 1 = the k-cliques of the graph (column 0 nodes, 1 edges, 2 triangles)
+ *   node_cliques  int64 [N, kmax]  column k - 1 = the k-cliques that contain the node (column 0 is 1, column 1 the degree)
+ *   omega         int32 [G]        the clique number, exact whatever kmax is; 0 for a graph without nodes
+ *
+ * PEEL ORDER: key[v] int32 = the index of the pass in which v leaves the level-synchronous core peel.  At level
+ *   k = 0, 1, ... a pass removes every node whose remaining degree is at most k AT THE START of that pass; a level
+ *   repeats passes until one removes nothing.  Only passes that remove a node are numbered; the numbering runs on across
+ *   levels and starts again at 0 for every graph.  The key is unique, and core[v] (the level at which v left) is the
+ *   core number of CORE / TRUSS.  Under a key the OUT-NEIGHBOURS of v are its neighbours u with (key[u], u) >
+ *   (key[v], v); under the peel key there are at most core[v] of them, hence at most the graph's degeneracy.
+ *
+ * CENSUS: for every root v, on the subgraph induced by v's out-neighbours: a branch holds r "held" nodes (v first) and
+ *   p "pivot" nodes and a candidate set P.  It picks a pivot u in P (the member with most neighbours in P, the first of
+ *   those), recurses on P & N(u) with u added to the pivots, and then for every w in P \ N(u) \ {u} in turn recurses on
+ *   P & N(w) with w held and removes w from P.  A leaf (P empty) adds, for k = r .. min(r + p, kmax), C(p, k - r) to the
+ *   graph's column k and to every held node's column k, and C(p - 1, k - r - 1) to every pivot node's column k when
+ *   k > r; and raises omega to r + p.  No branch is cut, so omega is exact for any kmax.
+ * ORDER INDEPENDENCE: the counts depend neither on the key, nor on the pivot rule, nor on the order of branches, roots
+ *   or atomics -- only the work and the device's capacity do.  Host and device agree bit for bit.
+ *
+ * HOST desco_peel_order (core_out may be NULL) and desco_clique_census (key int32 [N], any non-negative values, or NULL
+ *   = the peel key is computed): OpenMP over graphs (num_threads 0 = the runtime's default); the result does not depend
+ *   on num_threads.  No limit on the out-degree: multi-word bitsets, Pascal rows mod 2^64 up to the largest out-degree.
+ *   DESCO_EINVAL naming the entry point, before any output is written, for what desco_core_truss refuses, for kmax
+ *   outside 1..DESCO_CLIQUE_MAX_K and for a negative key.
+ * DEVICE desco_peel_order_dev (gfx950): device arrays; ONE launch on `stream` for the graphs graph_ids[0 .. num_ids)
+ *   (int64, device; NULL = all num_graphs), one workgroup per graph, the CSR and the remaining degrees in LDS.  A graph
+ *   of n nodes and m edges needs 2 n + 2 m + 8 32-bit words (csrc/clique_census.hpp); max_words is the caller's bound on
+ *   that over the launch's graphs and sizes the launch's LDS; above DESCO_PEEL_DEV_MAX_WORDS it is refused (DESCO_EINVAL
+ *   naming the limit).  status int32 [G]: 0, or -1 -- and no other word of the graph written -- for a graph that breaks
+ *   the bound or holds an id outside itself, a loop or an unsorted row.  core_out may be NULL.
+ * DEVICE desco_clique_census_dev (gfx950): device arrays, key required; two launches on `stream` for the graphs
+ *   graph_ids[0 .. num_ids) (NULL = all).  The first checks every graph of the launch and zeroes its output rows; the
+ *   second runs one wave per root, the root's d <= max_out out-neighbours as d 64-bit adjacency rows in LDS, the lanes
+ *   taking the first-level branches, each with its own stack in LDS.  max_out is the caller's bound on the out-degree
+ *   over the launch's graphs and sizes the LDS per wave (csrc/clique_census.hpp); above DESCO_CLIQUE_DEV_MAX_OUT it is
+ *   refused (DESCO_EINVAL naming the limit).  status int32 [G]: 0, or -1 -- and nothing else of the graph written -- for
+ *   a graph with a root of more than max_out out-neighbours, a col id outside the graph, a loop or an unsorted row.
+ *   Only the launch's graphs are written.  No allocation, no synchronisation; tallies by 64-bit atomics.
+ * ------------------------------------------------------------------------------------------ */
+#define DESCO_CLIQUE_MAX_K 64
+#define DESCO_CLIQUE_DEV_MAX_OUT 64
+#define DESCO_PEEL_DEV_MAX_WORDS 40960 /* 160 KiB of LDS: e.g. 5000 nodes with 15000 edges */
+#define DESCO_PEEL_WAVE_WORDS 512
+int desco_peel_order(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col, int64_t num_graphs,
+                     int num_threads, int32_t* key_out, int32_t* core_out);
+int desco_clique_census(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col, int64_t num_graphs,
+                        const int32_t* key, int kmax, int num_threads, int64_t* graph_cliques, int64_t* node_cliques,
+                        int32_t* omega);
+int desco_peel_order_dev(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col, int64_t num_graphs,
+                         const int64_t* graph_ids, int64_t num_ids, int64_t max_words, int32_t* key_out,
+                         int32_t* core_out, int32_t* status, desco_stream_t stream);
+int desco_clique_census_dev(const int64_t* graph_ptr, const int64_t* rowptr, const int32_t* col, int64_t num_graphs,
+                            const int32_t* key, int kmax, const int64_t* graph_ids, int64_t num_ids, int max_out,
+                            int64_t* graph_cliques, int64_t* node_cliques, int32_t* omega, int32_t* status,
+                            desco_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * COLOUR REFINEMENT: 1-WL colour classes of the segments of a typed CSR block (csrc/wl_refine.hpp, csrc/wl_refine.cpp,
  * csrc/wl_refine_dev.hip).  Two segments with equal signatures after L rounds get the same prediction from every
  * L-layer model that maps a row to a function of its own state and, per GROUP of relation slots, the sum over its
