@@ -88,6 +88,10 @@ SIGNATURES = {
     "desco_graphlet_correlation_dev": (c_int, [vp, i64, i64, vp, i64, vp, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp,
                                                vp]),
     "desco_gcd_matrix_dev": (c_int, [vp, i64, vp, i64, i64, vp, i64, vp]),
+    "desco_gdd_build": (c_int, [vp, i64, vp, i64, vp, i32, vp, vp, vp, i32]),
+    "desco_gdd_agreement": (c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, i32, vp, i64, vp, i32]),
+    "desco_gdd_build_dev": (c_int, [vp, i64, i64, vp, i64, vp, i32, vp, i64, i64, vp, vp, vp, vp, vp]),
+    "desco_gdd_agreement_dev": (c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, i32, vp, i64, vp, vp]),
     "desco_orbit_table": (c_int, [vp, vp, vp, i32, vp, vp, vp]),
     "desco_orbit_counts": (c_int, [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
     "desco_orbit_counts_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, vp, vp]),

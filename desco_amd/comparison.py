@@ -25,8 +25,9 @@ from . import _lib
 from . import groundtruth as gt
 from .graphs import GraphSet
 
-# who served the last graphlet_correlation / gcd / nearest / dataset_gcd call: "host", "device", or "device+host" when
-# segments above the device's row bound were computed by the host twin and merged
+# who served the last graphlet_correlation / gcd / nearest / dataset_gcd call (or graphlet_distribution / gdd_agreement /
+# gdd_nearest / dataset_gdda): "host", "device", or "device+host" when segments above the device's row bound were computed
+# by the host twin and merged
 last_backend = None
 
 MAX_COLUMNS = 128                   # DESCO_GCM_MAX_COLUMNS (include/desco_hip.h)
@@ -37,7 +38,9 @@ NOT_LAUNCHED = 1                    # ``status`` of a segment that no launch of 
 _BACKENDS = ("auto", "host", "device")
 # what "auto" does with a GPU present, per stage: the device only where it won on both measured shapes
 # (tools/bench_graph_comparison.py)
-AUTO_DEVICE = {"gcm": True, "gcd": True}
+AUTO_DEVICE = {"gcm": True, "gcd": True,
+               # the degree distributions (tools/bench_gdd.py): "gdd" the builder, "gdda" the agreement
+               "gdd": True, "gdda": True}
 
 
 def _check_backend(backend):
@@ -382,5 +385,393 @@ def dataset_gcd(a, b=None, orbits="gcd11", induced: bool = True, dummy_row: bool
     used = {r.last_backend for r in ra + rb}
     va, vb = np.concatenate([r.vector() for r in ra]), np.concatenate([r.vector() for r in rb])
     out = _gcd_host(va, vb, num_threads)
+    last_backend = used.pop() if len(used) == 1 else "device+host"
+    return out
+
+
+# ---- graphlet degree distributions and their agreement (GDDA; Przulj 2007) ------------------------------------------------
+# Where the correlation matrices above compare the SHAPE of the orbit columns -- two complete graphs of different sizes are
+# at distance 0 -- the degree distributions compare their magnitudes: per segment and column the list of (k, N(k)), how
+# much of the segment touches the orbit k times, and per pair of segments 1 - the scaled Euclidean distance of the two
+# lists, averaged over the columns.  The arithmetic is defined in include/desco_hip.h, "GRAPHLET DEGREE DISTRIBUTION";
+# the host twin (csrc/graphlet_distribution.cpp) and the gfx950 kernels (csrc/graphlet_distribution_dev.hip) return the
+# same bits.  mean="geometric" is formed here from the per-orbit agreements and is NOT bit-defined.
+
+class GraphletDistribution:
+    """The graphlet degree distributions of S segments over C orbit columns in the layout of the C ABI: ``len`` int32
+    [S, C], ``key`` int64 [N * C], ``val`` float64 [N * C] -- the list of (s, c) starts at ``seg[s] * C + c * n_s`` --,
+    ``seg`` int64 [S + 1] (always a numpy array), ``columns`` int32 [C].  numpy arrays from ``graphlet_distribution``,
+    tensors on the GPU from ``graphlet_distribution_device`` (``cpu()`` / ``cuda()`` move them), which also sets
+    ``status`` int32 [S]: 0 computed, -1 refused by the kernel, ``NOT_LAUNCHED`` outside ``segment_ids``."""
+
+    def __init__(self, len_, key, val, seg, columns, status=None, backend=None):
+        self.len, self.key, self.val, self.seg, self.columns = len_, key, val, seg, columns
+        self.status, self.last_backend = status, backend
+        self._seg_dev = None
+
+    @property
+    def on_device(self) -> bool:
+        return isinstance(self.key, torch.Tensor)
+
+    def cpu(self) -> "GraphletDistribution":
+        host = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else x          # noqa: E731
+        return GraphletDistribution(host(self.len), host(self.key), host(self.val), self.seg, self.columns,
+                                    host(self.status), self.last_backend)
+
+    def cuda(self, device="cuda") -> "GraphletDistribution":
+        if self.on_device:
+            return self
+        put = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(device)   # noqa: E731
+        return GraphletDistribution(put(self.len), put(self.key), put(self.val), self.seg, self.columns,
+                                    put(self.status), self.last_backend)
+
+    def rows(self, r0: int, r1: int) -> "GraphletDistribution":
+        """The segments r0 .. r1 - 1 as a view: the same key / val arrays, a slice of ``seg`` and ``len``."""
+        return GraphletDistribution(self.len[r0:r1], self.key, self.val, self.seg[r0:r1 + 1], self.columns,
+                                    None if self.status is None else self.status[r0:r1], self.last_backend)
+
+    def lists(self, s: int):
+        """[(keys, vals)] of segment s, one pair of arrays per column."""
+        C, a, n = len(self.columns), int(self.seg[s]), int(self.seg[s + 1] - self.seg[s])
+        host = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else x          # noqa: E731
+        ln = host(self.len[s])
+        key, val = host(self.key[a * C:(a + n) * C]), host(self.val[a * C:(a + n) * C])
+        return [(key[c * n:c * n + int(ln[c])].copy(), val[c * n:c * n + int(ln[c])].copy()) for c in range(C)]
+
+    def __len__(self):
+        return self.len.shape[0]
+
+
+def _gdd_columns(orbits) -> np.ndarray:
+    columns = orbit_set(orbits)
+    if len(columns) < 1:
+        raise ValueError("the degree distributions need at least one orbit column")
+    return columns
+
+
+def _gdd_host(table: np.ndarray, seg: np.ndarray, columns: np.ndarray, num_threads: int):
+    """desco_gdd_build on an int64 table: (len, key, val) numpy arrays."""
+    nseg, C = len(seg) - 1, len(columns)
+    table = np.ascontiguousarray(table, dtype=np.int64)
+    N = table.shape[0]
+    ln = np.zeros((nseg, C), dtype=np.int32)
+    key = np.zeros(N * C, dtype=np.int64)
+    val = np.zeros(N * C, dtype=np.float64)
+    ptr = lambda a: a.ctypes.data if a.size else None                                   # noqa: E731
+    _lib.check(_lib.lib().desco_gdd_build(seg.ctypes.data, nseg, ptr(table), table.shape[1], ptr(columns), C, ptr(ln),
+                                          ptr(key), ptr(val), num_threads), "desco_gdd_build")
+    return ln, key, val
+
+
+def _gdd_device(table: torch.Tensor, seg: np.ndarray, columns: np.ndarray, ids=None,
+                max_rows: int = None) -> GraphletDistribution:
+    """The builder kernel on the segments ``ids`` (default: all) of an int64 table on the GPU.  One launch per size
+    class: the segments up to WAVE_ROWS rows, and the others with the bound min(largest, DEVICE_MAX_ROWS) -- a segment
+    above it is refused by the kernel (status -1).  ``max_rows``: one launch with that bound instead."""
+    L = _lib.lib()
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or table.dim() != 2 or not table.is_cuda:
+        raise RuntimeError("graphlet_distribution_device takes an int64 [N, columns] table on the GPU (no CPU fallback)")
+    dev = table.device
+    table = table.contiguous()
+    N, ld = table.shape
+    nseg, C = len(seg) - 1, len(columns)
+    ln = torch.zeros((nseg, C), dtype=torch.int32, device=dev)
+    key = torch.zeros(N * C, dtype=torch.int64, device=dev)
+    val = torch.zeros(N * C, dtype=torch.float64, device=dev)
+    status = torch.full((nseg,), NOT_LAUNCHED, dtype=torch.int32, device=dev)
+    ids = np.arange(nseg, dtype=np.int64) if ids is None else np.asarray(ids, dtype=np.int64)
+    if len(ids) and (ids.min() < 0 or ids.max() >= nseg):
+        raise ValueError("segment_ids outside the segments")
+    res = GraphletDistribution(ln, key, val, seg, columns, status, "device")
+    if len(ids) == 0:
+        return res
+    rows = np.diff(seg)
+    seg_d = gt._put(seg, np.int64, dev)
+    res._seg_dev = seg_d
+    if max_rows is not None:
+        launches = [(ids, int(max_rows))]
+    else:
+        small, large = ids[rows[ids] <= WAVE_ROWS], ids[rows[ids] > WAVE_ROWS]
+        launches = [(small, int(rows[small].max()) if len(small) else 0),
+                    (large, min(int(rows[large].max()), DEVICE_MAX_ROWS) if len(large) else 0)]
+    keep = []
+    ptr = lambda x: x.data_ptr() if x.numel() else None                                 # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for mine, bound in launches:
+            if len(mine) == 0:
+                continue
+            every = len(mine) == nseg and (mine == np.arange(nseg)).all()
+            ids_d = None if every else gt._put(mine, np.int64, dev)
+            keep.append(ids_d)
+            _lib.check(L.desco_gdd_build_dev(seg_d.data_ptr(), nseg, N, ptr(table), ld, columns.ctypes.data, C,
+                                             None if every else ids_d.data_ptr(), len(mine), bound, ln.data_ptr(),
+                                             ptr(key), ptr(val), status.data_ptr(), stream), "desco_gdd_build_dev")
+        torch.cuda.current_stream(dev).synchronize()                # the id lists are released here
+    return res
+
+
+def graphlet_distribution_device(graphs: GraphSet = None, orbits="all5", induced: bool = True, segments=None,
+                                 device="cuda", table: torch.Tensor = None, segment_ids=None) -> GraphletDistribution:
+    """``graphlet_distribution`` by the gfx950 kernel, everything kept on the GPU.  ``table``: an int64 orbit table that
+    is there already (``groundtruth.orbit_counts_device``; the columns of ``orbits`` index it), otherwise it is computed
+    from ``graphs``.  ``segment_ids``: only these segments are computed and written.  A segment of more than
+    ``DEVICE_MAX_ROWS`` rows is refused by the kernel: its ``status`` is -1 and its slots hold zeros --
+    ``graphlet_distribution(backend="auto")`` sends those to the host twin instead."""
+    columns = _gdd_columns(orbits)
+    if table is None:
+        if graphs is None:
+            raise ValueError("graphlet_distribution_device needs graphs or a table")
+        table = gt.orbit_counts_device(graphs, _table_queries(columns), device, induced)
+    if int(columns.max()) >= table.shape[1]:
+        raise ValueError("the table does not hold the columns asked for")
+    if graphs is None and segments is None:
+        raise ValueError("a table without graphs needs segments")
+    return _gdd_device(table, _segments(graphs, segments, table.shape[0]), columns, segment_ids)
+
+
+def _gdd_merge_refused(res: GraphletDistribution, table: torch.Tensor, num_threads: int) -> GraphletDistribution:
+    """``res`` on the host, the segments the kernel refused computed by the twin."""
+    out = res.cpu()
+    refused = np.flatnonzero(out.status == -1)
+    if len(refused) == 0:
+        return out
+    C = len(out.columns)
+    for s in refused:
+        a, b = int(out.seg[s]), int(out.seg[s + 1])
+        part = table[a:b].cpu().numpy()
+        ln, key, val = _gdd_host(part, np.array([0, b - a], dtype=np.int64), out.columns, num_threads)
+        out.len[s], out.key[a * C:b * C], out.val[a * C:b * C], out.status[s] = ln[0], key, val, 0
+    out.last_backend = "device+host"
+    return out
+
+
+def graphlet_distribution(graphs: GraphSet, orbits="all5", induced: bool = True, segments=None, backend: str = "auto",
+                          num_threads: int = 0) -> GraphletDistribution:
+    """The graphlet degree distribution of every segment of ``graphs`` (default: of every graph) over the orbit columns
+    ``orbits``: per column the values k >= 1 that occur, ascending, with N(k) = (d_k / k) / sum_k (d_k / k), d_k the
+    nodes that touch the orbit k times.  numpy arrays in a ``GraphletDistribution``.  ``backend`` as for
+    ``graphlet_correlation``: with "auto" segments above ``DEVICE_MAX_ROWS`` go to the host twin and are merged
+    (``last_backend`` then reads "device+host")."""
+    global last_backend
+    _check_backend(backend)
+    columns = _gdd_columns(orbits)
+    flat = _table_queries(columns)
+    if not _use_device(backend, "gdd"):
+        if backend == "auto" and torch.cuda.is_available():
+            table = gt.orbit_counts_device(graphs, flat, "cuda", induced).cpu().numpy()
+        else:
+            table = _host_table(graphs, flat, induced, num_threads)
+        seg = _segments(graphs, segments, table.shape[0])
+        res = GraphletDistribution(*_gdd_host(table, seg, columns, num_threads), seg, columns, None, "host")
+    else:
+        table = gt.orbit_counts_device(graphs, flat, "cuda", induced)
+        seg = _segments(graphs, segments, table.shape[0])
+        res = _gdd_device(table, seg, columns)
+        if backend == "device":
+            if bool((res.status != 0).any()):
+                raise RuntimeError(f"graphlet_distribution: a segment has more than {DEVICE_MAX_ROWS} rows "
+                                   "(DESCO_GCM_DEV_MAX_ROWS); use backend='auto' or 'host'")
+            res = res.cpu()
+        else:
+            res = _gdd_merge_refused(res, table, num_threads)
+    last_backend = res.last_backend
+    return res
+
+
+def _geometric(per: "np.ndarray | torch.Tensor"):
+    """exp(mean(log A_c)) over the last axis, 0 where any A_c is 0.  Not bit-defined: log and exp are library calls."""
+    if isinstance(per, torch.Tensor):
+        zero = (per == 0).any(dim=-1)
+        g = torch.exp(torch.log(torch.where(per == 0, torch.ones_like(per), per)).mean(dim=-1))
+        return torch.where(zero, torch.zeros_like(g), g)
+    zero = (per == 0).any(axis=-1)
+    g = np.exp(np.log(np.where(per == 0, 1.0, per)).mean(axis=-1))
+    return np.where(zero, 0.0, g)
+
+
+def _gdda_host(a: GraphletDistribution, b: GraphletDistribution, per_orbit: bool, num_threads: int = 0,
+               out: np.ndarray = None):
+    """desco_gdd_agreement: (agree [Ga, Gb], per_orbit [Ga, Gb, C] or None)."""
+    Ga, Gb, C = len(a), len(b), len(a.columns)
+    if out is None:
+        out = np.empty((Ga, Gb), dtype=np.float64)
+    per = np.empty((Ga, Gb, C), dtype=np.float64) if per_orbit else None
+    ptr = lambda x: x.ctypes.data if x is not None and x.size else None                 # noqa: E731
+    cont = lambda x, t: np.ascontiguousarray(x, dtype=t)                                # noqa: E731
+    al, bl, aseg, bseg = cont(a.len, np.int32), cont(b.len, np.int32), cont(a.seg, np.int64), cont(b.seg, np.int64)
+    _lib.check(_lib.lib().desco_gdd_agreement(aseg.ctypes.data, ptr(al), ptr(a.key), ptr(a.val), Ga, bseg.ctypes.data,
+                                              ptr(bl), ptr(b.key), ptr(b.val), Gb, C, ptr(out),
+                                              out.strides[0] // 8 if out.size else Gb, ptr(per), num_threads),
+               "desco_gdd_agreement")
+    return out, per
+
+
+def _seg_on(d: GraphletDistribution, dev) -> torch.Tensor:
+    if d._seg_dev is None or d._seg_dev.device != dev or d._seg_dev.numel() != len(d.seg):
+        d._seg_dev = gt._put(np.ascontiguousarray(d.seg, dtype=np.int64), np.int64, dev)
+    return d._seg_dev
+
+
+def _gdda_device(a: GraphletDistribution, b: GraphletDistribution, per_orbit: bool, out: torch.Tensor = None):
+    """desco_gdd_agreement_dev: (agree [Ga, Gb], per_orbit [Ga, Gb, C] or None), tensors on the GPU."""
+    for d in (a, b):
+        if not d.on_device or not d.key.is_cuda:
+            raise RuntimeError("gdd_agreement_device takes distributions on the GPU (no CPU fallback); "
+                               "GraphletDistribution.cuda() uploads host-built ones")
+    dev = a.key.device
+    Ga, Gb, C = len(a), len(b), len(a.columns)
+    if out is None:
+        out = torch.empty((Ga, Gb), dtype=torch.float64, device=dev)
+    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float64 or
+            tuple(out.shape) != (Ga, Gb) or (out.numel() and out.stride(1) != 1)):
+        raise RuntimeError("gdd_agreement_device: out must be a float64 [Ga, Gb] view on the GPU with unit column stride")
+    per = torch.empty((Ga, Gb, C), dtype=torch.float64, device=dev) if per_orbit else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None               # noqa: E731
+    al, bl = a.len.contiguous(), b.len.contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().desco_gdd_agreement_dev(_seg_on(a, dev).data_ptr(), ptr(al), ptr(a.key), ptr(a.val), Ga,
+                                                      _seg_on(b, dev).data_ptr(), ptr(bl), ptr(b.key), ptr(b.val), Gb,
+                                                      C, ptr(out), out.stride(0) if out.numel() else Gb, ptr(per),
+                                                      torch.cuda.current_stream(dev).cuda_stream),
+                   "desco_gdd_agreement_dev")
+        if al.data_ptr() != a.len.data_ptr() or bl.data_ptr() != b.len.data_ptr():
+            torch.cuda.current_stream(dev).synchronize()            # contiguous copies are released on return
+    return out, per
+
+
+def _gdd_pair(a, b):
+    b = a if b is None else b
+    if not isinstance(a, GraphletDistribution) or not isinstance(b, GraphletDistribution):
+        raise ValueError("gdd_agreement takes GraphletDistribution objects")
+    if not np.array_equal(a.columns, b.columns):
+        raise ValueError("the two distributions are over different orbit columns")
+    return a, b
+
+
+def _check_mean(mean):
+    if mean not in ("arithmetic", "geometric"):
+        raise ValueError(f"unknown mean {mean!r}: 'arithmetic' or 'geometric'")
+
+
+def _gdda(one, a, b, mean, per_orbit, chunk_rows, out, empty, cat):
+    """The agreement matrix of ``a`` x ``b`` by ``one(a_rows, b, per_orbit, out_rows)``.  The arithmetic mean needs no
+    per-orbit values; the geometric mean is formed ``chunk_rows`` rows of ``a`` at a time so that [Ga, Gb, C] is held
+    whole only where the caller asked for it."""
+    Ga, Gb = len(a), len(b)
+    if mean == "arithmetic":
+        return one(a, b, per_orbit, out)
+    if out is None:
+        out = empty((Ga, Gb))
+    step, pers = max(int(chunk_rows), 1), []
+    for r0 in range(0, Ga, step):
+        r1 = min(Ga, r0 + step)
+        _, per = one(a.rows(r0, r1), b, True, None)
+        out[r0:r1] = _geometric(per)
+        if per_orbit:
+            pers.append(per)
+    return out, (cat(pers) if per_orbit else None)
+
+
+def gdd_agreement_device(a: GraphletDistribution, b: GraphletDistribution = None, mean: str = "arithmetic",
+                         per_orbit: bool = False, out: torch.Tensor = None, chunk_rows: int = 256):
+    """``gdd_agreement`` by the gfx950 kernel on distributions that are on the GPU: float64 [Ga, Gb] there (and the
+    per-orbit tensor with ``per_orbit``).  ``out``: a float64 view on the GPU with unit column stride to write into;
+    only its [Ga, Gb] elements are written."""
+    _check_mean(mean)
+    a, b = _gdd_pair(a, b)
+    dev = a.key.device if a.on_device else "cpu"
+    agree, per = _gdda(_gdda_device, a, b, mean, per_orbit, chunk_rows, out,
+                       lambda shape: torch.empty(shape, dtype=torch.float64, device=dev),
+                       lambda ps: torch.cat(ps) if ps else torch.empty((0, len(b), len(a.columns)), dtype=torch.float64,
+                                                                       device=dev))
+    return (agree, per) if per_orbit else agree
+
+
+def gdd_agreement(a: GraphletDistribution, b: GraphletDistribution = None, mean: str = "arithmetic",
+                  per_orbit: bool = False, backend: str = "auto", num_threads: int = 0, chunk_rows: int = 256):
+    """The graphlet degree distribution agreement between the segments of ``a`` and of ``b`` (default: ``a`` against
+    itself): float64 [Ga, Gb] in 0 .. 1, 1 for equal distributions; with ``per_orbit`` also the agreements A_c per
+    column, [Ga, Gb, C].  ``mean``: "arithmetic" (Przulj's, bit-defined) or "geometric" -- exp(mean(log A_c)), 0 if any
+    A_c is 0, formed in Python from the per-orbit values and not bit-defined."""
+    global last_backend
+    _check_backend(backend)
+    _check_mean(mean)
+    a, b = _gdd_pair(a, b)
+    if _use_device(backend, "gdda"):
+        same = b is a
+        a = a.cuda()
+        b = a if same else b.cuda()
+        res = gdd_agreement_device(a, b, mean, per_orbit, None, chunk_rows)
+        res = tuple(r.cpu().numpy() for r in res) if per_orbit else res.cpu().numpy()
+        last_backend = "device"
+    else:
+        same = b is a
+        a = a.cpu()
+        b = a if same else b.cpu()
+        agree, per = _gdda(lambda x, y, po, out: _gdda_host(x, y, po, num_threads, out), a, b, mean, per_orbit,
+                           chunk_rows, None, lambda shape: np.empty(shape, dtype=np.float64),
+                           lambda ps: np.concatenate(ps) if ps else np.empty((0, len(b), len(a.columns))))
+        res = (agree, per) if per_orbit else agree
+        last_backend = "host"
+    return res
+
+
+def gdd_nearest(train: GraphletDistribution, target: GraphletDistribution, k: int = 1, backend: str = "auto",
+                num_threads: int = 0, chunk_rows: int = 2048):
+    """For every segment of ``target`` the ``k`` segments of ``train`` it agrees with best: (indices int64 [Gt, k],
+    agreements float64 [Gt, k]), largest agreement first, equal agreements in ascending index.  The matrix is built
+    ``chunk_rows`` target rows at a time and never held whole."""
+    global last_backend
+    _check_backend(backend)
+    target, train = _gdd_pair(target, train)
+    use_dev = _use_device(backend, "gdda")
+    x, y = (target.cuda(), train.cuda()) if use_dev else (target.cpu(), train.cpu())
+    Gt, Gr = len(x), len(y)
+    if k < 1 or k > Gr:
+        raise ValueError("k must be in 1 .. the number of training segments")
+    idx = np.zeros((Gt, k), dtype=np.int64)
+    agree = np.zeros((Gt, k), dtype=np.float64)
+    step = max(int(chunk_rows), 1)
+    for r0 in range(0, Gt, step):
+        r1 = min(Gt, r0 + step)
+        if use_dev:
+            d, order = torch.sort(_gdda_device(x.rows(r0, r1), y, False)[0], dim=1, descending=True, stable=True)
+            idx[r0:r1], agree[r0:r1] = order[:, :k].cpu().numpy(), d[:, :k].cpu().numpy()
+        else:
+            d, _ = _gdda_host(x.rows(r0, r1), y, False, num_threads)
+            order = np.argsort(-d, axis=1, kind="stable")[:, :k]
+            idx[r0:r1], agree[r0:r1] = order, np.take_along_axis(d, order, axis=1)
+    last_backend = "device" if use_dev else "host"
+    return idx, agree
+
+
+def _gdd_concat(parts) -> GraphletDistribution:
+    """Host distributions that each cover their whole table, as one: the tables stacked."""
+    C = len(parts[0].columns)
+    seg, base = [np.zeros(1, dtype=np.int64)], 0
+    for p in parts:
+        if int(p.seg[0]) != 0 or int(p.seg[-1]) * C != len(p.key):
+            raise ValueError("only distributions over whole tables can be joined")
+        seg.append(np.asarray(p.seg[1:], dtype=np.int64) + base)
+        base += int(p.seg[-1])
+    return GraphletDistribution(np.concatenate([p.len for p in parts]), np.concatenate([p.key for p in parts]),
+                                np.concatenate([p.val for p in parts]), np.concatenate(seg), parts[0].columns)
+
+
+def dataset_gdda(a, b=None, orbits="all5", induced: bool = True, mean: str = "arithmetic", backend: str = "auto",
+                 num_threads: int = 0) -> np.ndarray:
+    """Agreement between whole data sets: ``a`` and ``b`` (default: ``a``) are lists of GraphSets, and all the nodes of a
+    set form ONE segment.  float64 [len(a), len(b)].  A set of more than ``DEVICE_MAX_ROWS`` nodes is above the
+    builder kernel's row bound, so with "auto" its distribution comes from the host twin, as in ``dataset_gcd``."""
+    global last_backend
+    one = lambda g: graphlet_distribution(g, orbits, induced, np.array([0, g.num_nodes], dtype=np.int64),     # noqa: E731
+                                          backend, num_threads)
+    ra = [one(g) for g in ([a] if isinstance(a, GraphSet) else a)]
+    rb = ra if b is None else [one(g) for g in ([b] if isinstance(b, GraphSet) else b)]
+    used = {r.last_backend for r in ra + rb}
+    da = _gdd_concat(ra)
+    out = gdd_agreement(da, da if b is None else _gdd_concat(rb), mean, False, backend, num_threads)
+    used.add(last_backend)
     last_backend = used.pop() if len(used) == 1 else "device+host"
     return out

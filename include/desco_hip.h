@@ -651,6 +651,67 @@ int desco_graphlet_correlation_dev(const int64_t* seg_ptr, int64_t num_segs, int
 int desco_gcd_matrix_dev(const double* x, int64_t Gx, const double* y, int64_t Gy, int64_t P, double* out, int64_t ldo,
                          desco_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GRAPHLET DEGREE DISTRIBUTION: per segment and orbit column, how many nodes touch the orbit k times, and the
+ * graphlet degree distribution agreement between segments (GDDA; Przulj, "Biological network comparison using graphlet
+ * degree distribution", Bioinformatics 2007; csrc/graphlet_distribution.hpp, csrc/graphlet_distribution.cpp,
+ * csrc/graphlet_distribution_dev.hip).  Unlike the graphlet correlation it sees magnitude: two complete graphs of
+ * different sizes have correlation distance 0 and agreement 0 on every orbit that both touch.
+ *
+ * INPUT: as for GRAPHLET CORRELATION -- counts int64 [N][ld]; columns int32 [C], a HOST array, entries in 0 .. ld - 1,
+ *   C in 1 .. DESCO_GCM_MAX_COLUMNS; seg_ptr int64 [S + 1], monotone; n_s = the rows of segment s.  No dummy row.
+ * DISTRIBUTION of (segment s, column c): the distinct values k >= 1 of the column over the segment's rows in ascending
+ *   order, k_0 < k_1 < ..., with multiplicities d_i (rows whose value is below 1 are left out: Przulj's k starts at 1).
+ *   S_i = (double)d_i / (double)k_i (both conversions round to nearest);  T = 0, T = T + S_i for i ascending IN THAT
+ *   ORDER;  N_i = S_i / T.  The list may be empty (no node of the segment touches the orbit): then N is 0 everywhere.
+ *   Keys and multiplicities are integers that do not depend on the order of the rows, so relabelling a graph changes
+ *   no bit.
+ * STORAGE (both builders): len int32 [S][C], key int64 [N * C], val double [N * C]; the list of (s, c) occupies the
+ *   positions seg_ptr[s] * C + c * n_s + i, i < len[s][c]; the other positions of a computed segment are written as 0
+ *   (a real key is never 0).  No scan, no allocation, no atomics and no synchronisation are needed to place a list.
+ * AGREEMENT of segments x and y in column c: acc = 0; over the union of the two key lists in ascending key,
+ *   t = N_x(k) - N_y(k) with a missing key contributing 0 (so t is N_x(k) or -N_y(k) there), acc = fma(t, t, acc) --
+ *   a fixed order, no parallel reduction inside a pair.  D_c = sqrt(0.5 * acc);  A_c = D_c > 1.0 ? 0.0 : 1.0 - D_c (the
+ *   clamp only guards rounding).  Two empty lists give A_c = 1; an empty list against a non-empty one gives
+ *   1 - sqrt(0.5 sum N^2): this project's convention, STATED here and not pinned against GraphCrunch.
+ *   Of the pair: sum = 0, sum = sum + A_c for c = 0 .. C - 1 IN THAT ORDER; agree = sum / (double)C.
+ *   agree[i * ldo + j] for x_i and y_j, ldo >= Gy: agree may be a strided view and only those Gx * Gy elements are
+ *   written; per_orbit[(i * Gy + j) * C + c] = A_c, or NULL.  The chain does not see the sign of t: agree(x, y) and
+ *   agree(y, x) are the same bits, and agree(x, x) is exactly 1.
+ *   Every step is one correctly rounded IEEE double operation, none contracted except the written fma.
+ *
+ * HOST desco_gdd_build: OpenMP over (segment, column), a sort and its runs; no row limit beyond memory.
+ * HOST desco_gdd_agreement: OpenMP over the segments of x, a two-pointer merge per pair and column.  Neither result
+ *   depends on num_threads (0 = the runtime's default).  DESCO_EINVAL naming the entry point for: a null pointer where
+ *   an array is needed, a negative count, C outside 1 .. 128, a column index outside the table, a seg_ptr that is
+ *   negative or not monotone, a len outside 0 .. n_s, ldo < Gy -- before anything is written.
+ * DEVICE desco_gdd_build_dev (gfx950): device arrays (columns on the host); ONE launch on `stream` for the segments
+ *   seg_ids[0 .. num_ids) (int64, device; NULL = all num_segs), a block per (segment, column) with the column in LDS:
+ *   one wave up to DESCO_GCM_WAVE_ROWS, four above.  The list's own key / val slots serve as the sort's scratch.
+ *   max_rows is the caller's bound on n_s over the launch and sizes its LDS; a bound above DESCO_GCM_DEV_MAX_ROWS is
+ *   refused (DESCO_EINVAL naming the limit): a larger segment goes to the host routine.  status int32 [S]: 0 for a
+ *   computed segment; -1, and nothing of it written, for one over the launch's bound or with rows outside
+ *   0 .. num_rows.  Only the launch's segments are written.  T is added up by one wave in the defined order.
+ * DEVICE desco_gdd_agreement_dev (gfx950): ONE launch, a 32 x 32 tile of pairs per block; per column the tile's lists
+ *   are staged in LDS where they fit and read from global memory where they do not, so lists of ANY length are
+ *   accepted (host-built lists of long segments too); every pair's merge and fma chain runs in ascending key on the
+ *   fp64 vector pipe.  A len outside 0 .. n_s is clamped.  Both: no allocation, no synchronisation, no global atomics;
+ *   the results equal the host routines bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+int desco_gdd_build(const int64_t* seg_ptr, int64_t num_segs, const int64_t* counts, int64_t ld,
+                    const int32_t* columns, int C, int32_t* len, int64_t* key, double* val, int num_threads);
+int desco_gdd_agreement(const int64_t* x_seg_ptr, const int32_t* x_len, const int64_t* x_key, const double* x_val,
+                        int64_t Gx, const int64_t* y_seg_ptr, const int32_t* y_len, const int64_t* y_key,
+                        const double* y_val, int64_t Gy, int C, double* agree, int64_t ldo, double* per_orbit,
+                        int num_threads);
+int desco_gdd_build_dev(const int64_t* seg_ptr, int64_t num_segs, int64_t num_rows, const int64_t* counts, int64_t ld,
+                        const int32_t* columns, int C, const int64_t* seg_ids, int64_t num_ids, int64_t max_rows,
+                        int32_t* len, int64_t* key, double* val, int32_t* status, desco_stream_t stream);
+int desco_gdd_agreement_dev(const int64_t* x_seg_ptr, const int32_t* x_len, const int64_t* x_key, const double* x_val,
+                            int64_t Gx, const int64_t* y_seg_ptr, const int32_t* y_len, const int64_t* y_key,
+                            const double* y_val, int64_t Gy, int C, double* agree, int64_t ldo, double* per_orbit,
+                            desco_stream_t stream);
+
 /* HOST: exact canonical (induced, symmetry-normalised) counts of connected query graphs with
  * 2..6 nodes for every node of every graph: out[v][q] = #{S : max(S) = v, G[S] isomorphic to q}.
  * Replaces the VF2 ground truth (workload.py:327-348 MatchSubgraphWorker divided by
