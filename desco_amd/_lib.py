@@ -120,6 +120,9 @@ SIGNATURES = {
     "desco_canonical_counts_match_labelled_mode": (c_int, [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "desco_canonical_counts_match_labelled_mode_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp,
                                                                i64, i32, i32, i64, i64, vp, vp]),
+    "desco_list_occurrences": (c_int, [vp, i64, vp, vp, vp, i64, i32, i32, i64, i64, vp, i64, vp]),
+    "desco_list_occurrences_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, i32, i32, i64, i64,
+                                           vp, i64, vp, i64, vp, vp, vp]),
     "desco_canonical_noninduced_transform_dev": (c_int, [vp, i64, vp, i64, i32, i32, i32, vp, i64, vp]),
     "desco_linear_smallk_f32": (c_int, [vp, i64, i32, vp, vp, vp, i64, i64, i32, vp]),
     "desco_csr_gather_sum_f32": (c_int, [vp, i64, vp, vp, i64, i32, vp, vp]),

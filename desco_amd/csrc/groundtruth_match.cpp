@@ -48,6 +48,7 @@
 
 #include "groundtruth_esu.hpp"
 #include "groundtruth_match.hpp"
+#include "occurrences.hpp"
 
 namespace {
 
@@ -341,7 +342,9 @@ int build_plan_labelled(const char* who, const int32_t* q_nodes, const int32_t* 
 
 // One graph's matcher state.  LAB: the labelled matcher, which tests a candidate's label before its adjacency bits.
 // IND: induced matching (a clear GTM_ADJ bit means NOT adjacent); else a clear bit asks nothing.
-template <bool LAB, bool IND>
+// LIST (desco_list_occurrences): the first `room` maps found are also stored, in query-node order and with global
+// ids, as rows dst[found * k ...]; the caller compares `found` with `room` afterwards.
+template <bool LAB, bool IND, bool LIST = false>
 struct Matcher {
   GraphBits g;
   const int64_t* rowptr;
@@ -352,6 +355,15 @@ struct Matcher {
   int k;
   int img[GTM_KMAX];
   int64_t found;
+  int32_t* dst = nullptr;              // LIST
+  int64_t room = 0;
+
+  void emit(int last) {
+    if (found >= room) return;
+    int32_t* row = dst + found * k;
+    for (int i = 0; i + 1 < k; ++i) row[rec[GTM_NODE + i]] = (int32_t)(g.base + img[i]);
+    row[rec[GTM_NODE + k - 1]] = (int32_t)(g.base + last);
+  }
 
   bool fits(int level, int u) const {
     if (LAB && lab[u] != rec[GTML_LABEL + level]) return false;
@@ -374,6 +386,7 @@ struct Matcher {
       if (u >= v) break;                       // rows ascend: every image but the anchor's is below the root
       if (!fits(level, u)) continue;
       if (level + 1 == k) {
+        if (LIST) emit(u);
         ++found;
       } else {
         img[level] = u;
@@ -659,4 +672,125 @@ extern "C" int desco_canonical_counts_match_labelled_mode(const int64_t* graph_p
                                                num_classes, num_threads, out)
                  : counts_match_labelled<false>(who, graph_ptr, num_graphs, rowptr, col, labels, plan, plan_entries,
                                                 num_classes, num_threads, out);
+}
+
+// ---- OCCURRENCE LISTING (include/desco_hip.h): the matcher's maps written out instead of counted ----------------------
+
+int desco::list_plan_check(const char* who, const int32_t* plan, int64_t plan_entries) {
+  const std::string w(who);
+  if (!plan || plan_entries < GTM_HEAD || plan[0] != 1)
+    return fail(DESCO_EINVAL, (w + ": one query per call (plan[0] must be 1)").c_str());
+  if (const int rc = match_plan_check(who, plan, plan_entries, 1)) return rc;
+  for (int a = 0; a < plan[1]; ++a) {
+    const int32_t* rec = plan + GTM_HEAD + (int64_t)a * GTM_REC;
+    const int k = rec[GTM_K];
+    uint32_t seen = 0;
+    for (int i = 0; i < k; ++i)
+      if (rec[GTM_NODE + i] >= 0 && rec[GTM_NODE + i] < k) seen |= 1u << rec[GTM_NODE + i];
+    if (seen != (1u << k) - 1u || rec[GTM_NODE] != rec[GTM_ANCHOR] || k != plan[GTM_HEAD + GTM_K])
+      return fail(DESCO_EINVAL, (w + ": malformed plan record (positions must permute the query's nodes)").c_str());
+  }
+  return 0;
+}
+
+namespace {
+
+template <bool IND>
+int list_occurrences(const std::string& who, const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                     const int32_t* col, const int32_t* plan, int num_threads, int64_t node_begin, int64_t node_end,
+                     const int64_t* ptr, int32_t* rows) {
+  const int num_anchors = plan[1];
+  const int k = num_anchors ? plan[GTM_HEAD + GTM_K] : 0;
+  // the graphs that hold a node of [node_begin, node_end)
+  const int64_t g0 = std::upper_bound(graph_ptr, graph_ptr + num_graphs + 1, node_begin) - graph_ptr - 1;
+  const int64_t g1 = std::lower_bound(graph_ptr, graph_ptr + num_graphs + 1, node_end) - graph_ptr;
+#ifdef _OPENMP
+  const int nt = num_threads > 0 ? num_threads : omp_get_max_threads();
+#else
+  const int nt = 1;
+  (void)num_threads;
+#endif
+  bool oom = false;
+  int64_t bad = -1;                                // a node whose segment is not the number of its maps
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+  for (int64_t gi = g0; gi < g1; ++gi) {
+    Matcher<false, IND, true> m;
+    std::vector<int64_t> order;
+    std::vector<int32_t> tmp;
+    try {
+      m.g.build(graph_ptr, gi, rowptr, col);
+      const int64_t base = m.g.base, n = m.g.n;
+      m.rowptr = rowptr;
+      m.col = col;
+      const int64_t v0 = std::max<int64_t>(node_begin - base, 0), v1 = std::min<int64_t>(node_end - base, n);
+      for (int v = (int)v0; v < (int)v1; ++v) {
+        const int64_t seg = ptr[base + v + 1] - ptr[base + v];
+        m.v = v;
+        m.img[0] = v;
+        m.found = 0;
+        m.room = seg;
+        m.dst = rows + (ptr[base + v] - ptr[node_begin]) * k;
+        if (v > 0 && rowptr[base + v] != rowptr[base + v + 1])
+          for (int a = 0; a < num_anchors; ++a) {
+            m.rec = plan + GTM_HEAD + (int64_t)a * GTM_REC;
+            m.k = k;
+            m.extend(1);
+          }
+        if (m.found != seg) {
+#pragma omp critical(desco_list_occurrences_bad)
+          if (bad < 0 || base + v < bad) bad = base + v;
+          continue;
+        }
+        if (seg < 2) continue;
+        // the segment in ascending lexicographic order of its rows
+        order.resize((size_t)seg);
+        for (int64_t r = 0; r < seg; ++r) order[(size_t)r] = r;
+        const int32_t* d = m.dst;
+        std::sort(order.begin(), order.end(), [d, k](int64_t x, int64_t y) {
+          return std::lexicographical_compare(d + x * k, d + x * k + k, d + y * k, d + y * k + k);
+        });
+        tmp.assign(d, d + seg * k);
+        for (int64_t r = 0; r < seg; ++r)
+          std::memcpy(m.dst + r * k, tmp.data() + order[(size_t)r] * k, sizeof(int32_t) * (size_t)k);
+      }
+    } catch (const std::bad_alloc&) {
+#pragma omp atomic write
+      oom = true;
+    }
+  }
+  if (oom) return fail(DESCO_ENOMEM, (who + ": out of memory").c_str());
+  if (bad >= 0)
+    return fail(DESCO_EINVAL, (who + ": ptr is not the scan of this query's canonical counts (first at node " +
+                               std::to_string(bad) + ")").c_str());
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int desco_list_occurrences(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr,
+                                      const int32_t* col, const int32_t* plan, int64_t plan_entries, int induced,
+                                      int num_threads, int64_t node_begin, int64_t node_end, const int64_t* ptr,
+                                      int64_t rows_capacity, int32_t* rows) {
+  const std::string who = "desco_list_occurrences";
+  if (num_graphs < 0 || rows_capacity < 0) return fail(DESCO_EINVAL, (who + ": negative size").c_str());
+  if (!graph_ptr || !rowptr || !ptr || (rows_capacity > 0 && !rows))
+    return fail(DESCO_EINVAL, (who + ": null pointer").c_str());
+  if (induced != 0 && induced != 1) return fail(DESCO_EINVAL, (who + ": induced must be 0 or 1").c_str());
+  if (const int rc = list_plan_check(who.c_str(), plan, plan_entries)) return rc;
+  const int64_t total = graph_ptr[num_graphs];
+  if (node_begin < 0 || node_end < node_begin || node_end > total)
+    return fail(DESCO_EINVAL, (who + ": node range outside [0, num_nodes]").c_str());
+  if (rowptr[total] > 0 && !col) return fail(DESCO_EINVAL, (who + ": null pointer").c_str());
+  for (int64_t v = node_begin; v < node_end; ++v)                // every segment lies inside rows: no store outside it
+    if (ptr[v + 1] < ptr[v]) return fail(DESCO_EINVAL, (who + ": ptr must not descend").c_str());
+  if (ptr[node_end] - ptr[node_begin] > rows_capacity)
+    return fail(DESCO_EINVAL, (who + ": rows_capacity is below ptr[node_end] - ptr[node_begin]").c_str());
+  try {
+    return induced ? list_occurrences<true>(who, graph_ptr, num_graphs, rowptr, col, plan, num_threads, node_begin,
+                                            node_end, ptr, rows)
+                   : list_occurrences<false>(who, graph_ptr, num_graphs, rowptr, col, plan, num_threads, node_begin,
+                                             node_end, ptr, rows);
+  } catch (const std::bad_alloc&) {
+    return fail(DESCO_ENOMEM, (who + ": out of memory").c_str());
+  }
 }

@@ -1327,3 +1327,14 @@ def _canonical_counts_labelled_vf2(graphs: GraphSet, queries: Sequence, node_fea
                 out[base + max(vmap.keys()), qi] += 1
         out[:, qi] /= sym
     return out
+
+
+# ---- occurrence listing (desco_amd/occurrences.py, which is built on this module: re-exported on first use) ----------
+_OCCURRENCE_NAMES = ("Occurrences", "list_occurrences", "list_occurrences_device", "iter_occurrences")
+
+
+def __getattr__(name):
+    if name in _OCCURRENCE_NAMES:
+        from . import occurrences
+        return getattr(occurrences, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

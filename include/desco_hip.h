@@ -972,6 +972,54 @@ int desco_canonical_noninduced_transform_dev(const int64_t* counts, int64_t ldc,
                                              int64_t ldo, desco_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * OCCURRENCE LISTING: the occurrences themselves ("which ones"), where the matchers above answer "how many".
+ *
+ * For a graph set and ONE query q (connected, loop-free, 2..16 nodes: a plan of desco_canonical_match_plan with
+ * plan[0] = 1) the listing is rows, int32 [M][k], and ptr, int64 [N + 1].
+ *   Row       one row per occurrence; column a is the image of QUERY NODE a (the query's own numbering, not the plan's
+ *             matching positions: rec[4 + i] is the query node of position i).  Ids are global node ids, as col holds.
+ *   induced = 1   an occurrence is a node subset S with G[S] isomorphic to q; its row is the one map q -> G[S] that
+ *             meets the plan's order constraints.
+ *   induced = 0   an occurrence is a copy of q: an image edge set (P3 has three in a triangle).  A monomorphism onto a
+ *             copy H is an isomorphism q -> H, so the maps onto H number |Aut(q)|, Aut(q) permutes them freely, and
+ *             the same constraints select one: one row per copy.
+ *   Segments  ptr is the exclusive scan of the query's canonical counts in the same mode (out[:, 0] of
+ *             desco_canonical_counts_match_mode): rows [ptr[v], ptr[v + 1]) are the occurrences whose largest node is v,
+ *             so column `anchor` of each equals v, anchor = rec[2] of the record that found the row; a query with
+ *             several anchor orbits mixes records in one segment.
+ *   Order     inside a segment, ascending lexicographic order of the k columns (rows of a segment are pairwise
+ *             different: the order is total).  Given the plan, rows and ptr are fully defined: the two entry points
+ *             below (the second with the caller's sort) return the same bits for any slicing, chunking and thread count.
+ *
+ * HOST (OpenMP over graphs): lists the anchors [node_begin, node_end) into rows, row ptr[v] - ptr[node_begin] first,
+ * in the final order.  Refused, by name: a plan with plan[0] != 1 or whose records do not permute the query's nodes,
+ * null pointers, negative sizes, a node range outside [0, N], a descending ptr, rows_capacity below
+ * ptr[node_end] - ptr[node_begin] -- and, after the walk, a ptr whose segment differs from the number of maps found at
+ * some node (named in the message; no row is ever stored outside its segment). */
+int desco_list_occurrences(const int64_t* graph_ptr, int64_t num_graphs, const int64_t* rowptr, const int32_t* col,
+                           const int32_t* plan, int64_t plan_entries, int induced, int num_threads, int64_t node_begin,
+                           int64_t node_end, const int64_t* ptr, int64_t rows_capacity, int32_t* rows);
+/* DEVICE (csrc/occurrences_dev.hip): the listing instantiation of the matcher kernel.  Arguments up to entry_end as
+ * desco_canonical_counts_match_mode_dev (num_queries must be 1), slices as there; then ptr [N + 1] (device), ptr_base =
+ * the row index of the first row of `rows` (ptr[v0] when the call's entries are those of the anchors from v0 on, so that
+ * a chunk of anchors is emitted into a buffer of its own), cursor: int32 [N], rows: int32 [rows_capacity][k] and
+ * overflow: one int32 (all device).  The call with entry_begin = 0 zeroes cursor and *overflow and builds the bitset
+ * rows.  A lane that completes a map takes slot = cursor[v]++ and stores its row at ptr[v] - ptr_base + slot; a slot
+ * outside [0, ptr[v + 1] - ptr[v]) or a row outside [0, rows_capacity) is NOT stored and sets *overflow = 1, so no
+ * store leaves rows whatever ptr, cursor and plan_dev hold.  Rows of a segment arrive in any order: the caller sorts
+ * every segment after the last slice.  With the right ptr, afterwards cursor[v] = ptr[v + 1] - ptr[v] for the anchors
+ * covered and *overflow = 0.  Refused, by name: what desco_canonical_counts_match_mode_dev refuses, num_queries or
+ * plan[0] != 1, records that do not permute the query's nodes, null pointers, negative sizes, entry ranges outside
+ * [0, num_entries].  Enqueues on `stream`, does not allocate or synchronise. */
+int desco_list_occurrences_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes, const int64_t* rowptr,
+                               int64_t num_entries, const int32_t* col, const int32_t* node_graph,
+                               const int64_t* bit_off, uint64_t* bits, int64_t num_words, const int32_t* plan_host,
+                               const int32_t* plan_dev, int64_t plan_entries, int num_queries, int induced,
+                               int64_t entry_begin, int64_t entry_end, const int64_t* ptr, int64_t ptr_base,
+                               int32_t* cursor, int64_t rows_capacity, int32_t* rows, int32_t* overflow,
+                               desco_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * DEVICE kernels
  * ------------------------------------------------------------------------------------------ */
 
