@@ -79,6 +79,9 @@ SIGNATURES = {
     "desco_canonical_counts": (c_int, [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp]),
     "desco_canonical_class_table": (c_int, [vp, vp, vp, i32, vp, vp]),
     "desco_canonical_counts_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, vp, vp]),
+    "desco_canonical_class_table6": (c_int, [vp, vp, vp, i32, vp, vp]),
+    "desco_canonical_counts6_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, i64, i64, vp,
+                                            vp]),
     "desco_sampled_counts": (c_int, [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, ctypes.c_uint64, i64, i64, i32, i32,
                                      i32, vp]),
     "desco_sampled_counts_dev": (c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, vp, ctypes.c_uint64,

@@ -160,6 +160,34 @@ extern "C" int desco_canonical_class_table(const int32_t* q_nodes, const int32_t
   return 0;
 }
 
+// HOST helper: the class table of the 6-node device kernel (groundtruth6_dev.hip, g6_count_kernel): the table above
+// with the block of the 2^15 masks of 6 nodes behind it (ESU6_OFF), queries of 2..6 nodes, at most 142.
+extern "C" int desco_canonical_class_table6(const int32_t* q_nodes, const int32_t* q_edge_ptr,
+                                            const int32_t* q_edges, int num_queries, int16_t* table,
+                                            int* kmax_out) {
+  if (!q_nodes || !q_edge_ptr || !table || !kmax_out || num_queries < 0 || num_queries > desco::ESU6_MAXQ)
+    return desco::fail(DESCO_EINVAL, "desco_canonical_class_table6: bad argument (at most 142 queries)");
+  for (int i = 0; i < desco::ESU6_ENTRIES; ++i) table[i] = -1;
+  int kmax = 0;
+  for (int q = 0; q < num_queries; ++q) {
+    const int k = q_nodes[q];
+    if (k < 2 || k > desco::ESU6_KMAX)
+      return desco::fail(DESCO_EINVAL, "desco_canonical_class_table6: queries must have 2..6 nodes");
+    kmax = std::max(kmax, k);
+    uint32_t m = 0;
+    if (const int rc = desco::query_mask("desco_canonical_class_table6", q_edge_ptr, q_edges, q, k, &m)) return rc;
+    bool clash = false;                              // every relabeling of the query (720 for 6 nodes) is a mask of its class
+    for_each_relabeling(k, m, [&](uint32_t r, const int*) {
+      int16_t& slot = table[desco::ESU6_OFF[k] + r];
+      clash |= slot >= 0 && slot != q;
+      slot = (int16_t)q;
+    });
+    if (clash) return desco::fail(DESCO_EINVAL, "desco_canonical_class_table6: two queries are isomorphic");
+  }
+  *kmax_out = kmax;
+  return 0;
+}
+
 // ---- orbit counts (graphlet degree vectors) ---------------------------------------------------------------------------
 // orbit[v][(q,o)] = #{S containing v : G[S] isomorphic to q by a map that takes v into orbit o of Aut(q)}.  The orbits
 // of a query are those of its automorphism group on the node positions, numbered in ascending order of their smallest

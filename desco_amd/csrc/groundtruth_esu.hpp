@@ -21,6 +21,9 @@ namespace desco {
 // class table of the device enumerators: for k = 2..5 nodes the 2^(k(k-1)/2) adjacency masks start at ESU_OFF[k]
 constexpr int ESU_KMAX_DEV = 5, ESU_ENTRIES = 1098;
 constexpr int ESU_OFF[ESU_KMAX_DEV + 2] = {0, 0, 0, 2, 10, 74, ESU_ENTRIES};
+// class table of the 6-node device enumerator (groundtruth6_dev.hip): the same blocks, then the 2^15 masks of 6 nodes
+constexpr int ESU6_KMAX = 6, ESU6_ENTRIES = 33866, ESU6_MAXQ = 142;      // 142 = 1 + 2 + 6 + 21 + 112 classes
+constexpr int ESU6_OFF[ESU6_KMAX + 2] = {0, 0, 0, 2, 10, 74, ESU_ENTRIES, ESU6_ENTRIES};
 
 inline int pair_bit(int a, int b) { return b * (b - 1) / 2 + a; }   // a < b
 

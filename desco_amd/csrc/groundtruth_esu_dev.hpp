@@ -1,13 +1,15 @@
 // THE device ESU walk of the exact ground-truth kernels (gt_count_kernel, go_count_kernel and ge_count_kernel in
-// groundtruth_dev.hip, gtl_count_kernel in groundtruth_label_dev.hip): each kernel is a visitor over it.
+// groundtruth_dev.hip, gtl_count_kernel in groundtruth_label_dev.hip, g6_count_kernel in groundtruth6_dev.hip): each
+// kernel is a visitor over it.
 //
 // Enumeration: ESU without extension lists.  In ESU a node u enters the extension set when the FIRST subset node
 // adjacent to it is added, and choices are made in list order; with key(u) = (insertion index of that first
 // neighbour, position of u in its adjacency row) this is exactly "chosen nodes have strictly increasing keys".  So a
 // level is two nested loops over the adjacency rows of the subset's nodes, starting behind the previous key, and a
 // candidate is taken iff it is below the root, not in the subset and adjacent to no earlier subset node -- the same
-// adjacency bits then extend the induced-subgraph mask.  No per-thread lists: the subset (<= 5 nodes), the mask and
-// the loop cursors live in registers (levels are template-unrolled).
+// adjacency bits then extend the induced-subgraph mask.  No per-thread lists: the subset (<= 5 nodes, <= 6 for a
+// visitor that asks for it: esu_kmax below), the mask and the loop cursors live in registers (levels are
+// template-unrolled).
 //
 // Work item = one CSR entry (v, u0) with u0 < v: the subtree of subsets whose first chosen node is u0, handled by
 // ONE WAVE: the candidates for the next node (the rest of v's row, then u0's row) are dealt round-robin to the 64
@@ -93,29 +95,37 @@ struct esu_with_veto : std::false_type {};
 template <class V>
 struct esu_with_veto<V, std::void_t<decltype(V::kWithVeto)>> : std::true_type {};
 
+// the walk's depth: a visitor that declares `static constexpr int kMax = 6` (groundtruth6_dev.hip) is walked to six
+// nodes, its S has kMax entries and its masks up to kMax (kMax - 1) / 2 bits; one that declares nothing is walked to
+// ESU_KMAX_DEV = 5
+template <class V, class = void>
+struct esu_kmax : std::integral_constant<int, ESU_KMAX> {};
+template <class V>
+struct esu_kmax<V, std::void_t<decltype(V::kMax)>> : std::integral_constant<int, V::kMax> {};
+
 template <int NS, class V>
-__device__ __forceinline__ typename V::Path esu_push(V& vis, const int (&S)[ESU_KMAX], typename V::Path path, int u,
+__device__ __forceinline__ typename V::Path esu_push(V& vis, const int (&S)[esu_kmax<V>::value], typename V::Path path, int u,
                                                      unsigned ab, int ci, int64_t e) {
   if constexpr (esu_with_entry<V>::value) return vis.template push_at<NS>(path, S, u, ab, ci, e);
   else return vis.template push<NS>(path, u);
 }
 
 template <int NS, class V>
-__device__ __forceinline__ void esu_close(V& vis, const int (&S)[ESU_KMAX], typename V::Path path,
+__device__ __forceinline__ void esu_close(V& vis, const int (&S)[esu_kmax<V>::value], typename V::Path path,
                                           typename V::Level& level) {
   if constexpr (esu_with_entry<V>::value) vis.template close_at<NS>(S, path, level);
   else vis.template close<NS>(S, level);
 }
 
 template <int NS, class V>
-__device__ void esu_extend(const EsuGraph& g, V& vis, const int (&S)[ESU_KMAX], unsigned mask, typename V::Path path,
+__device__ void esu_extend(const EsuGraph& g, V& vis, const int (&S)[esu_kmax<V>::value], unsigned mask, typename V::Path path,
                            int ci0, int cp0);
 
 // candidate at position e of the adjacency row (starting at r0) of S[ci] for node number NS of the subset: taken iff
 // it is below the root, new, and adjacent to no subset node before S[ci].  Returns false when the row has passed the
 // root's id (rows ascend: nothing further qualifies).
 template <int NS, class V>
-__device__ __forceinline__ bool esu_try(const EsuGraph& g, V& vis, const int (&S)[ESU_KMAX], unsigned mask,
+__device__ __forceinline__ bool esu_try(const EsuGraph& g, V& vis, const int (&S)[esu_kmax<V>::value], unsigned mask,
                                         typename V::Path path, int ci, int64_t r0, int64_t e,
                                         typename V::Level& level) {
   const int u = (int)(g.col[e] - g.base);
@@ -134,11 +144,12 @@ __device__ __forceinline__ bool esu_try(const EsuGraph& g, V& vis, const int (&S
     if (!vis.template keep<NS + 1>(p2)) return true;
   }
   vis.template found<NS + 1>(S, u, m2, p2, level);
-  if constexpr (NS + 1 < ESU_KMAX) {
+  constexpr int KM = esu_kmax<V>::value;
+  if constexpr (NS + 1 < KM) {
     if (NS + 1 < g.kmax) {
-      int S2[ESU_KMAX];
+      int S2[KM];
 #pragma unroll
-      for (int j = 0; j < ESU_KMAX; ++j) S2[j] = j < NS ? S[j] : 0;
+      for (int j = 0; j < KM; ++j) S2[j] = j < NS ? S[j] : 0;
       S2[NS] = u;
       esu_extend<NS + 1>(g, vis, S2, m2, p2, ci, (int)(e - r0) + 1);
     }
@@ -148,7 +159,7 @@ __device__ __forceinline__ bool esu_try(const EsuGraph& g, V& vis, const int (&S
 
 // choose node number NS of the subset (S[0..NS-1] chosen, induced mask `mask`); candidates start at key (ci0, cp0)
 template <int NS, class V>
-__device__ void esu_extend(const EsuGraph& g, V& vis, const int (&S)[ESU_KMAX], unsigned mask, typename V::Path path,
+__device__ void esu_extend(const EsuGraph& g, V& vis, const int (&S)[esu_kmax<V>::value], unsigned mask, typename V::Path path,
                            int ci0, int cp0) {
   typename V::Level level{};
 #pragma unroll
@@ -167,7 +178,7 @@ template <class V>
 __device__ __forceinline__ void esu_wave_walk(const EsuGraph& g, V& vis, int64_t v, int64_t e, int u0, int lane,
                                               typename V::Path path) {
   if (g.kmax <= 2) return;
-  const int S[ESU_KMAX] = {g.lv, u0, 0, 0, 0};
+  const int S[esu_kmax<V>::value] = {g.lv, u0};      // (the other entries are 0)
   const int64_t v0 = g.rowptr[v], v1 = g.rowptr[v + 1];
   const int64_t w0 = g.rowptr[g.base + u0], w1 = g.rowptr[g.base + u0 + 1];
   const int64_t rest = v1 - (e + 1), total = rest + (w1 - w0);

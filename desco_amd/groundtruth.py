@@ -84,10 +84,98 @@ class _DeviceGraphs:
         return _put(a, dt, self.dev)
 
 
+# name of the backend that served the ESU columns (queries of at most 6 nodes) of the last canonical_counts call:
+# "host", "device" (the 2..5-node kernels) or "device6" (the 6-node kernel, canonical_counts6_device)
+last_esu_backend = None
+# Whether "auto" sends calls with a 6-node column to canonical_counts6_device.  True only if
+# tools/bench_groundtruth_six.py shows the device ahead of the host twin (16 threads) on both of its shapes: it does
+# (2026-10-21, one MI355X: 46x on COX2-shaped x64, 14x on the Syn_1827-shaped prefix; README).
+AUTO_USES_DEVICE6 = True
+_DEVICE6_MAX_QUERIES = 142          # every connected class of 2..6 nodes: 1 + 2 + 6 + 21 + 112
+
+
+def _device6_eligible(graphs: GraphSet, q_nodes: np.ndarray) -> bool:
+    """``_device_eligible`` for the 6-node kernel: a GPU, queries of 2..6 nodes, at most 142, bitsets within the limit."""
+    if not torch.cuda.is_available() or len(q_nodes) == 0 or len(q_nodes) > _DEVICE6_MAX_QUERIES:
+        return False
+    if q_nodes.min() < 2 or q_nodes.max() > 6:
+        return False
+    return int(_bitset_words(graphs).sum()) <= _DEVICE_BITSET_LIMIT_WORDS
+
+
+def _class_table6(queries: Sequence):
+    """``_class_table`` for the 6-node kernel: (int16 [33866], largest query size, number of queries)."""
+    _, q_nodes, q_edge_ptr, q_edges = _flatten_queries(queries)
+    table = np.empty(33866, dtype=np.int16)
+    kmax = ctypes.c_int(0)
+    _lib.check(_lib.lib().desco_canonical_class_table6(q_nodes.ctypes.data, q_edge_ptr.ctypes.data,
+                                                       q_edges.ctypes.data if len(q_edges) else None,
+                                                       len(q_nodes), table.ctypes.data, ctypes.byref(kmax)),
+               "desco_canonical_class_table6")
+    return table, int(kmax.value), len(q_nodes)
+
+
+def _census6_on(d: "_DeviceGraphs", table: np.ndarray, kmax: int, Q: int, slice_entries) -> torch.Tensor:
+    """The 6-node census kernel on a graph set that is on the device (d.N > 0, Q > 0): int64 [d.N, Q]; one launch per
+    slice of the CSR entries, the stream synchronised and the status checked after every slice."""
+    slice_entries = _MATCH_SLICE_WAVES if slice_entries is None else int(slice_entries)     # one wave per entry
+    if slice_entries < 1:
+        raise ValueError("slice_entries must be positive")
+    out = torch.empty((d.N, Q), dtype=torch.int64, device=d.dev)
+    cls = d.put(table, np.int16)
+    L = _lib.lib()
+    with torch.cuda.device(d.dev):
+        stream = torch.cuda.current_stream(d.dev)
+        _sliced(d.E, slice_entries, stream, lambda e0, e1: _lib.check(
+            L.desco_canonical_counts6_dev(*d.head, cls.data_ptr(), kmax, Q, e0, e1, out.data_ptr(),
+                                          stream.cuda_stream), "desco_canonical_counts6_dev"))
+    return out
+
+
+def canonical_counts6_device(graphs: GraphSet, queries: Sequence, device="cuda", induced: bool = True,
+                             slice_entries=None) -> torch.Tensor:
+    """The counts of ``canonical_counts`` for queries of 2..6 nodes computed on the MI355X by the ESU walk at depth six
+    (csrc/groundtruth6_dev.hip): every column in ONE walk.  Returns a [num_nodes, num_queries] int64 tensor on
+    ``device``, bit-identical to the host enumerator.
+    ``induced=True``: the queries are pairwise non-isomorphic and at most 142 (every connected class of 2..6 nodes).
+    ``induced=False``: the non-induced counts of any number of queries, duplicates included: the census of all classes
+    of the queries' sizes in one walk, then ``desco_canonical_noninduced_transform_dev`` in chunks of 32 classes.
+    The CSR entries are cut into slices of ``slice_entries`` (default ``_MATCH_SLICE_WAVES``: one wave per entry), one
+    launch each; the slicing does not change the result.  Empty graph sets and no queries give zeros without a launch.
+    Raises RuntimeError naming "2..6 nodes" or "isomorphic" for queries it does not take."""
+    dev = torch.device(device)
+    flat = _flatten_queries(queries)[0]
+    if any(n < 2 or n > 6 for n, _ in flat):
+        raise RuntimeError("canonical_counts6_device: queries must have 2..6 nodes")
+    if not induced:
+        out = torch.zeros((graphs.num_nodes, len(flat)), dtype=torch.int64, device=dev)
+        if not flat:
+            return out
+        groups = _census_plan(flat)                 # (refuses disconnected queries and loops)
+        if graphs.num_nodes == 0:
+            return out
+        classes = [c for cl, _, _ in groups for c in cl]
+        census = canonical_counts6_device(graphs, classes, dev, slice_entries=slice_entries)
+        c_first = 0
+        for cl, idx, m in groups:                   # (a size's classes only feed that size's columns)
+            part = torch.empty((graphs.num_nodes, len(idx)), dtype=torch.int64, device=dev)
+            for c0 in range(0, len(cl), 32):
+                c1 = min(c0 + 32, len(cl))
+                _transform_device(census[:, c_first + c0:c_first + c1], m[c0:c1], part, c0 > 0)
+            out[:, torch.tensor(idx, device=dev)] = part
+            c_first += len(cl)
+        return out
+    table, kmax, Q = _class_table6(flat)
+    if graphs.num_nodes == 0 or Q == 0:
+        return torch.zeros((graphs.num_nodes, Q), dtype=torch.int64, device=dev)
+    return _census6_on(_DeviceGraphs(graphs, dev), table, kmax, Q, slice_entries)
+
+
 def canonical_counts_device(graphs: GraphSet, queries: Sequence, device="cuda", induced: bool = True) -> torch.Tensor:
     """The counts of ``canonical_counts`` computed on the MI355X (csrc/groundtruth_dev.hip):
     queries of 2..5 nodes, at most 32, pairwise non-isomorphic.  Returns a [num_nodes, num_queries]
-    int64 tensor on ``device``.
+    int64 tensor on ``device``.  (6-node queries are refused here, naming "2..5 nodes": they are
+    ``canonical_counts6_device``'s.)
     ``induced=False``: the non-induced counts (see ``canonical_counts``) of queries of 2..5 nodes, any number of them,
     duplicates included: the census of all connected classes of the queries' sizes by the same kernel, then the exact
     int64 transform on the device (``desco_canonical_noninduced_transform_dev``), without a round trip."""
@@ -131,7 +219,12 @@ def canonical_counts(graphs: GraphSet, queries: Sequence, num_threads: int = 0,
     ``backend``: "host" (OpenMP), "device" (HIP kernels), "auto", or "vf2" (the reference's procedure in Python:
     the yardstick of the tests and the way out for queries above 16 nodes).
     Columns of queries with at most 6 nodes go to the ESU enumerators -- "auto": the device when a GPU is present
-    and the queries fit its path (2..5 nodes, <= 32, distinct classes), else the host.  Columns of larger queries
+    and the queries fit its path (2..5 nodes, <= 32, distinct classes), else the host; a call with a 6-node column
+    sends ALL its columns of at most 6 nodes to ``canonical_counts6_device`` in one walk when ``AUTO_USES_DEVICE6``
+    and the set is eligible (a GPU, bitsets within the limit, at most 142 distinct classes), else to the host.
+    ``last_esu_backend`` names the one that served them ("host", "device", "device6").  ``backend="device"`` keeps
+    meaning the 2..5-node kernels and refuses a 6-node query naming "2..5 nodes": ask ``canonical_counts6_device``.
+    Columns of larger queries
     go to the matcher (``canonical_counts_match``) with the same ``backend``; the results are joined in query order.
     ``induced=False``: NON-INDUCED counts, count[v][q] = #{injective f : f maps every edge of q onto an edge of G,
     max(im f) = v} / |Aut(q)| -- occurrences that need only CONTAIN the query's edges (P3 in a triangle: 3, all at the
@@ -156,15 +249,34 @@ def canonical_counts(graphs: GraphSet, queries: Sequence, num_threads: int = 0,
         if small:
             out[:, small] = canonical_counts(graphs, [flat[i] for i in small], num_threads, backend, induced)
         return out
+    global last_esu_backend
     if not induced:
         return _noninduced_small(graphs, flat, backend, num_threads)
+    if backend == "auto" and _auto_device6(graphs, q_nodes):        # a 6-node column: every column in one walk
+        try:
+            out = canonical_counts6_device(graphs, flat).cpu().double()
+            last_esu_backend = "device6"
+            return out
+        except RuntimeError as e:
+            if "isomorphic" not in str(e):
+                raise                           # (duplicate query classes: host path below)
     if backend == "device" or (backend == "auto" and _device_eligible(graphs, q_nodes)):
         try:
-            return canonical_counts_device(graphs, queries).cpu().double()
+            out = canonical_counts_device(graphs, queries).cpu().double()
+            last_esu_backend = "device"
+            return out
         except RuntimeError as e:
             if backend == "device" or "isomorphic" not in str(e):
                 raise                           # (duplicate query classes: host path below)
-    return torch.from_numpy(_induced_host_int64(graphs, flat, num_threads)).double()
+    out = torch.from_numpy(_induced_host_int64(graphs, flat, num_threads)).double()
+    last_esu_backend = "host"
+    return out
+
+
+def _auto_device6(graphs: GraphSet, q_nodes: np.ndarray) -> bool:
+    """Whether "auto" sends these ESU columns (at most 6 nodes) to the 6-node kernel: the measured switch, a 6-node
+    column among them, and the set eligible.  Calls without a 6-node column go where they went."""
+    return bool(AUTO_USES_DEVICE6 and len(q_nodes) and q_nodes.max() == 6 and _device6_eligible(graphs, q_nodes))
 
 
 # ---- non-induced counts of small queries: census of all classes + an exact transform ---------------------------------
@@ -285,14 +397,26 @@ def _noninduced_device(graphs: GraphSet, flat, dev) -> torch.Tensor:
 def _noninduced_small(graphs: GraphSet, flat, backend: str, num_threads: int) -> torch.Tensor:
     """Non-induced counts of queries of at most 6 nodes as a [num_nodes, len(flat)] double tensor on the CPU.  The census
     of a size goes where induced columns of that size go: the device when ``backend`` says so or "auto" finds the
-    classes eligible (2..5 nodes, a GPU, bitsets within the limit), else the host enumerator and numpy int64."""
+    classes eligible (2..5 nodes, a GPU, bitsets within the limit), else the host enumerator and numpy int64.  "auto" with
+    a 6-node query: every size in one walk of the 6-node kernel (``canonical_counts6_device(induced=False)``) when
+    ``AUTO_USES_DEVICE6`` and the set is eligible.  Sets ``last_esu_backend``."""
+    global last_esu_backend
+    # (any number of queries: what the kernel counts are the classes of their sizes, 142 at most)
+    if backend == "auto" and _auto_device6(graphs, np.array(sorted({n for n, _ in flat}), dtype=np.int32)):
+        last_esu_backend = "device6"                # a 6-node column: the census of every size in one walk
+        return canonical_counts6_device(graphs, flat, induced=False).cpu().double()
     out = np.zeros((graphs.num_nodes, len(flat)), dtype=np.int64)
+    served = set()
     for classes, idx, m in _census_plan(flat):
         sizes = np.array([n for n, _ in classes], dtype=np.int32)
         if backend == "device" or (backend == "auto" and _device_eligible(graphs, sizes[:32])):
             out[:, idx] = _noninduced_device(graphs, [flat[i] for i in idx], torch.device("cuda")).cpu().numpy()
+            served.add("device")
         else:
             out[:, idx] = _induced_host_int64(graphs, classes, num_threads) @ m
+            served.add("host")
+    if served:                                      # (a call served by both names the host: its census is the larger)
+        last_esu_backend = "host" if "host" in served else "device"
     return torch.from_numpy(out).double()
 
 

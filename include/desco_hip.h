@@ -741,6 +741,29 @@ int desco_canonical_counts_dev(const int64_t* graph_ptr, int64_t num_graphs, int
                                int64_t num_words, const int16_t* cls, int kmax, int num_queries,
                                int64_t* out, desco_stream_t stream);
 
+/* The same counts on the GPU for queries of 2..6 nodes (csrc/groundtruth6_dev.hip): the walk at depth six, every
+ * column in one walk.  Queries as for desco_canonical_counts: 2..6 nodes, pairwise non-isomorphic, at most 142 (every
+ * connected class of 2..6 nodes: 1 + 2 + 6 + 21 + 112).
+ * HOST helper desco_canonical_class_table6: table[33866] = for k = 2..6 nodes and every adjacency mask on k nodes
+ *   (bit b(b-1)/2 + a for the pair a < b; the masks of k nodes start at offsets 0, 2, 10, 74, 1098; entries 0..1097 are
+ *   those of desco_canonical_class_table for the same queries) the index of the query of that isomorphism class, or
+ *   -1; *kmax = the largest query.  DESCO_EINVAL naming the entry point for a null pointer, a size outside "2..6
+ *   nodes", "isomorphic" queries, a "bad query edge" and more than 142 queries.
+ * DEVICE desco_canonical_counts6_dev: the device arguments of desco_canonical_counts_dev up to num_words, cls = the
+ *   table above (device pointer), kmax in 2..6, num_queries in 1..142 (0: nothing to do), then the slice
+ *   [entry_begin, entry_end) of the CSR entries.  The launch contract is desco_canonical_counts_match_dev's: the call
+ *   with entry_begin = 0 zeroes out and builds the bitset rows, every call ADDS the counts of its slice; the caller
+ *   cuts [0, num_entries) into ascending slices.  out: int64 [N][num_queries], bit-identical to the host enumerator
+ *   from call to call and for every slicing.  Enqueues on `stream`, does not allocate or synchronise; bad arguments
+ *   are refused by name before anything is launched. */
+int desco_canonical_class_table6(const int32_t* q_nodes, const int32_t* q_edge_ptr, const int32_t* q_edges,
+                                 int num_queries, int16_t* table, int* kmax);
+int desco_canonical_counts6_dev(const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes,
+                                const int64_t* rowptr, int64_t num_entries, const int32_t* col,
+                                const int32_t* node_graph, const int64_t* bit_off, uint64_t* bits,
+                                int64_t num_words, const int16_t* cls, int kmax, int num_queries,
+                                int64_t entry_begin, int64_t entry_end, int64_t* out, desco_stream_t stream);
+
 /* ORBIT COUNTS (graphlet degree vectors): how many occurrences of a query contain node v, with v in a given position
  * of the query -- unlike the canonical counts above they do not depend on the node numbering.
  *   Query: connected, loop-free, 2..5 nodes, given as for desco_canonical_counts; pairwise non-isomorphic.
