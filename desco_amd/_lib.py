@@ -163,6 +163,9 @@ SIGNATURES = {
     "desco_table_rows_pool3_f32": (c_int, [vp, vp, vp, vp, vp, i64, vp, vp, vp]),
     "desco_table_rows_pooln_f32": (c_int, [i32, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
     "desco_table_rows_pooln_max_layers": (c_int, []),
+    "desco_class_rows_pool_f32": (c_int, [i32, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, i64, vp]),
+    "desco_class_rows_pool_max_rows": (c_int, []),
+    "desco_gather_rows_f32": (c_int, [vp, i64, i64, vp, i64, i32, vp, i64, vp]),
     "desco_index_range_check_i32": (c_int, [vp, i64, i64, vp, vp]),
     "desco_gemm_bf16x6_f32": (c_int, [vp, i64, i32, vp, i64, i32, vp, i32, vp, i32, vp, i32, vp, i32, f32,
                                       vp, i64, i64, vp]),

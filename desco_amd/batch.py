@@ -32,6 +32,7 @@ def _i32(a, device):
 # NeighborhoodBatch._level_csr
 _LevelCSR = namedtuple("_LevelCSR", "col low csrc qsrc start tdeg dmax cstart ctdeg cdmax deg pos")
 _CanonTables = namedtuple("_CanonTables", "uptr1 levels size offset anchor_rows")
+_PoolClasses = namedtuple("_PoolClasses", "pcls prep rep_ptr bits slot nslots anch_row")
 
 
 def _transpose_index(vrowptr: np.ndarray, vcol: np.ndarray, n_src: int):
@@ -600,6 +601,79 @@ class NeighborhoodBatch(_TrainIndexMixin):
             return None
         acls, ua = r
         return (acls.to(torch.int32).contiguous(), self._lowest_rows(acls, ua).contiguous())
+
+    # eligibility bounds of pool_class_index, the path's own and about profit only, on the NEIGHBORHOODS like the anchor
+    # index's: what the class form saves -- the pooling walk, post_mp.0, the tail and the count head on all but U_p rows --
+    # grows with them, what it adds (a U_p-row launch of each, a gather of [B, Q] counts) does not.  Tests on small blocks lower
+    # them on their batch object; at the defaults those blocks keep the launches their tests pin
+    POOL_CLASS_MIN_ROWS = 1 << 20
+    POOL_CLASS_MIN_ROWS_PER_CLASS = 8
+
+    def pool_class_index(self, layer_num: int):
+        """The neighborhoods' classes under everything behind the trunk of a model of ``layer_num`` = L layers (built once per
+        batch and L, on the batch's device): ``(pcls, prep)`` or None; defined only where ``anchor_class_index(L)`` is.
+
+        post_mp.0's operand row of neighborhood b is its anchor row plus, per layer, the pooled sum of its count rows as the
+        fused pooling forms it: running sums in row order, cut at the 16-row tile boundaries of the GLOBAL row index, the
+        pieces added left to right.  Every summand is a row of a class table and the classes nest, so the whole row is a
+        function of the anchor class ``acls[b]``, of ``count_ptr[b] & 15`` (where the cuts fall inside the neighborhood) and
+        of the ordered top-level count classes of its rows; all that follows -- post_mp, the count head -- is row-local.
+        ``pcls`` [B] int32 is each neighborhood's class under that triple, ``prep`` [U_p] int64 the lowest neighborhood of
+        each class.  Exact (``_refine_classes``).  None unless the block has at least POOL_CLASS_MIN_ROWS neighborhoods and
+        POOL_CLASS_MIN_ROWS_PER_CLASS U_p <= B."""
+        cache = self.__dict__.setdefault("_pool_class", {})
+        if layer_num not in cache:
+            cache[layer_num] = res = self._build_pool_classes(layer_num)
+            if res is not None and res[0].is_cuda:
+                from . import ops
+                # the classes address the representatives' rows of counts (desco_gather_rows_f32)
+                ops.index_range_check(res[0], res[1].numel())
+        return cache[layer_num]
+
+    def _build_pool_classes(self, L):
+        B = self.num_rows - self.num_count
+        if B < max(self.POOL_CLASS_MIN_ROWS, 1):                                # (small blocks leave before any work)
+            return None
+        ac = self.anchor_class_index(L)
+        if ac is None:
+            return None
+        top = self._table_level(L)                                              # (there: the anchor index needs level L)
+        cls, u = top[0].to(torch.int64), (top[1].numel() - 1) // self.slots
+        cp = self.count_ptr.to(torch.int64)
+        start, rows = cp[:-1], cp[1:] - cp[:-1]
+        # the start key, made dense: the anchor class and the neighborhood's first row inside its tile
+        uniq, key = torch.unique(ac[0].to(torch.int64) * 16 + (start & 15), return_inverse=True)
+        r = self._refine_classes(key, uniq.numel(), start, rows, cls, int(rows.max().item()), u + 1,
+                                 B // self.POOL_CLASS_MIN_ROWS_PER_CLASS)
+        if r is None:
+            return None
+        pcls, up = r
+        return (pcls.to(torch.int32).contiguous(), self._lowest_rows(pcls, up).contiguous())
+
+    def pool_class_launch_index(self, layer_num: int):
+        """What the pass needs to run on the representatives of ``pool_class_index(layer_num)`` (built once, on the device):
+        a ``_PoolClasses`` or None.  ``rep_ptr`` [U_p + 1] int32 is the representatives' compact row pointer (their row
+        counts, summed), ``bits`` / ``slot`` / ``nslots`` its fused-pooling index, ``anch_row`` [U_p] int32 their anchor
+        classes."""
+        cache = self.__dict__.setdefault("_pool_class_launch", {})
+        if layer_num not in cache:
+            idx = self.pool_class_index(layer_num)
+            if idx is not None:
+                from . import ops
+                pcls, prep = idx
+                cp = self.count_ptr.to(torch.int64)
+                rows = (cp[1:] - cp[:-1])[prep]
+                rep_ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=rows.device), rows.cumsum(0)])
+                total = int(rep_ptr[-1].item())
+                rep_ptr = rep_ptr.to(torch.int32).contiguous()
+                bits, slot, totals = ops.pool_index_dev(rep_ptr, prep.numel(), total)
+                nslots, _, smallest, _ = totals.tolist()
+                if smallest <= 0:
+                    raise ValueError("fused pooling needs at least one count row per neighborhood")
+                idx = _PoolClasses(pcls, prep, rep_ptr, bits, slot, int(nslots),
+                                   self.anchor_class_index(layer_num)[0][prep].contiguous())
+            cache[layer_num] = idx
+        return cache[layer_num]
 
     def canonical_class_tables(self, layer_num: int):
         """What the pass needs to keep the canonical rows of X_1 .. X_L as tables of their distinct rows (built once per batch

@@ -1405,6 +1405,192 @@ extern "C" int desco_table_rows_pool3_f32(const float* const* tables, const int6
                                      pool_bits, pool_slot, stream);
 }
 
+// The pooled sums of the table layers on one REPRESENTATIVE per pooling class (gnn_model.POOL_CLASS_TABLE,
+// NeighborhoodBatch.pool_class_index): neighborhoods that agree in their anchor class, in where the 16-row tile cuts fall inside
+// them (count_ptr & 15) and in the ordered top-level classes of their count rows get bit-equal rows of post_mp.0's operand, so
+// the walk above need not visit every count row.  One wave per representative u, one lane per column: its count rows are rows
+// s .. s + n - 1 of the block (s = count_ptr[rep[u]]), read from the tables through the layers' ids AT THEIR ORIGINAL POSITIONS,
+// and summed as the walk and post_mp.0 sum them -- a running sum from 0.f down the rows, cut after every row i with
+// (i & 15) == 15, the (at most three) pieces combined as ((p0 + p1) + p2), absent pieces 0.f.  The result goes where post_mp.0
+// looks for the pieces of segment u of the COMPACT row pointer rep_ptr (rep_ptr[u + 1] - rep_ptr[u] = n) under that pointer's
+// own pooling index: the combined sum into the segment's first slot, zeros into its continuation slots, ((P + 0) + 0) = P.
+//  * lane j holds the id of row s + j (one load per layer, all layers' loads issued together);
+//  * the rows of CRP_BATCH layers are in flight CRP_ROWS at a time (32 loads per wait), each a 256-byte read per wave.
+namespace desco {
+constexpr int CRP_BATCH = 4, CRP_ROWS = 8;
+constexpr int CRP_MAX_ROWS = 33;                           // rows of a representative: at most three pieces wherever it starts
+
+template <int NL>
+__global__ __launch_bounds__(256) void class_rows_pool_kernel(PoolTables p, const int32_t* __restrict__ count_ptr,
+                                                              int64_t num_neigh, int64_t num_rows,
+                                                              const int64_t* __restrict__ rep,
+                                                              const int32_t* __restrict__ rep_ptr, int64_t num_rep,
+                                                              const uint32_t* __restrict__ pool_bits,
+                                                              const int32_t* __restrict__ pool_slot, int64_t num_slots) {
+  static_assert(NL >= 1 && NL <= POOLN_MAX, "one to eight layers");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t u = (int64_t)blockIdx.x * 4 + wave; u < num_rep; u += (int64_t)gridDim.x * 4) {
+    // (a representative outside the block -- the caller's error -- reads the nearest neighborhood, never out of bounds)
+    int64_t b = rep[u];
+    b = b < 0 ? 0 : (b < num_neigh ? b : num_neigh - 1);
+    const int s = __builtin_amdgcn_readfirstlane(count_ptr[b]);
+    int n = __builtin_amdgcn_readfirstlane(count_ptr[b + 1]) - s;
+    const int a = __builtin_amdgcn_readfirstlane(rep_ptr[u]);
+    // (wave-uniform.  No rows: no slots.  More rows than three pieces can hold, rows outside the block or a compact segment
+    //  of another length -- the caller's errors -- write nothing: the tiles below then lie inside the compact index)
+    if (n <= 0 || n > CRP_MAX_ROWS || s < 0 || (int64_t)s + n > num_rows || a < 0 ||
+        __builtin_amdgcn_readfirstlane(rep_ptr[u + 1]) - a != n)
+      continue;
+    // the segment's slots under the compact pointer, as post_mp.0 finds them (DESCO_POOL_ROW of gemm_split.hip)
+    const int t0 = a >> 4, t1 = (a + n - 1) >> 4;
+    const int64_t slot[3] = {
+        (int64_t)__builtin_amdgcn_readfirstlane(pool_slot[t0]) +
+            __popc(__builtin_amdgcn_readfirstlane(pool_bits[t0]) & ((1u << (a & 15)) - 1u)),
+        t1 > t0 ? (int64_t)__builtin_amdgcn_readfirstlane(pool_slot[t0 + 1]) : -1,
+        t1 > t0 + 1 ? (int64_t)__builtin_amdgcn_readfirstlane(pool_slot[t0 + 2]) : -1};
+    int idv[NL];
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+      // (an id outside its table -- the caller's error, desco_index_range_check_i32 finds it -- reads the nearest table row)
+      const int c = p.t[k].ids[s + (lane < n ? lane : n - 1)];
+      idv[k] = c < 0 ? 0 : (c < p.t[k].num ? c : p.t[k].num - 1);
+    }
+    const int e = s + n;
+#pragma unroll
+    for (int k0 = 0; k0 < NL; k0 += CRP_BATCH) {
+      float piece[3][CRP_BATCH];
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) {
+        // piece pc: the rows of the segment inside tile (s >> 4) + pc of the block
+        const int lo = pc == 0 ? s : ((s >> 4) + pc) << 4;
+        const int tile_end = ((s >> 4) + pc + 1) << 4;
+        const int cnt = (e < tile_end ? e : tile_end) - lo;            // (<= 0: the segment ends before this tile)
+        float run[CRP_BATCH];
+#pragma unroll
+        for (int q = 0; q < CRP_BATCH; ++q) run[q] = 0.f;
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += CRP_ROWS) {
+          if (r0 < cnt) {                                              // (wave-uniform)
+            float v[CRP_BATCH][CRP_ROWS];
+#pragma unroll
+            for (int q = 0; q < CRP_BATCH; ++q) {
+              if (k0 + q < NL) {
+                const int k = k0 + q < NL ? k0 + q : NL - 1;
+                const float* tb = p.t[k].table + lane;
+                const int64_t ld = p.t[k].ld;
+#pragma unroll
+                for (int r = 0; r < CRP_ROWS; ++r) {
+                  // (a row past the piece repeats the segment's last row: read, never summed)
+                  const int j = lo - s + r0 + r;
+                  v[q][r] = tb[(int64_t)__builtin_amdgcn_readlane(idv[k], j < n ? j : n - 1) * ld];
+                }
+              }
+            }
+#pragma unroll
+            for (int r = 0; r < CRP_ROWS; ++r)
+              if (r0 + r < cnt) {                                      // (wave-uniform)
+#pragma unroll
+                for (int q = 0; q < CRP_BATCH; ++q)
+                  if (k0 + q < NL) run[q] += v[q][r];
+              }
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < CRP_BATCH; ++q) piece[pc][q] = run[q];
+      }
+#pragma unroll
+      for (int q = 0; q < CRP_BATCH; ++q) {
+        if (k0 + q < NL) {
+          float* part = p.t[k0 + q < NL ? k0 + q : NL - 1].part + lane;
+          const float sum = (piece[0][q] + piece[1][q]) + piece[2][q];
+          if (slot[0] >= 0 && slot[0] < num_slots) part[slot[0] * 64] = sum;
+          if (slot[1] >= 0 && slot[1] < num_slots) part[slot[1] * 64] = 0.f;
+          if (slot[2] >= 0 && slot[2] < num_slots) part[slot[2] * 64] = 0.f;
+        }
+      }
+    }
+  }
+}
+
+template <int NL>
+int launch_class_rows_pool(const PoolTables& p, const int32_t* count_ptr, int64_t num_neigh, int64_t num_rows,
+                           const int64_t* rep, const int32_t* rep_ptr, int64_t num_rep, const uint32_t* pool_bits,
+                           const int32_t* pool_slot, int64_t num_slots, hipStream_t st) {
+  int64_t blocks = (num_rep + 3) / 4;                      // four representatives per block
+  if (blocks > 8 * 256) blocks = 8 * 256;
+  hipLaunchKernelGGL((class_rows_pool_kernel<NL>), dim3((unsigned)blocks), dim3(256), 0, st, p, count_ptr, num_neigh,
+                     num_rows, rep, rep_ptr, num_rep, pool_bits, pool_slot, num_slots);
+  return launch_status("desco_class_rows_pool_f32");
+}
+
+// dst[b, 0:ncols] = src[rows[b], 0:ncols]: one 32-lane group per destination row (the count head's rows are 29 wide)
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ src, int64_t lds, int64_t num_src,
+                                                          const int32_t* __restrict__ rows, int64_t num_dst, int ncols,
+                                                          float* __restrict__ dst, int64_t ldd) {
+  const int c0 = threadIdx.x & 31;
+  for (int64_t b = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5); b < num_dst; b += (int64_t)gridDim.x * 8) {
+    // (a row outside the source -- the caller's error, desco_index_range_check_i32 finds it -- reads the nearest row)
+    int64_t r = rows[b];
+    r = r < 0 ? 0 : (r < num_src ? r : num_src - 1);
+    for (int c = c0; c < ncols; c += 32) dst[b * ldd + c] = src[r * lds + c];
+  }
+}
+}  // namespace desco
+
+extern "C" int desco_class_rows_pool_max_rows(void) { return desco::CRP_MAX_ROWS; }
+
+extern "C" int desco_class_rows_pool_f32(int num_layers, const float* const* tables, const int64_t* ldts,
+                                         const int64_t* num_tables, const int32_t* const* ids, float* const* pool_parts,
+                                         const int32_t* count_ptr, int64_t num_neigh, int64_t num_rows, const int64_t* rep,
+                                         const int32_t* rep_ptr, int64_t num_rep, const uint32_t* pool_bits,
+                                         const int32_t* pool_slot, int64_t num_slots, desco_stream_t stream) {
+  using namespace desco;
+  if (num_rep == 0) return 0;
+  bool bad = num_layers < 1 || num_layers > POOLN_MAX || !tables || !ldts || !num_tables || !ids || !pool_parts ||
+             !count_ptr || !rep || !rep_ptr || !pool_bits || !pool_slot || num_rep < 0 || num_neigh < 1 || num_rows < 1 ||
+             num_rows > INT32_MAX || num_slots < 1;
+  for (int k = 0; k < num_layers && !bad; ++k) {
+    bad = !tables[k] || !ids[k] || !pool_parts[k] || num_tables[k] < 1 || num_tables[k] > INT32_MAX || ldts[k] < 64 ||
+          mis16(tables[k]) || mis16(pool_parts[k]);
+    for (int j = 0; j < k && !bad; ++j) bad = pool_parts[j] == pool_parts[k];
+  }
+  if (bad)
+    return fail(DESCO_EINVAL, "desco_class_rows_pool_f32: bad argument (one to eight layers, per layer a table, ids and "
+                              "partial rows of their own, count_ptr, the representatives, their row pointer and its pooling "
+                              "index present, tables of 1 .. 2^31 - 1 rows of at least 64 floats)");
+  PoolTables p{};
+  for (int k = 0; k < POOLN_MAX; ++k) {
+    const int s = k < num_layers ? k : num_layers - 1;     // (entries past the last layer repeat it: never used, never null)
+    p.t[k] = PoolTable{tables[s], ldts[s], (int)num_tables[s], ids[s], pool_parts[s]};
+    p.lds_off[k] = -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+#define DESCO_CRP_CASE(n_)                                                                                          \
+  case n_:                                                                                                          \
+    return launch_class_rows_pool<n_>(p, count_ptr, num_neigh, num_rows, rep, rep_ptr, num_rep, pool_bits, pool_slot, \
+                                      num_slots, st);
+  switch (num_layers) {
+    DESCO_CRP_CASE(1) DESCO_CRP_CASE(2) DESCO_CRP_CASE(3) DESCO_CRP_CASE(4) DESCO_CRP_CASE(5) DESCO_CRP_CASE(6)
+    DESCO_CRP_CASE(7)
+    default: return launch_class_rows_pool<8>(p, count_ptr, num_neigh, num_rows, rep, rep_ptr, num_rep, pool_bits,
+                                              pool_slot, num_slots, st);
+  }
+#undef DESCO_CRP_CASE
+}
+
+extern "C" int desco_gather_rows_f32(const float* src, int64_t lds, int64_t num_src, const int32_t* rows, int64_t num_dst,
+                                     int ncols, float* dst, int64_t ldd, desco_stream_t stream) {
+  if (num_dst == 0) return 0;
+  if (!src || !rows || !dst || num_dst < 0 || num_src < 1 || ncols < 1 || lds < ncols || ldd < ncols || src == dst)
+    return fail(DESCO_EINVAL, "desco_gather_rows_f32: bad argument (a source of at least one row, rows of at least ncols "
+                              "floats, dst != src)");
+  int64_t blocks = (num_dst + 7) / 8;
+  if (blocks > 16 * 256) blocks = 16 * 256;
+  hipLaunchKernelGGL(desco::gather_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, lds, num_src,
+                     rows, num_dst, ncols, dst, ldd);
+  return launch_status("desco_gather_rows_f32");
+}
+
 extern "C" int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch,
                                            desco_stream_t stream) {
   if (n == 0) return 0;

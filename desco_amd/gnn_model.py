@@ -554,6 +554,18 @@ class BaseGNN(nn.Module):
             return shmp_forward_train(self, data, drop_key)
         return shmp_forward(self, data)
 
+    def forward_classes(self, data):
+        """``forward`` at inference for callers whose own work is row-local (the count head): ``(emb, rows)`` with ``rows``
+        None and ``emb`` = ``forward(data)``, or (POOL_CLASS_TABLE) ``emb`` one row per pooling class and ``forward(data)`` =
+        ``emb[rows]``, which is then never formed"""
+        train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if self.conv_type == "GOSSIP" or not isinstance(data, NeighborhoodBatch) or self.is_wide() or train:
+            return self(data), None
+        self.gnn_core.row_types()                # (a hetero model that has not been converted yet is refused, as in forward)
+        if self.gnn_core.is_homogeneous():
+            return self(data), None
+        return shmp_forward_classes(self, data)
+
     def is_wide(self) -> bool:
         """True for a SAGE model of another width than 64 (it runs the wide path, shmp_forward_wide) and for a plain GIN /
         GCN model of ANY width (plain_forward): both work on operands zero-padded to padded_width(hidden_dim)"""
@@ -666,11 +678,12 @@ POST_TAIL_FUSED = os.environ.get("DESCO_POST_TAIL_FUSED", "1") != "0"
 
 
 class _PostMp0(object):
-    """post_mp.0's output computed by _shmp_pooled itself (the pooled operand never materialised)"""
-    __slots__ = ("h0",)
+    """post_mp.0's output computed by _shmp_pooled itself (the pooled operand never materialised).  ``rows``: None, or
+    (POOL_CLASS_TABLE) ``h0`` holds one row per pooling class and neighborhood b's row is ``h0[rows[b]]`` ([B] int32)"""
+    __slots__ = ("h0", "rows")
 
-    def __init__(self, h0):
-        self.h0 = h0
+    def __init__(self, h0, rows=None):
+        self.h0, self.rows = h0, rows
 
 
 def _post_mp(pk, pooled):
@@ -817,9 +830,28 @@ ANCHOR_CLASS_TABLE = os.environ.get("DESCO_ANCHOR_CLASS_TABLE", "1") != "0"
 CANON_CLASS_TABLES = os.environ.get("DESCO_CANON_CLASS_TABLES", "1") != "0"
 
 
+# ... and everything behind the trunk: where ANCHOR_CLASS_TABLE is taken, a neighborhood's row of post_mp.0's operand is a
+# function of its anchor class, of where the pooling's 16-row tile cuts fall inside it and of the ordered top-level classes of
+# its count rows (NeighborhoodBatch.pool_class_index: COX2-shaped x64 has 52 k such classes for 1.2 M neighborhoods), and the
+# rest of the model is row-local.  The pooled sums are formed on one representative per class (desco_class_rows_pool_f32, in
+# place of the walk over all count rows, in the walk's order of additions), post_mp and the count head run on those rows, and
+# the counts are handed out to the neighborhoods by one gather (desco_gather_rows_f32).  Blocks of at least
+# NeighborhoodBatch.POOL_CLASS_MIN_ROWS neighborhoods
+POOL_CLASS_TABLE = os.environ.get("DESCO_POOL_CLASS_TABLE", "1") != "0"
+
+
 def shmp_forward(gnn: BaseGNN, batch) -> torch.Tensor:
     """BaseGNN.forward, hetero path (gnn_model.py:58-109) -> graph embeddings [B, 64]."""
-    return _post_mp(gnn.packed(), _shmp_pooled(gnn, batch, fuse_post0=True))                 # :108
+    emb, rows = shmp_forward_classes(gnn, batch)
+    return emb if rows is None else ops.gather_rows(emb, rows)
+
+
+def shmp_forward_classes(gnn: BaseGNN, batch):
+    """``shmp_forward`` with the embeddings as the pass leaves them: ``(emb, rows)``, ``rows`` None and ``emb`` [B, 64], or
+    (POOL_CLASS_TABLE) ``emb`` one row per pooling class and neighborhood b's embedding ``emb[rows[b]]`` -- for callers whose
+    own work is row-local too (the count head)"""
+    pooled = _shmp_pooled(gnn, batch, fuse_post0=True)
+    return _post_mp(gnn.packed(), pooled), (pooled.rows if isinstance(pooled, _PostMp0) else None)          # :108
 
 
 def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
@@ -892,8 +924,23 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
     # slots' sources remapped to its rows, and the count launch's OWN rows: from their degrees by these coefficients (l = 1), or
     # through these ids (above that)
     src = {}
+    # post_mp.0 can form its operand itself (POOL_POST_FUSED) -- given the partial sums of every layer, see below
+    post_fusable = (nb and fuse_post0 and POOL_POST_FUSED and const_input and GEMM_BF16X6 and "post_nk" in pk and L <= 8
+                    and batch.max_count_rows() <= 33)
+    # the anchor MLP on the classes of anchor operands (acls: the index), the canonical rows as tables per level (ctabs), the
+    # pooled sums and all behind them on the pooling classes (pidx: there the first layer's sums, too, come from the tables)
+    acls = ctabs = pidx = None
+    if (ANCHOR_CLASS_TABLE and DEEP_LAYER_TABLES and L in lev and post_fusable and ANCHOR_POST_FUSED and canon_once
+            and L in (2, 5, 8)):
+        acls = batch.anchor_class_index(L)
+        if CANON_CLASS_TABLES and acls is not None:
+            ctabs = batch.canonical_class_tables(L)
+        if POOL_CLASS_TABLE and acls is not None and pool_tables and batch.max_count_rows() <= ops.class_rows_pool_max_rows():
+            pidx = batch.pool_class_launch_index(L)
     if fpool:
         pbits, pslot, nslots = batch.pool_index()
+        if pidx is not None:
+            nslots = pidx.nslots                       # (the partial arrays hold the representatives' slots only)
     if const_input:
         x0 = {t: pk["pre"][t][1] for t, *_ in groups}
         src_of_slot = (lambda t, s: ("count" if s < 2 else "canonical")) if nb else (lambda t, s: t)
@@ -929,16 +976,6 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
             ops.linear_smallk(feat[r0:r1], wt, b, out=x[r0:r1])               # :231
         X = [x]
     first = len(X) - 1
-    # post_mp.0 can form its operand itself (POOL_POST_FUSED) -- given the partial sums of every layer, see below
-    post_fusable = (nb and fuse_post0 and POOL_POST_FUSED and const_input and GEMM_BF16X6 and "post_nk" in pk and L <= 8
-                    and batch.max_count_rows() <= 33)
-    # the anchor MLP on the classes of anchor operands (acls: the index), the canonical rows as tables per level (ctabs)
-    acls = ctabs = None
-    if (ANCHOR_CLASS_TABLE and DEEP_LAYER_TABLES and L in lev and post_fusable and ANCHOR_POST_FUSED and canon_once
-            and L in (2, 5, 8)):
-        acls = batch.anchor_class_index(L)
-        if CANON_CLASS_TABLES and acls is not None:
-            ctabs = batch.canonical_class_tables(L)
     # emb["canonical"] [B, P] (operand of the anchor MLP): the canonical launches write their column block directly
     # (out2), so no concatenation pass is needed
     canon = torch.empty((B, P), device=dev) if (nb and ctabs is None) else None
@@ -1014,6 +1051,14 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                         src[k] = (lv.vcol, None, lv.cls)
                     if (k + 1) in lev:
                         continue
+                    if pidx is not None:
+                        # no walk: every layer's pooled sums on the representatives of the pooling classes, their rows read
+                        # through the ids at their original positions
+                        assert k == L and first_pool is not None, "pooling classes without the table form of every layer"
+                        walk, first_pool = [first_pool] + [(tbl[j], lev[j].cls, pool_parts[j]) for j in range(2, k + 1)], None
+                        ops.class_rows_pool(walk, batch.count_ptr, r1 - r0, pidx.prep, pidx.rep_ptr, pidx.bits, pidx.slot,
+                                            pidx.nslots)
+                        continue
                     for j in range(2, k):
                         pool = pool + (tbl[j], lev[j].cls, pool_parts[j])
                     if first_pool is not None:
@@ -1065,6 +1110,12 @@ def _shmp_pooled(gnn: BaseGNN, batch, fuse_post0: bool = False):
                 else:
                     a_u, bound_u = canon[:, H:].index_select(0, acls[1]), canon_max.index_select(0, acls[1])
                 anch_tab = ops.gemm_f16x3(a_u, aw16, ab16, act=ops.ACT_LEAKY, slope=0.1, row_scale=bound_u)
+                if pidx is not None:
+                    # one row per pooling class: the representatives' segments, each layer's combined sum in the segment's
+                    # first slot and zeros behind it -- the expressions of the launch below on bit-equal terms
+                    return _PostMp0(ops.pool_post(anch_tab, [pool_parts[l] for l in range(1, L + 1)], pidx.bits, pidx.slot,
+                                                  pidx.rep_ptr, x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1,
+                                                  anch_row=pidx.anch_row), pidx.pcls)
                 return _PostMp0(ops.pool_post(anch_tab, [pool_parts[l] for l in range(1, L + 1)], pbits, pslot, seg_ptr,
                                               x0[groups[0][0]], w0, b0, ops.ACT_LEAKY, 0.1, anch_row=acls[0]))
             return _PostMp0(ops.anchor_pool_post(canon[:, H:], aw16, ab16, canon_max,

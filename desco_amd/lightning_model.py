@@ -302,7 +302,12 @@ class NeighborhoodCountingModel(_LightningLike):
         if self.emb_model.is_wide():
             return self._logits_wide(batch, exp2)
         emb_q = self.get_query_emb()
-        emb_t = self.emb_model(batch)
+        # (gnn_model.POOL_CLASS_TABLE: the embeddings may come one row per pooling class -- the head is row-local, so it runs
+        #  on those rows and the neighborhoods' counts are gathered from its result, ``rows`` [B] the neighborhoods' classes)
+        emb_t, rows = self.emb_model.forward_classes(batch)
+        out = getattr(batch, "out_buf", None) if exp2 else None
+        head_out = out if rows is None else None
+        spread = (lambda r: r) if rows is None else (lambda r: ops.gather_rows(r, rows, out=out))
         hp = self._head_pack()
         from . import gnn_model as GM
         fused_head = (HEAD_FROM_EMB and GM.GEMM_BF16X6 and GM.GEMM_F16X3 and not torch.is_grad_enabled()
@@ -326,16 +331,14 @@ class NeighborhoodCountingModel(_LightningLike):
             # the [B, 256] target half is never written: formed block by block inside the head's launch
             if "w_t_f16" not in hp:
                 hp["w_t_f16"] = ops.split_f16_planes(self.count_model[0].weight[:, :emb_t.shape[1]].contiguous())
-            return ops.count_head_emb(emb_t, hp["w_t_f16"], Qh, hp["w2"], hp["b2"], slope, exp2,
-                                      out=getattr(batch, "out_buf", None) if exp2 else None)
+            return spread(ops.count_head_emb(emb_t, hp["w_t_f16"], Qh, hp["w2"], hp["b2"], slope, exp2, out=head_out))
         if Qh.shape[0] <= 32:
             # (InferencePipeline hands every block a slice of ONE persistent result tensor: no torch.cat per pass)
-            return ops.count_head(T, Qh, hp["w2"], hp["b2"], slope, exp2,
-                                  out=getattr(batch, "out_buf", None) if exp2 else None)
+            return spread(ops.count_head(T, Qh, hp["w2"], hp["b2"], slope, exp2, out=head_out))
         # more than 32 queries (labelled queries of --use_node_feature: 784 for input_dim 2): the head
         # kernel keeps one accumulator per query in registers, so the query axis goes in groups of 32
-        return torch.cat([ops.count_head(T, Qh[q0:q0 + 32], hp["w2"], hp["b2"], slope, exp2)
-                          for q0 in range(0, Qh.shape[0], 32)], dim=1)
+        return spread(torch.cat([ops.count_head(T, Qh[q0:q0 + 32], hp["w2"], hp["b2"], slope, exp2)
+                                 for q0 in range(0, Qh.shape[0], 32)], dim=1))
 
     def graph_to_count(self, batch) -> torch.Tensor:                         # :198-222
         with torch.no_grad():

@@ -835,6 +835,57 @@ def table_rows_pool(table: torch.Tensor, cls: torch.Tensor, num_rows: int, out: 
                        "table_rows_pool")
 
 
+def class_rows_pool_max_rows() -> int:
+    """the most count rows a representative of ``class_rows_pool`` may have (33: three pieces wherever it starts)"""
+    return int(_lib.lib().desco_class_rows_pool_max_rows())
+
+
+def class_rows_pool(layers, count_ptr: torch.Tensor, num_rows: int, rep: torch.Tensor, rep_ptr: torch.Tensor,
+                    bits: torch.Tensor, slot: torch.Tensor, num_slots: int) -> None:
+    """the pooled sums of 1 .. 8 table layers ``(table, ids, pool_part)`` on the representative neighborhoods ``rep`` [U]
+    int64 of ``count_ptr`` instead of the walk over all ``num_rows`` count rows (desco_class_rows_pool_f32): per layer the
+    rows ``table[ids[i]]`` of representative u, i = count_ptr[rep[u]] .. count_ptr[rep[u] + 1] - 1, summed in the walk's
+    order and combined as ``pool_post`` combines the walk's partial rows, ((p0 + p1) + p2).  ``rep_ptr`` [U + 1] int32 is the
+    representatives' compact row pointer and ``bits`` / ``slot`` / ``num_slots`` its pooling index (``pool_index_dev``);
+    ``pool_part`` [num_slots, 64] gets the combined sum in each segment's first slot and zeros in its continuation slots --
+    ``pool_post(..., bits, slot, rep_ptr, ...)`` then forms for row u the operand row of neighborhood rep[u], bit for bit."""
+    n, U = len(layers), rep.numel()
+    assert rep.dtype == torch.int64 and rep.is_contiguous() and rep_ptr.numel() == U + 1 and count_ptr.is_contiguous()
+    for tk, ik, pk_ in layers:
+        assert ik.is_contiguous() and ik.numel() >= num_rows and tk.shape[1] >= 64 and tuple(pk_.shape) == (num_slots, 64)
+    if U == 0:
+        return
+    rows = [_rows(tk, "table") for tk, _, _ in layers]
+    arr = lambda ct, vals: (ct * n)(*vals)
+    with _Timed("class_rows_pool_kernel", 0.0, 4.0 * n * U):
+        _lib.check(_lib.lib().desco_class_rows_pool_f32(
+            n, arr(ctypes.c_void_p, [r[0] for r in rows]), arr(ctypes.c_int64, [r[1] for r in rows]),
+            arr(ctypes.c_int64, [tk.shape[0] for tk, _, _ in layers]),
+            arr(ctypes.c_void_p, [_dev(ik, "ids", torch.int32) for _, ik, _ in layers]),
+            arr(ctypes.c_void_p, [_dev(pk_, "pool_part") for _, _, pk_ in layers]),
+            _dev(count_ptr, "count_ptr", torch.int32), count_ptr.numel() - 1, num_rows, _dev(rep, "rep", torch.int64),
+            _dev(rep_ptr, "rep_ptr", torch.int32), U, _dev(bits, "pool_bits", torch.int32),
+            _dev(slot, "pool_slot", torch.int32), num_slots, _stream()), "class_rows_pool")
+
+
+def gather_rows(src: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b] = src[rows[b]] (desco_gather_rows_f32): ``src`` [U, C] with unit inner stride, ``rows`` [B] int32 in [0, U) --
+    not checked here: the caller range-checks them once where it builds them -- ``out`` [B, C] (optional) likewise"""
+    B, C = rows.numel(), src.shape[1]
+    assert rows.dim() == 1 and rows.is_contiguous() and (B == 0 or src.shape[0] > 0)
+    if out is None:
+        out = torch.empty((B, C), device=src.device, dtype=torch.float32)
+    assert tuple(out.shape) == (B, C)
+    if B == 0:
+        return out
+    sp, lds = _rows(src, "src")
+    op, ldo = _rows(out, "out")
+    with _Timed("gather_rows_kernel", 0.0, 8.0 * B * C + 4.0 * B):
+        _lib.check(_lib.lib().desco_gather_rows_f32(sp, lds, src.shape[0], _dev(rows, "rows", torch.int32), B, C, op, ldo,
+                                                    _stream()), "gather_rows")
+    return out
+
+
 def index_range_check(idx: torch.Tensor, bound: int) -> None:
     """raise unless every entry of the int32 device index lies in [0, bound) (desco_index_range_check_i32; synchronises:
     once per index, never in the pass)"""

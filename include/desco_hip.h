@@ -1433,6 +1433,28 @@ int desco_table_rows_pooln_f32(int num_layers, const float* const* tables, const
                                const int32_t* const* ids, float* const* pool_parts, int64_t num_rows,
                                const uint32_t* pool_bits, const int32_t* pool_slot, desco_stream_t stream);
 int desco_table_rows_pooln_max_layers(void);
+/* The pooled sums of num_layers = 1 .. 8 table layers on one REPRESENTATIVE neighborhood per pooling class (host side:
+ * NeighborhoodBatch.pool_class_index, gnn_model.POOL_CLASS_TABLE) instead of the walk over every count row.  The layer arrays
+ * are HOST arrays as above.  Representative u = neighborhood rep[u] of count_ptr [num_neigh + 1]; its count rows are rows
+ * s .. s + n - 1 of the block's num_rows (s = count_ptr[rep[u]], 1 <= n <= desco_class_rows_pool_max_rows() = 33), read as
+ * tables[k][ids[k][i]] with the ids at their original positions.  Per layer the rows are summed exactly as the walk and
+ * desco_pool_post_bf16x6_f32 sum them for that neighborhood: running sums from 0.f in row order, cut after every row i with
+ * (i & 15) == 15, the pieces combined as ((p0 + p1) + p2) with absent pieces 0.f.  rep_ptr [num_rep + 1] is the compact row
+ * pointer of the representatives (rep_ptr[u + 1] - rep_ptr[u] = n) and pool_bits / pool_slot ITS pooling index
+ * (desco_pool_index_dev on rep_ptr, num_slots slots): pool_parts[k] [num_slots, 64] receives the combined sum in the first
+ * slot of segment u and zeros in its continuation slots, so that desco_pool_post_rows_bf16x6_f32 on (rep_ptr, that index,
+ * pool_parts) forms for row u, bit for bit, the operand row it forms for neighborhood rep[u] from the walk's partial rows.
+ * A representative that breaks the contract writes nothing; ids outside their table read the nearest table row. */
+int desco_class_rows_pool_f32(int num_layers, const float* const* tables, const int64_t* ldts, const int64_t* num_tables,
+                              const int32_t* const* ids, float* const* pool_parts, const int32_t* count_ptr,
+                              int64_t num_neigh, int64_t num_rows, const int64_t* rep, const int32_t* rep_ptr,
+                              int64_t num_rep, const uint32_t* pool_bits, const int32_t* pool_slot, int64_t num_slots,
+                              desco_stream_t stream);
+int desco_class_rows_pool_max_rows(void);
+/* dst[b, 0:ncols] = src[rows[b], 0:ncols] for b < num_dst (rows in [0, num_src); one outside reads the nearest row): the
+ * counts of the pooling classes handed out to their neighborhoods. */
+int desco_gather_rows_f32(const float* src, int64_t lds, int64_t num_src, const int32_t* rows, int64_t num_dst, int ncols,
+                          float* dst, int64_t ldd, desco_stream_t stream);
 /* DESCO_EINVAL when one of idx[0 .. n) (device) lies outside [0, bound); scratch: one device word.  Synchronises the
  * stream: for indices built once per batch, not for the pass. */
 int desco_index_range_check_i32(const int32_t* idx, int64_t n, int64_t bound, int32_t* scratch, desco_stream_t stream);
