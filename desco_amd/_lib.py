@@ -232,6 +232,10 @@ SIGNATURES = {
     "desco_count_head_wide_f32": (c_int, [vp, i64, vp, i64, i32, vp, f32, vp, f32, i32, vp, i64, i64, i32, vp]),
     "desco_gossip_f16_stream": (c_int, [vp, vp, vp, vp, vp, vp]),
     "desco_gossip_fused_f16x3_f32": (c_int, [vp, vp, vp, i64, i32] + [vp] * 14 + [f32, vp, vp, vp, vp]),
+    "desco_gossip_plan_words": (i64, [i64, i32]),
+    "desco_gossip_plan": (c_int, [vp, vp, i64, vp, vp, vp]),
+    "desco_gossip_plan_host": (c_int, [vp, vp, i64, vp, vp]),
+    "desco_gossip_planned_f16x3_f32": (c_int, [vp, vp, i64, i32, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp]),
     "desco_csr_gather_sum_add_f32": (c_int, [vp, i64, vp, vp, i64, vp, i64, vp, i64, vp]),
     "desco_shmp_bwd_dx_f32": (c_int, [vp, i64, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, i64, vp, f32, vp, vp]),
     "desco_add_rows_f32": (c_int, [vp, i64, vp, i64, i64, i32, vp]),

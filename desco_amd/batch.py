@@ -945,7 +945,27 @@ class GossipBatch:
         self.x = None if x is None else x.to(device).float().contiguous()
         self.y = None if y is None else y.to(device)
         self._tile_perm = None
+        self._plans = {}
+        self._long_row_share = None
         self._work_queue = None
+
+    def gossip_plan(self, tiled: bool = True):
+        """Plan of the planned fused gossip kernel (ops.gossip_plan) in the kernel's group order with (``tiled``) or
+        without the tile order: a function of the CSR alone, computed on first use and kept."""
+        if tiled not in self._plans:
+            from . import ops
+            self._plans[tiled] = ops.gossip_plan(self.rowptr, self.col, self.num_nodes,
+                                                 self.tile_perm if tiled else None)
+        return self._plans[tiled]
+
+    @property
+    def long_row_share(self) -> float:
+        """share of the nodes with more than four neighbours (from the host CSR; what gnn_model.gossip_takes_plan
+        routes the fused gossip launch by)"""
+        if self._long_row_share is None:
+            deg = np.diff(np.asarray(self.graphs.rowptr))
+            self._long_row_share = float((deg > 4).mean()) if deg.size else 0.0
+        return self._long_row_share
 
     @property
     def work_queue(self):

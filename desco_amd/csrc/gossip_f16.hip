@@ -40,6 +40,7 @@
 //     query (the comment above GF16_REQ; tools/isa_waits.py, tests/test_gossip_isa_waits.py).
 #include "tu_no_packed_f32_begin.hpp"
 #include "common_device.hpp"
+#include <type_traits>
 
 namespace desco {
 
@@ -75,10 +76,52 @@ struct Args {
   const uint8_t* tperm;     // [tiles*128] phase-1 slot -> row of the tile, or null
   unsigned long long* queue;  // {next ticket, finished blocks}: zero before the first launch that uses it, left zero
   unsigned grid_blocks;     // gridDim.x (set by the launcher)
+  static constexpr bool planned = false;
+};
+
+// Operands of the planned kernel (gossip_planned_f16_kernel): the per-batch plan (desco_gossip_plan) instead of
+// rowptr / tile order, and the per-weight-version operands packed -- nine pointers instead of twenty-two.
+constexpr int PLAN_REC = 8;        // int32 words per node slot: row, deg, lt | valid << 31, four neighbour rows, e0
+struct PArgs {
+  const float4* scal;       // [N*Q] (a0, b0, a1, x);  N * Q * 16 < 2^32: a record's byte offset fits 32 bits
+  const int32_t* col;       // (read for neighbours beyond the fourth only)
+  const int32_t* plan;      // [groups][16][PLAN_REC] records, then [groups] largest degree of the group
+  int64_t num_nodes;
+  int Q;
+  const float* g1;          // [Q]
+  const float* pzz;         // [Q,192]: p_q | z_q | zp_q
+  const float* cst;         // [900]: u, d1, tp, b3 (64 each), b5, w7 (256 each), r, t (64 each) = the LDS image; winv[4]
+  const short* wstream;
+  float b7;
+  float* out;               // [N,Q]
+  unsigned long long* queue;
+  unsigned grid_blocks;
+  static constexpr bool planned = true;
 };
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// Buffer descriptors of the planned kernel's arrays (none for the other kernel): a buffer load takes the array in four
+// SGPRs, a 32-bit lane offset in one VGPR and a scalar offset, and checks the lane offset against the array's size.
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+__device__ __forceinline__ rsrc_t make_rsrc(const void* p, const uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+template <bool PLANNED>
+struct PlanRsrc {
+  template <class A> __device__ __forceinline__ PlanRsrc(const A&, int64_t) {}
+};
+template <>
+struct PlanRsrc<true> {
+  rsrc_t scal, pzz, plan, out;
+  template <class A>
+  __device__ __forceinline__ PlanRsrc(const A& g, const int64_t groups)
+      : scal(make_rsrc(g.scal, (uint32_t)(g.num_nodes * g.Q * 16))),
+        pzz(make_rsrc(g.pzz, (uint32_t)g.Q * 768u)),
+        plan(make_rsrc(g.plan, (uint32_t)(groups * (16 * 8 + 1) * 4))),
+        out(make_rsrc(g.out, (uint32_t)(g.num_nodes * g.Q * 4))) {}
+};
 
 // max / sum over the four lanes (r, r+16, r+32, r+48) that share a node in the MFMA layouts
 __device__ __forceinline__ float quarters_max(const float f) {      // f >= 0
@@ -244,7 +287,12 @@ constexpr int WCST = 896;                   // u, d1, tp, b3 (64 each), b5, w7 (
 constexpr size_t LDS_WAVE = (size_t)9 * WBLK * 2 + (size_t)WCST * 4 + (size_t)8 * (WCOLS * 16 + 64) * 4;
 static_assert(LDS_WAVE <= 160 * 1024, "gossip_f16: LDS budget exceeded");
 
-__global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t num_groups) {
+// One body for both kernels: A = Args (gossip_fused_f16_kernel: rowptr / col / tile order read per work unit) or PArgs
+// (gossip_planned_f16_kernel: the unit's addressing read from the plan, 32-bit record offsets against scalar bases).
+// Everything between the first and the last MFMA of a query is the same text for both.
+template <class A>
+__device__ __forceinline__ void gossip_f16_body(const A& g, const int64_t num_groups) {
+  constexpr bool PLAN = A::planned;
   extern __shared__ __attribute__((aligned(16))) uint4 gf_lds[];
   short* WB = reinterpret_cast<short*>(gf_lds);                       // nine resident weight blocks
   float* cst = reinterpret_cast<float*>(WB + 9 * WBLK);
@@ -259,20 +307,30 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
   {
     const uint4* src = reinterpret_cast<const uint4*>(g.wstream);
     for (int i = tid; i < 9 * WBLK * 2 / 16; i += GNT) gf_lds[i] = src[i];
-    for (int i = tid; i < 64; i += GNT) {
-      cst[i] = g.u[i];
-      cst[64 + i] = g.d1[i];
-      cst[128 + i] = g.tp[i];
-      cst[192 + i] = g.b3[i];
-      cst[768 + i] = g.r[i];
-      cst[832 + i] = g.t[i];
-    }
-    for (int i = tid; i < 256; i += GNT) {
-      cst[256 + i] = g.b5[i];
-      cst[512 + i] = g.w7[i];
+    if constexpr (PLAN) {                              // the constants arrive as the LDS image: one linear copy
+      const uint4* csrc = reinterpret_cast<const uint4*>(g.cst);
+      for (int i = tid; i < WCST / 4; i += GNT) gf_lds[9 * WBLK * 2 / 16 + i] = csrc[i];
+    } else {
+      for (int i = tid; i < 64; i += GNT) {
+        cst[i] = g.u[i];
+        cst[64 + i] = g.d1[i];
+        cst[128 + i] = g.tp[i];
+        cst[192 + i] = g.b3[i];
+        cst[768 + i] = g.r[i];
+        cst[832 + i] = g.t[i];
+      }
+      for (int i = tid; i < 256; i += GNT) {
+        cst[256 + i] = g.b5[i];
+        cst[512 + i] = g.w7[i];
+      }
     }
   }
-  const float winv1 = g.winv[0], winvp = g.winv[1], winv3 = g.winv[2], winv5 = g.winv[3];
+  float winv1, winvp, winv3, winv5;
+  if constexpr (PLAN) {
+    winv1 = g.cst[WCST], winvp = g.cst[WCST + 1], winv3 = g.cst[WCST + 2], winv5 = g.cst[WCST + 3];
+  } else {
+    winv1 = g.winv[0], winvp = g.winv[1], winv3 = g.winv[2], winv5 = g.winv[3];
+  }
   __syncthreads();                                     // the only barrier: weights and constants are in place
   // LDS byte addresses of this lane's fragment chunk of k step 0 / 1 in weight block 0, tile 0, hi plane
   const uint32_t wa0 = (uint32_t)(uintptr_t)(WB + wrow * 64 + (((0 + q4) ^ wswz) << 3));
@@ -299,40 +357,96 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
   // this lane's 16 features of the standard-order operands (hh, h1): 8 q4 .. +7 and 32 + 8 q4 .. +7
   const int fa = 8 * q4, fb = 32 + 8 * q4;
 #define GW_V4(p_) (*reinterpret_cast<const f32x4*>(p_))
+  // Planned kernel: every per-query load is (scalar base that moves with q) + (32-bit lane offset fixed for the unit or
+  // the kernel) + immediate -- a buffer load, no vector instruction for the address.
+#define GP_LD4(T_, rs_, voff_, soff_)                                                          \
+  __builtin_bit_cast(T_, __builtin_amdgcn_raw_buffer_load_b128(rs_, (int)(voff_), (int)(soff_), 0))
+#define GP_LD1(rs_, voff_, soff_) __builtin_amdgcn_raw_buffer_load_b32(rs_, (int)(voff_), (int)(soff_), 0)
+  const PlanRsrc<PLAN> rs(g, num_groups);
+  const uint32_t qs16 = (uint32_t)Q * 16u;             // bytes between the records of two nodes
+  const uint32_t pzo = 32u * (uint32_t)q4;             // this lane's p / z quads: bytes 4 fa into a [192] row
+  const uint32_t zpo = 4u * (uint32_t)lane;
+  // (the planned kernel is one register short of its budget with `lane` kept beside zpo: its lane tests read zpo)
+#define GW_LANE_BELOW(n_) (PLAN ? zpo < 4u * (n_) : lane < (n_))
+  // The plan record of a unit's group travels one unit ahead: a lane fetches words 2 q4, 2 q4 + 1 of its node's record
+  // (the wave reads the group's 512 bytes in one coalesced load) and the four quarters exchange them at the top of the
+  // unit; the group's largest degree comes beside it.
+  u32x2 pc = {0u, 0u};
+  int gm = 0;
+  const uint32_t prec = 4u * (uint32_t)(wrow * PLAN_REC + 2 * q4);
+#define GP_REQ(u_)                                                                             \
+  if constexpr (PLAN) {                                                                        \
+    const uint32_t un_ = (uint32_t)(u_);                                                       \
+    const uint32_t gn_ = un_ < (uint32_t)nunits ? un_ / (uint32_t)QC : 0u;                     \
+    pc = __builtin_amdgcn_raw_buffer_load_b64(rs.plan, (int)prec, (int)(gn_ * (64u * PLAN_REC)), 0);  \
+    gm = g.plan[(size_t)num_groups * (16 * PLAN_REC) + gn_];                                   \
+  }
+#define GW_TICKET()                                                                            \
+  (PLAN ? (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)tk)                           \
+        : ((int64_t)__builtin_amdgcn_readfirstlane((int)(tk & 0xffffffffull)) |                \
+           ((int64_t)__builtin_amdgcn_readfirstlane((int)((unsigned long long)tk >> 32)) << 32)))
+  GP_REQ(unit)
   while (unit < nunits) {
     // ticket of the next unit: in flight over this one
-    unsigned long long tk = 0;
-    if (lane == 0) tk = nwaves + atomicAdd(g.queue, 1ull);
-    const int64_t grp = unit / QC;
+    // (planned: fewer than 2^32 tickets under the entry's bound -- the ticket is the low word, one register)
+    typename std::conditional<PLAN, unsigned, unsigned long long>::type tk = 0;
+    if (GW_LANE_BELOW(1)) {
+      if constexpr (PLAN) tk = (unsigned)nwaves + atomicAdd(reinterpret_cast<unsigned*>(g.queue), 1u);
+      else tk = nwaves + atomicAdd(g.queue, 1ull);
+    }
+    int64_t nunit = 0;
+    int64_t grp;
+    if constexpr (PLAN) grp = (int64_t)((uint32_t)unit / (uint32_t)QC);     // (units < 2^28 under the entry's bound)
+    else grp = unit / QC;
     const int qa = (int)(unit - grp * QC) * WQ;
     const int qb = qa + WQ < Q ? qa + WQ : Q;
-    // this lane's node.  With a tile order (desco_gossip_tile_order: the rows of a 128-node tile sorted by degree, pairs
-    // dealt to eight waves in snake order) group gi of the tile takes sorted ranks 16 gi .. 16 gi + 15 -- rank t sits
-    // at slot 16 w + 2 (t >> 4) + (t & 1) with w = its pair's snake position -- so the 16 nodes of a wave have similar
-    // degrees and the neighbour loop below (as many steps as the group's largest degree) wastes few lanes.
-    int64_t row_raw = grp * 16 + wrow;
-    if (g.tperm) {
-      const int gi = (int)(grp & 7), sl = wrow >> 1;
-      const int64_t t0 = (grp >> 3) * GT;
-      row_raw = t0 + g.tperm[t0 + 16 * ((gi & 1) ? 7 - sl : sl) + 2 * gi + (wrow & 1)];
-    }
-    const bool valid = row_raw < g.num_nodes;
-    const int64_t row = valid ? row_raw : g.num_nodes - 1;
-    const int e0 = g.rowptr[row];
-    const int deg = valid ? g.rowptr[row + 1] - e0 : 0;
-    int maxdeg = deg;
-    for (int m = 1; m < 16; m <<= 1) {
-      const int o = __shfl_xor(maxdeg, m, 64);
-      maxdeg = maxdeg > o ? maxdeg : o;
-    }
-    maxdeg = __builtin_amdgcn_readfirstlane(maxdeg);
-    const int nst = maxdeg < WCOLS ? maxdeg : WCOLS;
-    for (int i = q4; i < nst; i += 4)
-      if (i < deg) ecolw[i * 16 + wrow] = g.col[e0 + i];
-    // bit i: neighbour i of this node has the smaller id (gate g1 instead of 1 - g1); the same for every query
+    bool valid;
+    int64_t row;
+    int e0, deg, maxdeg;
     uint32_t lt = 0;
-    for (int i = 0; i < nst; ++i)
-      if (i < deg && ecolw[i * 16 + wrow] < (int)row) lt |= 1u << i;
+    uint32_t o_s = 0, o_0 = 0, o_1 = 0, o_2 = 0, o_3 = 0;      // planned: byte offsets of the own / neighbour records
+    float ga0 = 0.f, ga1 = 0.f, ga2 = 0.f, ga3 = 0.f;          // planned: gate of neighbour i = ga_i gq + max(-ga_i, 0)
+    if constexpr (PLAN) {
+      int w[PLAN_REC];
+#pragma unroll
+      for (int k = 0; k < PLAN_REC; ++k) w[k] = __shfl((int)pc[k & 1], wrow + 16 * (k >> 1), 64);
+      row = 0, deg = 0, e0 = 0;                          // (read where they are needed: the loop beyond four neighbours)
+      lt = (uint32_t)w[2] & 0x7fffu;
+      valid = w[2] >= 0;
+      maxdeg = __builtin_amdgcn_readfirstlane(gm);
+      o_s = (uint32_t)w[0] * qs16;
+      o_0 = (uint32_t)w[3] * qs16; o_1 = (uint32_t)w[4] * qs16; o_2 = (uint32_t)w[5] * qs16; o_3 = (uint32_t)w[6] * qs16;
+#define GP_GA(i_) ((i_) < w[1] ? (((lt >> (i_)) & 1u) ? 1.f : -1.f) : 0.f)
+      ga0 = GP_GA(0); ga1 = GP_GA(1); ga2 = GP_GA(2); ga3 = GP_GA(3);
+#undef GP_GA
+    } else {
+      // this lane's node.  With a tile order (desco_gossip_tile_order: the rows of a 128-node tile sorted by degree, pairs
+      // dealt to eight waves in snake order) group gi of the tile takes sorted ranks 16 gi .. 16 gi + 15 -- rank t sits
+      // at slot 16 w + 2 (t >> 4) + (t & 1) with w = its pair's snake position -- so the 16 nodes of a wave have similar
+      // degrees and the neighbour loop below (as many steps as the group's largest degree) wastes few lanes.
+      int64_t row_raw = grp * 16 + wrow;
+      if (g.tperm) {
+        const int gi = (int)(grp & 7), sl = wrow >> 1;
+        const int64_t t0 = (grp >> 3) * GT;
+        row_raw = t0 + g.tperm[t0 + 16 * ((gi & 1) ? 7 - sl : sl) + 2 * gi + (wrow & 1)];
+      }
+      valid = row_raw < g.num_nodes;
+      row = valid ? row_raw : g.num_nodes - 1;
+      e0 = g.rowptr[row];
+      deg = valid ? g.rowptr[row + 1] - e0 : 0;
+      maxdeg = deg;
+      for (int m = 1; m < 16; m <<= 1) {
+        const int o = __shfl_xor(maxdeg, m, 64);
+        maxdeg = maxdeg > o ? maxdeg : o;
+      }
+      maxdeg = __builtin_amdgcn_readfirstlane(maxdeg);
+      const int nst = maxdeg < WCOLS ? maxdeg : WCOLS;
+      for (int i = q4; i < nst; i += 4)
+        if (i < deg) ecolw[i * 16 + wrow] = g.col[e0 + i];
+      // bit i: neighbour i of this node has the smaller id (gate g1 instead of 1 - g1); the same for every query
+      for (int i = 0; i < nst; ++i)
+        if (i < deg && ecolw[i * 16 + wrow] < (int)row) lt |= 1u << i;
+    }
 
     // Everything query q needs from memory travels one query ahead: issued in front of the GEMM chain of query q - 1
     // (in front of the loop for the first one), consumed at the top of query q.
@@ -344,17 +458,32 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
 #define GW_PREFETCH(q_)                                                                        \
   {                                                                                            \
     const int qn_ = (q_);                                                                      \
-    nzp = g.zp[qn_ * 64 + lane];                                                               \
-    ngq = g.g1[qn_];                                                                           \
-    nsi = g.scal[row * Q + qn_];                                                               \
-    np0 = GW_V4(g.p + qn_ * 64 + fa); np1 = GW_V4(g.p + qn_ * 64 + fa + 4);                    \
-    np2 = GW_V4(g.p + qn_ * 64 + fb); np3 = GW_V4(g.p + qn_ * 64 + fb + 4);                    \
-    nz0 = GW_V4(g.z + qn_ * 64 + fa); nz1 = GW_V4(g.z + qn_ * 64 + fa + 4);                    \
-    nz2 = GW_V4(g.z + qn_ * 64 + fb); nz3 = GW_V4(g.z + qn_ * 64 + fb + 4);                    \
-    if (maxdeg > 0) nr0 = GW_NREC(0);                                                          \
-    if (maxdeg > 1) nr1 = GW_NREC(1);                                                          \
-    if (maxdeg > 2) nr2 = GW_NREC(2);                                                          \
-    if (maxdeg > 3) nr3 = GW_NREC(3);                                                          \
+    if constexpr (PLAN) {                                                                      \
+      ngq = g.g1[qn_];                                                                         \
+      const uint32_t tq_ = (uint32_t)qn_ * 768u, sq_ = (uint32_t)qn_ * 16u;                    \
+      nzp = __uint_as_float(GP_LD1(rs.pzz, zpo, tq_ + 512u));                                  \
+      nsi = GP_LD4(float4, rs.scal, o_s, sq_);                                                 \
+      np0 = GP_LD4(f32x4, rs.pzz, pzo, tq_);        np1 = GP_LD4(f32x4, rs.pzz, pzo, tq_ + 16u);  \
+      np2 = GP_LD4(f32x4, rs.pzz, pzo, tq_ + 128u); np3 = GP_LD4(f32x4, rs.pzz, pzo, tq_ + 144u); \
+      nz0 = GP_LD4(f32x4, rs.pzz, pzo, tq_ + 256u); nz1 = GP_LD4(f32x4, rs.pzz, pzo, tq_ + 272u); \
+      nz2 = GP_LD4(f32x4, rs.pzz, pzo, tq_ + 384u); nz3 = GP_LD4(f32x4, rs.pzz, pzo, tq_ + 400u); \
+      if (maxdeg > 0) nr0 = GP_LD4(float4, rs.scal, o_0, sq_);                                 \
+      if (maxdeg > 1) nr1 = GP_LD4(float4, rs.scal, o_1, sq_);                                 \
+      if (maxdeg > 2) nr2 = GP_LD4(float4, rs.scal, o_2, sq_);                                 \
+      if (maxdeg > 3) nr3 = GP_LD4(float4, rs.scal, o_3, sq_);                                 \
+    } else {                                                                                   \
+      nzp = g.zp[qn_ * 64 + lane];                                                             \
+      ngq = g.g1[qn_];                                                                         \
+      nsi = g.scal[row * Q + qn_];                                                             \
+      np0 = GW_V4(g.p + qn_ * 64 + fa); np1 = GW_V4(g.p + qn_ * 64 + fa + 4);                  \
+      np2 = GW_V4(g.p + qn_ * 64 + fb); np3 = GW_V4(g.p + qn_ * 64 + fb + 4);                  \
+      nz0 = GW_V4(g.z + qn_ * 64 + fa); nz1 = GW_V4(g.z + qn_ * 64 + fa + 4);                  \
+      nz2 = GW_V4(g.z + qn_ * 64 + fb); nz3 = GW_V4(g.z + qn_ * 64 + fb + 4);                  \
+      if (maxdeg > 0) nr0 = GW_NREC(0);                                                        \
+      if (maxdeg > 1) nr1 = GW_NREC(1);                                                        \
+      if (maxdeg > 2) nr2 = GW_NREC(2);                                                        \
+      if (maxdeg > 3) nr3 = GW_NREC(3);                                                        \
+    }                                                                                          \
   }
     GW_PREFETCH(qa)
 
@@ -362,7 +491,10 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
       // zp_q: one float per lane into this wave's row, read back as quads in block 3 (same wave, same in-order queue)
       asm volatile("ds_write_b32 %0, %1" : : "v"(zpl), "v"(nzp));
       const float gq = ngq;
-      const float4 si = nsi;                           // (a0, b0, a1, x)
+      float4 si = nsi;                                 // (a0, b0, a1, x)
+      // (planned: the record is taken here, where the top of the query waits for it anyway; without this the compiler
+      // counts si.z as still in flight at the first epilogue and drains the next query's operands there, vmcnt(0))
+      if constexpr (PLAN) asm volatile("" : "+v"(si.x), "+v"(si.y), "+v"(si.z), "+v"(si.w));
       f32x4 acc0, acc1, acc2, acc3;
       Frag XH, X1;
       float s_a;
@@ -383,20 +515,47 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
     h3 = fma4(g_, GW_H1(rec_, 3), h3);                                                         \
   }
 #define GW_GATE(i_) ((i_) < deg ? (((lt >> (i_)) & 1u) ? gq : 1.f - gq) : 0.f)
-        if (maxdeg > 0) GW_ADD(c0, GW_GATE(0))
-        if (maxdeg > 1) GW_ADD(c1, GW_GATE(1))
-        if (maxdeg > 2) GW_ADD(c2, GW_GATE(2))
-        if (maxdeg > 3) GW_ADD(c3, GW_GATE(3))
+// (planned: ga_i in {1, -1, 0}; 1 gq + 0 = gq, -1 gq + 1 = 1 - gq with its one rounding, 0 gq + 0 = 0: the same gates
+// as the selects of GW_GATE for every FINITE gq -- the gates are sigmoids.  For gq = NaN or Inf an absent neighbour's
+// gate is NaN here and 0 there; the present neighbours' gates, and with them the node's result, are NaN in both.)
+#define GP_GATE(i_) (PLAN ? __builtin_fmaf(ga##i_, gq, __builtin_fmaxf(-ga##i_, 0.f)) : GW_GATE(i_))
+        if (maxdeg > 0) GW_ADD(c0, GP_GATE(0))
+        if (maxdeg > 1) GW_ADD(c1, GP_GATE(1))
+        if (maxdeg > 2) GW_ADD(c2, GP_GATE(2))
+        if (maxdeg > 3) GW_ADD(c3, GP_GATE(3))
+#undef GP_GATE
+        if constexpr (PLAN) {
+          // (row, deg and e0 are needed beyond the fourth neighbour only: read again from the record there, from L2,
+          // instead of held in registers through every query chain)
+          if (maxdeg > 4) {
+            const uint32_t rec_ = (uint32_t)grp * (64u * PLAN_REC), slot_ = 4u * PLAN_REC * (uint32_t)wrow;
+            row = (int)GP_LD1(rs.plan, slot_, rec_);
+            deg = (int)GP_LD1(rs.plan, slot_, rec_ + 4u);
+            e0 = (int)GP_LD1(rs.plan, slot_, rec_ + 28u);
+          }
+        }
         for (int i = 4; i < maxdeg; i += 4) {          // beyond the prefetched four: four records in flight per step
           int j0 = (int)row, j1 = j0, j2 = j0, j3 = j0;
-#define GW_COL(j_, k_) if (i + (k_) < deg) j_ = i + (k_) < WCOLS ? ecolw[(i + (k_)) * 16 + wrow] : g.col[e0 + i + (k_)];
+// (planned: no staged columns -- the plan holds the first four neighbours, the others come from col)
+#define GW_COL(j_, k_)                                                                         \
+  if (i + (k_) < deg) j_ = (!PLAN && i + (k_) < WCOLS) ? ecolw[(i + (k_)) * 16 + wrow] : g.col[e0 + i + (k_)];
           GW_COL(j0, 0) GW_COL(j1, 1) GW_COL(j2, 2) GW_COL(j3, 3)
 #undef GW_COL
-          const float4 a0 = g.scal[(int64_t)j0 * Q + q];
-          float4 a1 = a0, a2 = a0, a3 = a0;
-          if (i + 1 < maxdeg) a1 = g.scal[(int64_t)j1 * Q + q];
-          if (i + 2 < maxdeg) a2 = g.scal[(int64_t)j2 * Q + q];
-          if (i + 3 < maxdeg) a3 = g.scal[(int64_t)j3 * Q + q];
+          float4 a0, a1, a2, a3;
+          if constexpr (PLAN) {
+            const uint32_t sq_ = (uint32_t)q * 16u;
+            a0 = GP_LD4(float4, rs.scal, (uint32_t)j0 * qs16, sq_);
+            a1 = a2 = a3 = a0;
+            if (i + 1 < maxdeg) a1 = GP_LD4(float4, rs.scal, (uint32_t)j1 * qs16, sq_);
+            if (i + 2 < maxdeg) a2 = GP_LD4(float4, rs.scal, (uint32_t)j2 * qs16, sq_);
+            if (i + 3 < maxdeg) a3 = GP_LD4(float4, rs.scal, (uint32_t)j3 * qs16, sq_);
+          } else {
+            a0 = g.scal[(int64_t)j0 * Q + q];
+            a1 = a2 = a3 = a0;
+            if (i + 1 < maxdeg) a1 = g.scal[(int64_t)j1 * Q + q];
+            if (i + 2 < maxdeg) a2 = g.scal[(int64_t)j2 * Q + q];
+            if (i + 3 < maxdeg) a3 = g.scal[(int64_t)j3 * Q + q];
+          }
 #define GW_GT(j_, k_) (i + (k_) < deg ? ((j_) < (int)row ? gq : 1.f - gq) : 0.f)
           GW_ADD(a0, GW_GT(j0, 0))
           if (i + 1 < maxdeg) GW_ADD(a1, GW_GT(j1, 1))
@@ -413,6 +572,14 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
         s_a = f16_scale_for(m);
         make_frag(h0, h1, h2, h3, s_a, XH);
         make_frag(s0, s1, s2, s3, s_a, X1);
+      }
+      if constexpr (PLAN) {
+        // The next unit's plan record, requested in front of EVERY query chain of this unit (the same 8 bytes per lane
+        // again, from L2): the ticket drawn at the top of the unit returned in front of the first query's operands, and
+        // as a request of the last query only it sat on a path of its own, where the compiler copied the loaded
+        // registers at once and waited for them in front of the chain.
+        nunit = GW_TICKET();
+        GP_REQ(nunit)
       }
       if (q + 1 < qb) GW_PREFETCH(q + 1)
       Frag XC;
@@ -477,18 +644,43 @@ __global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t n
 #undef GW_HEAD
 #undef GW_HEAD1
       const float part = quarters_sum((hp[0] + hp[1]) + (hp[2] + hp[3]));
-      if (lane < 16 && valid) g.out[row * Q + q] = part + g.b7 + si.w;
+      if (GW_LANE_BELOW(16) && valid) {
+        if constexpr (PLAN)
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(part + g.b7 + si.w), rs.out, (int)(o_s >> 2), q * 4, 0);
+        else g.out[row * Q + q] = part + g.b7 + si.w;
+      }
     }
-    unit = (int64_t)__builtin_amdgcn_readfirstlane((int)(tk & 0xffffffffull)) |
-           ((int64_t)__builtin_amdgcn_readfirstlane((int)(tk >> 32)) << 32);
+    if constexpr (!PLAN) nunit = GW_TICKET();
+    unit = nunit;
   }
+#undef GW_TICKET
+#undef GP_REQ
+#undef GP_LD4
+#undef GP_LD1
 #undef GW_PREFETCH
 #undef GW_NREC
 #undef GW_V4
-  if (lane == 0 && atomicAdd(g.queue + 1, 1ull) == nwaves - 1) {        // last wave out: leave the queue clean
+  // (planned: the lane id formed again here -- as asm, or the compiler merges it with the one of the kernel's head and
+  // keeps that in a register through the loop, the one register the kernel does not have)
+  bool first_lane = lane == 0;
+  if constexpr (PLAN) {
+    uint32_t l_;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l_));
+    first_lane = l_ == 0u;
+  }
+  if (first_lane && atomicAdd(g.queue + 1, 1ull) == nwaves - 1) {        // last wave out: leave the queue clean
     g.queue[0] = 0;
     g.queue[1] = 0;
   }
+#undef GW_LANE_BELOW
+}
+
+__global__ __launch_bounds__(GNT) void gossip_fused_f16_kernel(Args g, int64_t num_groups) {
+  gossip_f16_body(g, num_groups);
+}
+// (tools/isa_waits.py picks a kernel by a substring of its name: this one must not contain the other's)
+__global__ __launch_bounds__(GNT) void gossip_planned_f16_kernel(PArgs g, int64_t num_groups) {
+  gossip_f16_body(g, num_groups);
 }
 
 // The weight stream: block b of the nine 64 x 64 blocks (W1[:, 0:64], W1[:, 64:128], Wp[:, 0:64], Wp[:, 64:128], W3,
@@ -515,10 +707,100 @@ __global__ __launch_bounds__(256) void gossip_f16_stream_kernel(const short* __r
   stream[b * WBLK + WPL + dst] = src[(int64_t)rows * ld + s];       // lo plane
 }
 
+// The plan of a batch (desco_gossip_plan): what a work unit of the planned kernel needs to know of its group's 16 node
+// slots, a function of the CSR (and the tile order) alone.  Slot s of group gr is the node the unplanned kernel's lane
+// wrow = s of that group works on; an empty slot (a ragged last group or tile) takes the last row, degree 0, and the
+// `empty` bit.  One routine for the device kernel and the host twin.
+__host__ __device__ inline int64_t plan_slot_row(const int64_t gr, const int s, const uint8_t* tperm) {
+  if (!tperm) return gr * 16 + s;
+  const int gi = (int)(gr & 7), sl = s >> 1;
+  const int64_t t0 = (gr >> 3) * GT;
+  return t0 + tperm[t0 + 16 * ((gi & 1) ? 7 - sl : sl) + 2 * gi + (s & 1)];
+}
+__host__ __device__ inline void plan_slot(const int32_t* rowptr, const int32_t* col, const int64_t num_nodes,
+                                          const uint8_t* tperm, const int64_t gr, const int s, int32_t* rec) {
+  const int64_t row_raw = plan_slot_row(gr, s, tperm);
+  const bool valid = row_raw < num_nodes;
+  const int32_t row = (int32_t)(valid ? row_raw : num_nodes - 1);
+  const int32_t e0 = rowptr[row];
+  const int32_t deg = valid ? rowptr[row + 1] - e0 : 0;
+  uint32_t lt = valid ? 0u : 0x80000000u;
+  for (int i = 0; i < deg && i < WCOLS; ++i)
+    if (col[e0 + i] < row) lt |= 1u << i;
+  rec[0] = row;
+  rec[1] = deg;
+  rec[2] = (int32_t)lt;
+  for (int i = 0; i < 4; ++i) rec[3 + i] = i < deg ? col[e0 + i] : row;
+  rec[7] = e0;
+}
+// one thread per node slot; the 16 slots of a group are 16 neighbouring lanes
+__global__ __launch_bounds__(256) void gossip_plan_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                          const int64_t num_nodes, const uint8_t* __restrict__ tperm,
+                                                          const int64_t groups, int32_t* __restrict__ plan) {
+  const int64_t slot = (int64_t)__builtin_amdgcn_workgroup_id_x() * 256 + __builtin_amdgcn_workitem_id_x();
+  const bool live = slot < groups * 16;
+  int32_t rec[PLAN_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (live) plan_slot(rowptr, col, num_nodes, tperm, slot >> 4, (int)(slot & 15), rec);
+  int maxdeg = rec[1];
+  for (int m = 1; m < 16; m <<= 1) {
+    const int o = __shfl_xor(maxdeg, m, 64);
+    maxdeg = maxdeg > o ? maxdeg : o;
+  }
+  if (!live) return;
+  int4* dst = reinterpret_cast<int4*>(plan + slot * PLAN_REC);
+  dst[0] = make_int4(rec[0], rec[1], rec[2], rec[3]);
+  dst[1] = make_int4(rec[4], rec[5], rec[6], rec[7]);
+  if ((slot & 15) == 0) plan[groups * (16 * PLAN_REC) + (slot >> 4)] = maxdeg;
+}
+
 }  // namespace gf16
 }  // namespace desco
 
 using namespace desco;
+
+namespace {
+// groups of 16 node slots: with a tile order the eighths of whole 128-node tiles
+inline int64_t gossip_groups(const int64_t num_nodes, const bool tiled) {
+  return tiled ? (num_nodes + gf16::GT - 1) / gf16::GT * 8 : (num_nodes + 15) / 16;
+}
+}  // namespace
+
+extern "C" int64_t desco_gossip_plan_words(int64_t num_nodes, int tiled) {
+  if (num_nodes < 0) return -1;
+  return gossip_groups(num_nodes, tiled != 0) * (16 * gf16::PLAN_REC + 1);
+}
+
+extern "C" int desco_gossip_plan(const int32_t* rowptr, const int32_t* col, int64_t num_nodes, const uint8_t* tile_perm,
+                                 int32_t* plan, desco_stream_t stream) {
+  using namespace gf16;
+  if (num_nodes == 0) return 0;
+  // (col may be null where the batch has no edge: it is read for rows of degree > 0 only)
+  if (!rowptr || !plan || num_nodes < 0 || num_nodes > INT32_MAX || mis16(plan))
+    return fail(DESCO_EINVAL, "desco_gossip_plan: bad argument");
+  const int64_t groups = gossip_groups(num_nodes, tile_perm != nullptr);
+  hipLaunchKernelGGL(gossip_plan_kernel, dim3((unsigned)((groups * 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     rowptr, col, num_nodes, tile_perm, groups, plan);
+  return launch_status("desco_gossip_plan");
+}
+
+extern "C" int desco_gossip_plan_host(const int32_t* rowptr, const int32_t* col, int64_t num_nodes,
+                                      const uint8_t* tile_perm, int32_t* plan) {
+  using namespace gf16;
+  if (num_nodes == 0) return 0;
+  if (!rowptr || !plan || num_nodes < 0 || num_nodes > INT32_MAX)
+    return fail(DESCO_EINVAL, "desco_gossip_plan_host: bad argument");
+  const int64_t groups = gossip_groups(num_nodes, tile_perm != nullptr);
+  for (int64_t gr = 0; gr < groups; ++gr) {
+    int32_t maxdeg = 0;
+    for (int s = 0; s < 16; ++s) {
+      int32_t* rec = plan + (gr * 16 + s) * PLAN_REC;
+      plan_slot(rowptr, col, num_nodes, tile_perm, gr, s, rec);
+      maxdeg = rec[1] > maxdeg ? rec[1] : maxdeg;
+    }
+    plan[groups * (16 * PLAN_REC) + gr] = maxdeg;
+  }
+  return 0;
+}
 
 extern "C" int desco_gossip_f16_stream(const int16_t* w1_planes, const int16_t* wp_planes, const int16_t* w3_planes,
                                        const int16_t* w5_planes, int16_t* stream, desco_stream_t st) {
@@ -556,6 +838,34 @@ extern "C" int desco_gossip_fused_f16x3_f32(const float* scal4, const int32_t* r
   a.grid_blocks = grid;
   hipLaunchKernelGGL(gossip_fused_f16_kernel, dim3(grid), dim3(GNT), LDS_WAVE, (hipStream_t)stream, a, groups);
   return launch_status("desco_gossip_fused_f16x3_f32");
+}
+
+
+extern "C" int desco_gossip_planned_f16x3_f32(const float* scal4, const int32_t* col, int64_t num_nodes, int num_q,
+                                              const float* g1, const float* pzz, const float* cst,
+                                              const int16_t* wstream, float b7, float* out, const int32_t* plan,
+                                              int tiled, uint64_t* queue, desco_stream_t stream) {
+  using namespace gf16;
+  if (num_nodes == 0) return 0;
+  // (col may be null where the batch has no edge, as for desco_gossip_fused_f16x3_f32)
+  if (!scal4 || !g1 || !pzz || !cst || !wstream || !out || !plan || !queue || num_nodes < 0 || num_q < 1 ||
+      num_q > 65535 || mis16(scal4) || mis16(wstream) || mis16(pzz) || mis16(cst) || mis16(plan) || mis8(queue) ||
+      (reinterpret_cast<uintptr_t>(out) & 3) != 0)
+    return fail(DESCO_EINVAL, "desco_gossip_planned_f16x3_f32: bad argument");
+  // a record's byte offset (row * Q * 16) and a group's offset in the plan travel in 32 bits
+  const int64_t groups = gossip_groups(num_nodes, tiled != 0);
+  if (num_nodes * (int64_t)num_q * 16 >= (int64_t)1 << 32 || groups * (16 * PLAN_REC + 1) * 4 >= (int64_t)1 << 32)
+    return fail(DESCO_EINVAL, "desco_gossip_planned_f16x3_f32: num_nodes * num_q * 16 must be below 2^32 "
+                              "(use desco_gossip_fused_f16x3_f32)");
+  PArgs a{reinterpret_cast<const float4*>(scal4), col, plan, num_nodes, num_q, g1, pzz, cst,
+          reinterpret_cast<const short*>(wstream), b7, out, reinterpret_cast<unsigned long long*>(queue)};
+  if (hipError_t e = size_dynamic_lds<gossip_planned_f16_kernel>((int)LDS_WAVE); e != hipSuccess)
+    return fail((int)e, "desco_gossip_planned_f16x3_f32: cannot size LDS");
+  const int64_t units = groups * ((num_q + WQ - 1) / WQ);
+  const unsigned grid = persistent_grid((units + 7) / 8);
+  a.grid_blocks = grid;
+  hipLaunchKernelGGL(gossip_planned_f16_kernel, dim3(grid), dim3(GNT), LDS_WAVE, (hipStream_t)stream, a, groups);
+  return launch_status("desco_gossip_planned_f16x3_f32");
 }
 
 #include "tu_no_packed_f32_end.hpp"

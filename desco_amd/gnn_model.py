@@ -51,6 +51,10 @@ CANON_ROWS_ONCE = os.environ.get("DESCO_CANON_ROWS_ONCE", "1") != "0"
 # degree-balanced row order inside the fused gossip kernel's 128-node tiles (desco_gossip_tile_order); results are
 # bit-identical with and without it
 GOSSIP_TILE_ORDER = os.environ.get("DESCO_GOSSIP_TILE_ORDER", "1") != "0"
+# the f16x3 gossip pass through the planned kernel (desco_gossip_planned_f16x3_f32: per-batch plan, packed operands,
+# buffer loads) wherever its 32-bit bound holds (ops.gossip_plan_fits); results are bit-identical either way.
+# DESCO_GOSSIP_PLAN=0: the launches of desco_gossip_fused_f16x3_f32 everywhere.
+GOSSIP_PLAN = os.environ.get("DESCO_GOSSIP_PLAN", "1") != "0"
 _RELEASED = object()        # placeholder of a layer's rows that shmp_forward has released
 
 TARGET_NODE_TYPES = ["count", "canonical"]
@@ -1812,8 +1816,30 @@ def _gossip_query_terms(gnn: BaseGNN, pk: dict, query_emb: torch.Tensor) -> dict
     (g0, g1), *terms = _gossip_layer0_terms(gnn.gnn_core, gnn.post_mp[0], query_emb.float(), pk["w_pre"], pk["b_pre"])
     q = dict(zip(("p", "r", "t", "z", "tp", "zp"), (v.contiguous() for v in terms)))
     q["g0"], q["g1"] = g0.contiguous(), g1.contiguous()
+    if "wstream" in pk:
+        # the planned kernel's packed operands: [Q, 192] = p | z | zp, and the kernel's constant image + 1 / scales
+        (_, b3), (_, b5) = pk["post"]
+        q["pzz"] = torch.cat([q["p"], q["z"], q["zp"]], 1).contiguous()
+        q["cst"] = torch.cat([pk["u1"], pk["d1"], q["tp"], b3, b5, pk["w7"], q["r"], q["t"], pk["winv"]]).contiguous()
     pk["qcache"] = (key, q)
     return q
+
+
+# The planned kernel holds a node's first four neighbours in its plan record; further ones it reads in every query from
+# the record and col again, where the unplanned kernel stages 15 columns per work unit in LDS.  Its measured gain is on
+# molecule shapes (largest degree 4); batches in which more than this share of the nodes has more than four neighbours
+# keep the unplanned launch -- exactly the launches from before the switch.  (The tile order sorts a tile's rows by degree,
+# so the share of nodes is also about the share of 16-node groups that run the loop beyond four.)
+GOSSIP_PLAN_LONG_ROW_SHARE = 1.0 / 16.0
+
+
+def gossip_takes_plan(gnn: BaseGNN, batch: GossipBatch, num_q: int, tiled: bool = True) -> bool:
+    """whether ``gossip_forward`` launches the planned kernel for a column group of ``num_q`` queries of ``batch``: the
+    two-layer f16x3 pass, the switch on, the kernel's 32-bit bound kept, few rows beyond four neighbours.  The one place
+    that decides it: the pipeline builds a batch's plan only where this holds."""
+    return (GOSSIP_F16X3 and GOSSIP_PLAN and gnn.gnn_core.layer_num == 2 and batch.num_nodes > 0
+            and batch.device.type == "cuda" and ops.gossip_plan_fits(batch.num_nodes, num_q, tiled)
+            and batch.long_row_share <= GOSSIP_PLAN_LONG_ROW_SHARE)
 
 
 def gossip_forward(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tensor) -> torch.Tensor:
@@ -1844,7 +1870,12 @@ def gossip_forward(gnn: BaseGNN, batch: GossipBatch, query_emb: torch.Tensor) ->
              "w1s": pk["fused_w1s"], "wps": pk["fused_wps"], "w3s": pk["fused_w3s"], "b3": b3,
              "w5s": pk["fused_w5s"], "b5": b5, "w7": pk["w7"], "b7": pk["b7"]}
         tperm = batch.tile_perm if GOSSIP_TILE_ORDER else None
-        if GOSSIP_F16X3:
+        dst = getattr(batch, "out_buf", None) if (q0 == 0 and q1 == Q) else None
+        if gossip_takes_plan(gnn, batch, q1 - q0, tperm is not None):
+            vp = {"g1": v["g1"], "pzz": sl(q["pzz"]), "cst": q["cst"], "wstream": pk["wstream"], "b7": pk["b7"]}
+            outs.append(ops.gossip_planned_f16(scal4, batch.col, N, q1 - q0, vp, batch.work_queue,
+                                               batch.gossip_plan(tperm is not None), tperm is not None, out=dst))
+        elif GOSSIP_F16X3:
             v["wstream"], v["winv"] = pk["wstream"], pk["winv"]
             outs.append(ops.gossip_fused_f16(scal4, batch.rowptr, batch.col, N, q1 - q0, v, batch.work_queue,
                                              tile_perm=tperm,

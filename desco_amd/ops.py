@@ -1457,6 +1457,85 @@ def gossip_fused_f16(scal: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor
     return out
 
 
+GOSSIP_PLAN_REC = 8        # int32 words per node slot of a gossip plan (include/desco_hip.h)
+
+
+def gossip_plan_fits(num_nodes: int, num_q: int, tiled: bool = True) -> bool:
+    """the planned gossip kernel's bound: a record's byte offset (row * Q * 16) and the plan itself stay below 2^32"""
+    groups = ((num_nodes + 127) // 128) * 8 if tiled else (num_nodes + 15) // 16
+    return num_nodes * num_q * 16 < 2 ** 32 and groups * (16 * GOSSIP_PLAN_REC + 1) * 4 < 2 ** 32
+
+
+def gossip_plan(rowptr: torch.Tensor, col: torch.Tensor, num_nodes: int,
+                tile_perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 plan of the planned fused gossip kernel (desco_gossip_plan): per group of 16 node slots -- in the kernel's
+    group order, with or without the tile order -- 16 records (row, degree, smaller-id mask, first four neighbour rows,
+    first edge) and the group's largest degree.  A function of the CSR alone: a batch computes it once.  CPU tensors go
+    through the host twin (same words)."""
+    L = _lib.lib()
+    words = int(L.desco_gossip_plan_words(num_nodes, 0 if tile_perm is None else 1))
+    if words < 0:
+        raise ValueError("gossip_plan: num_nodes must not be negative")
+    if tile_perm is not None and tile_perm.numel() < ((num_nodes + 127) // 128) * 128:
+        raise ValueError("gossip_plan: tile_perm is shorter than the tiles of this batch")
+    if rowptr.numel() < num_nodes + 1:
+        raise ValueError("gossip_plan: rowptr is shorter than num_nodes + 1")
+    plan = torch.empty((words,), device=rowptr.device, dtype=torch.int32)
+    if not num_nodes:
+        return plan
+    if rowptr.device.type == "cpu":
+        def host(t, dt):
+            if t.dtype != dt or not t.is_contiguous() or t.device.type != "cpu":
+                raise ValueError("gossip_plan: host operands must be contiguous CPU tensors of the right type")
+            return t.data_ptr()
+        _lib.check(L.desco_gossip_plan_host(host(rowptr, torch.int32), host(col, torch.int32), num_nodes,
+                                            None if tile_perm is None else host(tile_perm, torch.uint8),
+                                            plan.data_ptr()), "gossip_plan_host")
+        return plan
+    _lib.check(L.desco_gossip_plan(_dev(rowptr, "rowptr", torch.int32), _dev(col, "col", torch.int32), num_nodes,
+                                   None if tile_perm is None else _dev(tile_perm, "tile_perm", torch.uint8),
+                                   _dev(plan, "plan", torch.int32), _stream()), "gossip_plan")
+    return plan
+
+
+def gossip_planned_f16(scal: torch.Tensor, col: torch.Tensor, num_nodes: int, num_q: int, v: dict,
+                       queue: torch.Tensor, plan: torch.Tensor, tiled: bool,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gossip_fused_f16`` through the planned kernel (desco_gossip_planned_f16x3_f32): the same pred [N, Q] bit for
+    bit.  ``plan``: gossip_plan of the batch (``tiled``: built with a tile order); ``v``: g1 [Q], pzz [Q, 192] =
+    p | z | zp, cst [900] = u, d1, tp, b3, b5, w7, r, t, winv, wstream, b7.  Needs gossip_plan_fits(N, Q)."""
+    if out is None:
+        out = torch.empty((num_nodes, num_q), device=scal.device, dtype=torch.float32)
+    elif tuple(out.shape) != (num_nodes, num_q) or not out.is_contiguous():
+        raise ValueError("gossip_planned_f16: `out` must be a contiguous [N, Q] tensor")
+    L = _lib.lib()
+    if plan.numel() != int(L.desco_gossip_plan_words(num_nodes, 1 if tiled else 0)):
+        raise ValueError("gossip_planned_f16: the plan was not built for this batch")
+    if queue.dtype != torch.int64 or queue.numel() < 2:
+        raise ValueError("gossip_planned_f16: queue must hold two int64 words")
+    if tuple(v["pzz"].shape) != (num_q, 192) or v["cst"].numel() != 900 or v["g1"].numel() != num_q:
+        raise ValueError("gossip_planned_f16: pzz must be [Q, 192], cst [900], g1 [Q]")
+    if scal.numel() != num_nodes * num_q * 4:
+        raise ValueError("gossip_planned_f16: scal must hold [N * Q, 4] floats")
+    for n in ("g1", "pzz", "cst", "wstream"):
+        if not v[n].is_contiguous():
+            raise ValueError(f"gossip_planned_f16: operand {n} must be contiguous")
+    rows = float(num_nodes) * num_q
+    # (the profiler's label is the stage's, as for gossip_fused_f16: the roofline tables key the matrix-pipe peak on it.
+    # The bytes are the ALGORITHM's, the same as that entry's, so that the two launches are priced alike: what the
+    # planned kernel reads on top -- the plan's 512-byte group record once per (group, query) and the group's
+    # largest-degree word beside it, in place of rowptr / tile order once per (group, five queries) -- is left out.)
+    with _Timed("gossip_fused_f16_kernel", rows * GOSSIP_FUSED_FLOPS_PER_ROW,
+                rows * 20.0 + 4.0 * (col.numel() * (1 + 4 * num_q) + num_nodes)):
+        _lib.check(L.desco_gossip_planned_f16x3_f32(_dev(scal, "scal"), _dev(col, "col", torch.int32), num_nodes, num_q,
+                                                    _dev(v["g1"], "g1"), _dev(v["pzz"], "pzz"), _dev(v["cst"], "cst"),
+                                                    _dev(v["wstream"], "wstream", torch.int16), float(v["b7"]),
+                                                    _dev(out, "out"), _dev(plan, "plan", torch.int32),
+                                                    1 if tiled else 0, _dev(queue, "queue", torch.int64), _stream()),
+                   "gossip_planned_f16")
+    return out
+
+
 def rowdot_add(y: torch.Tensor, w: torch.Tensor, b: float, add: Optional[torch.Tensor],
                out: Optional[torch.Tensor] = None):
     """out[r] = add[r] + y[r,:] . w + b   (``out``: a contiguous [R] tensor to write, else a new one)"""

@@ -208,9 +208,14 @@ class InferencePipeline:
         self.gossip_batches = []
         for g0, g1 in zip(cuts[:-1], cuts[1:]):
             n0, n1 = int(self.graphs.graph_ptr[g0]), int(self.graphs.graph_ptr[g1])
-            self.gossip_batches.append((n0, n1, GossipBatch(self.graphs.subset(g0, g1), self.device)))
-            self.gossip_batches[-1][2].tile_perm        # built here, outside any stream capture
-            self.gossip_batches[-1][2].work_queue
+            gb = GossipBatch(self.graphs.subset(g0, g1), self.device)
+            self.gossip_batches.append((n0, n1, gb))
+            gb.tile_perm                                # built here, outside any stream capture
+            # ... and the planned kernel's plan, where gossip_forward will launch it (column groups of at most 64 queries)
+            gnn = getattr(self.gm, "emb_model", None)
+            if gnn is not None and GMOD.gossip_takes_plan(gnn, gb, min(Q, 64), GMOD.GOSSIP_TILE_ORDER):
+                gb.gossip_plan(GMOD.GOSSIP_TILE_ORDER)
+            gb.work_queue
         self.num_queries = Q
 
     # ---- hipGraph replay --------------------------------------------------------------------------

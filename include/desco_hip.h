@@ -1576,6 +1576,30 @@ int desco_gossip_fused_f16x3_f32(const float* scal4, const int32_t* rowptr, cons
  * barrier at the end: with rows in node order the phase takes 1.3-1.8x its balanced time).  NULL = node order.
  * The result does not depend on it bit for bit (every row's sum keeps its own CSR order). */
 int desco_gossip_tile_order(const int32_t* rowptr, int64_t num_nodes, uint8_t* tile_perm, desco_stream_t stream);
+/* The PLANNED form of desco_gossip_fused_f16x3_f32: the same network, bit for bit, with everything a work unit needs to
+ * know of its 16 nodes read from a per-batch plan instead of computed from rowptr / col / tile_perm, the per-query loads
+ * issued as buffer loads (scalar base that moves with the query + a 32-bit lane offset), and the operands packed.
+ *   desco_gossip_plan: a function of the CSR (and the tile order) alone, once per batch.  plan holds
+ *     desco_gossip_plan_words(num_nodes, tile_perm != NULL) int32 words, 16-byte aligned: per group of 16 node slots
+ *     (group order = the kernel's: rows 16 g .. 16 g + 15, or with a tile order the degree-sorted ranks of the 128-node
+ *     tile) 16 records of 8 words -- row, degree, bit i = neighbour i < 15 has the smaller id (bit 31: empty slot), the
+ *     rows of the first four neighbours (the node's own row from the degree on), the node's first edge -- so a wave reads
+ *     its group's 512 bytes in one coalesced load; then one word per group, its largest degree.  An empty slot takes
+ *     the last row with degree 0.  desco_gossip_plan_host is the host twin (host pointers, same words).  col may be
+ *     NULL where the batch has no edge (it is read for rows of degree > 0 only), here and in the planned entry.
+ *   desco_gossip_planned_f16x3_f32: pzz [num_q][192] = p_q | z_q | zp_q; cst [900] = u, d1, tp, b3 (64 each), b5, w7
+ *     (256 each), r, t (64 each) -- the kernel's LDS image -- then winv[4]; both 16-byte aligned.  tiled = the plan was
+ *     built with a tile order.  Needs num_nodes * num_q * 16 < 2^32 (a record's byte offset travels in 32 bits);
+ *     DESCO_EINVAL above it: callers use desco_gossip_fused_f16x3_f32 there.  queue as for that entry. */
+int64_t desco_gossip_plan_words(int64_t num_nodes, int tiled);
+int desco_gossip_plan(const int32_t* rowptr, const int32_t* col, int64_t num_nodes, const uint8_t* tile_perm,
+                      int32_t* plan, desco_stream_t stream);
+int desco_gossip_plan_host(const int32_t* rowptr, const int32_t* col, int64_t num_nodes, const uint8_t* tile_perm,
+                           int32_t* plan);
+int desco_gossip_planned_f16x3_f32(const float* scal4, const int32_t* col, int64_t num_nodes, int num_q,
+                                   const float* g1, const float* pzz, const float* cst, const int16_t* wstream,
+                                   float b7, float* out, const int32_t* plan, int tiled, uint64_t* queue,
+                                   desco_stream_t stream);
 
 /* One GossipConv layer l >= 1 of a gossip model of any depth (--gossip_layer_num != 2), over all
  * R = num_nodes * num_q rows (node i, query q) = row i * num_q + q, all matrices rows of 64 floats:
